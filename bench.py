@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- the hot path's headline benchmark (BASELINE.json: affinity-map Mpixels/s, fwd+bwd).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 A "step" is one pass of the hot path over one batch: embedding_loss forward (affinity maps + fused
@@ -11,7 +11,11 @@ CVPPP-shaped B=8 x D=16 x 544 x 544 embeddings per GPU, the shipped K=10 stencil
 (shifts 1,3,5,9,27 x neighbor 4), fp32, synthetic inputs already resident in HBM.  Images are
 independent units: ranks shard the batch with no data-path collective (weak scaling, 8 images per GPU).
 
-Rank 0 prints ONE JSON line; besides the contract fields it carries
+A plain run settles the GPU, runs W warm-up steps, times ONE batch of exactly K steps and prints ONE JSON
+line (rank 0): metric, value, unit, higher_is_better, dtype, ms_per_step (= that batch / K) and the workload.
+--dump-outputs DIR then also writes what the last timed step returned: loss, all_loss (per offset), and fixed
+seeded samples of affs and of the embedding's gradient, as DIR/<name>.npy in float32.
+--full adds every other leg to the line, among them
   "roofline":     the dominant kernel's algorithmic bytes / its HIP-event duration vs 8 TB/s HBM
   "cpu_baseline": the reference's op sequence (torch CPU, all host cores) on a bounded sample
 """
@@ -186,16 +190,39 @@ def other_config(args, pkg, dev, world, rank, dist, fence, cname=None, compact=F
         else:
             spec = op.AffinitySpec(3, offsets, None, pkg._lib.BORDER_CROP_ZERO, pkg._lib.NORM_CROPPED)
 
+    last = {}  # what the latest step handed its caller (--dump-outputs writes the last timed step's)
+
     def step():
         E.grad = None
-        loss, affs, _ = op.FusedAffinityMSE.apply(E, E2, T, Wt, M, spec)
+        loss, affs, parts = op.FusedAffinityMSE.apply(E, E2, T, Wt, M, spec)
         pkg.backward(loss)  # loss.backward() seeded with a cached ones-scalar (no per-step fill kernel)
+        last["loss"], last["affs"], last["all_loss"] = loss, affs, parts
 
     settle = settle_gpu(step, 0.6 if compact else 1.5)
     for _ in range(3 if compact else max(args.warmup, 3)):
         step()
+    npx = B * int(np.prod(dims))
+    if not compact:
+        # the line's headline: ONE timed batch of exactly --steps steps (as main()'s)
+        dt = timed_batches(step, fence, steps, dist, dev, nb=1)[0]
+        value = world * npx * steps / dt / 1e6
+        if args.dump_outputs and rank == 0:
+            dump_outputs(args.dump_outputs, dict(last, grad=E.grad))
+        line = {
+            "metric": "affinity-map Mpixels/sec (fwd+bwd)", "value": round(value, 2), "unit": "Mpx/s",
+            "n_gpus": world, "steps": steps, "warmup": args.warmup, "ms_per_step": round(dt / steps * 1e3, 5),
+            "timing": "one batch of %d steps between barrier + synchronize (max over ranks)" % steps,
+            "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f16 storage / f32 arithmetic" if c["f16"] else "f32",
+            "data": "synthetic",
+            "config": {"workload": "%s: B=%d per GPU x D=%d x %s, K=%d offsets" % (c["what"], B, Dm, "x".join(str(v) for v in dims), K),
+                       "images_per_gpu": B, "embedding_dim": Dm, "dims": dims, "offsets": K, "sharding": "batch across ranks, no data-path collective"},
+            "settle_steps": settle,
+        }
+        if not args.full:
+            return line if rank == 0 else None
     bst = batch_stats(timed_batches(step, fence, steps, dist, dev), steps)  # median of N_BATCHES batches (see main())
-    dt = bst["median"] * 1e-3 * steps
+    if compact:
+        dt = bst["median"] * 1e-3 * steps
     # the same step started with plain loss.backward() -- what a drop-in caller of INTEGRATION.md section 2 executes (autograd seeds
     # the scalar's backward with a ones_like fill kernel); untimed for `value`, reported beside it
     def step_seed():
@@ -204,7 +231,6 @@ def other_config(args, pkg, dev, world, rank, dist, fence, cname=None, compact=F
         loss.backward()
 
     dt_seed = None if compact else wall_time_s(step_seed, fence, steps)
-    npx = B * int(np.prod(dims))
     value = world * npx * steps / dt / 1e6
     if rank != 0:
         return None
@@ -238,15 +264,10 @@ def other_config(args, pkg, dev, world, rank, dist, fence, cname=None, compact=F
                 "mpx_s": round(value, 1), "kernel_ms": {"fwd": round(kf, 5), "bwd": round(kb, 5)}, "dominant": dom,
                 "frac": round(achieved / HBM_PEAK_GBS, 4), "pair_frac": round(step_gbs / HBM_PEAK_GBS, 4),
                 "traffic": pmc_traffic(cname, dom)}
-    out = {
-        "metric": "affinity-map Mpixels/sec (fwd+bwd)", "value": round(value, 2), "unit": "Mpx/s",
-        "n_gpus": world, "steps": steps, "warmup": args.warmup, "ms_per_step": round(dt / steps * 1e3, 5),
-        "ms_min": round(bst["min"], 5), "ms_max": round(bst["max"], 5), "batches_ms": bst["all"],
-        "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f16 storage / f32 arithmetic" if c["f16"] else "f32",
-        "data": "synthetic",
-        "config": {"workload": "%s: B=%d per GPU x D=%d x %s, K=%d offsets" % (c["what"], B, Dm, "x".join(str(v) for v in dims), K),
-                   "images_per_gpu": B, "embedding_dim": Dm, "dims": dims, "offsets": K, "sharding": "batch across ranks, no data-path collective"},
-        "ms_per_step_autograd_seed": round(dt_seed / steps * 1e3, 5), "settle_steps": settle,
+    out = dict(line, **{
+        "ms_min": round(bst["min"], 5), "ms_max": round(bst["max"], 5), "batches_ms": bst["all"], "batches_ms_median": round(bst["median"], 5),
+        "batches_timing": "%d more batches of %d steps after the headline's, each timed like it" % (n_batches(steps), steps),
+        "ms_per_step_autograd_seed": round(dt_seed / steps * 1e3, 5),
         "kernel_ms": {"fwd": round(kf, 5), "bwd": round(kb, 5)}, "kernel_ms_spread": kspread,
         # the launch floor as a number: the entry points' launches (forward + loss finish + backward) captured in a
         # HIP graph and replayed back to back -- no Python, no ctypes, no autograd between them
@@ -260,7 +281,7 @@ def other_config(args, pkg, dev, world, rank, dist, fence, cname=None, compact=F
                      "frac": round(achieved / HBM_PEAK_GBS, 4), "traffic": pmc_traffic(args.config, dom) if B == c["B"] else None,
                      "algorithmic_bytes_per_px": ab[dom], "px_per_launch": npx,
                      "ms": round(max(kf, kb), 5), "fwd_plus_bwd_GBs": round(step_gbs, 1), "fwd_plus_bwd_frac": round(step_gbs / HBM_PEAK_GBS, 4)},
-    }
+    })
     if world == 1 and not args.no_cpu_baseline:
         # bounded sample: one image (2D) / one 24 x 256 x 256 block of the sub-volume (3D), same op sequence on the host cores
         if c["ndim"] == 2:
@@ -446,7 +467,7 @@ def timed_batches(step, fence, steps, dist, red_dev, nb=None):
     nb = nb or n_batches(steps)
     out = []
     was = gc.isenabled()  # (no gc.collect() here: 50-100 ms of host work with the GPU idle and the first batches read 5-80 % slow while its
-    gc.disable()          #  clocks come back -- gpurun_out/r5_bench_s20_3.json; the collection happens before the settle phase instead)
+    gc.disable()          #  clocks come back -- seen in round 5's 20-step runs; the collection happens before the settle phase instead)
     try:
         for _ in range(nb):
             fence()
@@ -469,6 +490,22 @@ def batch_stats(dts, steps):
     """median / min / max of the batches, as ms per step"""
     ms = sorted(d / steps * 1e3 for d in dts)
     return {"median": ms[len(ms) // 2], "min": ms[0], "max": ms[-1], "all": [round(d / steps * 1e3, 5) for d in dts]}
+
+
+DUMP_SAMPLE = 1 << 22  # --dump-outputs: elements kept of a larger output (16 MB of float32; the headline's affs / grad are 95 / 152 MB)
+
+
+def dump_outputs(path, outs):
+    """--dump-outputs: the arrays the last timed step handed its caller, as path/<name>.npy in float32.  An output of more than
+    DUMP_SAMPLE elements is written as a fixed sample of its flattened elements (numpy default_rng(0) indices, drawn with
+    replacement: the same for every run with the same arguments)."""
+    os.makedirs(path, exist_ok=True)
+    for name, x in outs.items():
+        x = x.detach().reshape(-1)
+        if x.numel() > DUMP_SAMPLE:
+            idx = np.random.default_rng(0).integers(0, x.numel(), size=DUMP_SAMPLE)
+            x = x[torch.from_numpy(idx).to(x.device)]
+        np.save(os.path.join(path, name + ".npy"), x.float().cpu().numpy())
 
 
 def wall_time_s(step, fence, steps, warm=5):
@@ -739,6 +776,10 @@ def main():
     ap.add_argument("--no-configs", action="store_true", help="skip the default run's `configs` leg (every other BASELINE config, compact)")
     ap.add_argument("--no-section", action="store_true",
                     help="skip the multi-scale loss-section timings (profiling runs: per-kernel averages then cover the full-size launches only)")
+    ap.add_argument("--full", action="store_true",
+                    help="every leg beside the headline: batch spread, autograd seed, per-kernel / roofline / graph figures, GPU state, "
+                         "train leg, loss sections, the other configs, cpu_baseline (the --no-* options above act on these legs)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write what the last timed step returned (rank 0) as DIR/<name>.npy")
     args = ap.parse_args()
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -786,12 +827,7 @@ def main():
             torch.cuda.synchronize()
 
     if args.config != "c2":
-        out = other_config(args, pkg, dev, world, rank, dist, fence)
-        if dist is not None:
-            dist.barrier()
-            dist.destroy_process_group()
-        if out is not None:
-            print(json.dumps(out), flush=True)
+        finish(dist, other_config(args, pkg, dev, world, rank, dist, fence))
         return
 
     offsets = pkg.multi_offset(SHIFTS, NEIGHBOR)
@@ -802,10 +838,13 @@ def main():
     T, Wt, M = torch.from_numpy(t).to(dev), torch.from_numpy(w).to(dev), torch.from_numpy(m).to(dev)
     crit = pkg.WeightedMSE()
 
+    last = {}  # what the latest step handed its caller (--dump-outputs writes the last timed step's)
+
     def step():
         E.grad = None
-        loss, affs, _ = pkg.embedding_loss(E, T, Wt, M, crit, offsets)
+        loss, affs, all_loss = pkg.embedding_loss(E, T, Wt, M, crit, offsets)
         pkg.backward(loss)  # loss.backward() seeded with a cached ones-scalar (no per-step fill kernel)
+        last["loss"], last["affs"], last["all_loss"] = loss, affs, all_loss.tensor
         return loss
 
     # Settle first (untimed, before the W warm-up steps): a GPU that has just been handed over idles at its lowest clocks
@@ -816,12 +855,30 @@ def main():
     settle = settle_gpu(step)
     for _ in range(args.warmup):
         step()
-    # N_BATCHES timed batches of exactly --steps steps, each between barrier + synchronize, max over ranks per batch; the MEDIAN batch is
-    # the headline, the fastest and the slowest are printed beside it
-    bst = batch_stats(timed_batches(step, fence, args.steps, dist, "cpu" if shared else dev), args.steps)
-    dt = bst["median"] * 1e-3 * args.steps
+    # the headline: ONE timed batch of exactly --steps steps between barrier + synchronize (max over ranks)
+    dt = timed_batches(step, fence, args.steps, dist, "cpu" if shared else dev, nb=1)[0]
     px_per_step = world * B * H * W
     value = px_per_step * args.steps / dt / 1e6
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, dict(last, grad=E.grad))
+    out = None
+    if rank == 0:
+        out = {
+            "metric": "affinity-map Mpixels/sec (fwd+bwd)", "value": round(value, 2), "unit": "Mpx/s",
+            "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(dt / args.steps * 1e3, 5),
+            "timing": "one batch of %d steps between barrier + synchronize (max over ranks)" % args.steps,
+            "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
+            "config": {"workload": "BASELINE configs[1]: CVPPP A1 embedding_loss fwd+bwd, B=%d per GPU x D=%d x %dx%d (530x500 padded), "
+                                   "K=%d offsets (shifts 1,3,5,9,27 x neighbor 4), circular border, u8 mask" % (B, D, H, W, K),
+                       "images_per_gpu": B, "embedding_dim": D, "height": H, "width": W, "offsets": K,
+                       "sharding": "batch across ranks, no data-path collective"},
+            "settle_steps": settle,
+        }
+    if not args.full:
+        finish(dist, out)
+        return
+    # --full: the spread of N_BATCHES (21 when short) more batches of exactly --steps steps, each timed like the headline's
+    bst = batch_stats(timed_batches(step, fence, args.steps, dist, "cpu" if shared else dev), args.steps)
     # the same step started with plain loss.backward(): what a drop-in caller executes -- autograd seeds a
     # scalar's backward with a ones_like fill kernel (about 5 us); reported beside the headline, never in place of it
     def step_seed():
@@ -842,7 +899,6 @@ def main():
         except Exception as ex:  # the headline line must not be lost to the second metric's leg
             train = {"train_imgs_per_s": None, "train_error": repr(ex)[:300]}
 
-    out = None
     if rank == 0:
         # ---- per-kernel durations (HIP events on the launch stream) through the C ABI --------------------
         op, L = pkg.affinity_op, pkg._lib.lib()
@@ -986,19 +1042,11 @@ def main():
         achieved = launch_bytes / (kt[dom] * 1e-3) / 1e9
         step_gbs = ab["step"] * B * H * W / ((kt["fwd"] + kt["bwd"]) * 1e-3) / 1e9
         traffic = pmc_traffic("c2" if B == B_PER_GPU else "c2b%d" % B, dom)  # (a key per batch size: profiles/r4_final_pmc.sh)
-        out = {
-            "metric": "affinity-map Mpixels/sec (fwd+bwd)", "value": round(value, 2), "unit": "Mpx/s",
-            "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(dt / args.steps * 1e3, 5),
-            "ms_min": round(bst["min"], 5), "ms_max": round(bst["max"], 5), "batches_ms": bst["all"],
-            "timing": "median of %d batches of %d steps (each between barrier + synchronize; max over ranks per batch)" % (n_batches(args.steps), args.steps),
-            "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
-            "config": {"workload": "BASELINE configs[1]: CVPPP A1 embedding_loss fwd+bwd, B=%d per GPU x D=%d x %dx%d (530x500 padded), "
-                                   "K=%d offsets (shifts 1,3,5,9,27 x neighbor 4), circular border, u8 mask" % (B, D, H, W, K),
-                       "images_per_gpu": B, "embedding_dim": D, "height": H, "width": W, "offsets": K,
-                       "sharding": "batch across ranks, no data-path collective"},
+        out.update({
+            "ms_min": round(bst["min"], 5), "ms_max": round(bst["max"], 5), "batches_ms": bst["all"], "batches_ms_median": round(bst["median"], 5),
+            "batches_timing": "%d more batches of %d steps after the headline's, each timed like it" % (n_batches(args.steps), args.steps),
             # pixels are counted on the padded tensor the op processes (544^2 per CVPPP image); the same rate in
             # images and in pixels of the un-padded 530x500 image
-            "settle_steps": settle,
             "gpu_state": gpu_state,
             "ms_per_step_autograd_seed": round(dt_seed / args.steps * 1e3, 5),
             "value_autograd_seed": round(px_per_step * args.steps / dt_seed / 1e6, 2),
@@ -1024,10 +1072,15 @@ def main():
                          "algorithmic_bytes_per_px": ab[dom], "px_per_launch": B * H * W,
                          "ms": round(kt[dom], 5), "ms_drained": round(kt_iso[dom], 5),
                          "fwd_plus_bwd_GBs": round(step_gbs, 1), "fwd_plus_bwd_frac": round(step_gbs / HBM_PEAK_GBS, 4)},
-        }
+        })
         if world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(offsets, e, t, w, m)
             out["speedup_vs_cpu"] = round(value / out["cpu_baseline"]["best_cpu_value"], 1)  # vs the faster CPU line
+    finish(dist, out)
+
+
+def finish(dist, out):
+    """end the process group (every rank) and print the line (rank 0)"""
     if dist is not None:
         dist.barrier()
         dist.destroy_process_group()

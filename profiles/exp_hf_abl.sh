@@ -6,7 +6,7 @@ CSRC=$ROOT/pixel-embedded-affinity_amd/csrc
 for tag in "" hf_NODMA hf_NOGATHER hf_NODMA_NOGATHER hf_NOTW hf_NOSTORE hf_NOTW_NOSTORE ""; do
   lib=$CSRC/libpea_hip${tag:+_$tag}.so
   [ -f $lib ] || continue
-  PEA_HIP_LIB=$lib timeout -k 10 120 python3 $ROOT/bench.py --config c5 --steps 100 --warmup 10 --no-cpu-baseline > /tmp/abl.json 2>/tmp/abl.err || { echo "$tag FAILED"; tail -3 /tmp/abl.err; continue; }
+  PEA_HIP_LIB=$lib timeout -k 10 120 python3 $ROOT/bench.py --full --config c5 --steps 100 --warmup 10 --no-cpu-baseline > /tmp/abl.json 2>/tmp/abl.err || { echo "$tag FAILED"; tail -3 /tmp/abl.err; continue; }
   python3 - "${tag:-full}" <<'PY'
 import json, sys
 j = json.loads(open('/tmp/abl.json').read().strip().splitlines()[-1]); print('%-22s' % sys.argv[1], j['kernel_ms'])

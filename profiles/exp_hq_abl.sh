@@ -7,7 +7,7 @@ CSRC=$ROOT/pixel-embedded-affinity_amd/csrc
 for tag in "" hq_NOSTORE hq_NOLOAD hq_NOGATHER hq_NOWRITE hq_NOSTORE_NOGATHER hq_NOLOAD_NOWRITE ""; do
   lib=$CSRC/libpea_hip${tag:+_$tag}.so
   [ -f $lib ] || continue
-  PEA_HIP_LIB=$lib timeout -k 10 120 python3 $ROOT/bench.py --config c5 --steps 60 --warmup 10 --no-cpu-baseline > /tmp/abl.json 2>/tmp/abl.err || { echo "$tag FAILED"; tail -3 /tmp/abl.err; continue; }
+  PEA_HIP_LIB=$lib timeout -k 10 120 python3 $ROOT/bench.py --full --config c5 --steps 60 --warmup 10 --no-cpu-baseline > /tmp/abl.json 2>/tmp/abl.err || { echo "$tag FAILED"; tail -3 /tmp/abl.err; continue; }
   python3 -c "
 import json; j=json.loads(open('/tmp/abl.json').read().strip().splitlines()[-1]); print('%-22s' % '${tag:-full}', j['kernel_ms'])"
 done

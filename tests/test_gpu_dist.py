@@ -148,7 +148,7 @@ def test_bench_two_ranks_path_runs_and_reports_whole_job_throughput():
     env = dict(os.environ, MASTER_ADDR="127.0.0.1", HSA_ENABLE_IPC_MODE_LEGACY="0")
     common = ["--steps", "30", "--warmup", "3", "--no-cpu-baseline", "--no-section"]
     two = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
-                          "--master-port", str(_free_port()), os.path.join(root, "bench.py"), "--gpus", "2"] + common,
+                          "--master-port", str(_free_port()), os.path.join(root, "bench.py"), "--gpus", "2", "--full"] + common,
                          capture_output=True, text=True, timeout=600, env=env, cwd=root)
     assert two.returncode == 0, two.stderr[-2000:]
     lines = [l for l in two.stdout.splitlines() if l.startswith("{")]
@@ -172,3 +172,34 @@ def test_bench_two_ranks_path_runs_and_reports_whole_job_throughput():
         assert 0.3 < r2["value"] / r1["value"] < 1.5
     else:        # one GPU each, no data-path collective: close to twice the rate
         assert r2["value"] / r1["value"] > 1.6
+
+
+def test_bench_plain_run_times_exactly_steps_and_dumps_the_last_step(tmp_path):
+    """a plain `bench.py --steps K --warmup W --dump-outputs DIR` (fresh child process): the line holds the headline fields and
+    nothing from the --full legs, `steps` is K, `value` and `ms_per_step` describe the same K steps, and DIR holds what the last
+    timed step returned: float32, at most 64 MB in all, the loss equal to the sum of its per-offset parts"""
+    import json
+    import subprocess
+    import sys
+    root = ge.ROOT
+    out = tmp_path / "dump"
+    run = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "7", "--warmup", "2",
+                          "--dump-outputs", str(out)], capture_output=True, text=True, timeout=300, cwd=root)
+    assert run.returncode == 0, run.stderr[-2000:]
+    lines = [l for l in run.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1, run.stdout[-2000:]
+    r = json.loads(lines[0])
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert k in r, k
+    assert r["steps"] == 7 and r["warmup"] == 2 and r["unit"] == "Mpx/s" and r["higher_is_better"] is True and r["dtype"] == "f32"
+    assert not any(k in r for k in ("roofline", "kernel_ms", "cpu_baseline", "configs", "train_imgs_per_s", "batches_ms"))
+    B, H, W = r["config"]["images_per_gpu"], r["config"]["height"], r["config"]["width"]
+    assert abs(r["value"] * 1e6 * r["ms_per_step"] * 1e-3 / (B * H * W) - 1.0) < 1e-3
+    files = sorted(p.name for p in out.iterdir())
+    assert files == ["affs.npy", "all_loss.npy", "grad.npy", "loss.npy"], files
+    assert sum(p.stat().st_size for p in out.iterdir()) <= 64 << 20
+    arrs = {f[:-4]: np.load(out / f) for f in files}
+    assert all(a.dtype == np.float32 and np.isfinite(a).all() for a in arrs.values())
+    assert arrs["all_loss"].shape == (r["config"]["offsets"],) and arrs["loss"].size == 1
+    np.testing.assert_allclose(arrs["all_loss"].sum(), arrs["loss"].item(), rtol=1e-5)
+    assert np.abs(arrs["grad"]).max() > 0 and np.abs(arrs["affs"]).max() <= 1.0 + 1e-5  # cosine similarities of unit embeddings
