@@ -23,7 +23,7 @@
  *                          scripts_cvppp/main.py:311, scripts_ac3ac4/main.py:232)
  *
  * Tensor layouts (all C-contiguous, exactly the reference's):
- *   e, e_other, de, de_other : [B, D, Z, Y, X]   f32 (PEA_F32) or f16 (PEA_F16);  2D => Z = 1
+ *   e, e_other, de, de_other : [B, D, Z, Y, X]   f32 (PEA_F32), f16 (PEA_F16) or bf16 (PEA_BF16);  2D => Z = 1
  *   target, weight, affs     : [B, K, Z, Y, X]   f32
  *   mask                     : [B, K, Z, Y, X]   u8   (NULL => all ones; the 3D path has none)
  *
@@ -58,9 +58,10 @@ extern "C" {
 #define PEA_BORDER_CROP_ZERO 1
 #define PEA_BORDER_REPLICATE 2 /* neighbour index clamped into the volume (nn.ReplicationPad3d + slice: shift_tensor,
                                   scripts_ac3ac4/loss/loss_embedding_mse.py:294-344; embedding_loss_norm6 :346-354) */
-/* storage dtype of e / de (arithmetic is always f32) */
+/* storage dtype of e / de (arithmetic is always f32; 16-bit stores of de round to nearest even, NaN kept) */
 #define PEA_F32 0
 #define PEA_F16 1
+#define PEA_BF16 2
 /* loss normaliser */
 #define PEA_NORM_BX 0
 #define PEA_NORM_CROPPED 1
@@ -93,7 +94,7 @@ typedef struct PeaDesc {
   int32_t dims[3]; /* Z, Y, X */
   int32_t K;       /* number of offsets, 1..PEA_MAX_K */
   int32_t border;  /* PEA_BORDER_* */
-  int32_t dtype;   /* PEA_F32 / PEA_F16 */
+  int32_t dtype;   /* PEA_F32 / PEA_F16 / PEA_BF16 */
   int32_t norm;    /* PEA_NORM_* */
   uint32_t flags;  /* PEA_FLAG_* */
   float eps;       /* clamp of the L2 norm: 1e-12 (F.normalize) or 1e-6 (nn.CosineSimilarity) */
@@ -231,7 +232,7 @@ int pea_affinity_bwd_dual_ex(const PeaDesc *desc, const void *e, const void *ema
                              const float *inv_norm, const float *inv_norm_other, const float *dloss, const float *dloss_cross,
                              void *de, void *stream);
 
-/* buf[0..n) *= scale[0] in place (dtype PEA_F32 / PEA_F16; f32 buffers 16-byte aligned).  `scale` is a DEVICE scalar
+/* buf[0..n) *= scale[0] in place (dtype PEA_F32 / PEA_F16 / PEA_BF16; f32 buffers 16-byte aligned).  `scale` is a DEVICE scalar
  * (autograd's grad_output): the kernel reads it and returns without touching buf when it is exactly 1, which is
  * what a plain loss.backward() hands to the gradient pea_affinity_fwd_bwd_labels produced for dloss = 1. */
 int pea_scale_inplace(void *buf, int dtype, size_t n, const float *scale, void *stream);

@@ -62,10 +62,14 @@ def _require_gpu(t, name):
         raise RuntimeError("%s is on %s: the affinity path runs on an MI355X only (no CPU fallback)" % (name, t.device))
 
 
+# storage dtype of the embedding -> PeaDesc.dtype (include/pea.h PEA_F32 / PEA_F16 / PEA_BF16)
+_DTYPE_CODE = {torch.float32: _lib.F32, torch.float16: _lib.F16, torch.bfloat16: _lib.BF16}
+
+
 def _embedding_arg(t, name):
     _require_gpu(t, name)
-    if t.dtype not in (torch.float32, torch.float16):
-        raise TypeError("%s must be float32 or float16, got %s" % (name, t.dtype))
+    if t.dtype not in _DTYPE_CODE:
+        raise TypeError("%s must be float32, float16 or bfloat16, got %s" % (name, t.dtype))
     return t if t.is_contiguous() else t.contiguous()
 
 
@@ -91,7 +95,7 @@ def make_desc(spec, e, tstride=0, wstride=0, mstride=0):
     """PeaDesc for `spec` on a tensor shaped like e.  Descriptors are immutable once built (the library takes them as
     const), so they are memoised: filling and validating one costs more host time than the launch it describes."""
     key = (spec.ndim, tuple(spec.offsets), tuple(spec.lam), spec.border, spec.norm, spec.eps, spec.act, tuple(e.shape),
-           e.dtype == torch.float16, int(tstride), int(wstride), int(mstride))
+           e.dtype, int(tstride), int(wstride), int(mstride))
     d = _DESC_CACHE.get(key)
     if d is not None:
         return d
@@ -132,7 +136,7 @@ def _build_desc(spec, e, tstride, wstride, mstride):
     d.dims[:] = dims
     d.K = spec.K
     d.border, d.norm, d.eps = spec.border, spec.norm, spec.eps
-    d.dtype = _lib.F16 if e.dtype == torch.float16 else _lib.F32
+    d.dtype = _DTYPE_CODE[e.dtype]
     d.flags = spec.act
     for i, o in enumerate(spec.offsets):
         if spec.border == _lib.BORDER_CIRCULAR:  # torch.roll is modular: fold into (-dim, dim)

@@ -30,7 +30,7 @@ int validate(const PeaDesc* d) {
     if (d->dims[a] < 1) return PEA_E_DESC;
   if (d->ndim == 2 && d->dims[0] != 1) return PEA_E_DESC;
   if (d->border != PEA_BORDER_CIRCULAR && d->border != PEA_BORDER_CROP_ZERO && d->border != PEA_BORDER_REPLICATE) return PEA_E_DESC;
-  if (d->dtype != PEA_F32 && d->dtype != PEA_F16) return PEA_E_DESC;
+  if (d->dtype != PEA_F32 && d->dtype != PEA_F16 && d->dtype != PEA_BF16) return PEA_E_DESC;
   if (d->norm < PEA_NORM_BX || d->norm > PEA_NORM_FULL) return PEA_E_DESC;
   if (!(d->eps > 0.f)) return PEA_E_DESC;
   if (d->target_bstride < 0 || d->weight_bstride < 0 || d->mask_bstride < 0) return PEA_E_DESC;
@@ -161,7 +161,7 @@ int pea_affinity_infer(const PeaDesc* desc, const void* e, const void* e_other, 
   const int rc = validate(desc);
   if (rc) return rc;
   if (!e || !affs) return PEA_E_NULL;
-  const size_t es = desc->dtype == PEA_F16 ? 2 : 4;
+  const size_t es = dtype_bytes(desc->dtype);
   if (misaligned(e, es) || misaligned(e_other, es) || misaligned(affs, 4)) return PEA_E_ALIGN;
   const KParams P = make_params(desc);
   FwdArgs A = {};
@@ -175,7 +175,7 @@ int pea_affinity_fwd_ex(const PeaDesc* desc, const void* e, const void* e_other,
   int rc = validate(desc);
   if (rc) return rc;
   if (!e || !target || !weight || !loss_out) return PEA_E_NULL;
-  const size_t es = desc->dtype == PEA_F16 ? 2 : 4;
+  const size_t es = dtype_bytes(desc->dtype);
   if (misaligned(e, es) || misaligned(e_other, es) || misaligned(affs, 4) || misaligned(g_out, 4) ||
       misaligned(target, 4) || misaligned(weight, 4) || misaligned(loss_out, 4) || misaligned(workspace, 8) ||
       misaligned(inv_norm_out, 4))
@@ -276,7 +276,7 @@ int pea_inv_norm(const PeaDesc* desc, const void* e, float* inv_norm_out, void* 
   const int rc = validate(desc);
   if (rc) return rc;
   if (!e || !inv_norm_out) return PEA_E_NULL;
-  if (misaligned(e, desc->dtype == PEA_F16 ? 2 : 4) || misaligned(inv_norm_out, 4)) return PEA_E_ALIGN;
+  if (misaligned(e, dtype_bytes(desc->dtype)) || misaligned(inv_norm_out, 4)) return PEA_E_ALIGN;
   const KParams P = make_params(desc);
   launch_inv_norm(P, desc->dtype, e, inv_norm_out, (hipStream_t)stream);
   return hip_rc();
@@ -293,7 +293,7 @@ int pea_affinity_bwd_ex2(const PeaDesc* desc, const void* e, const void* e_other
   if (rc) return rc;
   if (!e || !g || (!de && !de_other)) return PEA_E_NULL;
   if (de_other && !e_other) return PEA_E_NULL;
-  const size_t es = desc->dtype == PEA_F16 ? 2 : 4;
+  const size_t es = dtype_bytes(desc->dtype);
   if (misaligned(e, es) || misaligned(e_other, es) || misaligned(de, es) || misaligned(de_other, es) ||
       misaligned(g, 4) || misaligned(dloss, 4) || misaligned(inv_norm, 4) || misaligned(affs, 4))
     return PEA_E_ALIGN;
@@ -312,7 +312,7 @@ int pea_affinity_bwd_ex2(const PeaDesc* desc, const void* e, const void* e_other
     if (dt == PEA_F32 && zstep && zmarch_bwd(P, (const float*)e, inv_norm, g, affs, dloss, (float*)de, s)) return hip_rc();
     if (dt == PEA_F32 && zstep && box_bwd(P, (const float*)e, inv_norm, g, dloss, (float*)de, s)) return hip_rc();
     if (dt == PEA_F32 && xdma_bwd_self(P, (const float*)e, inv_norm, g, affs, dloss, (float*)de, s)) return hip_rc();
-    if (dt == PEA_F16 && xdma_bwd_self_h(P, e, inv_norm, g, affs, dloss, de, s)) return hip_rc();
+    if (dt != PEA_F32 && xdma_bwd_self_h(P, dt, e, inv_norm, g, affs, dloss, de, s)) return hip_rc();
     if (dt == PEA_F32 && box_bwd(P, (const float*)e, inv_norm, g, dloss, (float*)de, s)) return hip_rc();
     return run_bwd(P, dt, 3, e, e, e, g, dloss, de, s);
   }
@@ -320,8 +320,8 @@ int pea_affinity_bwd_ex2(const PeaDesc* desc, const void* e, const void* e_other
   if (de && !de_other && dt == PEA_F32 &&
       xdma_bwd_other(P, (const float*)e, (const float*)e_other, inv_norm, g, affs, dloss, (float*)de, accumulate, s))
     return hip_rc();  // detached second operand: the role-A cross kernel (inv_norm = the two planes pea_affinity_fwd_ex wrote)
-  if (de && !de_other && dt == PEA_F16 && inv_norm && !accumulate && env().bwd_xdma && !env().force_direct &&
-      xdma_h_bwd_other(P, e, e_other, inv_norm, g, affs, dloss, de, s))
+  if (de && !de_other && dt != PEA_F32 && inv_norm && !accumulate && env().bwd_xdma && !env().force_direct &&
+      xdma_h_bwd_other(P, dt, e, e_other, inv_norm, g, affs, dloss, de, s))
     return hip_rc();
   if (accumulate) return PEA_E_UNSUPPORTED;
   if (de) {
@@ -378,7 +378,7 @@ int pea_affinity_fwd_bwd_labels_ex(const PeaDesc* desc, const void* e, const voi
   int rc = validate(desc);
   if (rc) return rc;
   if (!e || !labels || !wtab || !loss_out || !de) return PEA_E_NULL;
-  const size_t es = desc->dtype == PEA_F16 ? 2 : 4;
+  const size_t es = dtype_bytes(desc->dtype);
   if (misaligned(e, es) || misaligned(e_other, es) || misaligned(de, es) || misaligned(affs, 4) || misaligned(labels, 4) ||
       misaligned(wtab, 4) || misaligned(loss_out, 4) || misaligned(dloss, 4) || misaligned(workspace, 8) || misaligned(scratch, 16))
     return PEA_E_ALIGN;
@@ -442,7 +442,7 @@ int pea_affinity_fwd_bwd_labels_dual(const PeaDesc* desc, const PeaDesc* desc_cr
       memcmp(desc->offsets, desc_cross->offsets, sizeof(desc->offsets)) != 0 || desc->flags != desc_cross->flags ||
       desc->eps != desc_cross->eps)
     return PEA_E_DESC;  // the two losses may differ in lambda and in the normaliser only
-  const size_t es = desc->dtype == PEA_F16 ? 2 : 4;
+  const size_t es = dtype_bytes(desc->dtype);
   if (misaligned(e, es) || misaligned(ema, es) || misaligned(de, es) || misaligned(affs, 4) || misaligned(labels, 4) ||
       misaligned(wtab, 4) || misaligned(loss_out, 4) || misaligned(loss_cross_out, 4) || misaligned(dloss, 4) ||
       misaligned(dloss_cross, 4) || misaligned(workspace, 8))
@@ -474,7 +474,7 @@ int pea_affinity_bwd_dual_ex(const PeaDesc* desc, const void* e, const void* ema
   const int rc = validate(desc);
   if (rc) return rc;
   if (!e || !ema || !g || !g_cross || !de) return PEA_E_NULL;
-  const size_t es = desc->dtype == PEA_F16 ? 2 : 4;
+  const size_t es = dtype_bytes(desc->dtype);
   if (misaligned(e, es) || misaligned(ema, es) || misaligned(de, es) || misaligned(g, 4) || misaligned(g_cross, 4) ||
       misaligned(dloss, 4) || misaligned(dloss_cross, 4) || misaligned(inv_norm, 4) || misaligned(inv_norm_other, 4))
     return PEA_E_ALIGN;

@@ -4,6 +4,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <type_traits>
+
 #include "../../include/pea.h"
 
 namespace pea {
@@ -36,9 +38,17 @@ template <>
 __device__ __forceinline__ float ld<float>(const float* p, size_t i) { return p[i]; }
 template <>
 __device__ __forceinline__ float ld<__half>(const __half* p, size_t i) { return __half2float(p[i]); }
+template <>
+__device__ __forceinline__ float ld<__bf16>(const __bf16* p, size_t i) { return (float)p[i]; }  // a 16-bit shift
 
 __device__ __forceinline__ void st(float* p, size_t i, float v) { p[i] = v; }
 __device__ __forceinline__ void st(__half* p, size_t i, float v) { p[i] = __float2half(v); }
+// a plain cast: v_cvt_pk_bf16_f32, round to nearest even with NaN kept (the integer-rounding trick turns some NaNs into 0 / inf)
+__device__ __forceinline__ void st(__bf16* p, size_t i, float v) { p[i] = (__bf16)v; }
+
+// the storage types of the embedding (PEA_F32 / PEA_F16 / PEA_BF16)
+template <typename T>
+constexpr bool is_emb_t = std::is_same<T, float>::value || std::is_same<T, __half>::value || std::is_same<T, __bf16>::value;
 
 // XCD-aware remap: hardware deals consecutive workgroup ids round-robin over the 8 XCDs, so
 // id % 8 labels the XCD group.  Give group g the contiguous logical tiles [g*tpx, (g+1)*tpx).

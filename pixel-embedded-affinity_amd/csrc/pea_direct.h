@@ -279,15 +279,15 @@ __global__ __launch_bounds__(kBlock) void k_bwd_direct_anyd(const KParams P, con
       }
     }
     proj = fmaf(ld(xb, c * S + p) * inv_p, Gc, proj);
-    if (sizeof(T) == 4) st(db, c * S + p, Gc);
-    // (f16 storage: G is recomputed in the last sweep instead of being rounded through dx)
+    if (std::is_same<T, float>::value) st(db, c * S + p, Gc);
+    // (16-bit storage: G is recomputed in the last sweep instead of being rounded through dx)
   }
   if (nrm < P.eps) proj = 0.f;  // clamp_min branch of F.normalize: d ehat / d e = I / eps
   const float sc = dl * inv_p;
   // (3) projection
   for (int c = 0; c < D; ++c) {
     float Gc;
-    if (sizeof(T) == 4) {
+    if (std::is_same<T, float>::value) {
       Gc = ld(db, c * S + p);
     } else {  // recompute (no f32 scratch per pixel): one more pass over the neighbours
       Gc = 0.f;

@@ -54,6 +54,8 @@ void env_reload();          // pea_reload_env(): tests that change a switch call
 unsigned env_generation();  // = env().gen; a new one with every env_reload(): memoised plans that baked a switch in (PEA_ZBLK_*, ..) are dropped
 
 inline bool misaligned(const void* p, size_t a) { return ((uintptr_t)p & (a - 1)) != 0; }
+// bytes per element of the embedding's storage dtype (validate() admits PEA_F32, PEA_F16 and PEA_BF16 only)
+inline size_t dtype_bytes(int dtype) { return dtype == PEA_F32 ? 4 : 2; }
 int& g_pending_error();  // per thread: an error met while preparing a launch (allow_lds), reported by the next hip_rc()
 inline int hip_rc() {
   int& pe = g_pending_error();
@@ -113,7 +115,7 @@ void launch_loss_state_init(LossState* st, int n, hipStream_t s);
 
 // Arguments of a forward launch, one struct for every family.
 struct FwdArgs {
-  const void* e;        // [B, D, S]  f32 / f16 (dtype)
+  const void* e;        // [B, D, S]  f32 / f16 / bf16 (dtype)
   const void* eo;       // second operand or == e
   const float* t;       // training only
   const float* w;
@@ -123,7 +125,7 @@ struct FwdArgs {
   LossState* st;        // training only
   float* loss_out;      // training only: [1 + K]
   float* inv_out;       // nullable: signed 1 / norm plane(s)
-  int dtype;            // PEA_F32 / PEA_F16
+  int dtype;            // PEA_F32 / PEA_F16 / PEA_BF16
   bool train;
 };
 // Each returns true if it launched (the caller then launches the loss finish).
@@ -149,13 +151,13 @@ bool box_bwd(const KParams& P, const float* x, const float* inv, const float* g,
 // backward: roles bit 0 = A (x is the first operand, neighbours nbA), bit 1 = B (x is the second operand, neighbours nbB)
 bool xdma_bwd_self(const KParams& P, const float* x, const float* inv, const float* g, const float* affs, const float* dl, float* dx,
                    hipStream_t s);  // affs: the raw cosine map or null
-bool xdma_bwd_self_h(const KParams& P, const void* x, const float* inv, const float* g, const float* affs, const float* dl, void* dx,
-                     hipStream_t s);  // f16 storage (pea_k_xdma_h.hip)
-bool xdma_h_fwd_self(const KParams& P, const FwdArgs& A, hipStream_t s);  // f16 storage forward / inference (pea_k_xdma_h.hip)
-// f16 storage, the cross loss with a detached second operand (pea_k_xdma_h.hip): forward (two 1 / norm planes) and the role-A backward
+bool xdma_bwd_self_h(const KParams& P, int dtype, const void* x, const float* inv, const float* g, const float* affs, const float* dl,
+                     void* dx, hipStream_t s);  // f16 / bf16 storage (pea_k_xdma_h.hip)
+bool xdma_h_fwd_self(const KParams& P, const FwdArgs& A, hipStream_t s);  // f16 / bf16 storage forward / inference (pea_k_xdma_h.hip)
+// f16 / bf16 storage, the cross loss with a detached second operand (pea_k_xdma_h.hip): forward (two 1 / norm planes) and the role-A backward
 // (projection first: needs the cross loss' raw map)
 bool xdma_h_fwd_other(const KParams& P, const FwdArgs& A, hipStream_t s);
-bool xdma_h_bwd_other(const KParams& P, const void* e, const void* e_other, const float* inv2, const float* g, const float* affs,
+bool xdma_h_bwd_other(const KParams& P, int dtype, const void* e, const void* e_other, const float* inv2, const float* g, const float* affs,
                       const float* dl, void* de, hipStream_t s);
 // f16 storage backward with producer / consumer waves (pea_k_xdma_hq.hip; D = 32 / 64, small crosses, PEA_H16_HW=2)
 bool xdma_hq_bwd_self(const KParams& P, const void* x, const float* inv, const float* g, const float* affs, const float* dl, void* dx,

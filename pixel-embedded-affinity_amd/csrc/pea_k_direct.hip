@@ -170,12 +170,15 @@ int bwd_direct(const KParams& P, int roles, const void* x, const void* nbA, cons
 
 void direct_fwd(const KParams& P, const FwdArgs& A, hipStream_t s) {
   if (A.dtype == PEA_F16) { if (A.train) fwd_direct<__half, true>(P, A, s); else fwd_direct<__half, false>(P, A, s); }
+  else if (A.dtype == PEA_BF16) { if (A.train) fwd_direct<__bf16, true>(P, A, s); else fwd_direct<__bf16, false>(P, A, s); }
   else { if (A.train) fwd_direct<float, true>(P, A, s); else fwd_direct<float, false>(P, A, s); }
 }
 
 int direct_bwd(const KParams& P, int dtype, int roles, const void* x, const void* nbA, const void* nbB, const float* g,
                const float* dl, void* dx, hipStream_t s) {
-  return dtype == PEA_F16 ? bwd_direct<__half>(P, roles, x, nbA, nbB, g, dl, dx, s) : bwd_direct<float>(P, roles, x, nbA, nbB, g, dl, dx, s);
+  if (dtype == PEA_F16) return bwd_direct<__half>(P, roles, x, nbA, nbB, g, dl, dx, s);
+  if (dtype == PEA_BF16) return bwd_direct<__bf16>(P, roles, x, nbA, nbB, g, dl, dx, s);
+  return bwd_direct<float>(P, roles, x, nbA, nbB, g, dl, dx, s);
 }
 
 }  // namespace pea
@@ -188,7 +191,7 @@ __global__ __launch_bounds__(256) void k_scale_inplace(T* __restrict__ buf, size
   const float sc = scale[0];
   if (sc == 1.0f) return;  // the common loss.backward() case: nothing to do, nothing touched
   const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
-  if (sizeof(T) == 4) {
+  if (std::is_same<T, float>::value) {
     if (i < n4) {
       f4 v = ((f4*)buf)[i];
       v.x *= sc; v.y *= sc; v.z *= sc; v.w *= sc;
@@ -313,7 +316,7 @@ __global__ __launch_bounds__(256) void k_scale_multi(const ScaleMulti M, const f
   T* buf = (T*)M.buf[blockIdx.y];
   const size_t n = (size_t)M.n[blockIdx.y];
   const size_t stride = (size_t)gridDim.x * 256, t = (size_t)blockIdx.x * 256 + threadIdx.x;
-  if (sizeof(T) == 4 && (((uintptr_t)buf) & 15) == 0) {
+  if (std::is_same<T, float>::value && (((uintptr_t)buf) & 15) == 0) {
     const size_t n4 = n / 4;
     for (size_t i = t; i < n4; i += stride) {
       f4 v = ((f4*)buf)[i];
@@ -332,7 +335,7 @@ extern "C" {
 
 int pea_scale_inplace(void* buf, int dtype, size_t n, const float* scale, void* stream) {
   if (!buf || !scale) return PEA_E_NULL;
-  if (dtype != PEA_F32 && dtype != PEA_F16) return PEA_E_DESC;
+  if (dtype != PEA_F32 && dtype != PEA_F16 && dtype != PEA_BF16) return PEA_E_DESC;
   if (misaligned(buf, dtype == PEA_F32 ? 16 : 2) || misaligned(scale, 4)) return PEA_E_ALIGN;
   if (n == 0) return PEA_OK;
   hipStream_t s = (hipStream_t)stream;
@@ -341,7 +344,8 @@ int pea_scale_inplace(void* buf, int dtype, size_t n, const float* scale, void* 
   const size_t blocks = (items + 255) / 256;
   if (blocks > 0x7fffffffULL) return PEA_E_UNSUPPORTED;
   if (dtype == PEA_F32) hipLaunchKernelGGL(k_scale_inplace<float>, dim3((unsigned)blocks), dim3(256), 0, s, (float*)buf, n4, n, scale);
-  else hipLaunchKernelGGL(k_scale_inplace<__half>, dim3((unsigned)blocks), dim3(256), 0, s, (__half*)buf, n4, n, scale);
+  else if (dtype == PEA_F16) hipLaunchKernelGGL(k_scale_inplace<__half>, dim3((unsigned)blocks), dim3(256), 0, s, (__half*)buf, n4, n, scale);
+  else hipLaunchKernelGGL(k_scale_inplace<__bf16>, dim3((unsigned)blocks), dim3(256), 0, s, (__bf16*)buf, n4, n, scale);
   return hip_rc();
 }
 
@@ -398,7 +402,7 @@ int pea_stitch_finalize(float* out_affs, const float* weight_map, int C, size_t 
 
 int pea_scale_inplace_multi(void* const* bufs, const size_t* counts, int nbuf, int dtype, const float* scale, void* stream) {
   if (!bufs || !counts || !scale) return PEA_E_NULL;
-  if (nbuf < 1 || nbuf > 8 || (dtype != PEA_F32 && dtype != PEA_F16)) return PEA_E_DESC;
+  if (nbuf < 1 || nbuf > 8 || (dtype != PEA_F32 && dtype != PEA_F16 && dtype != PEA_BF16)) return PEA_E_DESC;
   ScaleMulti M = {};
   size_t nmax = 0;
   for (int i = 0; i < nbuf; ++i) {
@@ -412,7 +416,8 @@ int pea_scale_inplace_multi(void* const* bufs, const size_t* counts, int nbuf, i
   if (nmax == 0) return PEA_OK;
   const unsigned gx = (unsigned)std::min<size_t>((nmax / 4 + 255) / 256 + 1, 512);  // grid-stride: a fixed, small grid
   if (dtype == PEA_F32) hipLaunchKernelGGL(k_scale_multi<float>, dim3(gx, (unsigned)nbuf), dim3(256), 0, (hipStream_t)stream, M, scale);
-  else hipLaunchKernelGGL(k_scale_multi<__half>, dim3(gx, (unsigned)nbuf), dim3(256), 0, (hipStream_t)stream, M, scale);
+  else if (dtype == PEA_F16) hipLaunchKernelGGL(k_scale_multi<__half>, dim3(gx, (unsigned)nbuf), dim3(256), 0, (hipStream_t)stream, M, scale);
+  else hipLaunchKernelGGL(k_scale_multi<__bf16>, dim3(gx, (unsigned)nbuf), dim3(256), 0, (hipStream_t)stream, M, scale);
   return hip_rc();
 }
 

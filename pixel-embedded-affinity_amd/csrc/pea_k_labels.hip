@@ -89,6 +89,8 @@ bool labels_step(const KParams& P, int dtype, const void* e, const void* e_other
   }
   if (dtype == PEA_F16) {
     if (P.D == 16) PEA_LAB(__half, 16) else PEA_LAB(__half, 32)
+  } else if (dtype == PEA_BF16) {
+    if (P.D == 16) PEA_LAB(__bf16, 16) else PEA_LAB(__bf16, 32)
   } else {
     if (P.D == 16) PEA_LAB(float, 16) else PEA_LAB(float, 32)
   }
@@ -100,8 +102,9 @@ bool labels_step_dual(const KParams& P, const KParams& P2, int dtype, const void
                       const float* dl2, void* de, hipStream_t s) {
   if ((P.D != 16 && P.D != 32) || env().force_direct) return false;
 #define PEA_LD(T_, D_) try_fused_labels_dual<T_, D_>(P, P2, (const T_*)e, (const T_*)ema, labels, wtab, lflags, affs, st, st2, dl, dl2, (T_*)de, s)
-  if (P.D == 16) return dtype == PEA_F16 ? PEA_LD(__half, 16) : PEA_LD(float, 16);
-  return dtype == PEA_F16 ? PEA_LD(__half, 32) : PEA_LD(float, 32);
+  if (dtype == PEA_F16) return P.D == 16 ? PEA_LD(__half, 16) : PEA_LD(__half, 32);
+  if (dtype == PEA_BF16) return P.D == 16 ? PEA_LD(__bf16, 16) : PEA_LD(__bf16, 32);
+  return P.D == 16 ? PEA_LD(float, 16) : PEA_LD(float, 32);
 #undef PEA_LD
 }
 

@@ -169,6 +169,7 @@ bool tiled_fwd(const KParams& P, const FwdArgs& A, hipStream_t s, bool* wrote_in
   if (env().force_direct) return false;
   const FwdT T_ = {A.e, A.eo, A.t, A.w, A.m, A.affs, A.gout, A.st, A.inv_out};
   if (A.dtype == PEA_F16) return A.train ? fwd_any<__half, true>(P, T_, s, wrote_inv) : fwd_any<__half, false>(P, T_, s, wrote_inv);
+  if (A.dtype == PEA_BF16) return A.train ? fwd_any<__bf16, true>(P, T_, s, wrote_inv) : fwd_any<__bf16, false>(P, T_, s, wrote_inv);
   return A.train ? fwd_any<float, true>(P, T_, s, wrote_inv) : fwd_any<float, false>(P, T_, s, wrote_inv);
 }
 
@@ -177,6 +178,8 @@ bool tiled_bwd(const KParams& P, int dtype, int roles, const void* x, const void
   if (env().force_direct || (P.D != 16 && P.D != 32)) return false;
   if (dtype == PEA_F16)
     return P.D == 16 ? bwd_roles<__half, 16>(P, roles, x, nbA, nbB, g, dl, dx, s) : bwd_roles<__half, 32>(P, roles, x, nbA, nbB, g, dl, dx, s);
+  if (dtype == PEA_BF16)
+    return P.D == 16 ? bwd_roles<__bf16, 16>(P, roles, x, nbA, nbB, g, dl, dx, s) : bwd_roles<__bf16, 32>(P, roles, x, nbA, nbB, g, dl, dx, s);
   return P.D == 16 ? bwd_roles<float, 16>(P, roles, x, nbA, nbB, g, dl, dx, s) : bwd_roles<float, 32>(P, roles, x, nbA, nbB, g, dl, dx, s);
 }
 

@@ -88,7 +88,7 @@ bool bwd_self(const KParams& P, const float* x, const float* inv, const float* g
 //  tiled kernel moves fewer bytes than six ring planes do.)
 bool xdma_fwd_self(const KParams& P, const FwdArgs& A, hipStream_t s) {
   if (!env().fwd_xdma || env().force_direct || A.eo != A.e) return false;
-  if (A.dtype == PEA_F16) {  // f16 storage: pea_xdma_h16.h
+  if (A.dtype == PEA_F16 || A.dtype == PEA_BF16) {  // 16-bit storage: pea_xdma_h16.h
     return xdma_h_fwd_self(P, A, s);  // pea_k_xdma_h.hip
   }
   if (!A.train) {
@@ -164,7 +164,7 @@ static bool fwd_other_wide(const KParams& P, const FwdArgs& A, hipStream_t s) {
 
 bool xdma_fwd_other(const KParams& P, const FwdArgs& A, hipStream_t s) {
   if (!env().fwd_xdma || env().force_direct || !A.train || !A.inv_out) return false;
-  if (A.dtype == PEA_F16) return xdma_h_fwd_other(P, A, s);  // pea_k_xdma_h.hip
+  if (A.dtype == PEA_F16 || A.dtype == PEA_BF16) return xdma_h_fwd_other(P, A, s);  // pea_k_xdma_h.hip
   if (A.dtype != PEA_F32) return false;
   if (P.D != 16 && P.D != 32 && P.D != 64) return false;
   const float *e = (const float*)A.e, *e_other = (const float*)A.eo;
@@ -311,6 +311,7 @@ bool xdma_bwd_dual(const KParams& P, const float* e, const float* ema, const flo
 void launch_inv_norm(const KParams& P, int dtype, const void* e, float* inv, hipStream_t s) {
   const dim3 grid((unsigned)(P.tiles_per_xcd * kXcd)), blk(kBlock);
   if (dtype == PEA_F16) hipLaunchKernelGGL(k_inv_norm<__half>, grid, blk, 0, s, P, (const __half*)e, inv);
+  else if (dtype == PEA_BF16) hipLaunchKernelGGL(k_inv_norm<__bf16>, grid, blk, 0, s, P, (const __bf16*)e, inv);
   else hipLaunchKernelGGL(k_inv_norm<float>, grid, blk, 0, s, P, (const float*)e, inv);
 }
 
@@ -320,10 +321,10 @@ int xdma_cross_supported(const KParams& P, int dtype, int mode) {
   if ((P.D != 16 && P.D != 32 && P.D != 64) || env().force_direct) return 0;
   if (!(mode ? env().bwd_xdma : env().fwd_xdma)) return 0;
   XPlan X;
-  if (dtype == PEA_F16) {  // pea_xdma_h16.h: 2D self loss
+  if (dtype == PEA_F16 || dtype == PEA_BF16) {  // pea_xdma_h16.h: 2D self loss (bf16: pea_k_xdma_h.hip builds the same scope)
     if (P.X % 8 || P.Z != 1) return 0;
     if (mode == 2 || mode == 4) {  // the cross loss with a detached second operand: forward + projection-first role-A backward
-      if (!env().h16_hw || !env().bwd_pf || !env().fwd_xdma || (P.flags & kActMask) || P.K > kXP) return 0;
+      if ((dtype == PEA_F16 && !env().h16_hw) || !env().bwd_pf || !env().fwd_xdma || (P.flags & kActMask) || P.K > kXP) return 0;
       if (!plan(P, kXdmaPSUF, 1, &X) || X.C.nfz > 0) return 0;
       return (plan(P, kXdmaPSUF, 2, &X) && X.C.npz == 0 && X.C.npx <= kXP && X.C.npy <= kXP) ? 1 : 0;
     }
@@ -332,6 +333,7 @@ int xdma_cross_supported(const KParams& P, int dtype, int mode) {
     const int xp = P.D > 32 ? 8 : kXP;
     return (X.C.npx <= xp && X.C.npy <= xp) ? 1 : 0;
   }
+  if (dtype != PEA_F32) return 0;
   if (mode == 2 || mode == 4) {  // 4: does the backward of the cross loss with a detached second operand READ the raw map?
     if (!env().fwd_xdma) return 0;
     if (P.D == 32 || P.D == 64) {

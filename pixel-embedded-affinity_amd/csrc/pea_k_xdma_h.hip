@@ -1,4 +1,4 @@
-// pea_k_xdma_h.hip -- launchers of the LDS-DMA cross kernels for f16 storage (pea_xdma_h16.h).  One translation unit of libpea_hip.so
+// pea_k_xdma_h.hip -- launchers of the LDS-DMA cross kernels for 16-bit storage, f16 and bf16 (pea_xdma_h16.h).  One translation unit of libpea_hip.so
 // (pea_host.h); split from pea_k_xdma.hip for compile time (the f32 projection-first backward: pea_k_xdma_pf.hip).
 #include "pea_k_xdma_plan.h"
 #include "pea_xdma_h16.h"
@@ -8,10 +8,18 @@ namespace pea {
 
 namespace {
 
-// ---- f16 storage (pea_xdma_h16.h): 2D self loss / inference, X % 8 == 0 ---------------------------------------------------
-template <int D_T, bool TRAIN>
+// bf16 storage runs one form per kernel, the one f16 runs by default: the 16-bit working buffer (PEA_H16_HW >= 1) wherever f16 has
+// it -- forward, projection-first backward, the cross loss -- and the f32 working buffer in the plain backward.  PEA_H16_HW and the
+// producer / consumer backward (PEA_H16_HW=2, pea_xdma_hq.h) select among the f16 kernels only.  (Projection-first backward in bf16,
+// B=8 x 64 x 544^2, forward + backward: 0.431 ms with the bf16 working buffer -- shift / and unpack in front of the FMAs -- against
+// 0.470 ms with the f32 one; the bf16 step is 1.04x the f16 step without the producer / consumer kernel: profiles/bf16_ab.json.)
+template <typename T>
+constexpr bool kBf16 = std::is_same<T, __bf16>::value;
+
+// ---- 16-bit storage (pea_xdma_h16.h): 2D self loss / inference, X % 8 == 0 ------------------------------------------------
+template <typename T, int D_T, bool TRAIN>
 bool fwd_self_h(const KParams& P, const FwdArgs& A, hipStream_t s) {
-  const __half* e = (const __half*)A.e;
+  const T* e = (const T*)A.e;
   if (P.X % 8 || P.Z != 1 || misaligned(e, 16) || misaligned(A.t, 16) || misaligned(A.w, 16) || misaligned(A.affs, 16) ||
       misaligned(A.gout, 16) || misaligned(A.m, 4) || misaligned(A.inv_out, 4))
     return false;
@@ -20,13 +28,13 @@ bool fwd_self_h(const KParams& P, const FwdArgs& A, hipStream_t s) {
   if (!plan(P, kXdmaPSUF, 1, &X) || X.C.nfz > 0 || P.K > kXP) return false;
   const size_t lds = (size_t)5 * kXdmaPSUF * 256;  // two f32 working planes + six half-size ring planes
   const dim3 grid((unsigned)(X.C.tiles_per_xcd * kXcd)), blk(kXdmaTH * kXdmaTW);
-  if (env().h16_hw) {  // half-precision working buffer, v_dot2 gather: 48 VGPRs and 30 KB -- four workgroups per CU (five: 173 against 168 us)
+  if (kBf16<T> || env().h16_hw) {  // half-precision working buffer, v_dot2 gather: 48 VGPRs and 30 KB -- four workgroups per CU (five: 173 against 168 us)
     const size_t ldsh = (size_t)4 * kXdmaPSUF * 256;
     // (D = 64 with at most eight offsets -- BASELINE configs[4] -- walks eight slots instead of ten)
 #define PEA_HF(CROP_, NXP_)                                                                                          \
   {                                                                                                                  \
-    constexpr auto kern = k_fwd_xdma_h<D_T, kXdmaTH, kXdmaTW, kXdmaPSUF, CROP_, TRAIN, 8, true, NXP_>;               \
-    PEA_LAUNCH(kern, grid, blk, ldsh, s, P, X.C, e, A.t, A.w, A.m, A.affs, A.gout, A.st, A.inv_out, (const __half*)nullptr, (float*)nullptr) \
+    constexpr auto kern = k_fwd_xdma_h<D_T, kXdmaTH, kXdmaTW, kXdmaPSUF, CROP_, TRAIN, 8, true, NXP_, false, T>;     \
+    PEA_LAUNCH(kern, grid, blk, ldsh, s, P, X.C, e, A.t, A.w, A.m, A.affs, A.gout, A.st, A.inv_out, (const T*)nullptr, (float*)nullptr) \
   }
     const bool crop = P.border != PEA_BORDER_CIRCULAR;
     if (D_T == 64 && X.C.nf <= 8) { if (crop) PEA_HF(true, (D_T == 64 ? 8 : kXP)) else PEA_HF(false, (D_T == 64 ? 8 : kXP)) }
@@ -34,18 +42,20 @@ bool fwd_self_h(const KParams& P, const FwdArgs& A, hipStream_t s) {
 #undef PEA_HF
     return true;
   }
-  if (P.border != PEA_BORDER_CIRCULAR) {
-    constexpr auto kern = k_fwd_xdma_h<D_T, kXdmaTH, kXdmaTW, kXdmaPSUF, true, TRAIN, 6>;
-    PEA_LAUNCH(kern, grid, blk, lds, s, P, X.C, e, A.t, A.w, A.m, A.affs, A.gout, A.st, A.inv_out, (const __half*)nullptr, (float*)nullptr)
-  } else {
-    constexpr auto kern = k_fwd_xdma_h<D_T, kXdmaTH, kXdmaTW, kXdmaPSUF, false, TRAIN, 6>;
-    PEA_LAUNCH(kern, grid, blk, lds, s, P, X.C, e, A.t, A.w, A.m, A.affs, A.gout, A.st, A.inv_out, (const __half*)nullptr, (float*)nullptr)
+  if constexpr (!kBf16<T>) {
+    if (P.border != PEA_BORDER_CIRCULAR) {
+      constexpr auto kern = k_fwd_xdma_h<D_T, kXdmaTH, kXdmaTW, kXdmaPSUF, true, TRAIN, 6>;
+      PEA_LAUNCH(kern, grid, blk, lds, s, P, X.C, e, A.t, A.w, A.m, A.affs, A.gout, A.st, A.inv_out, (const __half*)nullptr, (float*)nullptr)
+    } else {
+      constexpr auto kern = k_fwd_xdma_h<D_T, kXdmaTH, kXdmaTW, kXdmaPSUF, false, TRAIN, 6>;
+      PEA_LAUNCH(kern, grid, blk, lds, s, P, X.C, e, A.t, A.w, A.m, A.affs, A.gout, A.st, A.inv_out, (const __half*)nullptr, (float*)nullptr)
+    }
   }
   return true;
 }
 
-template <int D_T>
-bool bwd_self_h(const KParams& P, const __half* x, const float* inv, const float* g, const float* affs, const float* dl, __half* dx,
+template <typename T, int D_T>
+bool bwd_self_h(const KParams& P, const T* x, const float* inv, const float* g, const float* affs, const float* dl, T* dx,
                 hipStream_t s) {
   if (P.X % 8 || P.Z != 1 || misaligned(x, 16) || misaligned(inv, 16) || misaligned(g, 4) || misaligned(dx, 2) || misaligned(affs, 4))
     return false;
@@ -63,15 +73,15 @@ bool bwd_self_h(const KParams& P, const __half* x, const float* inv, const float
       const bool few = D_T == 64 && X.C.npx <= 8 && X.C.npy <= 8;
 #define PEA_HPF(CROP_, PSU_, WPE_)                                                                   \
   {                                                                                                  \
-    if (env().h16_hw && few) {                                                                       \
-      constexpr auto kern = k_bwd_xdma_h<D_T, kXdmaTH, kXdmaTW, PSU_, CROP_, XPS, true, WPE_, true>;  \
-      PEA_LAUNCH(kern, grid, blk, (size_t)5 * PSU_ * 256, s, P, X.C, x, inv, g, affs, dl, dx, (const __half*)nullptr, (const float*)nullptr) \
-    } else if (env().h16_hw) {                                                                       \
-      constexpr auto kern = k_bwd_xdma_h<D_T, kXdmaTH, kXdmaTW, PSU_, CROP_, kXP, true, WPE_, true>;  \
-      PEA_LAUNCH(kern, grid, blk, (size_t)5 * PSU_ * 256, s, P, X.C, x, inv, g, affs, dl, dx, (const __half*)nullptr, (const float*)nullptr) \
-    } else {                                                                                         \
+    if ((kBf16<T> || env().h16_hw) && few) {                                                         \
+      constexpr auto kern = k_bwd_xdma_h<D_T, kXdmaTH, kXdmaTW, PSU_, CROP_, XPS, true, WPE_, true, false, T>;  \
+      PEA_LAUNCH(kern, grid, blk, (size_t)5 * PSU_ * 256, s, P, X.C, x, inv, g, affs, dl, dx, (const T*)nullptr, (const float*)nullptr) \
+    } else if (kBf16<T> || env().h16_hw) {                                                           \
+      constexpr auto kern = k_bwd_xdma_h<D_T, kXdmaTH, kXdmaTW, PSU_, CROP_, kXP, true, WPE_, true, false, T>;  \
+      PEA_LAUNCH(kern, grid, blk, (size_t)5 * PSU_ * 256, s, P, X.C, x, inv, g, affs, dl, dx, (const T*)nullptr, (const float*)nullptr) \
+    } else if constexpr (!kBf16<T>) {                                                                \
       constexpr auto kern = k_bwd_xdma_h<D_T, kXdmaTH, kXdmaTW, PSU_, CROP_, kXP, true, WPE_>;        \
-      PEA_LAUNCH(kern, grid, blk, (size_t)5 * PSU_ * 256, s, P, X.C, x, inv, g, affs, dl, dx, (const __half*)nullptr, (const float*)nullptr) \
+      PEA_LAUNCH(kern, grid, blk, (size_t)5 * PSU_ * 256, s, P, X.C, x, inv, g, affs, dl, dx, (const T*)nullptr, (const float*)nullptr) \
     }                                                                                                \
   }
       // (87 VGPRs: the conversion's temporaries keep it above the 80 a third workgroup would need; small planes all the same --
@@ -89,19 +99,19 @@ bool bwd_self_h(const KParams& P, const __half* x, const float* inv, const float
   const size_t lds = (size_t)5 * kXdmaPSUH * 256;
   const dim3 grid((unsigned)(X.C.tiles_per_xcd * kXcd));
   if (crop) {
-    constexpr auto kern = k_bwd_xdma_h<D_T, kXdmaTH, kXdmaTW, kXdmaPSUH, true, XP>;
-    PEA_LAUNCH(kern, grid, blk, lds, s, P, X.C, x, inv, g, (const float*)nullptr, dl, dx, (const __half*)nullptr, (const float*)nullptr)
+    constexpr auto kern = k_bwd_xdma_h<D_T, kXdmaTH, kXdmaTW, kXdmaPSUH, true, XP, false, 4, false, false, T>;
+    PEA_LAUNCH(kern, grid, blk, lds, s, P, X.C, x, inv, g, (const float*)nullptr, dl, dx, (const T*)nullptr, (const float*)nullptr)
   } else {
-    constexpr auto kern = k_bwd_xdma_h<D_T, kXdmaTH, kXdmaTW, kXdmaPSUH, false, XP>;
-    PEA_LAUNCH(kern, grid, blk, lds, s, P, X.C, x, inv, g, (const float*)nullptr, dl, dx, (const __half*)nullptr, (const float*)nullptr)
+    constexpr auto kern = k_bwd_xdma_h<D_T, kXdmaTH, kXdmaTW, kXdmaPSUH, false, XP, false, 4, false, false, T>;
+    PEA_LAUNCH(kern, grid, blk, lds, s, P, X.C, x, inv, g, (const float*)nullptr, dl, dx, (const T*)nullptr, (const float*)nullptr)
   }
   return true;
 }
 
-// ---- f16 storage, the cross loss with a detached second operand (k_fwd_xdma_h<.., OTHER>, k_bwd_xdma_h<.., PF, HW, OTHER>): 2D, X % 8 == 0
-template <int D_T>
+// ---- 16-bit storage, the cross loss with a detached second operand (k_fwd_xdma_h<.., OTHER>, k_bwd_xdma_h<.., PF, HW, OTHER>): 2D, X % 8 == 0
+template <typename T, int D_T>
 bool fwd_other_h(const KParams& P, const FwdArgs& A, hipStream_t s) {
-  const __half *e = (const __half*)A.e, *eo = (const __half*)A.eo;
+  const T *e = (const T*)A.e, *eo = (const T*)A.eo;
   if (P.X % 8 || P.Z != 1 || misaligned(e, 16) || misaligned(eo, 16) || misaligned(A.t, 16) || misaligned(A.w, 16) || misaligned(A.affs, 16) ||
       misaligned(A.gout, 16) || misaligned(A.m, 4) || misaligned(A.inv_out, 4) || ((P.tbs | P.wbs | P.mbs) & 3))
     return false;
@@ -112,7 +122,7 @@ bool fwd_other_h(const KParams& P, const FwdArgs& A, hipStream_t s) {
   float* inv_other = A.inv_out + (size_t)P.B * P.S;
 #define PEA_HFO(CROP_, NXP_)                                                                                                  \
   {                                                                                                                          \
-    constexpr auto kern = k_fwd_xdma_h<D_T, kXdmaTH, kXdmaTW, kXdmaPSUF, CROP_, true, 6, true, NXP_, true>;                   \
+    constexpr auto kern = k_fwd_xdma_h<D_T, kXdmaTH, kXdmaTW, kXdmaPSUF, CROP_, true, 6, true, NXP_, true, T>;                \
     PEA_LAUNCH(kern, grid, blk, lds, s, P, X.C, eo, A.t, A.w, A.m, A.affs, A.gout, A.st, A.inv_out, e, inv_other)             \
   }
   const bool crop = P.border != PEA_BORDER_CIRCULAR;
@@ -122,9 +132,9 @@ bool fwd_other_h(const KParams& P, const FwdArgs& A, hipStream_t s) {
   return true;
 }
 
-template <int D_T>
-bool bwd_other_h(const KParams& P, const __half* e, const __half* eo, const float* inv2, const float* g, const float* affs, const float* dl,
-                 __half* de, hipStream_t s) {
+template <typename T, int D_T>
+bool bwd_other_h(const KParams& P, const T* e, const T* eo, const float* inv2, const float* g, const float* affs, const float* dl,
+                 T* de, hipStream_t s) {
   if (P.X % 8 || P.Z != 1 || misaligned(e, 16) || misaligned(eo, 16) || misaligned(inv2, 16) || ((size_t)P.B * P.S) % 4 ||
       misaligned(g, 4) || misaligned(affs, 4) || misaligned(de, 2))
     return false;
@@ -137,7 +147,7 @@ bool bwd_other_h(const KParams& P, const __half* e, const __half* eo, const floa
   const bool few = D_T == 64 && X.C.npx <= 8 && X.C.npy <= 8;
 #define PEA_HBO(CROP_, XP_)                                                                                                   \
   {                                                                                                                          \
-    constexpr auto kern = k_bwd_xdma_h<D_T, kXdmaTH, kXdmaTW, kXdmaPSUF, CROP_, XP_, true, 4, true, true>;                    \
+    constexpr auto kern = k_bwd_xdma_h<D_T, kXdmaTH, kXdmaTW, kXdmaPSUF, CROP_, XP_, true, 4, true, true, T>;                 \
     PEA_LAUNCH(kern, grid, blk, lds, s, P, X.C, eo, inv_other, g, affs, dl, de, e, inv2)                                      \
   }
   const bool crop = P.border != PEA_BORDER_CIRCULAR;
@@ -147,43 +157,69 @@ bool bwd_other_h(const KParams& P, const __half* e, const __half* eo, const floa
   return true;
 }
 
+template <typename T>
+bool fwd_other_t(const KParams& P, const FwdArgs& A, hipStream_t s) {
+  if (P.D == 16) return fwd_other_h<T, 16>(P, A, s);
+  if (P.D == 32) return fwd_other_h<T, 32>(P, A, s);
+  if (P.D == 64) return fwd_other_h<T, 64>(P, A, s);
+  return false;
+}
+
+template <typename T>
+bool bwd_other_t(const KParams& P, const void* e, const void* e_other, const float* inv2, const float* g, const float* affs,
+                 const float* dl, void* de, hipStream_t s) {
+  if (P.D == 16) return bwd_other_h<T, 16>(P, (const T*)e, (const T*)e_other, inv2, g, affs, dl, (T*)de, s);
+  if (P.D == 32) return bwd_other_h<T, 32>(P, (const T*)e, (const T*)e_other, inv2, g, affs, dl, (T*)de, s);
+  if (P.D == 64) return bwd_other_h<T, 64>(P, (const T*)e, (const T*)e_other, inv2, g, affs, dl, (T*)de, s);
+  return false;
+}
+
+template <typename T>
+bool fwd_self_t(const KParams& P, const FwdArgs& A, hipStream_t s) {
+  if (P.D == 16) return A.train ? fwd_self_h<T, 16, true>(P, A, s) : fwd_self_h<T, 16, false>(P, A, s);
+  if (P.D == 32) return A.train ? fwd_self_h<T, 32, true>(P, A, s) : fwd_self_h<T, 32, false>(P, A, s);
+  if (P.D == 64) return A.train ? fwd_self_h<T, 64, true>(P, A, s) : fwd_self_h<T, 64, false>(P, A, s);
+  return false;
+}
+
+template <typename T>
+bool bwd_self_t(const KParams& P, const void* x, const float* inv, const float* g, const float* affs, const float* dl, void* dx,
+                hipStream_t s) {
+  if (P.D == 16) return bwd_self_h<T, 16>(P, (const T*)x, inv, g, affs, dl, (T*)dx, s);
+  if (P.D == 32) return bwd_self_h<T, 32>(P, (const T*)x, inv, g, affs, dl, (T*)dx, s);
+  if (P.D == 64) return bwd_self_h<T, 64>(P, (const T*)x, inv, g, affs, dl, (T*)dx, s);
+  return false;
+}
+
 }  // namespace
 
 
 bool xdma_h_fwd_other(const KParams& P, const FwdArgs& A, hipStream_t s) {
+  if (A.dtype == PEA_BF16) return fwd_other_t<__bf16>(P, A, s);
   if (!env().h16_hw) return false;
-  if (P.D == 16) return fwd_other_h<16>(P, A, s);
-  if (P.D == 32) return fwd_other_h<32>(P, A, s);
-  if (P.D == 64) return fwd_other_h<64>(P, A, s);
-  return false;
+  return fwd_other_t<__half>(P, A, s);
 }
 
-bool xdma_h_bwd_other(const KParams& P, const void* e, const void* e_other, const float* inv2, const float* g, const float* affs,
+bool xdma_h_bwd_other(const KParams& P, int dtype, const void* e, const void* e_other, const float* inv2, const float* g, const float* affs,
                       const float* dl, void* de, hipStream_t s) {
-  if (!env().h16_hw || !env().bwd_pf || !affs || (P.flags & kActMask)) return false;
-  if (P.D == 16) return bwd_other_h<16>(P, (const __half*)e, (const __half*)e_other, inv2, g, affs, dl, (__half*)de, s);
-  if (P.D == 32) return bwd_other_h<32>(P, (const __half*)e, (const __half*)e_other, inv2, g, affs, dl, (__half*)de, s);
-  if (P.D == 64) return bwd_other_h<64>(P, (const __half*)e, (const __half*)e_other, inv2, g, affs, dl, (__half*)de, s);
-  return false;
+  if (!env().bwd_pf || !affs || (P.flags & kActMask)) return false;
+  if (dtype == PEA_BF16) return bwd_other_t<__bf16>(P, e, e_other, inv2, g, affs, dl, de, s);
+  if (!env().h16_hw) return false;
+  return bwd_other_t<__half>(P, e, e_other, inv2, g, affs, dl, de, s);
 }
 
 // entry points used by pea_k_xdma.hip's dispatchers
 bool xdma_h_fwd_self(const KParams& P, const FwdArgs& A, hipStream_t s) {
-  if (P.D == 16) return A.train ? fwd_self_h<16, true>(P, A, s) : fwd_self_h<16, false>(P, A, s);
-  if (P.D == 32) return A.train ? fwd_self_h<32, true>(P, A, s) : fwd_self_h<32, false>(P, A, s);
-  if (P.D == 64) return A.train ? fwd_self_h<64, true>(P, A, s) : fwd_self_h<64, false>(P, A, s);
-  return false;
+  return A.dtype == PEA_BF16 ? fwd_self_t<__bf16>(P, A, s) : fwd_self_t<__half>(P, A, s);
 }
 
 
-bool xdma_bwd_self_h(const KParams& P, const void* x, const float* inv, const float* g, const float* affs, const float* dl, void* dx,
-                     hipStream_t s) {
+bool xdma_bwd_self_h(const KParams& P, int dtype, const void* x, const float* inv, const float* g, const float* affs, const float* dl,
+                     void* dx, hipStream_t s) {
   if (!inv || !env().bwd_xdma || env().force_direct) return false;
+  if (dtype == PEA_BF16) return bwd_self_t<__bf16>(P, x, inv, g, affs, dl, dx, s);
   if (env().h16_hw == 2 && env().bwd_pf && xdma_hq_bwd_self(P, x, inv, g, affs, dl, dx, s)) return true;  // pea_k_xdma_hq.hip
-  if (P.D == 16) return bwd_self_h<16>(P, (const __half*)x, inv, g, affs, dl, (__half*)dx, s);
-  if (P.D == 32) return bwd_self_h<32>(P, (const __half*)x, inv, g, affs, dl, (__half*)dx, s);
-  if (P.D == 64) return bwd_self_h<64>(P, (const __half*)x, inv, g, affs, dl, (__half*)dx, s);
-  return false;
+  return bwd_self_t<__half>(P, x, inv, g, affs, dl, dx, s);
 }
 
 }  // namespace pea

@@ -89,19 +89,26 @@ template <bool NTL = false>
 __device__ __forceinline__ void bs32(rsrc_t r, float v, unsigned vo, unsigned so) {
   __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v), r, vo, so, NTL ? kAuxNT : 0);
 }
-// embedding element of storage type T (f32 or f16); vo in bytes of T
+// embedding element of storage type T (f32, f16 or bf16); vo in bytes of T.  (Dispatch on the type, not on its size: f16 and bf16
+// are both two bytes, and decoding one as the other compiles and silently computes garbage.)
 template <typename T>
 __device__ __forceinline__ float bl_emb(rsrc_t r, unsigned vo, unsigned so) {
-  if (sizeof(T) == 4) return bl32(r, vo, so);
-  return __half2float(__builtin_bit_cast(__half, __builtin_amdgcn_raw_buffer_load_b16(r, vo, so, 0)));
+  static_assert(is_emb_t<T>, "embedding storage is f32, f16 or bf16");
+  if constexpr (std::is_same<T, float>::value) return bl32(r, vo, so);
+  else if constexpr (std::is_same<T, __half>::value)
+    return __half2float(__builtin_bit_cast(__half, __builtin_amdgcn_raw_buffer_load_b16(r, vo, so, 0)));
+  else return (float)__builtin_bit_cast(__bf16, __builtin_amdgcn_raw_buffer_load_b16(r, vo, so, 0));
 }
 // NTL: non-temporal.  The gradient planes are written once and not read again by the kernel that writes them; as plain
 // stores they push the embedding / g lines that the neighbouring tiles are about to re-read out of the XCD's 4 MB L2
 // (measured on the cross backward: 140 us with plain stores, 97 us with nt stores, 136 us with sc1 alone).
 template <typename T, bool NTL = false>
 __device__ __forceinline__ void bs_emb(rsrc_t r, float v, unsigned vo, unsigned so) {
-  if (sizeof(T) == 4) bs32<NTL>(r, v, vo, so);
-  else __builtin_amdgcn_raw_buffer_store_b16(__builtin_bit_cast(unsigned short, __float2half(v)), r, vo, so, NTL ? kAuxNT : 0);
+  static_assert(is_emb_t<T>, "embedding storage is f32, f16 or bf16");
+  if constexpr (std::is_same<T, float>::value) bs32<NTL>(r, v, vo, so);
+  else if constexpr (std::is_same<T, __half>::value)
+    __builtin_amdgcn_raw_buffer_store_b16(__builtin_bit_cast(unsigned short, __float2half(v)), r, vo, so, NTL ? kAuxNT : 0);
+  else __builtin_amdgcn_raw_buffer_store_b16(__builtin_bit_cast(unsigned short, (__bf16)v), r, vo, so, NTL ? kAuxNT : 0);
 }
 
 // sum over the 64 lanes, result valid in lane 63: 6 DPP adds (no LDS traffic)

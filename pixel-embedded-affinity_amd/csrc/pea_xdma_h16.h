@@ -1,5 +1,7 @@
 // pea_xdma_h16.h -- the LDS-DMA cross kernels (pea_xdma.h) for f16 STORAGE of the embedding (BASELINE.json configs[4]: D = 64 in
-// half precision; e and d loss / d e are __half, all arithmetic f32, target / weight / affs / g / 1/norm stay f32).
+// half precision; e and d loss / d e are __half, all arithmetic f32, target / weight / affs / g / 1/norm stay f32).  The same kernels
+// serve bf16 storage (T = __bf16: loads widen by a 16-bit shift, the gather pairs on v_dot2c_f32_bf16, the backward unpacks the two
+// halves of a register with v_lshlrev_b32 16 / v_and_b32 0xffff0000 in front of plain FMAs, d e is stored by v_cvt_pk_bf16_f32).
 //
 // Round 2 left f16 storage on the box kernels (tiled / chunked forward, direct backward: 0.93 ms at B=8 x 64 x 544^2 against 0.65 ms
 // for the same shape stored in f32): an f16 plane in LDS costs MORE instructions per channel in the gather (ds_read_u16 has no
@@ -26,6 +28,21 @@
 namespace pea {
 
 typedef _Float16 h4_t __attribute__((ext_vector_type(4)));
+
+// the 16-bit storage types (PEA_F16: __half, PEA_BF16: __bf16) as vector elements.  Loads widen to f32 by a plain conversion
+// (f16: v_cvt_f32_f16 or v_fma_mix; bf16: a 16-bit shift), products of two 16-bit values are exact in f32 either way.
+template <typename T> struct h16_elem;
+template <> struct h16_elem<__half> { typedef _Float16 type; };
+template <> struct h16_elem<__bf16> { typedef __bf16 type; };
+template <typename T> using h16e_t = typename h16_elem<T>::type;
+template <typename T> using h16x2_t = h16e_t<T> __attribute__((ext_vector_type(2)));
+template <typename T> using h16x4_t = h16e_t<T> __attribute__((ext_vector_type(4)));
+template <typename T> using h16x8_t = h16e_t<T> __attribute__((ext_vector_type(8)));
+// acc + <a, b> over the two channels of a pair: v_dot2c_f32_f16 / v_dot2c_f32_bf16 (f32 accumulation)
+__device__ __forceinline__ float dot2(h16x2_t<__half> a, h16x2_t<__half> b, float acc) { return __builtin_amdgcn_fdot2(a, b, acc, false); }
+__device__ __forceinline__ float dot2(h16x2_t<__bf16> a, h16x2_t<__bf16> b, float acc) {
+  return __builtin_amdgcn_fdot2_f32_bf16(a, b, acc, false);
+}
 
 // geometry of this lane's DMA items: up to two QUADS (4 pixels: the f32 1 / norm plane, and the conversion) and one OCT
 // (8 pixels: the f16 channel planes).  Same region order as pea_xdma.h (VF rows of TW pixels, then strip rows of SW pixels).
@@ -88,15 +105,15 @@ __device__ __forceinline__ void x_items(const KParams& P, const XParams& C, int 
 // The layout is free here (this step writes it, not the DMA), and it is what makes the gather cheap: one ds_read_b64 per
 // (offset, role) pair delivers both channels at 256 B/clk, where the planar form needs ds_read2st64_b32 at 128 B/clk -- and the
 // stamps (profiles/microbench/stamp_bwd.hip) say the gather phases are bound by exactly that pipe.
-template <int PS, int NT>
+template <typename T, int PS, int NT>
 __device__ __forceinline__ void convert_chunk(char* W, const char* R, int rbuf, int qa) {
   constexpr int PH = PS / 2;
 #pragma unroll
   for (int s = 0; s < 2; ++s) {
     const int q = s * NT + (int)threadIdx.x;  // = (s * (NT / 64) + wave) * 64 + lane: the quads this lane moved by DMA as well
     if (q < qa) {
-      const h4_t h0 = *(const h4_t*)(R + (rbuf * 2) * PH + q * 8);
-      const h4_t h1 = *(const h4_t*)(R + (rbuf * 2 + 1) * PH + q * 8);
+      const h16x4_t<T> h0 = *(const h16x4_t<T>*)(R + (rbuf * 2) * PH + q * 8);
+      const h16x4_t<T> h1 = *(const h16x4_t<T>*)(R + (rbuf * 2 + 1) * PH + q * 8);
       f4 a, b;
       a.x = (float)h0.x; a.y = (float)h1.x; a.z = (float)h0.y; a.w = (float)h1.y;
       b.x = (float)h0.z; b.y = (float)h1.z; b.z = (float)h0.w; b.w = (float)h1.w;
@@ -110,18 +127,17 @@ __device__ __forceinline__ void convert_chunk(char* W, const char* R, int rbuf, 
 // pixel): no conversion at all, half the bytes to write and a quarter of the bytes to gather -- the forward's per-pair work is
 // `dot += <own, v>`, `ssq += <v, v>` over the two channels, which is exactly v_dot2_f32_f16 (f16 products are exact in f32, the
 // accumulation is f32): one ds_read_b32 + two v_dot2 per pair, scalar accumulators (half the registers of the packed-f32 form).
-typedef _Float16 h2_t __attribute__((ext_vector_type(2)));
-template <int PS, int NT>
+// (bf16 the same with v_dot2_f32_bf16)
+template <typename T, int PS, int NT>
 __device__ __forceinline__ void interleave_chunk(char* W, const char* R, int rbuf, int qa) {
   constexpr int PH = PS / 2;
 #pragma unroll
   for (int s = 0; s < 2; ++s) {
     const int q = s * NT + (int)threadIdx.x;
     if (q < qa) {
-      const h4_t h0 = *(const h4_t*)(R + (rbuf * 2) * PH + q * 8);
-      const h4_t h1 = *(const h4_t*)(R + (rbuf * 2 + 1) * PH + q * 8);
-      typedef _Float16 h8_t __attribute__((ext_vector_type(8)));
-      *(h8_t*)(W + q * 16) = (h8_t){h0.x, h1.x, h0.y, h1.y, h0.z, h1.z, h0.w, h1.w};
+      const h16x4_t<T> h0 = *(const h16x4_t<T>*)(R + (rbuf * 2) * PH + q * 8);
+      const h16x4_t<T> h1 = *(const h16x4_t<T>*)(R + (rbuf * 2 + 1) * PH + q * 8);
+      *(h16x8_t<T>*)(W + q * 16) = (h16x8_t<T>){h0.x, h1.x, h0.y, h1.y, h0.z, h1.z, h0.w, h1.w};
     }
   }
 }
@@ -133,24 +149,28 @@ __device__ __forceinline__ float pf_finish(float acc, float o, float proj, float
 }
 
 // ------------------------------------------------------------------------------------------------------------------
-// backward, self loss (both roles), f16 e / de
+// backward, self loss (both roles), 16-bit e / de (T = __half or __bf16)
 // ------------------------------------------------------------------------------------------------------------------
 // PF: the projection first (pea_xdma_pf.h): `affs` = the raw cosine map of the forward; a chunk then finishes its two channels
 // (stored at once, in f16), there is no G array and no second read of the own pixel; WPE = 6 with the small planes.
 // HW: the working buffer stays in f16 (interleave_chunk: no conversion, half the LDS bytes written, a ds_read_b32 per pair instead of
-// a ds_read_b64); the FMAs take the halves directly (v_fma_mix_f32: f16 operand, f32 coefficient and accumulator -- the same arithmetic)
+// a ds_read_b64); the FMAs take the halves directly (v_fma_mix_f32: f16 operand, f32 coefficient and accumulator -- the same arithmetic;
+// bf16 has no v_fma_mix form: a v_lshlrev_b32 16 / v_and_b32 0xffff0000 unpack in front of plain FMAs)
 // OTHER: the cross loss with a detached second operand (ema_embedding_loss behind convert_consistency_flip's detach), role A: xt / invp
 // are the SECOND operand and its 1 / norm plane (staged: plan_xdma mode 2), the own pixel comes from the OWN tile staged beside each
 // chunk by wave 0 (f16: 1 KB per channel, no halo), `own_inv` is the own operand's signed 1 / norm plane.  Projection first only.
-template <int D_T, int TH, int TW, int PSU, bool CROP, int XP = kXP, bool PF = false, int WPE = 4, bool HW = false, bool OTHER = false>
-__global__ __launch_bounds__(TH* TW, WPE) void k_bwd_xdma_h(const KParams P, const XParams C, const __half* __restrict__ xt,
+template <int D_T, int TH, int TW, int PSU, bool CROP, int XP = kXP, bool PF = false, int WPE = 4, bool HW = false, bool OTHER = false,
+          typename T = __half>
+__global__ __launch_bounds__(TH* TW, WPE) void k_bwd_xdma_h(const KParams P, const XParams C, const T* __restrict__ xt,
                                                              const float* __restrict__ invp, const float* __restrict__ gin,
                                                              const float* __restrict__ affs, const float* __restrict__ dloss,
-                                                             __half* __restrict__ dx, const __half* __restrict__ own,
+                                                             T* __restrict__ dx, const T* __restrict__ own,
                                                              const float* __restrict__ own_inv) {
+  typedef h16e_t<T> E;
+  typedef h16x2_t<T> h2;
   constexpr int NT = TH * TW, PS = PSU * 256, PH = PS / 2, NP = D_T / 2;
   static_assert(TW == 32 && D_T % 2 == 0 && PS % 512 == 0, "lane mapping / channel pairs / half planes in whole 256-byte units");
-  static_assert(!OTHER || (PF && HW), "the role-A instantiation: projection first, f16 working buffer");
+  static_assert(!OTHER || (PF && HW), "the role-A instantiation: projection first, 16-bit working buffer");
   constexpr int OWNR = 5 * PS;  // OTHER: three buffers x two channels x 1 KB of own tile behind the working planes and the ring
   extern __shared__ f4 lds4[];
   char* lds = (char*)lds4;
@@ -264,19 +284,19 @@ __global__ __launch_bounds__(TH* TW, WPE) void k_bwd_xdma_h(const KParams P, con
     if constexpr (HW) {
       // (PEA_ABL_H_*: diagnostic builds of profiles/microbench/abl_bwd_h16.hip only -- timing with a phase compiled out)
 #ifndef PEA_ABL_H_NOILV
-      interleave_chunk<PS, NT>(W, R, ps % 3, C.QA);
+      interleave_chunk<T, PS, NT>(W, R, ps % 3, C.QA);
       lds_barrier();  // the working buffer holds chunk ps
 #endif
-      h2_t oh = *(const h2_t*)(W + vown);
+      h2 oh = *(const h2*)(W + vown);
       if (OTHER) {  // the own pixel from the own tile ([channel][512 pixels] halves)
-        oh.x = *(const _Float16*)(lds + OWNR + ((ps % 3) * 2) * 1024 + (int)threadIdx.x * 2);
-        oh.y = *(const _Float16*)(lds + OWNR + ((ps % 3) * 2 + 1) * 1024 + (int)threadIdx.x * 2);
+        oh.x = *(const E*)(lds + OWNR + ((ps % 3) * 2) * 1024 + (int)threadIdx.x * 2);
+        oh.y = *(const E*)(lds + OWNR + ((ps % 3) * 2 + 1) * 1024 + (int)threadIdx.x * 2);
       }
       o = (f2){(float)oh.x, (float)oh.y} * inv_own;
 #ifndef PEA_ABL_H_NOGATHER
 #pragma unroll
       for (int k = 0; k < XP; ++k) {
-        const h2_t v = *(const h2_t*)(W + ax[k]);
+        const h2 v = *(const h2*)(W + ax[k]);
         const float c = (k & 1) ? cx2[k / 2].y : cx2[k / 2].x;
         acc.x = __builtin_fmaf((float)v.x, c, acc.x);
         acc.y = __builtin_fmaf((float)v.y, c, acc.y);
@@ -284,7 +304,7 @@ __global__ __launch_bounds__(TH* TW, WPE) void k_bwd_xdma_h(const KParams P, con
       }
 #pragma unroll
       for (int k = 0; k < XP; ++k) {
-        const h2_t v = *(const h2_t*)(W + ay[k]);
+        const h2 v = *(const h2*)(W + ay[k]);
         const float c = (k & 1) ? cy2[k / 2].y : cy2[k / 2].x;
         acc.x = __builtin_fmaf((float)v.x, c, acc.x);
         acc.y = __builtin_fmaf((float)v.y, c, acc.y);
@@ -294,7 +314,7 @@ __global__ __launch_bounds__(TH* TW, WPE) void k_bwd_xdma_h(const KParams P, con
       acc = (f2){cx2[ps % (XP / 2)].x, cy2[ps % (XP / 2)].y};
 #endif
     } else {
-    convert_chunk<PS, NT>(W, R, ps % 3, C.QA);
+    convert_chunk<T, PS, NT>(W, R, ps % 3, C.QA);
     lds_barrier();  // the working buffer holds chunk ps
     o = *(const f2*)(W + 2 * vown);
     o = o * inv_own;
@@ -344,8 +364,8 @@ __global__ __launch_bounds__(TH* TW, WPE) void k_bwd_xdma_h(const KParams P, con
     }
 #ifndef PEA_ABL_H_NOSTORE
     if (PF) {
-      bs_emb<__half, true>(dB, sx, ph, hzo + (unsigned)(2 * ps) * hcs);
-      bs_emb<__half, true>(dB, sy, ph, hzo + (unsigned)(2 * ps + 1) * hcs);
+      bs_emb<T, true>(dB, sx, ph, hzo + (unsigned)(2 * ps) * hcs);
+      bs_emb<T, true>(dB, sy, ph, hzo + (unsigned)(2 * ps + 1) * hcs);
     }
 #endif
   }
@@ -363,31 +383,34 @@ __global__ __launch_bounds__(TH* TW, WPE) void k_bwd_xdma_h(const KParams P, con
       float ex, ey;
       if (KEEP) { ex = eh[ps].x * proj; ey = eh[ps].y * proj; }
       else {
-        ex = bl_emb<__half>(xB, ph, hzo + (unsigned)(2 * ps) * hcs) * pn;
-        ey = bl_emb<__half>(xB, ph, hzo + (unsigned)(2 * ps + 1) * hcs) * pn;
+        ex = bl_emb<T>(xB, ph, hzo + (unsigned)(2 * ps) * hcs) * pn;
+        ey = bl_emb<T>(xB, ph, hzo + (unsigned)(2 * ps + 1) * hcs) * pn;
       }
-      bs_emb<__half, true>(dB, (G[ps].x - ex) * sc, ph, hzo + (unsigned)(2 * ps) * hcs);
-      bs_emb<__half, true>(dB, (G[ps].y - ey) * sc, ph, hzo + (unsigned)(2 * ps + 1) * hcs);
+      bs_emb<T, true>(dB, (G[ps].x - ex) * sc, ph, hzo + (unsigned)(2 * ps) * hcs);
+      bs_emb<T, true>(dB, (G[ps].y - ey) * sc, ph, hzo + (unsigned)(2 * ps + 1) * hcs);
     }
   }
 }
 
 // ------------------------------------------------------------------------------------------------------------------
-// forward (self loss with TRAIN, or inference), f16 e; writes the f32 1 / norm plane for the backward.  Epilogue as k_fwd_xdma.
+// forward (self loss with TRAIN, or inference), 16-bit e (T = __half or __bf16); writes the f32 1 / norm plane for the backward.  Epilogue as k_fwd_xdma.
 // ------------------------------------------------------------------------------------------------------------------
-// HW: the working buffer stays in f16 (interleave_chunk) and the gather runs on v_dot2_f32_f16
+// HW: the working buffer stays in 16 bits (interleave_chunk) and the gather runs on v_dot2_f32_f16 / v_dot2_f32_bf16
 // NXP: offsets the gather walks (kXP = 10; 8 for tables with no more, e.g. BASELINE configs[4]'s offsets[:8] -- an unused slot costs
 // its LDS read and its two dot products all the same)
 // OTHER: the cross loss a_i(p) = <ehat(p), ehat_other(p + o_i)>: `e` is the SECOND operand (staged), the own pixel comes from the own
 // tile of `own` staged beside each chunk by wave 0; both 1 / norm planes are written (inv_out: own, inv_other_out: the second operand's)
-template <int D_T, int TH, int TW, int PSU, bool CROP, bool TRAIN, int WPE, bool HW = false, int NXP = kXP, bool OTHER = false>
-__global__ __launch_bounds__(TH* TW, WPE) void k_fwd_xdma_h(const KParams P, const XParams C, const __half* __restrict__ e,
+template <int D_T, int TH, int TW, int PSU, bool CROP, bool TRAIN, int WPE, bool HW = false, int NXP = kXP, bool OTHER = false,
+          typename T = __half>
+__global__ __launch_bounds__(TH* TW, WPE) void k_fwd_xdma_h(const KParams P, const XParams C, const T* __restrict__ e,
                                                              const float* __restrict__ target, const float* __restrict__ weight,
                                                              const uint8_t* __restrict__ mask, float* __restrict__ affs,
                                                              float* __restrict__ gout, LossState* __restrict__ st,
-                                                             float* __restrict__ inv_out, const __half* __restrict__ own,
+                                                             float* __restrict__ inv_out, const T* __restrict__ own,
                                                              float* __restrict__ inv_other_out) {
-  static_assert(!OTHER || (HW && TRAIN), "the cross-loss instantiation: f16 working buffer, training");
+  typedef h16e_t<T> E;
+  typedef h16x2_t<T> h2;
+  static_assert(!OTHER || (HW && TRAIN), "the cross-loss instantiation: 16-bit working buffer, training");
   constexpr int NT = TH * TW, PS = PSU * 256, PH = PS / 2, NP = D_T / 2, TP = NT, QP = TP / 4, NSL = QP / 64;
   constexpr int KMAX = kXP;
   constexpr int ITEMS = (KMAX * QP + NT - 1) / NT;
@@ -472,24 +495,24 @@ __global__ __launch_bounds__(TH* TW, WPE) void k_fwd_xdma_h(const KParams P, con
 #pragma unroll
   for (int ps = 0; ps < NP; ++ps) {
     if constexpr (HW) {
-      interleave_chunk<PS, NT>(W, R, ps % 3, C.QA);
+      interleave_chunk<T, PS, NT>(W, R, ps % 3, C.QA);
       lds_barrier();
-      h2_t o = *(const h2_t*)(W + vown);
+      h2 o = *(const h2*)(W + vown);
       if (OTHER) {
-        css = __builtin_amdgcn_fdot2(o, o, css, false);
-        o.x = *(const _Float16*)(lds + OWNR + ((ps % 3) * 2) * 1024 + (int)threadIdx.x * 2);
-        o.y = *(const _Float16*)(lds + OWNR + ((ps % 3) * 2 + 1) * 1024 + (int)threadIdx.x * 2);
+        css = dot2(o, o, css);
+        o.x = *(const E*)(lds + OWNR + ((ps % 3) * 2) * 1024 + (int)threadIdx.x * 2);
+        o.y = *(const E*)(lds + OWNR + ((ps % 3) * 2 + 1) * 1024 + (int)threadIdx.x * 2);
       }
-      oss = __builtin_amdgcn_fdot2(o, o, oss, false);
+      oss = dot2(o, o, oss);
 #pragma unroll
       for (int k = 0; k < NXP; ++k) {
-        const h2_t v = *(const h2_t*)(W + an[k]);
-        dot[k] = __builtin_amdgcn_fdot2(o, v, dot[k], false);
-        ssq[k] = __builtin_amdgcn_fdot2(v, v, ssq[k], false);
+        const h2 v = *(const h2*)(W + an[k]);
+        dot[k] = dot2(o, v, dot[k]);
+        ssq[k] = dot2(v, v, ssq[k]);
         if (k % 5 == 4) asm volatile("" ::: "memory");
       }
     } else {
-    convert_chunk<PS, NT>(W, R, ps % 3, C.QA);
+    convert_chunk<T, PS, NT>(W, R, ps % 3, C.QA);
     lds_barrier();
     const f2 o = *(const f2*)(W + 2 * vown);
     oss = __builtin_elementwise_fma(o, o, oss);

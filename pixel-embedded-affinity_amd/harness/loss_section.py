@@ -325,7 +325,7 @@ def _section_backward(ctx, dtotal):
         dl = dtotal.to(device=dev, dtype=torch.float32).contiguous()
         bufs = (ctypes.c_void_p * n)(*[g.data_ptr() for g in grads])
         cnts = (ctypes.c_size_t * n)(*[g.numel() for g in grads])
-        _lib.check(L.pea_scale_inplace_multi(bufs, cnts, n, _lib.F16 if grads[0].dtype == torch.float16 else _lib.F32, op._ptr(dl),
+        _lib.check(L.pea_scale_inplace_multi(bufs, cnts, n, op._DTYPE_CODE[grads[0].dtype], op._ptr(dl),
                                              op._stream()), "pea_scale_inplace_multi")
     return (None, None, None, None) + tuple(g if ctx.needs_input_grad[4 + k] else None for k, g in enumerate(grads))
 
