@@ -25,7 +25,8 @@
  * Tensor layouts (all C-contiguous, exactly the reference's):
  *   e, e_other, de, de_other : [B, D, Z, Y, X]   f32 (PEA_F32), f16 (PEA_F16) or bf16 (PEA_BF16);  2D => Z = 1
  *   target, weight, affs     : [B, K, Z, Y, X]   f32
- *   mask                     : [B, K, Z, Y, X]   u8   (NULL => all ones; the 3D path has none)
+ *   mask                     : [B, K, Z, Y, X]   u8, or f32 with PEA_FLAG_MASK_F32 (any value, fractions too);
+ *                                                  NULL => all ones; the 3D path has none
  *
  * Semantics (SURVEY.md section 8a closed forms; n(p) = max(||e(p)||_2, eps), ehat = e / n):
  *   a_i(p)  = < ehat(p), ehat_other(p + o_i) >          (ehat_other = ehat when e_other == NULL)
@@ -77,6 +78,11 @@ extern "C" {
                                     PEA_E_UNSUPPORTED where the role-A cross kernel does not apply (the caller adds two buffers),
                                     and for a self loss (e_other == NULL); ignored by the forward / inference calls */
 #define PEA_FLAG_ONE_MINUS 2u  /* a -> 1 - a         (what elf's mutex_watershed is handed: scripts_cvppp/utils/seg_mutex.py:4-5) */
+#define PEA_FLAG_MASK_F32 32u  /* the `mask` of pea_affinity_fwd / _fwd_ex / _fwd_dual_ex holds f32 values (the reference's mask.float(),
+                                  scripts_cvppp/loss/loss_embedding_mse.py:15,74; packed downN slices, main.py:284-287): pass it as
+                                  (const uint8_t *)(const void *)mask_f32; mask_bstride then counts f32 elements.  Any finite m is
+                                  honoured (r = a m - t m, g carries m^2).  Ignored where mask == NULL and by the backward / inference
+                                  calls; the labels-in calls, which derive their own masks, return PEA_E_DESC */
 
 /* error codes: 0 = ok, negative = PEA_E_*, positive = a hipError_t from the runtime */
 #define PEA_OK 0

@@ -88,21 +88,37 @@ def _batch_strided(t, name, dtype, shape):
     return t, (t.stride(0) if t.shape[0] > 1 else 0)
 
 
+def mask_arg(m, shape):
+    """-> (mask, batch stride in elements, descriptor flag of its type).  A float32 mask goes to the kernels as it is
+    (PEA_FLAG_MASK_F32: fractional values are honoured, as the reference's `affs * mask` after `mask.float()` does); other floating
+    dtypes are converted once with .float(); bool / uint8 masks take the u8 path (other integer dtypes are converted to uint8)."""
+    if m is None:
+        return None, 0, 0
+    if m.dtype == torch.bool:
+        m = m.view(torch.uint8)
+    if m.is_floating_point():
+        m, ms = _batch_strided(m, "mask", torch.float32, shape)
+        return m, ms, _lib.FLAG_MASK_F32
+    m, ms = _batch_strided(m, "mask", torch.uint8, shape)
+    return m, ms, 0
+
+
 _DESC_CACHE = {}
 
 
-def make_desc(spec, e, tstride=0, wstride=0, mstride=0):
-    """PeaDesc for `spec` on a tensor shaped like e.  Descriptors are immutable once built (the library takes them as
-    const), so they are memoised: filling and validating one costs more host time than the launch it describes."""
+def make_desc(spec, e, tstride=0, wstride=0, mstride=0, mflag=0):
+    """PeaDesc for `spec` on a tensor shaped like e (mflag: _lib.FLAG_MASK_F32 for an f32 mask, see mask_arg).  Descriptors are
+    immutable once built (the library takes them as const), so they are memoised: filling and validating one costs more host time
+    than the launch it describes."""
     key = (spec.ndim, tuple(spec.offsets), tuple(spec.lam), spec.border, spec.norm, spec.eps, spec.act, tuple(e.shape),
-           e.dtype, int(tstride), int(wstride), int(mstride))
+           e.dtype, int(tstride), int(wstride), int(mstride), int(mflag))
     d = _DESC_CACHE.get(key)
     if d is not None:
         return d
     if len(_DESC_CACHE) > 512:
         _DESC_CACHE.clear()
         _CROSS_OK.clear()  # (keyed by the identity of descriptors that are about to go away)
-    d = _DESC_CACHE[key] = _build_desc(spec, e, tstride, wstride, mstride)
+    d = _DESC_CACHE[key] = _build_desc(spec, e, tstride, wstride, mstride, mflag)
     return d
 
 
@@ -129,7 +145,7 @@ def cross_supported(d, mode):
 _lib._RELOAD_HOOKS.append(_CROSS_OK.clear)  # pea_cross_supported depends on the PEA_* switches
 
 
-def _build_desc(spec, e, tstride, wstride, mstride):
+def _build_desc(spec, e, tstride, wstride, mstride, mflag=0):
     dims = _spatial(e, spec.ndim)
     d = PeaDesc()
     d.abi, d.ndim, d.B, d.D = _lib.PEA_ABI_VERSION, spec.ndim, e.shape[0], e.shape[1]
@@ -137,7 +153,7 @@ def _build_desc(spec, e, tstride, wstride, mstride):
     d.K = spec.K
     d.border, d.norm, d.eps = spec.border, spec.norm, spec.eps
     d.dtype = _DTYPE_CODE[e.dtype]
-    d.flags = spec.act
+    d.flags = spec.act | int(mflag)
     for i, o in enumerate(spec.offsets):
         if spec.border == _lib.BORDER_CIRCULAR:  # torch.roll is modular: fold into (-dim, dim)
             o = tuple(int(v) - dims[a] * int(int(v) / dims[a]) if dims[a] else 0 for a, v in enumerate(o))
@@ -244,18 +260,14 @@ class FusedAffinityMSE(torch.autograd.Function):
         kshape = _affs_shape(e_c, spec.K)
         target, ts = _batch_strided(target, "target", torch.float32, kshape)
         weight, ws = _batch_strided(weight, "weightmap", torch.float32, kshape)
-        ms = 0
-        if mask is not None:
-            if mask.dtype == torch.bool:
-                mask = mask.view(torch.uint8)
-            mask, ms = _batch_strided(mask, "mask", torch.uint8, kshape)
+        mask, ms, mflag = mask_arg(mask, kshape)
         for t in (o_c, target, weight, mask):
             if t is not None and t.device != e_c.device:
                 raise RuntimeError("all operands must live on %s" % e_c.device)
         want_e = e.requires_grad
         want_o = e_other is not None and e_other.requires_grad
         with _on_device(e_c.device):
-            d = make_desc(spec, e_c, ts, ws, ms)
+            d = make_desc(spec, e_c, ts, ws, ms, mflag)
             L = _lib.lib()
             affs = torch.empty(kshape, dtype=torch.float32, device=e_c.device)
             loss_vec = torch.empty(1 + spec.K, dtype=torch.float32, device=e_c.device)

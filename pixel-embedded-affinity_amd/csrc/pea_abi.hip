@@ -187,7 +187,7 @@ int pea_affinity_fwd_ex(const PeaDesc* desc, const void* e, const void* e_other,
   A.e = e; A.eo = e_other ? e_other : e;
   A.t = target; A.w = weight; A.m = mask; A.affs = affs; A.gout = g_out;
   A.st = (LossState*)workspace; A.loss_out = loss_out; A.inv_out = inv_norm_out;
-  A.dtype = desc->dtype; A.train = true;
+  A.dtype = desc->dtype; A.train = true; A.mf32 = mask && (desc->flags & PEA_FLAG_MASK_F32);
   rc = run_fwd(P, A, s);
   if (rc) return rc;
   if (e_other && e_other == e && inv_norm_out) {
@@ -231,6 +231,7 @@ int pea_affinity_fwd_dual_ex(const PeaDesc* desc, const PeaDesc* desc_cross, con
   FwdArgs A = {}, A2 = {};
   A.e = e; A.eo = e; A.t = target; A.w = weight; A.m = mask; A.affs = affs; A.gout = g_out;
   A.st = (LossState*)workspace; A.loss_out = loss_out; A.inv_out = inv_norm_out; A.dtype = desc->dtype; A.train = true;
+  A.mf32 = mask && (desc->flags & PEA_FLAG_MASK_F32);  // (desc_cross agrees: the flags outside kActMask are compared above)
   A2 = A;
   A2.eo = ema; A2.affs = nullptr; A2.gout = g_cross_out; A2.st = (LossState*)workspace_cross; A2.loss_out = loss_cross_out;
   A2.inv_out = inv_norm_other_out;
@@ -377,6 +378,7 @@ int pea_affinity_fwd_bwd_labels_ex(const PeaDesc* desc, const void* e, const voi
                                    void* workspace, size_t workspace_bytes, void* scratch, size_t scratch_bytes, void* stream) {
   int rc = validate(desc);
   if (rc) return rc;
+  if (desc->flags & PEA_FLAG_MASK_F32) return PEA_E_DESC;  // the mask is derived from the labels: there is none to type
   if (!e || !labels || !wtab || !loss_out || !de) return PEA_E_NULL;
   const size_t es = dtype_bytes(desc->dtype);
   if (misaligned(e, es) || misaligned(e_other, es) || misaligned(de, es) || misaligned(affs, 4) || misaligned(labels, 4) ||
@@ -436,6 +438,7 @@ int pea_affinity_fwd_bwd_labels_dual(const PeaDesc* desc, const PeaDesc* desc_cr
   if (rc) return rc;
   rc = validate(desc_cross);
   if (rc) return rc;
+  if ((desc->flags | desc_cross->flags) & PEA_FLAG_MASK_F32) return PEA_E_DESC;  // (as pea_affinity_fwd_bwd_labels_ex)
   if (!e || !ema || !labels || !wtab || !loss_out || !loss_cross_out || !de) return PEA_E_NULL;
   if (desc->B != desc_cross->B || desc->D != desc_cross->D || desc->K != desc_cross->K || desc->dtype != desc_cross->dtype ||
       desc->border != desc_cross->border || memcmp(desc->dims, desc_cross->dims, sizeof(desc->dims)) != 0 ||

@@ -56,11 +56,11 @@ __device__ __forceinline__ void stage_region_raw(const KParams& P, const TParams
   }
 }
 
-template <typename T, int D_T, int DC, int TH, int TW, int PLQ, bool CROP, bool TRAIN, bool SELF>
+template <typename T, int D_T, int DC, int TH, int TW, int PLQ, bool CROP, bool TRAIN, bool SELF, typename MT = uint8_t>
 __global__ __launch_bounds__(TH* TW, (DC > 16 ? 2 : 4)) void k_fwd_tiled_chunked(const KParams P, const TParams Q, const T* __restrict__ e,
                                                                  const T* __restrict__ eo, const float* __restrict__ target,
                                                                  const float* __restrict__ weight,
-                                                                 const uint8_t* __restrict__ mask, float* __restrict__ affs,
+                                                                 const MT* __restrict__ mask, float* __restrict__ affs,
                                                                  float* __restrict__ gout, LossState* __restrict__ st) {
   typedef Lds<DC, PLQ> L;
   static_assert(D_T % DC == 0, "whole chunks");
@@ -191,7 +191,7 @@ __global__ __launch_bounds__(TH* TW, (DC > 16 ? 2 : 4)) void k_fwd_tiled_chunked
 #pragma unroll
   for (int k0 = 0; k0 < kChN; k0 += KN) {
     if (k0 < Q.n_near) {
-      if (TRAIN) fwd_load_twm<KN>(sa, U, Q.near, k0, Q.n_near, pb, pm);
+      if (TRAIN) fwd_load_twm<KN, MT>(sa, U, Q.near, k0, Q.n_near, pb, pm);
 #pragma unroll
       for (int u = 0; u < KN; ++u) {
         if (k0 + u < kChN && k0 + u < Q.n_near) {  // uniform
@@ -211,7 +211,7 @@ __global__ __launch_bounds__(TH* TW, (DC > 16 ? 2 : 4)) void k_fwd_tiled_chunked
 #pragma unroll
   for (int k = 0; k < kChF; k += 2) {
     if (k < Q.n_far) {
-      if (TRAIN) fwd_load_twm<2>(sf, U, Q.far, k, Q.n_far, pb, pm);
+      if (TRAIN) fwd_load_twm<2, MT>(sf, U, Q.far, k, Q.n_far, pb, pm);
 #pragma unroll
       for (int u = 0; u < 2; ++u) {
         if (k + u < Q.n_far) {

@@ -12,12 +12,12 @@ namespace pea {
 // forward (direct form): affs, (TRAIN) per-workgroup loss partials and g = d loss / d affs
 //   D_T > 0: channels unrolled, own pixel kept in registers;  D_T == 0: generic D, own pixel re-read (L1)
 // ------------------------------------------------------------------------------------------------
-template <typename T, int D_T, bool TRAIN>
+template <typename T, int D_T, bool TRAIN, typename MT = uint8_t>  // MT: the mask, u8 or f32 (PEA_FLAG_MASK_F32)
 __global__ __launch_bounds__(kBlock) void k_fwd_direct(const KParams P, const T* __restrict__ e,
                                                        const T* __restrict__ eo,
                                                        const float* __restrict__ target,
                                                        const float* __restrict__ weight,
-                                                       const uint8_t* __restrict__ mask,
+                                                       const MT* __restrict__ mask,
                                                        float* __restrict__ affs, float* __restrict__ gout,
                                                        LossState* __restrict__ st) {
   extern __shared__ float s_acc[];  // [K][kBlock], TRAIN only

@@ -119,7 +119,7 @@ struct FwdArgs {
   const void* eo;       // second operand or == e
   const float* t;       // training only
   const float* w;
-  const uint8_t* m;     // nullable
+  const uint8_t* m;     // nullable; f32 values when mf32
   float* affs;          // nullable
   float* gout;          // nullable
   LossState* st;        // training only
@@ -127,6 +127,7 @@ struct FwdArgs {
   float* inv_out;       // nullable: signed 1 / norm plane(s)
   int dtype;            // PEA_F32 / PEA_F16 / PEA_BF16
   bool train;
+  bool mf32;            // m != NULL holds f32 (PEA_FLAG_MASK_F32): the families without an f32-mask form decline the call
 };
 // Each returns true if it launched (the caller then launches the loss finish).
 bool xdma_fwd_self(const KParams& P, const FwdArgs& A, hipStream_t s);

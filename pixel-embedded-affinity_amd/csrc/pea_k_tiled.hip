@@ -28,7 +28,19 @@ struct FwdT {  // typed view of FwdArgs
   float *affs, *gout;
   LossState* st;
   float* inv_out;
+  bool mf32;  // m holds f32 (training): the kernels' MT = float forms
 };
+// launch a forward's u8-mask form `kern`, or -- training with an f32 mask -- its f32-mask form (KF: the parenthesised kernel,
+// instantiated where the launcher's constexpr kMF says so; the launcher has declined the call where it does not)
+#define PEA_LAUNCH_M(kern, KF, grid, blk, lds, s, P, Q, e, eo, ...)                                                        \
+  if (TRAIN && A.mf32) {                                                                                                   \
+    if constexpr (kMF) {                                                                                                   \
+      constexpr auto kernm = KF;                                                                                           \
+      PEA_LAUNCH(kernm, grid, blk, lds, s, P, Q, e, eo, A.t, A.w, (const float*)(const void*)A.m, __VA_ARGS__)             \
+    }                                                                                                                      \
+  } else {                                                                                                                 \
+    PEA_LAUNCH(kern, grid, blk, lds, s, P, Q, e, eo, A.t, A.w, A.m, __VA_ARGS__)                                           \
+  }
 
 // forward with the LDS-transposed, dwordx4 epilogue (k_fwd_tiled_v): 16x32 tiles, the dot products laid over the dead region,
 // two workgroups of 8 waves per CU.  The training forward wherever the LDS-DMA kernel (k_fwd_xdma) does not apply.
@@ -38,6 +50,8 @@ bool try_fwd_v(const KParams& P, const FwdT& A, float* inv_out, hipStream_t s) {
   if (P.border == PEA_BORDER_REPLICATE && !(std::is_same<T, float>::value && D_T == 16)) return false;
   if (misaligned(A.t, 16) || misaligned(A.w, 16) || misaligned(A.affs, 16) || misaligned(A.gout, 16) || misaligned(A.m, 4)) return false;
   if ((P.tbs | P.wbs | P.mbs | (long long)P.S) & 3) return false;
+  constexpr bool kMF = TRAIN && std::is_same<T, float>::value;  // f32-mask forms for f32 storage only (as try_fwd_tiled)
+  if (TRAIN && A.mf32 && (!kMF || misaligned(A.m, 16))) return false;  // (the f32 mask's quads are dwordx4 loads)
   constexpr TileCfg c = fwdv_cfg<D_T>();
   const size_t tp = (size_t)c.TH * c.TW;
   const size_t region = Lds<D_T, 1>::kBytes * (size_t)c.PLQ, dots = (size_t)P.K * tp * 4, parts = (size_t)P.K * (tp / 256) * 4;
@@ -52,7 +66,8 @@ bool try_fwd_v(const KParams& P, const FwdT& A, float* inv_out, hipStream_t s) {
 #define PEA_FV(CROP_, SELF_)                                                                                  \
   {                                                                                                           \
     constexpr auto kern = k_fwd_tiled_v<T, D_T, c.TH, c.TW, c.PLQ, true, CROP_, TRAIN, SELF_>;                \
-    PEA_LAUNCH(kern, grid, blk, lds, s, P, Q, e, eo, A.t, A.w, A.m, A.affs, A.gout, A.st, inv_out)            \
+    PEA_LAUNCH_M(kern, (k_fwd_tiled_v<T, D_T, c.TH, c.TW, c.PLQ, true, CROP_, TRAIN, SELF_, float>),            \
+                 grid, blk, lds, s, P, Q, e, eo, A.affs, A.gout, A.st, inv_out)                  \
   }
   const bool crop = P.border != PEA_BORDER_CIRCULAR;
   if (eo == e) { if (crop) PEA_FV(true, true) else PEA_FV(false, true) }
@@ -66,6 +81,10 @@ bool try_fwd_tiled(const KParams& P, const FwdT& A, float* inv_out, hipStream_t 
   constexpr TileCfg c = fwd_cfg<D_T>(0);
   constexpr int NT = c.TH * c.TW;
   if (P.border == PEA_BORDER_REPLICATE && !(std::is_same<T, float>::value && D_T == 16)) return false;
+  // f32-mask forms for f32 storage only (the library's size: 16-bit storage with an f32 mask takes the LDS-DMA kernels where the stencil
+  // is axis-aligned, the direct kernels where it is not); and the f32 mask has no second buffer resource (KParams::ksplit)
+  constexpr bool kMF = TRAIN && std::is_same<T, float>::value;
+  if (TRAIN && A.mf32 && (!kMF || P.ksplit != P.K)) return false;
   TParams Q;
   if (!plan_tiles_cached(P, c, false, &Q, true) || rep_mostly_far(P, Q)) return false;
   const size_t lds = Lds<D_T, c.PLQ>::kBytes + (TRAIN ? (size_t)(NT / 64) * P.K * sizeof(float) : 0);
@@ -74,7 +93,8 @@ bool try_fwd_tiled(const KParams& P, const FwdT& A, float* inv_out, hipStream_t 
 #define PEA_FT(CROP_, SELF_)                                                                                  \
   {                                                                                                           \
     constexpr auto kern = k_fwd_tiled<T, D_T, c.TH, c.TW, c.PLQ, CROP_, TRAIN, SELF_>;                        \
-    PEA_LAUNCH(kern, grid, blk, lds, s, P, Q, e, eo, A.t, A.w, A.m, A.affs, A.gout, A.st, inv_out)            \
+    PEA_LAUNCH_M(kern, (k_fwd_tiled<T, D_T, c.TH, c.TW, c.PLQ, CROP_, TRAIN, SELF_, float>),                    \
+                 grid, blk, lds, s, P, Q, e, eo, A.affs, A.gout, A.st, inv_out)                  \
   }
   const bool crop = P.border != PEA_BORDER_CIRCULAR;
   if (eo == e) { if (crop) PEA_FT(true, true) else PEA_FT(false, true) }
@@ -89,6 +109,8 @@ bool try_fwd_tiled(const KParams& P, const FwdT& A, float* inv_out, hipStream_t 
 template <typename T, int D_T, int DC, bool TRAIN>
 bool try_fwd_chunked(const KParams& P, const FwdT& A, hipStream_t s) {
   if (P.D != D_T || P.border == PEA_BORDER_REPLICATE) return false;
+  constexpr bool kMF = TRAIN && std::is_same<T, float>::value;  // f32-mask forms for f32 storage only (as try_fwd_tiled)
+  if (TRAIN && A.mf32 && !kMF) return false;
   constexpr TileCfg c = kCfg32;  // 16 x 32 tile, 1041 region pixels: 128 B (DC = 32) or 64 B (DC = 16) of LDS each
   TParams Q;
   if (!plan_tiles_cached(P, c, false, &Q) || Q.n_near > kChN || Q.n_far > kChF) return false;
@@ -99,7 +121,8 @@ bool try_fwd_chunked(const KParams& P, const FwdT& A, hipStream_t s) {
 #define PEA_FC(CROP_, SELF_)                                                                                  \
   {                                                                                                           \
     constexpr auto kern = k_fwd_tiled_chunked<T, D_T, DC, c.TH, c.TW, c.PLQ, CROP_, TRAIN, SELF_>;            \
-    PEA_LAUNCH(kern, grid, blk, lds, s, P, Q, e, eo, A.t, A.w, A.m, A.affs, A.gout, A.st)                     \
+    PEA_LAUNCH_M(kern, (k_fwd_tiled_chunked<T, D_T, DC, c.TH, c.TW, c.PLQ, CROP_, TRAIN, SELF_, float>),        \
+                 grid, blk, lds, s, P, Q, e, eo, A.affs, A.gout, A.st)                           \
   }
   const bool crop = P.border != PEA_BORDER_CIRCULAR;
   if (eo == e) {
@@ -167,7 +190,7 @@ bool bwd_roles(const KParams& P, int roles, const void* x, const void* nbA, cons
 bool tiled_fwd(const KParams& P, const FwdArgs& A, hipStream_t s, bool* wrote_inv) {
   *wrote_inv = false;
   if (env().force_direct) return false;
-  const FwdT T_ = {A.e, A.eo, A.t, A.w, A.m, A.affs, A.gout, A.st, A.inv_out};
+  const FwdT T_ = {A.e, A.eo, A.t, A.w, A.m, A.affs, A.gout, A.st, A.inv_out, A.train && A.mf32};
   if (A.dtype == PEA_F16) return A.train ? fwd_any<__half, true>(P, T_, s, wrote_inv) : fwd_any<__half, false>(P, T_, s, wrote_inv);
   if (A.dtype == PEA_BF16) return A.train ? fwd_any<__bf16, true>(P, T_, s, wrote_inv) : fwd_any<__bf16, false>(P, T_, s, wrote_inv);
   return A.train ? fwd_any<float, true>(P, T_, s, wrote_inv) : fwd_any<float, false>(P, T_, s, wrote_inv);

@@ -24,10 +24,19 @@ bool fwd_self(const KParams& P, const FwdArgs& A, hipStream_t s) {
   }
   if (!z3 && P.K > kXP) return false;
   if (z3 && P.K > kXP + 2) return false;
+  // an f32 mask (2D training only): the quads' masks are dwordx4 loads -- a plane that is not 16-byte aligned takes the next family
+  const bool mf = TRAIN && A.mf32;
+  if (mf && (z3 || misaligned(A.m, 16))) return false;
   const XParams& C = X.C;
   const dim3 grid((unsigned)(C.tiles_per_xcd * kXcd)), blk(kXdmaTH * kXdmaTW);
 #define PEA_XF(CROP_, PSU_, ZF_, WPE_)                                                                                      \
-  {                                                                                                                         \
+  if (mf) {                                                                                                                 \
+    if constexpr (TRAIN && ZF_ == 0) {                                                                                      \
+      constexpr auto kern = k_fwd_xdma<D_T, kXdmaTH, kXdmaTW, PSU_, CROP_, true, 0, false, WPE_, false, float>;             \
+      PEA_LAUNCH(kern, grid, blk, X.lds, s, P, C, e, t, w, (const float*)(const void*)A.m, A.affs, A.gout, A.st, A.inv_out, \
+                 (const float*)nullptr, (float*)nullptr, LabArgs{})                                                         \
+    }                                                                                                                       \
+  } else {                                                                                                                  \
     constexpr auto kern = k_fwd_xdma<D_T, kXdmaTH, kXdmaTW, PSU_, CROP_, TRAIN, ZF_, false, WPE_>;                          \
     PEA_LAUNCH(kern, grid, blk, X.lds, s, P, C, e, t, w, A.m, A.affs, A.gout, A.st, A.inv_out, (const float*)nullptr,       \
                (float*)nullptr, LabArgs{})                                                                                  \
@@ -117,6 +126,7 @@ bool xdma_fwd_dual(const KParams& P, const KParams& P2, const FwdArgs& A, const 
       misaligned(A.gout, 16) || misaligned(A2.gout, 16) || misaligned(A.m, 4) || misaligned(A.inv_out, 4) || misaligned(A2.inv_out, 4))
     return false;
   if ((P.tbs | P.wbs | P.mbs) & 3) return false;
+  if (A.mf32 && misaligned(A.m, 16)) return false;  // (the f32 mask's quads are dwordx4 loads)
   XPlan X;
   if (!plan(P, kXdmaPSUF, 1, &X) || X.C.nfz > 0) return false;
   DualFwdArgs DA = {};
@@ -124,11 +134,17 @@ bool xdma_fwd_dual(const KParams& P, const KParams& P2, const FwdArgs& A, const 
   for (int i = 0; i < kXK; ++i) DA.gs2[i] = i < P2.K ? P2.gscale[i] : 0.f;
   const dim3 grid((unsigned)(X.C.tiles_per_xcd * kXcd)), blk(kXdmaTH * kXdmaTW);
   const bool crop = P.border != PEA_BORDER_CIRCULAR;
-#define PEA_XFD(CROP_, NB_)                                                                            \
-  {                                                                                                    \
-    constexpr auto kern = k_fwd_xdma_dual<kXdmaTH, kXdmaTW, kXdmaPSUF, CROP_, NB_>;                    \
-    const size_t lds = (size_t)(NB_ == 3 ? 3 : 2) * 4 * kXdmaPSUF * 256;                               \
-    PEA_LAUNCH(kern, grid, blk, lds, s, P, X.C, e, A.t, A.w, A.m, A.affs, A.gout, A.st, A.inv_out, DA) \
+#define PEA_XFD(CROP_, NB_)                                                                                                \
+  {                                                                                                                        \
+    const size_t lds = (size_t)(NB_ == 3 ? 3 : 2) * 4 * kXdmaPSUF * 256;                                                   \
+    if (A.mf32) {                                                                                                          \
+      constexpr auto kern = k_fwd_xdma_dual<kXdmaTH, kXdmaTW, kXdmaPSUF, CROP_, NB_, float>;                               \
+      PEA_LAUNCH(kern, grid, blk, lds, s, P, X.C, e, A.t, A.w, (const float*)(const void*)A.m, A.affs, A.gout, A.st,       \
+                 A.inv_out, DA)                                                                                            \
+    } else {                                                                                                               \
+      constexpr auto kern = k_fwd_xdma_dual<kXdmaTH, kXdmaTW, kXdmaPSUF, CROP_, NB_>;                                      \
+      PEA_LAUNCH(kern, grid, blk, lds, s, P, X.C, e, A.t, A.w, A.m, A.affs, A.gout, A.st, A.inv_out, DA)                   \
+    }                                                                                                                      \
   }
   // (NB = 4: the ring of two four-plane buffers handed over in halves; the whole-buffer hand-off -- NB = 2, +2.6 % -- and the ring of
   //  three at one workgroup per CU -- NB = 3, +21 % -- were switches until round 6 and are no longer compiled: EXPERIMENTS.md)
@@ -150,15 +166,19 @@ static bool fwd_other_wide(const KParams& P, const FwdArgs& A, hipStream_t s) {
   if (!plan(P, kXdmaPSUF, 1, &X) || X.C.nfz > 0 || P.K > kXP || P.Z != 1) return false;
   const size_t lds = X.lds + (size_t)6 * 2048;  // + the own tiles: three buffers x two channels x 2 KB
   const dim3 grid((unsigned)(X.C.tiles_per_xcd * kXcd)), blk(kXdmaTH * kXdmaTW);
-  if (P.border != PEA_BORDER_CIRCULAR) {
-    constexpr auto kern = k_fwd_xdma<D_T, kXdmaTH, kXdmaTW, kXdmaPSUF, true, true, 0, true, 4>;
-    PEA_LAUNCH(kern, grid, blk, lds, s, P, X.C, e_other, A.t, A.w, A.m, A.affs, A.gout, A.st, A.inv_out, e,
-               A.inv_out + (size_t)P.B * P.S, LabArgs{})
-  } else {
-    constexpr auto kern = k_fwd_xdma<D_T, kXdmaTH, kXdmaTW, kXdmaPSUF, false, true, 0, true, 4>;
-    PEA_LAUNCH(kern, grid, blk, lds, s, P, X.C, e_other, A.t, A.w, A.m, A.affs, A.gout, A.st, A.inv_out, e,
-               A.inv_out + (size_t)P.B * P.S, LabArgs{})
+#define PEA_XFW(CROP_, MT_)                                                                                              \
+  {                                                                                                                      \
+    constexpr auto kern = k_fwd_xdma<D_T, kXdmaTH, kXdmaTW, kXdmaPSUF, CROP_, true, 0, true, 4, false, MT_>;             \
+    PEA_LAUNCH(kern, grid, blk, lds, s, P, X.C, e_other, A.t, A.w, (const MT_*)(const void*)A.m, A.affs, A.gout, A.st,   \
+               A.inv_out, e, A.inv_out + (size_t)P.B * P.S, LabArgs{})                                                   \
   }
+  const bool crop = P.border != PEA_BORDER_CIRCULAR;
+  if (A.mf32) {
+    if (crop) PEA_XFW(true, float) else PEA_XFW(false, float)
+  } else {
+    if (crop) PEA_XFW(true, uint8_t) else PEA_XFW(false, uint8_t)
+  }
+#undef PEA_XFW
   return true;
 }
 
@@ -172,6 +192,7 @@ bool xdma_fwd_other(const KParams& P, const FwdArgs& A, hipStream_t s) {
       misaligned(A.gout, 16) || misaligned(A.m, 4) || misaligned(A.inv_out, 4))
     return false;
   if ((P.tbs | P.wbs | P.mbs) & 3) return false;
+  if (A.mf32 && misaligned(A.m, 16)) return false;  // (the f32 mask's quads are dwordx4 loads)
   if (P.D == 32) return fwd_other_wide<32>(P, A, s);
   if (P.D == 64) return fwd_other_wide<64>(P, A, s);
   XPlan X;
@@ -182,6 +203,7 @@ bool xdma_fwd_other(const KParams& P, const FwdArgs& A, hipStream_t s) {
     z3 = true;
   }
   if (P.K > (z3 ? kXP + 2 : kXP)) return false;
+  if (z3 && A.mf32) return false;  // (the f32-mask forms are 2D)
   const dim3 grid((unsigned)(X.C.tiles_per_xcd * kXcd)), blk(kXdmaTH * kXdmaTW);
   const bool crop = P.border != PEA_BORDER_CIRCULAR;
 #define PEA_XFO(CROP_, PSU_, ZF_)                                                                                           \
@@ -190,12 +212,21 @@ bool xdma_fwd_other(const KParams& P, const FwdArgs& A, hipStream_t s) {
     PEA_LAUNCH(kern, grid, blk, X.lds, s, P, X.C, e_other, A.t, A.w, A.m, A.affs, A.gout, A.st, A.inv_out, e,               \
                A.inv_out + (size_t)P.B * P.S, LabArgs{})                                                                    \
   }
-  if (z3) {
+#define PEA_XFOM(CROP_)                                                                                                     \
+  {                                                                                                                         \
+    constexpr auto kern = k_fwd_xdma<16, kXdmaTH, kXdmaTW, kXdmaPSU, CROP_, true, 0, true, 4, false, float>;                \
+    PEA_LAUNCH(kern, grid, blk, X.lds, s, P, X.C, e_other, A.t, A.w, (const float*)(const void*)A.m, A.affs, A.gout, A.st,  \
+               A.inv_out, e, A.inv_out + (size_t)P.B * P.S, LabArgs{})                                                      \
+  }
+  if (A.mf32) {
+    if (crop) PEA_XFOM(true) else PEA_XFOM(false)
+  } else if (z3) {
     if (crop) PEA_XFO(true, kXdmaPSU3F, kXZ / 2) else PEA_XFO(false, kXdmaPSU3F, kXZ / 2)
   } else {
     if (crop) PEA_XFO(true, kXdmaPSU, 0) else PEA_XFO(false, kXdmaPSU, 0)
   }
 #undef PEA_XFO
+#undef PEA_XFOM
   return true;
 }
 

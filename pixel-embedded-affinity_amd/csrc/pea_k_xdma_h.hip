@@ -28,8 +28,25 @@ bool fwd_self_h(const KParams& P, const FwdArgs& A, hipStream_t s) {
   if (!plan(P, kXdmaPSUF, 1, &X) || X.C.nfz > 0 || P.K > kXP) return false;
   const size_t lds = (size_t)5 * kXdmaPSUF * 256;  // two f32 working planes + six half-size ring planes
   const dim3 grid((unsigned)(X.C.tiles_per_xcd * kXcd)), blk(kXdmaTH * kXdmaTW);
+  // an f32 mask (training): the 16-bit working buffer's kernel with dwordx4 mask quads, one slot count (kXP); a plane that is not
+  // 16-byte aligned, or PEA_H16_HW=0, takes the next family
+  const bool mf = TRAIN && A.mf32;
+  if (mf && (misaligned(A.m, 16) || !(kBf16<T> || env().h16_hw))) return false;
   if (kBf16<T> || env().h16_hw) {  // half-precision working buffer, v_dot2 gather: 48 VGPRs and 30 KB -- four workgroups per CU (five: 173 against 168 us)
     const size_t ldsh = (size_t)4 * kXdmaPSUF * 256;
+    if constexpr (TRAIN) {
+      if (mf) {
+#define PEA_HFM(CROP_)                                                                                                    \
+  {                                                                                                                       \
+    constexpr auto kern = k_fwd_xdma_h<D_T, kXdmaTH, kXdmaTW, kXdmaPSUF, CROP_, true, 8, true, kXP, false, T, float>;     \
+    PEA_LAUNCH(kern, grid, blk, ldsh, s, P, X.C, e, A.t, A.w, (const float*)(const void*)A.m, A.affs, A.gout, A.st,       \
+               A.inv_out, (const T*)nullptr, (float*)nullptr)                                                             \
+  }
+        if (P.border != PEA_BORDER_CIRCULAR) PEA_HFM(true) else PEA_HFM(false)
+#undef PEA_HFM
+        return true;
+      }
+    }
     // (D = 64 with at most eight offsets -- BASELINE configs[4] -- walks eight slots instead of ten)
 #define PEA_HF(CROP_, NXP_)                                                                                          \
   {                                                                                                                  \
@@ -120,6 +137,18 @@ bool fwd_other_h(const KParams& P, const FwdArgs& A, hipStream_t s) {
   const size_t lds = (size_t)4 * kXdmaPSUF * 256 + 6 * 1024;  // working plane + ring + the own tiles
   const dim3 grid((unsigned)(X.C.tiles_per_xcd * kXcd)), blk(kXdmaTH * kXdmaTW);
   float* inv_other = A.inv_out + (size_t)P.B * P.S;
+  if (A.mf32) {  // an f32 mask: dwordx4 mask quads, one slot count (kXP)
+    if (misaligned(A.m, 16)) return false;
+#define PEA_HFOM(CROP_)                                                                                                  \
+  {                                                                                                                      \
+    constexpr auto kern = k_fwd_xdma_h<D_T, kXdmaTH, kXdmaTW, kXdmaPSUF, CROP_, true, 6, true, kXP, true, T, float>;     \
+    PEA_LAUNCH(kern, grid, blk, lds, s, P, X.C, eo, A.t, A.w, (const float*)(const void*)A.m, A.affs, A.gout, A.st,      \
+               A.inv_out, e, inv_other)                                                                                  \
+  }
+    if (P.border != PEA_BORDER_CIRCULAR) PEA_HFOM(true) else PEA_HFOM(false)
+#undef PEA_HFOM
+    return true;
+  }
 #define PEA_HFO(CROP_, NXP_)                                                                                                  \
   {                                                                                                                          \
     constexpr auto kern = k_fwd_xdma_h<D_T, kXdmaTH, kXdmaTW, kXdmaPSUF, CROP_, true, 6, true, NXP_, true, T>;                \

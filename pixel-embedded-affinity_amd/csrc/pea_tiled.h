@@ -85,6 +85,34 @@ template <bool NTL = false>
 __device__ __forceinline__ float bl8(rsrc_t r, unsigned vo, unsigned so) {
   return (float)__builtin_amdgcn_raw_buffer_load_b8(r, vo, so, NTL ? kAuxNT : 0);
 }
+// The mask of the 2D training forwards: MT = uint8_t, or float (PEA_FLAG_MASK_F32: include/pea.h), a template parameter of each.
+// Per lane: m_load (vo / so address the pixel in an f32 plane, vo8 / so8 in the u8 plane).  Per quad of four x-adjacent pixels
+// (the dwordx4 epilogues): mq_t<MT> holds the four masks -- one dword of four bytes, or one dwordx4 requested at the same point.
+template <typename MT>
+constexpr bool kMaskF32 = std::is_same<MT, float>::value;
+template <typename MT>
+using mq_t = typename std::conditional<kMaskF32<MT>, f4, unsigned>::type;
+template <typename MT>
+__device__ __forceinline__ mq_t<MT> mq_ones() {
+  if constexpr (kMaskF32<MT>) return f4{1.f, 1.f, 1.f, 1.f};
+  else return 0x01010101u;
+}
+template <typename MT>
+__device__ __forceinline__ mq_t<MT> mq_load(rsrc_t r, unsigned vo, unsigned so, unsigned vo8, unsigned so8) {
+  static_assert(kMaskF32<MT> || std::is_same<MT, uint8_t>::value, "the mask is u8 or f32");
+  if constexpr (kMaskF32<MT>) return __builtin_bit_cast(f4, __builtin_amdgcn_raw_buffer_load_b128(r, vo, so, kAuxNT));
+  else return __builtin_amdgcn_raw_buffer_load_b32(r, vo8, so8, kAuxNT);
+}
+template <typename MT>
+__device__ __forceinline__ float mq_get(const mq_t<MT>& q, int j) {
+  if constexpr (kMaskF32<MT>) return q[j];
+  else return (float)((q >> (8 * j)) & 0xffu);
+}
+template <typename MT>
+__device__ __forceinline__ float m_load(rsrc_t r, unsigned vo, unsigned so, unsigned vo8, unsigned so8) {
+  if constexpr (kMaskF32<MT>) return bl32<true>(r, vo, so);
+  else return bl8<true>(r, vo8, so8);
+}
 template <bool NTL = false>
 __device__ __forceinline__ void bs32(rsrc_t r, float v, unsigned vo, unsigned so) {
   __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v), r, vo, so, NTL ? kAuxNT : 0);
@@ -307,7 +335,7 @@ struct Twm {
   float t[N], w[N], m[N];
 };
 
-template <int KN>
+template <int KN, typename MT = uint8_t>
 __device__ __forceinline__ void fwd_load_twm(Twm<KN>& r, const FwdU U, const OffEnt* __restrict__ ent, int k0, int n,
                                              unsigned pb, unsigned pm) {
 #pragma unroll
@@ -317,7 +345,7 @@ __device__ __forceinline__ void fwd_load_twm(Twm<KN>& r, const FwdU U, const Off
     const unsigned so = U.kzo + (hi ? i - U.ks : i) * U.kcs;
     r.t[u] = bl32<true>(hi ? U.tB1 : U.tB, pb, so);
     r.w[u] = bl32<true>(hi ? U.wB1 : U.wB, pb, so);
-    r.m[u] = U.has_m ? bl8<true>(U.mB, pm, (U.kzo >> 2) + i * U.S32) : 1.f;
+    r.m[u] = U.has_m ? m_load<MT>(U.mB, pb, so, pm, (U.kzo >> 2) + i * U.S32) : 1.f;  // (f32: ksplit == K, checked on the host)
   }
 }
 
@@ -341,11 +369,11 @@ __device__ __forceinline__ void fwd_finish(const FwdU U, int K, float* s_part, c
 // ------------------------------------------------------------------------------------------------
 // forward, tiled.  SELF: e_other == e (own pixel comes out of LDS too).
 // ------------------------------------------------------------------------------------------------
-template <typename T, int D_T, int TH, int TW, int PLQ, bool CROP, bool TRAIN, bool SELF>
+template <typename T, int D_T, int TH, int TW, int PLQ, bool CROP, bool TRAIN, bool SELF, typename MT = uint8_t>
 __global__ __launch_bounds__(TH* TW, (D_T > 16 ? 2 : 4)) void k_fwd_tiled(const KParams P, const TParams Q, const T* __restrict__ e,
                                                          const T* __restrict__ eo, const float* __restrict__ target,
                                                          const float* __restrict__ weight,
-                                                         const uint8_t* __restrict__ mask, float* __restrict__ affs,
+                                                         const MT* __restrict__ mask, float* __restrict__ affs,
                                                          float* __restrict__ gout, LossState* __restrict__ st, float* __restrict__ inv_out) {
   typedef Lds<D_T, PLQ> L;
   constexpr int NT = TH * TW, NW = NT / 64;
@@ -401,8 +429,8 @@ __global__ __launch_bounds__(TH* TW, (D_T > 16 ? 2 : 4)) void k_fwd_tiled(const 
   //     during the whole staging phase.  Exposed memory round trips per tile: one (the staging loads).
   Twm<KN> sa;
   Twm<2> sf;
-  if (TRAIN && Q.n_near > 0) fwd_load_twm<KN>(sa, U, Q.near, 0, Q.n_near, pb, pm);
-  if (TRAIN && Q.n_far > 0) fwd_load_twm<2>(sf, U, Q.far, 0, Q.n_far, pb, pm);
+  if (TRAIN && Q.n_near > 0) fwd_load_twm<KN, MT>(sa, U, Q.near, 0, Q.n_near, pb, pm);
+  if (TRAIN && Q.n_far > 0) fwd_load_twm<2, MT>(sf, U, Q.far, 0, Q.n_far, pb, pm);
   float own[D_T];
   if (!SELF) {
 #pragma unroll
@@ -454,7 +482,7 @@ __global__ __launch_bounds__(TH* TW, (D_T > 16 ? 2 : 4)) void k_fwd_tiled(const 
 
   // ---- near offsets: neighbour vector from LDS -----------------------------------------------------
   for (int k0 = 0; k0 < Q.n_near; k0 += KN) {
-    if (TRAIN && k0 > 0) fwd_load_twm<KN>(sa, U, Q.near, k0, Q.n_near, pb, pm);
+    if (TRAIN && k0 > 0) fwd_load_twm<KN, MT>(sa, U, Q.near, k0, Q.n_near, pb, pm);
 #pragma unroll
     for (int u = 0; u < KN; ++u) {
       if (k0 + u < Q.n_near) {  // uniform
@@ -478,7 +506,7 @@ __global__ __launch_bounds__(TH* TW, (D_T > 16 ? 2 : 4)) void k_fwd_tiled(const 
   // ---- far offsets: neighbour vectors straight from global (L2), two at a time ------------------------
   for (int k = 0; k < Q.n_far; k += 2) {
     if (k > 0) {
-      if (TRAIN) fwd_load_twm<2>(sf, U, Q.far, k, Q.n_far, pb, pm);
+      if (TRAIN) fwd_load_twm<2, MT>(sf, U, Q.far, k, Q.n_far, pb, pm);
       PEA_FWD_LOAD_FAR(fvA, fokA, k)
       if (k + 1 < Q.n_far) PEA_FWD_LOAD_FAR(fvB, fokB, k + 1)
     }
@@ -530,11 +558,11 @@ __device__ __forceinline__ void bs128(rsrc_t r, f4 v, unsigned vo, unsigned so) 
   asm volatile("s_nop 1" ::"v"(d) : "memory");
 }
 
-template <typename T, int D_T, int TH, int TW, int PLQ, bool OVL, bool CROP, bool TRAIN, bool SELF>
+template <typename T, int D_T, int TH, int TW, int PLQ, bool OVL, bool CROP, bool TRAIN, bool SELF, typename MT = uint8_t>
 __global__ __launch_bounds__(TH* TW, (D_T > 16 ? 2 : 4)) void k_fwd_tiled_v(const KParams P, const TParams Q, const T* __restrict__ e,
                                                            const T* __restrict__ eo, const float* __restrict__ target,
                                                            const float* __restrict__ weight,
-                                                           const uint8_t* __restrict__ mask, float* __restrict__ affs,
+                                                           const MT* __restrict__ mask, float* __restrict__ affs,
                                                            float* __restrict__ gout, LossState* __restrict__ st, float* __restrict__ inv_out) {
   typedef Lds<D_T, PLQ> L;
   constexpr int NT = TH * TW, TP = NT, QP = TP / 4, NSL = QP / 64;
@@ -572,7 +600,7 @@ __global__ __launch_bounds__(TH* TW, (D_T > 16 ? 2 : 4)) void k_fwd_tiled_v(cons
   unsigned ivo[ITEMS];   // byte offset of the quad in an f32 plane, kOOB if the quad is outside / slot unused
   int iqd[ITEMS], igy[ITEMS], igx[ITEMS], ioz[ITEMS];
   f4 t4[ITEMS], w4[ITEMS];
-  unsigned m4[ITEMS];
+  mq_t<MT> m4[ITEMS];
 #pragma unroll
   for (int it = 0; it < ITEMS; ++it) {
     const int tt = it * NT + (int)threadIdx.x;
@@ -592,8 +620,8 @@ __global__ __launch_bounds__(TH* TW, (D_T > 16 ? 2 : 4)) void k_fwd_tiled_v(cons
       const unsigned so = kzo + (unsigned)ien[it].i * kcs;
       t4[it] = __builtin_bit_cast(f4, __builtin_amdgcn_raw_buffer_load_b128(tB, ivo[it], so, kAuxNT));
       w4[it] = __builtin_bit_cast(f4, __builtin_amdgcn_raw_buffer_load_b128(wB, ivo[it], so, kAuxNT));
-      m4[it] = has_m ? __builtin_amdgcn_raw_buffer_load_b32(mB, lv ? ivo[it] >> 2 : kOOB, (kzo >> 2) + (unsigned)ien[it].i * (unsigned)P.S, kAuxNT)
-                     : 0x01010101u;
+      m4[it] = has_m ? mq_load<MT>(mB, ivo[it], so, lv ? ivo[it] >> 2 : kOOB, (kzo >> 2) + (unsigned)ien[it].i * (unsigned)P.S)
+                     : mq_ones<MT>();
     }
   }
 
@@ -704,7 +732,7 @@ __global__ __launch_bounds__(TH* TW, (D_T > 16 ? 2 : 4)) void k_fwd_tiled_v(cons
       f4 g4;
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
-        const float m = (float)((m4[it] >> (8 * j)) & 0xffu);
+        const float m = mq_get<MT>(m4[it], j);
         const float r = a4[j] * m - t4[it][j] * m;
         float wr = w4[it][j] * r;
         if (CROP && !rep) {  // a cropped-away neighbour carries no loss term (its a is already 0)

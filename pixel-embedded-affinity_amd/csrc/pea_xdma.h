@@ -686,10 +686,11 @@ struct LabArgs {
   const float* wtab;      // [B, K, 2]: weight of target-1 pixels, of target-0 pixels
   unsigned lflags;        // PEA_TGT_*
 };
-template <int D_T, int TH, int TW, int PSU, bool CROP, bool TRAIN, int ZF = 0, bool OTHER = false, int WPE = 4, bool LAB = false>
+template <int D_T, int TH, int TW, int PSU, bool CROP, bool TRAIN, int ZF = 0, bool OTHER = false, int WPE = 4, bool LAB = false,
+          typename MT = uint8_t>
 __global__ __launch_bounds__(TH* TW, WPE) void k_fwd_xdma(const KParams P, const XParams C, const float* __restrict__ e,
                                                            const float* __restrict__ target, const float* __restrict__ weight,
-                                                           const uint8_t* __restrict__ mask, float* __restrict__ affs,
+                                                           const MT* __restrict__ mask, float* __restrict__ affs,
                                                            float* __restrict__ gout, LossState* __restrict__ st,
                                                            float* __restrict__ inv_out,
                                                            const float* __restrict__ own, float* __restrict__ inv_other_out,
@@ -733,7 +734,7 @@ __global__ __launch_bounds__(TH* TW, WPE) void k_fwd_xdma(const KParams P, const
   unsigned ivo[ITEMS];
   int iqd[ITEMS], igy[ITEMS], igx[ITEMS], isl[ITEMS];
   f4 t4[ITEMS], w4[ITEMS];
-  unsigned m4[ITEMS];
+  mq_t<MT> m4[ITEMS];
   // (the 80-VGPR instantiations evaluate this after the channel loop: three registers less across it)
 #define PEA_XITEMS()                                                                                                      \
   int tid_i = (int)threadIdx.x;                                                                                           \
@@ -758,9 +759,9 @@ __global__ __launch_bounds__(TH* TW, WPE) void k_fwd_xdma(const KParams P, const
       const unsigned so = ezo + (unsigned)isl[it] * ecs;                                                                  \
       t4[it] = __builtin_bit_cast(f4, __builtin_amdgcn_raw_buffer_load_b128(tB, ivo[it], so, kAuxNT));                    \
       w4[it] = __builtin_bit_cast(f4, __builtin_amdgcn_raw_buffer_load_b128(wB, ivo[it], so, kAuxNT));                    \
-      m4[it] = has_m ? __builtin_amdgcn_raw_buffer_load_b32(mB, ivo[it] == kOOB ? kOOB : ivo[it] >> 2,                    \
-                                                           (ezo >> 2) + (unsigned)isl[it] * (unsigned)P.S, kAuxNT)        \
-                     : 0x01010101u;                                                                                       \
+      m4[it] = has_m ? mq_load<MT>(mB, ivo[it], so, ivo[it] == kOOB ? kOOB : ivo[it] >> 2,                            \
+                                   (ezo >> 2) + (unsigned)isl[it] * (unsigned)P.S)                                    \
+                     : mq_ones<MT>();                                                                                 \
     }                                                                                                                     \
   }
   if (!LATE && !LAB) PEA_XLOAD_TWM()
@@ -1063,7 +1064,7 @@ __global__ __launch_bounds__(TH* TW, WPE) void k_fwd_xdma(const KParams P, const
       const int ax_ = C.oax[sl], od_ = C.od[sl];
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
-        const float m = (float)((m4[it] >> (8 * j)) & 0xffu);
+        const float m = mq_get<MT>(m4[it], j);
         const float r = a4[j] * m - t4[it][j] * m;
         float wr = w4[it][j] * r;
         if (CROP) {  // a cropped-away neighbour carries no loss term (its a is already 0)

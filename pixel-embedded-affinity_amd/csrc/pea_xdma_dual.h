@@ -30,11 +30,11 @@ struct DualFwdArgs {
   float gs2[kXK];        // 2 lambda_i / N_i of the cross loss, per channel (the self loss': XParams::gs)
 };
 
-template <int TH, int TW, int PSU, bool CROP, int NB>
+template <int TH, int TW, int PSU, bool CROP, int NB, typename MT = uint8_t>
 __global__ __launch_bounds__(TH* TW, NB == 3 ? 2 : 4) void k_fwd_xdma_dual(const KParams P, const XParams C, const float* __restrict__ e,
                                                                            const float* __restrict__ target,
                                                                            const float* __restrict__ weight,
-                                                                           const uint8_t* __restrict__ mask, float* __restrict__ affs,
+                                                                           const MT* __restrict__ mask, float* __restrict__ affs,
                                                                            float* __restrict__ gout, LossState* __restrict__ st,
                                                                            float* __restrict__ inv_out, const DualFwdArgs DA) {
   constexpr int D_T = 16, NT = TH * TW, PS = PSU * 256, NP = D_T / 2, TP = NT, QP = TP / 4, NSL = QP / 64, KMAX = kXP;
@@ -321,7 +321,7 @@ __global__ __launch_bounds__(TH* TW, NB == 3 ? 2 : 4) void k_fwd_xdma_dual(const
   unsigned ivo[ITEMS];
   int iqd[ITEMS], igy[ITEMS], igx[ITEMS], isl[ITEMS];
   f4 t4[ITEMS], w4[ITEMS];
-  unsigned m4[ITEMS];
+  mq_t<MT> m4[ITEMS];
   int tid_i = (int)threadIdx.x;
   asm volatile("" : "+v"(tid_i));  // opaque: not hoisted back over the channel loop
 #pragma unroll
@@ -343,9 +343,9 @@ __global__ __launch_bounds__(TH* TW, NB == 3 ? 2 : 4) void k_fwd_xdma_dual(const
     const unsigned so = ezo + (unsigned)isl[it] * ecs;
     t4[it] = __builtin_bit_cast(f4, __builtin_amdgcn_raw_buffer_load_b128(tB, ivo[it], so, kAuxNT));
     w4[it] = __builtin_bit_cast(f4, __builtin_amdgcn_raw_buffer_load_b128(wB, ivo[it], so, kAuxNT));
-    m4[it] = has_m ? __builtin_amdgcn_raw_buffer_load_b32(mB, ivo[it] == kOOB ? kOOB : ivo[it] >> 2,
-                                                         (ezo >> 2) + (unsigned)isl[it] * (unsigned)P.S, kAuxNT)
-                   : 0x01010101u;
+    m4[it] = has_m ? mq_load<MT>(mB, ivo[it], so, ivo[it] == kOOB ? kOOB : ivo[it] >> 2,
+                                 (ezo >> 2) + (unsigned)isl[it] * (unsigned)P.S)
+                   : mq_ones<MT>();
   }
   lds_barrier();
 #pragma unroll
@@ -366,7 +366,7 @@ __global__ __launch_bounds__(TH* TW, NB == 3 ? 2 : 4) void k_fwd_xdma_dual(const
     const int ax_ = C.oax[sl], od_ = C.od[sl];
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
-      const float m = (float)((m4[it] >> (8 * j)) & 0xffu);
+      const float m = mq_get<MT>(m4[it], j);
       const float r = a4[j] * m - t4[it][j] * m;
       const float r2 = c4[j] * m - t4[it][j] * m;
       float wr = w4[it][j] * r, wr2 = w4[it][j] * r2;

@@ -401,10 +401,10 @@ __global__ __launch_bounds__(TH* TW, WPE) void k_bwd_xdma_h(const KParams P, con
 // OTHER: the cross loss a_i(p) = <ehat(p), ehat_other(p + o_i)>: `e` is the SECOND operand (staged), the own pixel comes from the own
 // tile of `own` staged beside each chunk by wave 0; both 1 / norm planes are written (inv_out: own, inv_other_out: the second operand's)
 template <int D_T, int TH, int TW, int PSU, bool CROP, bool TRAIN, int WPE, bool HW = false, int NXP = kXP, bool OTHER = false,
-          typename T = __half>
+          typename T = __half, typename MT = uint8_t>
 __global__ __launch_bounds__(TH* TW, WPE) void k_fwd_xdma_h(const KParams P, const XParams C, const T* __restrict__ e,
                                                              const float* __restrict__ target, const float* __restrict__ weight,
-                                                             const uint8_t* __restrict__ mask, float* __restrict__ affs,
+                                                             const MT* __restrict__ mask, float* __restrict__ affs,
                                                              float* __restrict__ gout, LossState* __restrict__ st,
                                                              float* __restrict__ inv_out, const T* __restrict__ own,
                                                              float* __restrict__ inv_other_out) {
@@ -571,7 +571,7 @@ __global__ __launch_bounds__(TH* TW, WPE) void k_fwd_xdma_h(const KParams P, con
   unsigned ivo[ITEMS];
   int iqd[ITEMS], igy[ITEMS], igx[ITEMS], isl[ITEMS];
   f4 t4[ITEMS], w4[ITEMS];
-  unsigned m4[ITEMS];
+  mq_t<MT> m4[ITEMS];
 #pragma unroll
   for (int it = 0; it < ITEMS; ++it) {
     const int tt = it * NT + tid_;
@@ -592,9 +592,9 @@ __global__ __launch_bounds__(TH* TW, WPE) void k_fwd_xdma_h(const KParams P, con
       const unsigned so = ezo + (unsigned)isl[it] * ecs;
       t4[it] = __builtin_bit_cast(f4, __builtin_amdgcn_raw_buffer_load_b128(tB, ivo[it], so, kAuxNT));
       w4[it] = __builtin_bit_cast(f4, __builtin_amdgcn_raw_buffer_load_b128(wB, ivo[it], so, kAuxNT));
-      m4[it] = has_m ? __builtin_amdgcn_raw_buffer_load_b32(mB, ivo[it] == kOOB ? kOOB : ivo[it] >> 2,
-                                                           (ezo >> 2) + (unsigned)isl[it] * (unsigned)P.S, kAuxNT)
-                     : 0x01010101u;
+      m4[it] = has_m ? mq_load<MT>(mB, ivo[it], so, ivo[it] == kOOB ? kOOB : ivo[it] >> 2,
+                                   (ezo >> 2) + (unsigned)isl[it] * (unsigned)P.S)
+                     : mq_ones<MT>();
     }
   }
   lds_barrier();
@@ -617,7 +617,7 @@ __global__ __launch_bounds__(TH* TW, WPE) void k_fwd_xdma_h(const KParams P, con
       const int ax_ = C.oax[sl], od_ = C.od[sl];
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
-        const float m = (float)((m4[it] >> (8 * j)) & 0xffu);
+        const float m = mq_get<MT>(m4[it], j);
         const float r = a4[j] * m - t4[it][j] * m;
         float wr = w4[it][j] * r;
         if (CROP) {

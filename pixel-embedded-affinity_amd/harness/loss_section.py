@@ -101,14 +101,9 @@ class _TensorSection(torch.autograd.Function):
                 t, w, m = tensors[0] if j == ncall - 1 else tensors[j]
                 t, ts = op._batch_strided(t, "target", torch.float32, kshape)
                 w, ws = op._batch_strided(w, "weightmap", torch.float32, kshape)
-                ms = 0
-                if m is not None:
-                    if m.dtype == torch.bool:
-                        m = m.view(torch.uint8)
-                    elif m.dtype != torch.uint8:  # the reference packs the deep-supervision masks as float thirds of `downN`
-                        m = m.to(torch.uint8)      # (runs on the stream of this loss: the side stream for the small scales)
-                    m, ms = op._batch_strided(m, "mask", torch.uint8, kshape)
-                d = op.make_desc(spec, e_c, ts, ws, ms)
+                # (the reference packs the deep-supervision masks as float thirds of `downN`: taken as they are, no copy)
+                m, ms, mflag = op.mask_arg(m, kshape)
+                d = op.make_desc(spec, e_c, ts, ws, ms, mflag)
                 work, wsb = op.workspace(dev, d)
                 g = torch.empty(kshape, dtype=torch.float32, device=dev)
                 inv = None
@@ -139,17 +134,11 @@ class _TensorSection(torch.autograd.Function):
                 t, w, m = tensors[0]
                 t, ts = op._batch_strided(t, "target", torch.float32, kshape)
                 w, ws = op._batch_strided(w, "weightmap", torch.float32, kshape)
-                ms = 0
-                if m is not None:
-                    if m.dtype == torch.bool:
-                        m = m.view(torch.uint8)
-                    elif m.dtype != torch.uint8:
-                        m = m.to(torch.uint8)
-                    m, ms = op._batch_strided(m, "mask", torch.uint8, kshape)
-                d0 = op.make_desc(spec0, e_c, ts, ws, ms)
+                m, ms, mflag = op.mask_arg(m, kshape)
+                d0 = op.make_desc(spec0, e_c, ts, ws, ms, mflag)
                 if not op.cross_supported(d0, 5):
                     return None
-                dx = op.make_desc(specx, e_c, ts, ws, ms)
+                dx = op.make_desc(specx, e_c, ts, ws, ms, mflag)
                 work, wsb = op.workspace(dev, d0, 2)
                 half = wsb // 2
                 g0 = torch.empty(kshape, dtype=torch.float32, device=dev)
@@ -413,7 +402,7 @@ def cvppp_loss_section(embedding, emds, ema_embedding, target, weightmap, affs_m
         for j, down in enumerate(downs):
             k = nb_half * (4 - j)
             m = down[:, 2 * k:3 * k]
-            tensors.append((down[:, 0:k], down[:, k:2 * k], m))  # (a float mask third is converted where its loss is launched: side stream)
+            tensors.append((down[:, 0:k], down[:, k:2 * k], m))  # (a float mask third goes to the kernels as it is: PEA_FLAG_MASK_F32)
         loss, pred, losses = _TensorSection.apply(specs, weights, ema_embedding, tensors, embedding, *emds)
         return loss, pred, _section_parts(losses, weights, self_emb, cross_emb)
     loss, pred, parts = cvppp_loss_section_composed(embedding, emds, ema_embedding, target, weightmap, affs_mask, downs, criterion,
