@@ -68,7 +68,7 @@ extern "C" {
 #define PEA_NORM_CROPPED 1
 #define PEA_NORM_FULL 2
 /* flags */
-/* activation of the affs OUTPUT (the loss and its gradient always use the raw cosine a); applied in this order: */
+/* activation of the affs OUTPUT (the loss and its gradient use the raw cosine a unless PEA_FLAG_LOSS_ACT is set); applied in this order: */
 #define PEA_FLAG_HALF_SHIFT 4u /* a -> (a + 1) / 2   (scripts_cvppp/loss/loss_embedding.py:10,35; for unit vectors also the L2 affinity
                                   1 - |ehat_p - ehat_q|^2 / 4 of scripts_ac3ac4/loss/embedding2affs_3d_l2.py:10-11) */
 #define PEA_FLAG_RELU_AFFS 1u  /* a -> max(a, 0)     (F.relu(pred), scripts_cvppp/main.py:312, inference.py:193) */
@@ -83,6 +83,21 @@ extern "C" {
                                   (const uint8_t *)(const void *)mask_f32; mask_bstride then counts f32 elements.  Any finite m is
                                   honoured (r = a m - t m, g carries m^2).  Ignored where mask == NULL and by the backward / inference
                                   calls; the labels-in calls, which derive their own masks, return PEA_E_DESC */
+#define PEA_FLAG_LOSS_ACT 64u   /* the LOSS of pea_affinity_fwd / _fwd_ex is taken on the ACTIVATED map, as the reference's sibling loss modules
+                                  do (scripts_cvppp/loss/loss_embedding.py:7-31, 49-73: clamp((cos + 1) / 2, 0, 1), eps 1e-6;
+                                  loss_embedding_exp.py:7-31: clamp(cos, 0, 1), eps 1e-6; loss_embedding_norm.py:7-36, 60-90: F.normalize,
+                                  eps 1e-12, then clamp((dot + 1) / 2, 0, 1) or, L2 mode, clamp(1 - |ehat_s - ehat|^2 / 4, 0, 1); the copies
+                                  under scripts_bbbc039v1/loss are the same files).  With v = HALF_SHIFT ? (a + 1) / 2 : a and
+                                  u = CLAMP01 ? min(max(v, 0), 1) : v (what the activation bits store in affs):
+                                      r_i(p) = u m - t m,   L_i = sum w r^2 / N_i,   g_i(p) = lambda_i 2 w m r s / N_i,
+                                      s = du / da = (HALF_SHIFT ? 1/2 : 1) * (CLAMP01 ? [0 <= v <= 1] : 1)
+                                  (torch.clamp's backward is inclusive at both edges).  g_out is still d loss / d a(raw): the backward
+                                  calls need nothing new and ignore the bit, as the inference calls do.  Valid with HALF_SHIFT, CLAMP01 or
+                                  both; with RELU_AFFS or ONE_MINUS, or with neither of the two, pea_desc_validate and every entry point
+                                  return PEA_E_DESC.  Entry points without the form return PEA_E_UNSUPPORTED before anything is launched:
+                                  pea_affinity_fwd_dual_ex (pea_cross_supported(desc, 5) == 0) and the three labels-in calls.  The L2 mode
+                                  of loss_embedding_norm.py equals (1 + cos) / 2 for unit vectors only: at a pixel with |e| < eps
+                                  F.normalize yields a non-unit vector and the two differ there; the library computes the cosine form */
 
 /* error codes: 0 = ok, negative = PEA_E_*, positive = a hipError_t from the runtime */
 #define PEA_OK 0

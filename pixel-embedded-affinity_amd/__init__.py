@@ -16,6 +16,12 @@ from .affinity_op import (AffinityMap, AffinitySpec, FusedAffinityMSE, Graphed, 
 from .loss.loss import WeightedMSE
 from .loss.loss_embedding_mse import (ema_embedding_loss, ema_embedding_loss_from_labels, embedding2affs, embedding_loss,
                                       embedding_loss_from_labels)
+from .loss import loss_embedding, loss_embedding_exp, loss_embedding_norm
+from .loss.loss_embedding import (ema_embedding_loss as ema_embedding_loss_half_clamp, embedding2affs as embedding2affs_half_clamp,
+                                  embedding_loss as embedding_loss_half_clamp)
+from .loss.loss_embedding_exp import embedding2affs as embedding2affs_clamp, embedding_loss as embedding_loss_clamp
+from .loss.loss_embedding_norm import (ema_embedding_loss as ema_embedding_loss_normalized, embedding2affs as embedding2affs_normalized,
+                                       embedding_loss as embedding_loss_normalized)
 from .loss.loss_embedding_mse_3d import (ema_embedding_loss_norm1, ema_embedding_loss_norm5, ema_embedding_loss_norm5_from_labels,
                                          ema_embedding_loss_norm6, embedding_loss_norm6,
                                          embedding_loss_norm1, embedding_loss_norm1_from_labels, embedding_loss_norm5,
@@ -44,5 +50,8 @@ __all__ = [
     "ema_embedding_loss_from_labels", "LabelsAffinityMSE", "cvppp_loss_section_from_labels", "cvppp_loss_section_composed", "ac3ac4_loss_section_composed",
     "ac3ac4_loss_section_from_labels",
     "embedding_loss_norm1_from_labels", "embedding_loss_norm5_from_labels", "ema_embedding_loss_norm5_from_labels",
+    "loss_embedding", "loss_embedding_exp", "loss_embedding_norm", "embedding_loss_half_clamp", "ema_embedding_loss_half_clamp",
+    "embedding2affs_half_clamp", "embedding_loss_clamp", "embedding2affs_clamp", "embedding_loss_normalized",
+    "ema_embedding_loss_normalized", "embedding2affs_normalized",
     "embedding_loss_norm6", "ema_embedding_loss_norm6", "EmbeddingHead", "OutConv", "head_conv3d_block", "cvppp_label_weight_tables", "cvppp_validation_section",
 ]

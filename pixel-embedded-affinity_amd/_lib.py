@@ -22,6 +22,7 @@ F32, F16, BF16 = 0, 1, 2
 NORM_BX, NORM_CROPPED, NORM_FULL = 0, 1, 2
 FLAG_RELU_AFFS, FLAG_ONE_MINUS, FLAG_HALF_SHIFT, FLAG_CLAMP01, FLAG_ACCUMULATE_DE = 1, 2, 4, 8, 16  # activation of the affs output (include/pea.h)
 FLAG_MASK_F32 = 32  # the mask of the training forwards holds f32 values (include/pea.h PEA_FLAG_MASK_F32)
+FLAG_LOSS_ACT = 64  # the loss of the training forwards is taken on the activated map (include/pea.h PEA_FLAG_LOSS_ACT)
 TGT_PADDING, TGT_BOTH_FOREGROUND, TGT_MASK_INSIDE, TGT_ACCUMULATE = 1, 2, 4, 8
 
 EXPORTS = ("pea_version", "pea_strerror", "pea_desc_validate", "pea_workspace_bytes", "pea_workspace_init", "pea_reload_env",

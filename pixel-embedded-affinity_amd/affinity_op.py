@@ -36,7 +36,8 @@ class AffinitySpec(object):
         if len(self.lam) != self.K:
             raise ValueError("lambda list must have one entry per offset")
         self.border, self.norm, self.eps = border, norm, float(eps)
-        self.act = int(act)  # _lib.FLAG_* activation bits of the affs output (the loss always uses the raw cosine)
+        # _lib.FLAG_* activation bits of the affs output; the loss uses the raw cosine unless FLAG_LOSS_ACT comes with them
+        self.act = int(act)
         self.relu = bool(relu) or bool(self.act & _lib.FLAG_RELU_AFFS)
 
     @property
@@ -474,6 +475,7 @@ ACTIVATIONS = {
     "mutex": _lib.FLAG_RELU_AFFS | _lib.FLAG_ONE_MINUS,            # 1 - relu(a): what seg_mutex hands to elf (utils/seg_mutex.py:4-5)
     "half": _lib.FLAG_HALF_SHIFT,                                  # (a + 1) / 2 = the L2 affinity 1 - |ehat_p - ehat_q|^2 / 4
     "half_clamp": _lib.FLAG_HALF_SHIFT | _lib.FLAG_CLAMP01,        # loss_embedding.py's embedding2affs: clamp((a + 1) / 2, 0, 1)
+    "clamp": _lib.FLAG_CLAMP01,                                    # loss_embedding_exp.py's embedding2affs: clamp(a, 0, 1)
 }
 
 

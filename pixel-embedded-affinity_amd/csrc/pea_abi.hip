@@ -34,6 +34,9 @@ int validate(const PeaDesc* d) {
   if (d->norm < PEA_NORM_BX || d->norm > PEA_NORM_FULL) return PEA_E_DESC;
   if (!(d->eps > 0.f)) return PEA_E_DESC;
   if (d->target_bstride < 0 || d->weight_bstride < 0 || d->mask_bstride < 0) return PEA_E_DESC;
+  if (d->flags & PEA_FLAG_LOSS_ACT) {  // the loss on the activated map: half shift and / or clamp, nothing else (include/pea.h)
+    if (!(d->flags & (PEA_FLAG_HALF_SHIFT | PEA_FLAG_CLAMP01)) || (d->flags & (PEA_FLAG_RELU_AFFS | PEA_FLAG_ONE_MINUS))) return PEA_E_DESC;
+  }
   const long long S = (long long)d->dims[0] * d->dims[1] * d->dims[2];
   if (S > 0x7fffffffLL - kBlock) return PEA_E_UNSUPPORTED;
   if ((S + kBlock - 1) / kBlock * (long long)d->B > 0x7fffff00LL) return PEA_E_UNSUPPORTED;
@@ -188,6 +191,7 @@ int pea_affinity_fwd_ex(const PeaDesc* desc, const void* e, const void* e_other,
   A.t = target; A.w = weight; A.m = mask; A.affs = affs; A.gout = g_out;
   A.st = (LossState*)workspace; A.loss_out = loss_out; A.inv_out = inv_norm_out;
   A.dtype = desc->dtype; A.train = true; A.mf32 = mask && (desc->flags & PEA_FLAG_MASK_F32);
+  A.lact = (desc->flags & PEA_FLAG_LOSS_ACT) != 0;
   rc = run_fwd(P, A, s);
   if (rc) return rc;
   if (e_other && e_other == e && inv_norm_out) {
@@ -207,6 +211,8 @@ int pea_affinity_fwd_dual_ex(const PeaDesc* desc, const PeaDesc* desc_cross, con
   if (rc) return rc;
   rc = validate(desc_cross);
   if (rc) return rc;
+  // the one-launch pair has no PEA_FLAG_LOSS_ACT form (pea_cross_supported(desc, 5) == 0): two pea_affinity_fwd_ex calls
+  if ((desc->flags | desc_cross->flags) & PEA_FLAG_LOSS_ACT) return PEA_E_UNSUPPORTED;
   if (!e || !ema || !target || !weight || !g_out || !g_cross_out || !inv_norm_out || !inv_norm_other_out || !loss_out || !loss_cross_out)
     return PEA_E_NULL;
   // one geometry, one stencil, one normaliser: the two descriptors may differ in lambda (affs0_weight of the cross loss) and in the
@@ -262,7 +268,7 @@ int pea_affinity_fwd(const PeaDesc* desc, const void* e, const void* e_other, co
 int pea_cross_supported(const PeaDesc* desc, int backward) {
   if (validate(desc)) return 0;
   const KParams P = make_params(desc);
-  if (backward == 5) return xdma_fwd_dual_supported(P, desc->dtype) ? 1 : 0;  // does pea_affinity_fwd_dual_ex fuse the pair?
+  if (backward == 5) return !(desc->flags & PEA_FLAG_LOSS_ACT) && xdma_fwd_dual_supported(P, desc->dtype) ? 1 : 0;  // does pea_affinity_fwd_dual_ex fuse the pair?
   if (backward == 4) return xdma_cross_supported(P, desc->dtype, 4);  // ... with a detached second operand?
   if (backward == 3) {  // does pea_affinity_bwd_ex2 READ the raw affinity map for this descriptor (self loss)?
     if (zmarch_bwd_supported(P, desc->dtype)) return 1;
@@ -379,6 +385,7 @@ int pea_affinity_fwd_bwd_labels_ex(const PeaDesc* desc, const void* e, const voi
   int rc = validate(desc);
   if (rc) return rc;
   if (desc->flags & PEA_FLAG_MASK_F32) return PEA_E_DESC;  // the mask is derived from the labels: there is none to type
+  if (desc->flags & PEA_FLAG_LOSS_ACT) return PEA_E_UNSUPPORTED;  // the labels-in kernels take the loss on the raw cosine only
   if (!e || !labels || !wtab || !loss_out || !de) return PEA_E_NULL;
   const size_t es = dtype_bytes(desc->dtype);
   if (misaligned(e, es) || misaligned(e_other, es) || misaligned(de, es) || misaligned(affs, 4) || misaligned(labels, 4) ||
@@ -439,6 +446,7 @@ int pea_affinity_fwd_bwd_labels_dual(const PeaDesc* desc, const PeaDesc* desc_cr
   rc = validate(desc_cross);
   if (rc) return rc;
   if ((desc->flags | desc_cross->flags) & PEA_FLAG_MASK_F32) return PEA_E_DESC;  // (as pea_affinity_fwd_bwd_labels_ex)
+  if ((desc->flags | desc_cross->flags) & PEA_FLAG_LOSS_ACT) return PEA_E_UNSUPPORTED;
   if (!e || !ema || !labels || !wtab || !loss_out || !loss_cross_out || !de) return PEA_E_NULL;
   if (desc->B != desc_cross->B || desc->D != desc_cross->D || desc->K != desc_cross->K || desc->dtype != desc_cross->dtype ||
       desc->border != desc_cross->border || memcmp(desc->dims, desc_cross->dims, sizeof(desc->dims)) != 0 ||

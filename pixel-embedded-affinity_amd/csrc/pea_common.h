@@ -94,6 +94,29 @@ __device__ __forceinline__ float act_affs(float a, unsigned af) {
   return a;
 }
 
+// PEA_FLAG_LOSS_ACT (the LACT instantiations of the training forwards): the loss is taken on u = act_affs(a, af), af = HALF_SHIFT and /
+// or CLAMP01 (pea_desc_validate admits nothing else).  The flags are wave-uniform, so the activation is four scalars and no branch:
+//   v = a * sc + of,  u = min(max(v, lo), hi)      (sc, of) = (1/2, 1/2) for the half shift, (lo, hi) = (0, 1) for the clamp, else infinite
+// -- the same bits act_affs stores ((a + 1) / 2 and a / 2 + 1/2 round alike: halving is exact) -- and the slope du / da is sc where the
+// clamp left v alone (u == v: torch.clamp's backward is INCLUSIVE at both edges), 0 where it did not.  The forward folds the slope
+// into g (act_g), so the backward kernels do not know about activations.  The epilogues keep v, not u, across their stores (u is two
+// instructions away from v; keeping both spilled in the 64-VGPR forwards).
+struct ActK {
+  float sc, of, lo, hi;
+};
+__device__ __forceinline__ ActK act_consts(unsigned af) {
+  ActK k;
+  k.sc = (af & PEA_FLAG_HALF_SHIFT) ? 0.5f : 1.0f;
+  k.of = (af & PEA_FLAG_HALF_SHIFT) ? 0.5f : 0.f;
+  k.lo = (af & PEA_FLAG_CLAMP01) ? 0.f : -__builtin_inff();
+  k.hi = (af & PEA_FLAG_CLAMP01) ? 1.0f : __builtin_inff();
+  return k;
+}
+__device__ __forceinline__ float act_v(float a, const ActK& k) { return fmaf(a, k.sc, k.of); }
+__device__ __forceinline__ float act_u(float v, const ActK& k) { return fminf(fmaxf(v, k.lo), k.hi); }
+// g of a term whose raw-cosine form is gs_sc * wr * m, gs_sc = gscale * ActK::sc (exact: sc is a power of two)
+__device__ __forceinline__ float act_g(float u, float v, float gs_sc, float wr, float m) { return u == v ? gs_sc * wr * m : 0.f; }
+
 __device__ __forceinline__ float inv_norm(float ss, float eps) { return 1.0f / fmaxf(sqrtf(ss), eps); }
 
 __device__ __forceinline__ float wave_sum(float v) {

@@ -12,7 +12,8 @@ namespace pea {
 // forward (direct form): affs, (TRAIN) per-workgroup loss partials and g = d loss / d affs
 //   D_T > 0: channels unrolled, own pixel kept in registers;  D_T == 0: generic D, own pixel re-read (L1)
 // ------------------------------------------------------------------------------------------------
-template <typename T, int D_T, bool TRAIN, typename MT = uint8_t>  // MT: the mask, u8 or f32 (PEA_FLAG_MASK_F32)
+// MT: the mask, u8 or f32 (PEA_FLAG_MASK_F32);  LACT: the loss on the activated map (PEA_FLAG_LOSS_ACT, act_u)
+template <typename T, int D_T, bool TRAIN, typename MT = uint8_t, bool LACT = false>
 __global__ __launch_bounds__(kBlock) void k_fwd_direct(const KParams P, const T* __restrict__ e,
                                                        const T* __restrict__ eo,
                                                        const float* __restrict__ target,
@@ -86,10 +87,17 @@ __global__ __launch_bounds__(kBlock) void k_fwd_direct(const KParams P, const T*
         float g = 0.f;
         if (q >= 0) {
           const float m = mask ? (float)mask[(size_t)b * P.mbs + in] : 1.f;
-          const float r = a * m - target[(size_t)b * P.tbs + in] * m;
+          float u = a, v = a, gsc = P.gscale[i];
+          if constexpr (LACT) {  // the loss on the activated value; its slope goes into g
+            const ActK AK = act_consts(P.flags & kActMask);
+            v = act_v(a, AK);
+            u = act_u(v, AK);
+            gsc *= AK.sc;
+          }
+          const float r = u * m - target[(size_t)b * P.tbs + in] * m;
           const float wr = weight[(size_t)b * P.wbs + in] * r;
           contrib = wr * r;
-          g = P.gscale[i] * wr * m;
+          g = LACT ? act_g(u, v, gsc, wr, m) : P.gscale[i] * wr * m;
         }
         if (gout) gout[kb + in] = g;
       }

@@ -128,6 +128,7 @@ struct FwdArgs {
   int dtype;            // PEA_F32 / PEA_F16 / PEA_BF16
   bool train;
   bool mf32;            // m != NULL holds f32 (PEA_FLAG_MASK_F32): the families without an f32-mask form decline the call
+  bool lact;            // training: the loss on the activated map (PEA_FLAG_LOSS_ACT); families without the form decline the call
 };
 // Each returns true if it launched (the caller then launches the loss finish).
 bool xdma_fwd_self(const KParams& P, const FwdArgs& A, hipStream_t s);

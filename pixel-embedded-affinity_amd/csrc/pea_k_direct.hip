@@ -118,17 +118,17 @@ void launch_loss_state_init(LossState* st, int n, hipStream_t s) {
 
 // ---- direct kernels ---------------------------------------------------------------------------------------------------------
 namespace {
-template <typename T, bool TRAIN, typename MT = uint8_t>
+template <typename T, bool TRAIN, typename MT = uint8_t, bool LACT = false>
 void fwd_direct(const KParams& P, const FwdArgs& A, hipStream_t s) {
   const T *ep = (const T*)A.e, *op = (const T*)A.eo;
   const MT* m = (const MT*)(const void*)A.m;
   const size_t lds = TRAIN ? (size_t)P.K * kBlock * sizeof(float) : 0;
   const dim3 g((unsigned)(P.tiles_per_xcd * kXcd)), blk(kBlock);
   switch (P.D) {
-    case 16: hipLaunchKernelGGL((k_fwd_direct<T, 16, TRAIN, MT>), g, blk, lds, s, P, ep, op, A.t, A.w, m, A.affs, A.gout, A.st); break;
-    case 32: hipLaunchKernelGGL((k_fwd_direct<T, 32, TRAIN, MT>), g, blk, lds, s, P, ep, op, A.t, A.w, m, A.affs, A.gout, A.st); break;
-    case 64: hipLaunchKernelGGL((k_fwd_direct<T, 64, TRAIN, MT>), g, blk, lds, s, P, ep, op, A.t, A.w, m, A.affs, A.gout, A.st); break;
-    default: hipLaunchKernelGGL((k_fwd_direct<T, 0, TRAIN, MT>), g, blk, lds, s, P, ep, op, A.t, A.w, m, A.affs, A.gout, A.st); break;
+    case 16: hipLaunchKernelGGL((k_fwd_direct<T, 16, TRAIN, MT, LACT>), g, blk, lds, s, P, ep, op, A.t, A.w, m, A.affs, A.gout, A.st); break;
+    case 32: hipLaunchKernelGGL((k_fwd_direct<T, 32, TRAIN, MT, LACT>), g, blk, lds, s, P, ep, op, A.t, A.w, m, A.affs, A.gout, A.st); break;
+    case 64: hipLaunchKernelGGL((k_fwd_direct<T, 64, TRAIN, MT, LACT>), g, blk, lds, s, P, ep, op, A.t, A.w, m, A.affs, A.gout, A.st); break;
+    default: hipLaunchKernelGGL((k_fwd_direct<T, 0, TRAIN, MT, LACT>), g, blk, lds, s, P, ep, op, A.t, A.w, m, A.affs, A.gout, A.st); break;
   }
 }
 
@@ -170,6 +170,18 @@ int bwd_direct(const KParams& P, int roles, const void* x, const void* nbA, cons
 }  // namespace
 
 void direct_fwd(const KParams& P, const FwdArgs& A, hipStream_t s) {
+  if (A.train && A.lact) {  // the loss on the activated map (PEA_FLAG_LOSS_ACT): the catch-all of every descriptor
+    if (A.mf32) {
+      if (A.dtype == PEA_F16) fwd_direct<__half, true, float, true>(P, A, s);
+      else if (A.dtype == PEA_BF16) fwd_direct<__bf16, true, float, true>(P, A, s);
+      else fwd_direct<float, true, float, true>(P, A, s);
+    } else {
+      if (A.dtype == PEA_F16) fwd_direct<__half, true, uint8_t, true>(P, A, s);
+      else if (A.dtype == PEA_BF16) fwd_direct<__bf16, true, uint8_t, true>(P, A, s);
+      else fwd_direct<float, true, uint8_t, true>(P, A, s);
+    }
+    return;
+  }
   if (A.train && A.mf32) {  // an f32 mask (PEA_FLAG_MASK_F32): training only
     if (A.dtype == PEA_F16) fwd_direct<__half, true, float>(P, A, s);
     else if (A.dtype == PEA_BF16) fwd_direct<__bf16, true, float>(P, A, s);

@@ -29,6 +29,7 @@ struct FwdT {  // typed view of FwdArgs
   LossState* st;
   float* inv_out;
   bool mf32;  // m holds f32 (training): the kernels' MT = float forms
+  bool lact;  // training: the loss on the activated map (PEA_FLAG_LOSS_ACT): the kernels' LACT forms
 };
 // launch a forward's u8-mask form `kern`, or -- training with an f32 mask -- its f32-mask form (KF: the parenthesised kernel,
 // instantiated where the launcher's constexpr kMF says so; the launcher has declined the call where it does not)
@@ -41,6 +42,22 @@ struct FwdT {  // typed view of FwdArgs
   } else {                                                                                                                 \
     PEA_LAUNCH(kern, grid, blk, lds, s, P, Q, e, eo, A.t, A.w, A.m, __VA_ARGS__)                                           \
   }
+
+// the same for the forwards that also have PEA_FLAG_LOSS_ACT forms (KL: u8 mask, instantiated wherever TRAIN; KLF: f32 mask, where kMF)
+#define PEA_LAUNCH_ML(kern, KF, KL, KLF, grid, blk, lds, s, P, Q, e, eo, ...)                                              \
+  if (TRAIN && A.lact) {                                                                                                   \
+    if constexpr (TRAIN) {                                                                                                 \
+      if (A.mf32) {                                                                                                        \
+        if constexpr (kMF) {                                                                                               \
+          constexpr auto kernlf = KLF;                                                                                     \
+          PEA_LAUNCH(kernlf, grid, blk, lds, s, P, Q, e, eo, A.t, A.w, (const float*)(const void*)A.m, __VA_ARGS__)        \
+        }                                                                                                                  \
+      } else {                                                                                                             \
+        constexpr auto kernl = KL;                                                                                         \
+        PEA_LAUNCH(kernl, grid, blk, lds, s, P, Q, e, eo, A.t, A.w, A.m, __VA_ARGS__)                                      \
+      }                                                                                                                    \
+    }                                                                                                                      \
+  } else PEA_LAUNCH_M(kern, KF, grid, blk, lds, s, P, Q, e, eo, __VA_ARGS__)
 
 // forward with the LDS-transposed, dwordx4 epilogue (k_fwd_tiled_v): 16x32 tiles, the dot products laid over the dead region,
 // two workgroups of 8 waves per CU.  The training forward wherever the LDS-DMA kernel (k_fwd_xdma) does not apply.
@@ -66,8 +83,10 @@ bool try_fwd_v(const KParams& P, const FwdT& A, float* inv_out, hipStream_t s) {
 #define PEA_FV(CROP_, SELF_)                                                                                  \
   {                                                                                                           \
     constexpr auto kern = k_fwd_tiled_v<T, D_T, c.TH, c.TW, c.PLQ, true, CROP_, TRAIN, SELF_>;                \
-    PEA_LAUNCH_M(kern, (k_fwd_tiled_v<T, D_T, c.TH, c.TW, c.PLQ, true, CROP_, TRAIN, SELF_, float>),            \
-                 grid, blk, lds, s, P, Q, e, eo, A.affs, A.gout, A.st, inv_out)                  \
+    PEA_LAUNCH_ML(kern, (k_fwd_tiled_v<T, D_T, c.TH, c.TW, c.PLQ, true, CROP_, TRAIN, SELF_, float>),           \
+                  (k_fwd_tiled_v<T, D_T, c.TH, c.TW, c.PLQ, true, CROP_, TRAIN, SELF_, uint8_t, true>),         \
+                  (k_fwd_tiled_v<T, D_T, c.TH, c.TW, c.PLQ, true, CROP_, TRAIN, SELF_, float, true>),           \
+                  grid, blk, lds, s, P, Q, e, eo, A.affs, A.gout, A.st, inv_out)                                \
   }
   const bool crop = P.border != PEA_BORDER_CIRCULAR;
   if (eo == e) { if (crop) PEA_FV(true, true) else PEA_FV(false, true) }
@@ -93,8 +112,10 @@ bool try_fwd_tiled(const KParams& P, const FwdT& A, float* inv_out, hipStream_t 
 #define PEA_FT(CROP_, SELF_)                                                                                  \
   {                                                                                                           \
     constexpr auto kern = k_fwd_tiled<T, D_T, c.TH, c.TW, c.PLQ, CROP_, TRAIN, SELF_>;                        \
-    PEA_LAUNCH_M(kern, (k_fwd_tiled<T, D_T, c.TH, c.TW, c.PLQ, CROP_, TRAIN, SELF_, float>),                    \
-                 grid, blk, lds, s, P, Q, e, eo, A.affs, A.gout, A.st, inv_out)                  \
+    PEA_LAUNCH_ML(kern, (k_fwd_tiled<T, D_T, c.TH, c.TW, c.PLQ, CROP_, TRAIN, SELF_, float>),                   \
+                  (k_fwd_tiled<T, D_T, c.TH, c.TW, c.PLQ, CROP_, TRAIN, SELF_, uint8_t, true>),                 \
+                  (k_fwd_tiled<T, D_T, c.TH, c.TW, c.PLQ, CROP_, TRAIN, SELF_, float, true>),                   \
+                  grid, blk, lds, s, P, Q, e, eo, A.affs, A.gout, A.st, inv_out)                                \
   }
   const bool crop = P.border != PEA_BORDER_CIRCULAR;
   if (eo == e) { if (crop) PEA_FT(true, true) else PEA_FT(false, true) }
@@ -111,6 +132,7 @@ bool try_fwd_chunked(const KParams& P, const FwdT& A, hipStream_t s) {
   if (P.D != D_T || P.border == PEA_BORDER_REPLICATE) return false;
   constexpr bool kMF = TRAIN && std::is_same<T, float>::value;  // f32-mask forms for f32 storage only (as try_fwd_tiled)
   if (TRAIN && A.mf32 && !kMF) return false;
+  if (TRAIN && A.lact) return false;  // no PEA_FLAG_LOSS_ACT form: the one-region kernels (D = 32) or the direct kernels take it
   constexpr TileCfg c = kCfg32;  // 16 x 32 tile, 1041 region pixels: 128 B (DC = 32) or 64 B (DC = 16) of LDS each
   TParams Q;
   if (!plan_tiles_cached(P, c, false, &Q) || Q.n_near > kChN || Q.n_far > kChF) return false;
@@ -190,7 +212,7 @@ bool bwd_roles(const KParams& P, int roles, const void* x, const void* nbA, cons
 bool tiled_fwd(const KParams& P, const FwdArgs& A, hipStream_t s, bool* wrote_inv) {
   *wrote_inv = false;
   if (env().force_direct) return false;
-  const FwdT T_ = {A.e, A.eo, A.t, A.w, A.m, A.affs, A.gout, A.st, A.inv_out, A.train && A.mf32};
+  const FwdT T_ = {A.e, A.eo, A.t, A.w, A.m, A.affs, A.gout, A.st, A.inv_out, A.train && A.mf32, A.train && A.lact};
   if (A.dtype == PEA_F16) return A.train ? fwd_any<__half, true>(P, T_, s, wrote_inv) : fwd_any<__half, false>(P, T_, s, wrote_inv);
   if (A.dtype == PEA_BF16) return A.train ? fwd_any<__bf16, true>(P, T_, s, wrote_inv) : fwd_any<__bf16, false>(P, T_, s, wrote_inv);
   return A.train ? fwd_any<float, true>(P, T_, s, wrote_inv) : fwd_any<float, false>(P, T_, s, wrote_inv);

@@ -27,14 +27,22 @@ bool fwd_self(const KParams& P, const FwdArgs& A, hipStream_t s) {
   // an f32 mask (2D training only): the quads' masks are dwordx4 loads -- a plane that is not 16-byte aligned takes the next family
   const bool mf = TRAIN && A.mf32;
   if (mf && (z3 || misaligned(A.m, 16))) return false;
+  const bool la = TRAIN && A.lact;  // the loss on the activated map (PEA_FLAG_LOSS_ACT): 2D training only, either mask type
+  if (la && z3) return false;
   const XParams& C = X.C;
   const dim3 grid((unsigned)(C.tiles_per_xcd * kXcd)), blk(kXdmaTH * kXdmaTW);
+#define PEA_XFK(CROP_, PSU_, WPE_, MT_, LACT_)                                                                              \
+  {                                                                                                                         \
+    constexpr auto kern = k_fwd_xdma<D_T, kXdmaTH, kXdmaTW, PSU_, CROP_, true, 0, false, WPE_, false, MT_, LACT_>;          \
+    PEA_LAUNCH(kern, grid, blk, X.lds, s, P, C, e, t, w, (const MT_*)(const void*)A.m, A.affs, A.gout, A.st, A.inv_out,     \
+               (const float*)nullptr, (float*)nullptr, LabArgs{})                                                           \
+  }
 #define PEA_XF(CROP_, PSU_, ZF_, WPE_)                                                                                      \
-  if (mf) {                                                                                                                 \
+  if (mf || la) {                                                                                                           \
     if constexpr (TRAIN && ZF_ == 0) {                                                                                      \
-      constexpr auto kern = k_fwd_xdma<D_T, kXdmaTH, kXdmaTW, PSU_, CROP_, true, 0, false, WPE_, false, float>;             \
-      PEA_LAUNCH(kern, grid, blk, X.lds, s, P, C, e, t, w, (const float*)(const void*)A.m, A.affs, A.gout, A.st, A.inv_out, \
-                 (const float*)nullptr, (float*)nullptr, LabArgs{})                                                         \
+      if (!la) PEA_XFK(CROP_, PSU_, WPE_, float, false)                                                                     \
+      else if (mf) PEA_XFK(CROP_, PSU_, WPE_, float, true)                                                                  \
+      else PEA_XFK(CROP_, PSU_, WPE_, uint8_t, true)                                                                        \
     }                                                                                                                       \
   } else {                                                                                                                  \
     constexpr auto kern = k_fwd_xdma<D_T, kXdmaTH, kXdmaTW, PSU_, CROP_, TRAIN, ZF_, false, WPE_>;                          \
@@ -54,6 +62,7 @@ bool fwd_self(const KParams& P, const FwdArgs& A, hipStream_t s) {
     if (crop) PEA_XF(true, kXdmaPSU, 0, 4) else PEA_XF(false, kXdmaPSU, 0, 4)
   }
 #undef PEA_XF
+#undef PEA_XFK
   return true;
 }
 
@@ -166,17 +175,20 @@ static bool fwd_other_wide(const KParams& P, const FwdArgs& A, hipStream_t s) {
   if (!plan(P, kXdmaPSUF, 1, &X) || X.C.nfz > 0 || P.K > kXP || P.Z != 1) return false;
   const size_t lds = X.lds + (size_t)6 * 2048;  // + the own tiles: three buffers x two channels x 2 KB
   const dim3 grid((unsigned)(X.C.tiles_per_xcd * kXcd)), blk(kXdmaTH * kXdmaTW);
-#define PEA_XFW(CROP_, MT_)                                                                                              \
+#define PEA_XFW(CROP_, MT_, LACT_)                                                                                       \
   {                                                                                                                      \
-    constexpr auto kern = k_fwd_xdma<D_T, kXdmaTH, kXdmaTW, kXdmaPSUF, CROP_, true, 0, true, 4, false, MT_>;             \
+    constexpr auto kern = k_fwd_xdma<D_T, kXdmaTH, kXdmaTW, kXdmaPSUF, CROP_, true, 0, true, 4, false, MT_, LACT_>;      \
     PEA_LAUNCH(kern, grid, blk, lds, s, P, X.C, e_other, A.t, A.w, (const MT_*)(const void*)A.m, A.affs, A.gout, A.st,   \
                A.inv_out, e, A.inv_out + (size_t)P.B * P.S, LabArgs{})                                                   \
   }
   const bool crop = P.border != PEA_BORDER_CIRCULAR;
-  if (A.mf32) {
-    if (crop) PEA_XFW(true, float) else PEA_XFW(false, float)
+  if (A.lact) {  // the loss on the activated map (PEA_FLAG_LOSS_ACT)
+    if (A.mf32) { if (crop) PEA_XFW(true, float, true) else PEA_XFW(false, float, true) }
+    else { if (crop) PEA_XFW(true, uint8_t, true) else PEA_XFW(false, uint8_t, true) }
+  } else if (A.mf32) {
+    if (crop) PEA_XFW(true, float, false) else PEA_XFW(false, float, false)
   } else {
-    if (crop) PEA_XFW(true, uint8_t) else PEA_XFW(false, uint8_t)
+    if (crop) PEA_XFW(true, uint8_t, false) else PEA_XFW(false, uint8_t, false)
   }
 #undef PEA_XFW
   return true;
@@ -203,7 +215,7 @@ bool xdma_fwd_other(const KParams& P, const FwdArgs& A, hipStream_t s) {
     z3 = true;
   }
   if (P.K > (z3 ? kXP + 2 : kXP)) return false;
-  if (z3 && A.mf32) return false;  // (the f32-mask forms are 2D)
+  if (z3 && (A.mf32 || A.lact)) return false;  // (the f32-mask and the PEA_FLAG_LOSS_ACT forms are 2D)
   const dim3 grid((unsigned)(X.C.tiles_per_xcd * kXcd)), blk(kXdmaTH * kXdmaTW);
   const bool crop = P.border != PEA_BORDER_CIRCULAR;
 #define PEA_XFO(CROP_, PSU_, ZF_)                                                                                           \
@@ -212,14 +224,17 @@ bool xdma_fwd_other(const KParams& P, const FwdArgs& A, hipStream_t s) {
     PEA_LAUNCH(kern, grid, blk, X.lds, s, P, X.C, e_other, A.t, A.w, A.m, A.affs, A.gout, A.st, A.inv_out, e,               \
                A.inv_out + (size_t)P.B * P.S, LabArgs{})                                                                    \
   }
-#define PEA_XFOM(CROP_)                                                                                                     \
+#define PEA_XFOM(CROP_, MT_, LACT_)                                                                                         \
   {                                                                                                                         \
-    constexpr auto kern = k_fwd_xdma<16, kXdmaTH, kXdmaTW, kXdmaPSU, CROP_, true, 0, true, 4, false, float>;                \
-    PEA_LAUNCH(kern, grid, blk, X.lds, s, P, X.C, e_other, A.t, A.w, (const float*)(const void*)A.m, A.affs, A.gout, A.st,  \
+    constexpr auto kern = k_fwd_xdma<16, kXdmaTH, kXdmaTW, kXdmaPSU, CROP_, true, 0, true, 4, false, MT_, LACT_>;           \
+    PEA_LAUNCH(kern, grid, blk, X.lds, s, P, X.C, e_other, A.t, A.w, (const MT_*)(const void*)A.m, A.affs, A.gout, A.st,    \
                A.inv_out, e, A.inv_out + (size_t)P.B * P.S, LabArgs{})                                                      \
   }
-  if (A.mf32) {
-    if (crop) PEA_XFOM(true) else PEA_XFOM(false)
+  if (A.lact) {  // the loss on the activated map (PEA_FLAG_LOSS_ACT)
+    if (A.mf32) { if (crop) PEA_XFOM(true, float, true) else PEA_XFOM(false, float, true) }
+    else { if (crop) PEA_XFOM(true, uint8_t, true) else PEA_XFOM(false, uint8_t, true) }
+  } else if (A.mf32) {
+    if (crop) PEA_XFOM(true, float, false) else PEA_XFOM(false, float, false)
   } else if (z3) {
     if (crop) PEA_XFO(true, kXdmaPSU3F, kXZ / 2) else PEA_XFO(false, kXdmaPSU3F, kXZ / 2)
   } else {

@@ -32,17 +32,25 @@ bool fwd_self_h(const KParams& P, const FwdArgs& A, hipStream_t s) {
   // 16-byte aligned, or PEA_H16_HW=0, takes the next family
   const bool mf = TRAIN && A.mf32;
   if (mf && (misaligned(A.m, 16) || !(kBf16<T> || env().h16_hw))) return false;
+  // the loss on the activated map (PEA_FLAG_LOSS_ACT): likewise the 16-bit working buffer's kernel with one slot count, either mask type
+  const bool la = TRAIN && A.lact;
+  if (la && !(kBf16<T> || env().h16_hw)) return false;
   if (kBf16<T> || env().h16_hw) {  // half-precision working buffer, v_dot2 gather: 48 VGPRs and 30 KB -- four workgroups per CU (five: 173 against 168 us)
     const size_t ldsh = (size_t)4 * kXdmaPSUF * 256;
     if constexpr (TRAIN) {
-      if (mf) {
-#define PEA_HFM(CROP_)                                                                                                    \
+      if (mf || la) {
+#define PEA_HFM(CROP_, MT_, LACT_)                                                                                        \
   {                                                                                                                       \
-    constexpr auto kern = k_fwd_xdma_h<D_T, kXdmaTH, kXdmaTW, kXdmaPSUF, CROP_, true, 8, true, kXP, false, T, float>;     \
-    PEA_LAUNCH(kern, grid, blk, ldsh, s, P, X.C, e, A.t, A.w, (const float*)(const void*)A.m, A.affs, A.gout, A.st,       \
+    /* (LOSS_ACT with an f32 mask and a cropped border takes 65 VGPRs: three workgroups per CU instead of a spill at four) */ \
+    constexpr int WPE_ = (LACT_ && CROP_ && std::is_same<MT_, float>::value) ? 6 : 8;                                     \
+    constexpr auto kern = k_fwd_xdma_h<D_T, kXdmaTH, kXdmaTW, kXdmaPSUF, CROP_, true, WPE_, true, kXP, false, T, MT_, LACT_>; \
+    PEA_LAUNCH(kern, grid, blk, ldsh, s, P, X.C, e, A.t, A.w, (const MT_*)(const void*)A.m, A.affs, A.gout, A.st,         \
                A.inv_out, (const T*)nullptr, (float*)nullptr)                                                             \
   }
-        if (P.border != PEA_BORDER_CIRCULAR) PEA_HFM(true) else PEA_HFM(false)
+        const bool crop = P.border != PEA_BORDER_CIRCULAR;
+        if (!la) { if (crop) PEA_HFM(true, float, false) else PEA_HFM(false, float, false) }
+        else if (mf) { if (crop) PEA_HFM(true, float, true) else PEA_HFM(false, float, true) }
+        else { if (crop) PEA_HFM(true, uint8_t, true) else PEA_HFM(false, uint8_t, true) }
 #undef PEA_HFM
         return true;
       }
@@ -137,15 +145,18 @@ bool fwd_other_h(const KParams& P, const FwdArgs& A, hipStream_t s) {
   const size_t lds = (size_t)4 * kXdmaPSUF * 256 + 6 * 1024;  // working plane + ring + the own tiles
   const dim3 grid((unsigned)(X.C.tiles_per_xcd * kXcd)), blk(kXdmaTH * kXdmaTW);
   float* inv_other = A.inv_out + (size_t)P.B * P.S;
-  if (A.mf32) {  // an f32 mask: dwordx4 mask quads, one slot count (kXP)
-    if (misaligned(A.m, 16)) return false;
-#define PEA_HFOM(CROP_)                                                                                                  \
+  if (A.mf32 || A.lact) {  // an f32 mask: dwordx4 mask quads; PEA_FLAG_LOSS_ACT: the loss on the activated map -- one slot count (kXP)
+    if (A.mf32 && misaligned(A.m, 16)) return false;
+#define PEA_HFOM(CROP_, MT_, LACT_)                                                                                      \
   {                                                                                                                      \
-    constexpr auto kern = k_fwd_xdma_h<D_T, kXdmaTH, kXdmaTW, kXdmaPSUF, CROP_, true, 6, true, kXP, true, T, float>;     \
-    PEA_LAUNCH(kern, grid, blk, lds, s, P, X.C, eo, A.t, A.w, (const float*)(const void*)A.m, A.affs, A.gout, A.st,      \
+    constexpr auto kern = k_fwd_xdma_h<D_T, kXdmaTH, kXdmaTW, kXdmaPSUF, CROP_, true, 6, true, kXP, true, T, MT_, LACT_>; \
+    PEA_LAUNCH(kern, grid, blk, lds, s, P, X.C, eo, A.t, A.w, (const MT_*)(const void*)A.m, A.affs, A.gout, A.st,        \
                A.inv_out, e, inv_other)                                                                                  \
   }
-    if (P.border != PEA_BORDER_CIRCULAR) PEA_HFOM(true) else PEA_HFOM(false)
+    const bool crop = P.border != PEA_BORDER_CIRCULAR;
+    if (!A.lact) { if (crop) PEA_HFOM(true, float, false) else PEA_HFOM(false, float, false) }
+    else if (A.mf32) { if (crop) PEA_HFOM(true, float, true) else PEA_HFOM(false, float, true) }
+    else { if (crop) PEA_HFOM(true, uint8_t, true) else PEA_HFOM(false, uint8_t, true) }
 #undef PEA_HFOM
     return true;
   }

@@ -351,16 +351,23 @@ __device__ __forceinline__ void fwd_load_twm(Twm<KN>& r, const FwdU U, const Off
 
 // one offset's epilogue: affs / g stores (dropped by the bounds check for lanes outside the image) and the
 // loss partial (wave-reduced, lane 63 writes)
-template <bool TRAIN>
+template <bool TRAIN, bool LACT = false>  // LACT: the loss on the activated map (PEA_FLAG_LOSS_ACT, act_u)
 __device__ __forceinline__ void fwd_finish(const FwdU U, int K, float* s_part, const OffEnt e, float a, bool valid, float t,
                                            float w, float m, unsigned pb) {
   const bool hi = (unsigned)e.i >= U.ks;  // uniform
   const unsigned so = U.kzo + (hi ? (unsigned)e.i - U.ks : (unsigned)e.i) * U.kcs;
-  if (U.has_a) bs32<true>(hi ? U.aB1 : U.aB, act_affs(a, U.af), pb, so);
+  float u = a, v = a;
+  ActK AK = {};
+  if constexpr (LACT) {
+    AK = act_consts(U.af);
+    v = act_v(a, AK);
+    u = act_u(v, AK);
+  }
+  if (U.has_a) bs32<true>(hi ? U.aB1 : U.aB, LACT ? u : act_affs(a, U.af), pb, so);
   if (TRAIN) {
-    const float r = a * m - t * m;
+    const float r = u * m - t * m;
     const float wr = valid ? w * r : 0.f;
-    if (U.has_g) bs32(hi ? U.gB1 : U.gB, e.gscale * wr * m, pb, so);
+    if (U.has_g) bs32(hi ? U.gB1 : U.gB, LACT ? act_g(u, v, e.gscale * AK.sc, wr, m) : e.gscale * wr * m, pb, so);
     const float red = wave_sum63(wr * r);
     if ((threadIdx.x & 63) == 63) s_part[(threadIdx.x >> 6) * K + e.i] = red;
   }
@@ -369,7 +376,7 @@ __device__ __forceinline__ void fwd_finish(const FwdU U, int K, float* s_part, c
 // ------------------------------------------------------------------------------------------------
 // forward, tiled.  SELF: e_other == e (own pixel comes out of LDS too).
 // ------------------------------------------------------------------------------------------------
-template <typename T, int D_T, int TH, int TW, int PLQ, bool CROP, bool TRAIN, bool SELF, typename MT = uint8_t>
+template <typename T, int D_T, int TH, int TW, int PLQ, bool CROP, bool TRAIN, bool SELF, typename MT = uint8_t, bool LACT = false>
 __global__ __launch_bounds__(TH* TW, (D_T > 16 ? 2 : 4)) void k_fwd_tiled(const KParams P, const TParams Q, const T* __restrict__ e,
                                                          const T* __restrict__ eo, const float* __restrict__ target,
                                                          const float* __restrict__ weight,
@@ -464,7 +471,7 @@ __global__ __launch_bounds__(TH* TW, (D_T > 16 ? 2 : 4)) void k_fwd_tiled(const 
       sq_ = fmaf(fv[c], fv[c], sq_);                                                               \
     }                                                                                              \
     const float a_ = fok ? dot_ * rnorm(sq_, Q.inv_eps) : 0.f;                                     \
-    fwd_finish<TRAIN>(U, P.K, s_part, Q.far[k], a_, fok, sf.t[u], sf.w[u], sf.m[u], pb);           \
+    fwd_finish<TRAIN, LACT>(U, P.K, s_part, Q.far[k], a_, fok, sf.t[u], sf.w[u], sf.m[u], pb);           \
   }
   if (Q.n_far > 0) PEA_FWD_LOAD_FAR(fvA, fokA, 0)
   if (Q.n_far > 1) PEA_FWD_LOAD_FAR(fvB, fokB, 1)
@@ -498,7 +505,7 @@ __global__ __launch_bounds__(TH* TW, (D_T > 16 ? 2 : 4)) void k_fwd_tiled(const 
           a = inside ? a : 0.f;
           valid = valid && inside;
         }
-        fwd_finish<TRAIN>(U, P.K, s_part, en, a, valid, sa.t[u], sa.w[u], sa.m[u], pb);
+        fwd_finish<TRAIN, LACT>(U, P.K, s_part, en, a, valid, sa.t[u], sa.w[u], sa.m[u], pb);
       }
     }
   }
@@ -558,7 +565,8 @@ __device__ __forceinline__ void bs128(rsrc_t r, f4 v, unsigned vo, unsigned so) 
   asm volatile("s_nop 1" ::"v"(d) : "memory");
 }
 
-template <typename T, int D_T, int TH, int TW, int PLQ, bool OVL, bool CROP, bool TRAIN, bool SELF, typename MT = uint8_t>
+template <typename T, int D_T, int TH, int TW, int PLQ, bool OVL, bool CROP, bool TRAIN, bool SELF, typename MT = uint8_t,
+          bool LACT = false>
 __global__ __launch_bounds__(TH* TW, (D_T > 16 ? 2 : 4)) void k_fwd_tiled_v(const KParams P, const TParams Q, const T* __restrict__ e,
                                                            const T* __restrict__ eo, const float* __restrict__ target,
                                                            const float* __restrict__ weight,
@@ -591,6 +599,7 @@ __global__ __launch_bounds__(TH* TW, (D_T > 16 ? 2 : 4)) void k_fwd_tiled_v(cons
   const unsigned kcs = (unsigned)P.S * 4u, kzo = (unsigned)z * YX * 4u;
   const bool has_a = affs != nullptr, has_g = gout != nullptr, has_m = mask != nullptr;
   const unsigned af = P.flags & kActMask;
+  const ActK AK = act_consts(af);  // LACT only
   const unsigned ecs = (unsigned)P.S * (unsigned)sizeof(T);
   const unsigned ezo = (unsigned)z * YX * (unsigned)sizeof(T);
 
@@ -722,9 +731,15 @@ __global__ __launch_bounds__(TH* TW, (D_T > 16 ? 2 : 4)) void k_fwd_tiled_v(cons
     const OffEnt en = ien[it];
     const f4 a4 = *(const f4*)(sA + en.i * TP + iqd[it] * 4);
     const unsigned so = kzo + (unsigned)en.i * kcs;
+    f4 v4 = a4;  // LACT: what the clamp sees (a4 is dead from here on)
+    if constexpr (LACT) {
+#pragma unroll
+      for (int j = 0; j < 4; ++j) v4[j] = act_v(a4[j], AK);
+    }
     if (has_a) {
-      f4 o = a4;
-      if (af) { o.x = act_affs(o.x, af); o.y = act_affs(o.y, af); o.z = act_affs(o.z, af); o.w = act_affs(o.w, af); }
+      f4 o = v4;
+      if constexpr (LACT) { o.x = act_u(o.x, AK); o.y = act_u(o.y, AK); o.z = act_u(o.z, AK); o.w = act_u(o.w, AK); }
+      else if (af) { o.x = act_affs(o.x, af); o.y = act_affs(o.y, af); o.z = act_affs(o.z, af); o.w = act_affs(o.w, af); }
       bs128<true>(aB, o, ivo[it], so);
     }
     if (TRAIN) {
@@ -733,14 +748,15 @@ __global__ __launch_bounds__(TH* TW, (D_T > 16 ? 2 : 4)) void k_fwd_tiled_v(cons
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
         const float m = mq_get<MT>(m4[it], j);
-        const float r = a4[j] * m - t4[it][j] * m;
+        const float u = LACT ? act_u(v4[j], AK) : v4[j];
+        const float r = u * m - t4[it][j] * m;
         float wr = w4[it][j] * r;
         if (CROP && !rep) {  // a cropped-away neighbour carries no loss term (its a is already 0)
           const bool inside = (unsigned)(igy[it] + ent_oy(en)) < (unsigned)P.Y && (unsigned)(igx[it] + j + ent_ox(en)) < (unsigned)P.X;
           const bool inz = (unsigned)(z + ioz[it]) < (unsigned)P.Z;
           wr = (inside && inz) ? wr : 0.f;
         }
-        g4[j] = en.gscale * wr * m;
+        g4[j] = LACT ? act_g(u, v4[j], en.gscale * AK.sc, wr, m) : en.gscale * wr * m;
         acc = fmaf(wr, r, acc);
       }
       if (has_g) bs128<false>(gB, g4, ivo[it], so);

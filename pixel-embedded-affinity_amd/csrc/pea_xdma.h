@@ -687,7 +687,7 @@ struct LabArgs {
   unsigned lflags;        // PEA_TGT_*
 };
 template <int D_T, int TH, int TW, int PSU, bool CROP, bool TRAIN, int ZF = 0, bool OTHER = false, int WPE = 4, bool LAB = false,
-          typename MT = uint8_t>
+          typename MT = uint8_t, bool LACT = false>
 __global__ __launch_bounds__(TH* TW, WPE) void k_fwd_xdma(const KParams P, const XParams C, const float* __restrict__ e,
                                                            const float* __restrict__ target, const float* __restrict__ weight,
                                                            const MT* __restrict__ mask, float* __restrict__ affs,
@@ -700,6 +700,7 @@ __global__ __launch_bounds__(TH* TW, WPE) void k_fwd_xdma(const KParams P, const
   constexpr bool OWNL = OTHER && D_T > 16;
   static_assert(!OWNL || ZF == 0, "cross-loss instantiation at D > 16: in-plane");
   static_assert(!LAB || (TRAIN && ZF == 0 && !OTHER), "labels-in instantiation: 2D self loss");
+  static_assert(!LACT || (TRAIN && ZF == 0 && !LAB), "loss on the activated map (PEA_FLAG_LOSS_ACT, act_u): 2D training forwards");
   constexpr int NT = TH * TW, PS = PSU * 256, NP = D_T / 2, TP = NT, QP = TP / 4, NSL = QP / 64;
   constexpr int KMAX = ZF > 0 ? kXP + 2 : kXP;      // channels the epilogue handles (norm5: 8 in-plane + 4 z offsets)
   constexpr int ITEMS = (KMAX * QP + NT - 1) / NT;
@@ -727,6 +728,7 @@ __global__ __launch_bounds__(TH* TW, WPE) void k_fwd_xdma(const KParams P, const
   const unsigned ecs = (unsigned)P.S * 4u, ezo = (unsigned)z * YX * 4u;
   const bool has_a = affs != nullptr, has_g = gout != nullptr, has_m = mask != nullptr;
   const unsigned af = P.flags & kActMask;
+  const ActK AK = act_consts(af);  // LACT only
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
 
   // ---- (0) the epilogue's operands: item = (offset, quad of 4 x-adjacent tile pixels); requested first
@@ -1052,9 +1054,15 @@ __global__ __launch_bounds__(TH* TW, WPE) void k_fwd_xdma(const KParams P, const
       if ((threadIdx.x & 63) == 63) s_part[sl * NSL + (iqd[it] >> 6)] = red;
       continue;
     }
+    f4 v4 = a4;  // LACT: what the clamp sees (a4 is dead from here on)
+    if constexpr (LACT) {
+#pragma unroll
+      for (int j = 0; j < 4; ++j) v4[j] = act_v(a4[j], AK);
+    }
     if (has_a) {
-      f4 o = a4;
-      if (af) { o.x = act_affs(o.x, af); o.y = act_affs(o.y, af); o.z = act_affs(o.z, af); o.w = act_affs(o.w, af); }
+      f4 o = v4;
+      if constexpr (LACT) { o.x = act_u(o.x, AK); o.y = act_u(o.y, AK); o.z = act_u(o.z, AK); o.w = act_u(o.w, AK); }
+      else if (af) { o.x = act_affs(o.x, af); o.y = act_affs(o.y, af); o.z = act_affs(o.z, af); o.w = act_affs(o.w, af); }
       bs128<true>(aB, o, ivo[it], so);
     }
     if (TRAIN) {
@@ -1065,13 +1073,14 @@ __global__ __launch_bounds__(TH* TW, WPE) void k_fwd_xdma(const KParams P, const
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
         const float m = mq_get<MT>(m4[it], j);
-        const float r = a4[j] * m - t4[it][j] * m;
+        const float u = LACT ? act_u(v4[j], AK) : v4[j];
+        const float r = u * m - t4[it][j] * m;
         float wr = w4[it][j] * r;
         if (CROP) {  // a cropped-away neighbour carries no loss term (its a is already 0)
           const int q = (ax_ == 1 ? igx[it] + j : ax_ == 0 ? igy[it] : z) + od_;
           wr = (unsigned)q < (unsigned)(ax_ == 1 ? P.X : ax_ == 0 ? P.Y : P.Z) ? wr : 0.f;
         }
-        g4[j] = gs * wr * m;
+        g4[j] = LACT ? act_g(u, v4[j], gs * AK.sc, wr, m) : gs * wr * m;
         acc = fmaf(wr, r, acc);
       }
       if (has_g) bs128<false>(gB, g4, ivo[it], so);

@@ -401,7 +401,7 @@ __global__ __launch_bounds__(TH* TW, WPE) void k_bwd_xdma_h(const KParams P, con
 // OTHER: the cross loss a_i(p) = <ehat(p), ehat_other(p + o_i)>: `e` is the SECOND operand (staged), the own pixel comes from the own
 // tile of `own` staged beside each chunk by wave 0; both 1 / norm planes are written (inv_out: own, inv_other_out: the second operand's)
 template <int D_T, int TH, int TW, int PSU, bool CROP, bool TRAIN, int WPE, bool HW = false, int NXP = kXP, bool OTHER = false,
-          typename T = __half, typename MT = uint8_t>
+          typename T = __half, typename MT = uint8_t, bool LACT = false>  // LACT: PEA_FLAG_LOSS_ACT (act_u), as k_fwd_xdma
 __global__ __launch_bounds__(TH* TW, WPE) void k_fwd_xdma_h(const KParams P, const XParams C, const T* __restrict__ e,
                                                              const float* __restrict__ target, const float* __restrict__ weight,
                                                              const MT* __restrict__ mask, float* __restrict__ affs,
@@ -436,6 +436,7 @@ __global__ __launch_bounds__(TH* TW, WPE) void k_fwd_xdma_h(const KParams P, con
   const unsigned ecs = (unsigned)P.S * 4u, ezo = (unsigned)z * YX * 4u;  // the f32 tensors
   const bool has_a = affs != nullptr, has_g = gout != nullptr, has_m = mask != nullptr;
   const unsigned af = P.flags & kActMask;
+  const ActK AK = act_consts(af);  // LACT only
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
   const int ly = threadIdx.x >> 5, lx = threadIdx.x & 31;
 
@@ -605,9 +606,15 @@ __global__ __launch_bounds__(TH* TW, WPE) void k_fwd_xdma_h(const KParams P, con
     const int sl = isl[it];
     const f4 a4 = *(const f4*)(sA + sl * TP + iqd[it] * 4);
     const unsigned so = ezo + (unsigned)sl * ecs;
+    f4 v4 = a4;  // LACT: what the clamp sees (a4 is dead from here on)
+    if constexpr (LACT) {
+#pragma unroll
+      for (int j = 0; j < 4; ++j) v4[j] = act_v(a4[j], AK);
+    }
     if (has_a) {
-      f4 o = a4;
-      if (af) { o.x = act_affs(o.x, af); o.y = act_affs(o.y, af); o.z = act_affs(o.z, af); o.w = act_affs(o.w, af); }
+      f4 o = v4;
+      if constexpr (LACT) { o.x = act_u(o.x, AK); o.y = act_u(o.y, AK); o.z = act_u(o.z, AK); o.w = act_u(o.w, AK); }
+      else if (af) { o.x = act_affs(o.x, af); o.y = act_affs(o.y, af); o.z = act_affs(o.z, af); o.w = act_affs(o.w, af); }
       bs128<true>(aB, o, ivo[it], so);
     }
     if (TRAIN) {
@@ -618,13 +625,14 @@ __global__ __launch_bounds__(TH* TW, WPE) void k_fwd_xdma_h(const KParams P, con
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
         const float m = mq_get<MT>(m4[it], j);
-        const float r = a4[j] * m - t4[it][j] * m;
+        const float u = LACT ? act_u(v4[j], AK) : v4[j];
+        const float r = u * m - t4[it][j] * m;
         float wr = w4[it][j] * r;
         if (CROP) {
           const int q = (ax_ == 1 ? igx[it] + j : igy[it]) + od_;
           wr = (unsigned)q < (unsigned)(ax_ == 1 ? P.X : P.Y) ? wr : 0.f;
         }
-        g4[j] = gs * wr * m;
+        g4[j] = LACT ? act_g(u, v4[j], gs * AK.sc, wr, m) : gs * wr * m;
         acc = fmaf(wr, r, acc);
       }
       if (has_g) bs128<false>(gB, g4, ivo[it], so);

@@ -94,7 +94,9 @@ class _TensorSection(torch.autograd.Function):
                 """forward launch of loss j -> (desc, g, affs, inv); planes: 1 / norm planes wanted for the cross backward
                 (1: self loss, 2: cross loss with the detached second operand), allocated where those kernels cover the shape"""
                 spec = specs[j]
-                if not want_affs and spec.act:  # a map nobody sees (the cross loss'): without the activation it can serve the backward
+                # a map nobody sees (the cross loss'): without the activation it can serve the backward -- unless the loss itself is
+                # taken on the activated map (FLAG_LOSS_ACT): then the bits are part of the loss and stay
+                if not want_affs and spec.act and not spec.act & _lib.FLAG_LOSS_ACT:
                     spec = copy.copy(spec)
                     spec.act = 0
                 kshape = op._affs_shape(e_c, spec.K)
@@ -125,7 +127,7 @@ class _TensorSection(torch.autograd.Function):
                 (2D, D = 16, f32, axis-aligned stencil: csrc/pea_xdma_dual.h) -> (d0, dx, g0, gx, pred, the two 1 / norm planes) or None"""
                 jx = ncall - 1
                 spec0, specx = specs[0], specs[jx]
-                if specx.act:  # the cross loss' map is not written
+                if specx.act and not specx.act & _lib.FLAG_LOSS_ACT:  # the cross loss' map is not written (FLAG_LOSS_ACT: part of the loss)
                     specx = copy.copy(specx)
                     specx.act = 0
                 if spec0.K != specx.K or o_c.data_ptr() == e_c.data_ptr():
