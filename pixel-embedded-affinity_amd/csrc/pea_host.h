@@ -15,6 +15,8 @@
 //   pea_k_head.hip     the embedding head (pea_head.h) and target generation (pea_targets.h)
 // Each kernel file exports a few plain functions (declared here) that pick the instantiation and launch it; a function returns
 // false when its family has no kernel for the descriptor and the caller tries the next one.  No device code crosses a file.
+// pea_dispatch.h holds what the launchers share to get from run-time facts (storage dtype, D, border, mask type, ..) to template
+// arguments: launch<KERNEL>() and the with_bool / with_storage / with_width / with_mask_form callers of generic lambdas.
 #pragma once
 #include <stdint.h>
 #include <string.h>

@@ -2,7 +2,7 @@
 // One translation unit of libpea_hip.so (pea_host.h).
 #include <algorithm>
 
-#include "pea_host.h"
+#include "pea_dispatch.h"
 #include "pea_boxm.h"
 
 namespace pea {
@@ -68,20 +68,11 @@ bool box_fwd(const KParams& P, const FwdArgs& A, hipStream_t s) {
   if (!plan(P, &C)) return false;
   const dim3 grid((unsigned)(C.tiles_per_xcd * kXcd)), blk(kBoxTH * kBoxTW);
   const float* e = (const float*)A.e;
-#define PEA_BF(CROP_, TRAIN_)                                                                                   \
-  {                                                                                                             \
-    constexpr auto kern = k_fwd_box<16, CROP_, TRAIN_>;                                                         \
-    if (allow_lds<kern>(kBoxLds)) return false;                                                                 \
-    hipLaunchKernelGGL(kern, grid, blk, kBoxLds, s, P, C, e, A.t, A.w, A.m, A.affs, A.gout, A.st, A.inv_out);   \
-  }
-  const bool crop = P.border != PEA_BORDER_CIRCULAR;
-  if (A.train) {
-    if (crop) PEA_BF(true, true) else PEA_BF(false, true)
-  } else {
-    if (crop) PEA_BF(true, false) else PEA_BF(false, false)
-  }
-#undef PEA_BF
-  return true;
+  return with_bool(P.border != PEA_BORDER_CIRCULAR, [&](auto crop) {
+    return with_bool(A.train, [&](auto train) {
+      return launch<k_fwd_box<16, crop.value, train.value>>(grid, blk, kBoxLds, s, P, C, e, A.t, A.w, A.m, A.affs, A.gout, A.st, A.inv_out);
+    });
+  });
 }
 
 // the marching backward (pea_boxm.h): CROP_ZERO volumes with enough tile columns for the CUs (PEA_ZMARCH=2: any); false = not taken
@@ -110,10 +101,7 @@ static bool box_bwd_march(const KParams& P, const BParams& C0, const float* x, c
   C.tiles_per_xcd = (C.ntiles + kXcd - 1) / kXcd;
   C.sup_x = C.sup_y = 0;  // (round 6: 2 x 8 blocks 1.935 ms, 4 x 8 1.96, super-blocks no better: profiles/r6_sup_n26b.txt)
   const dim3 grid((unsigned)(C.tiles_per_xcd * kXcd)), blk(kBoxTH * kBoxTW);
-  constexpr auto kern = k_bwd_boxm;
-  if (allow_lds<kern>(kBmLds)) return false;
-  hipLaunchKernelGGL(kern, grid, blk, kBmLds, s, P, C, M, x, inv, g, dl, dx);
-  return true;
+  return launch<k_bwd_boxm>(grid, blk, kBmLds, s, P, C, M, x, inv, g, dl, dx);
 }
 
 bool box_bwd(const KParams& P, const float* x, const float* inv, const float* g, const float* dl, float* dx, hipStream_t s) {
@@ -123,13 +111,9 @@ bool box_bwd(const KParams& P, const float* x, const float* inv, const float* g,
   if (!plan(P, &C)) return false;
   if (env().boxm && box_bwd_march(P, C, x, inv, g, dl, dx, s)) return true;
   const dim3 grid((unsigned)(C.tiles_per_xcd * kXcd)), blk(kBoxTH * kBoxTW);
-  if (P.border != PEA_BORDER_CIRCULAR) {
-    constexpr auto kern = k_bwd_box<16, true>;
-    hipLaunchKernelGGL(kern, grid, blk, kBoxLdsBwd, s, P, C, x, inv, g, dl, dx);
-  } else {
-    constexpr auto kern = k_bwd_box<16, false>;
-    hipLaunchKernelGGL(kern, grid, blk, kBoxLdsBwd, s, P, C, x, inv, g, dl, dx);
-  }
+  with_bool(P.border != PEA_BORDER_CIRCULAR, [&](auto crop) {
+    hipLaunchKernelGGL((k_bwd_box<16, crop.value>), grid, blk, kBoxLdsBwd, s, P, C, x, inv, g, dl, dx);
+  });
   return true;
 }
 

@@ -9,7 +9,7 @@
 #include <mutex>
 #include <vector>
 
-#include "pea_host.h"
+#include "pea_dispatch.h"
 #include "pea_direct.h"
 #include "pea_tiled.h"  // f4
 
@@ -136,68 +136,50 @@ template <typename T, int D_T>
 void bwd_direct_roles(const KParams& P, int roles, const T* x, const T* nbA, const T* nbB, const float* g, const float* dl, T* dx,
                       hipStream_t s) {
   const dim3 grid((unsigned)(P.tiles_per_xcd * kXcd)), blk(kBlock);
-  if (roles == 3) hipLaunchKernelGGL((k_bwd_direct<T, D_T, true, true>), grid, blk, 0, s, P, x, nbA, nbB, g, dl, dx);
-  else if (roles == 1) hipLaunchKernelGGL((k_bwd_direct<T, D_T, true, false>), grid, blk, 0, s, P, x, nbA, nbB, g, dl, dx);
-  else hipLaunchKernelGGL((k_bwd_direct<T, D_T, false, true>), grid, blk, 0, s, P, x, nbA, nbB, g, dl, dx);
+  auto go = [&](auto ra, auto rb) {
+    hipLaunchKernelGGL((k_bwd_direct<T, D_T, ra.value, rb.value>), grid, blk, 0, s, P, x, nbA, nbB, g, dl, dx);
+  };
+  if (roles == 3) go(std::true_type{}, std::true_type{});
+  else if (roles == 1) go(std::true_type{}, std::false_type{});
+  else go(std::false_type{}, std::true_type{});
 }
 
 template <typename T>
 int bwd_direct(const KParams& P, int roles, const void* x, const void* nbA, const void* nbB, const float* g, const float* dl, void* dx,
                hipStream_t s) {
-  switch (P.D) {
-    case 16: bwd_direct_roles<T, 16>(P, roles, (const T*)x, (const T*)nbA, (const T*)nbB, g, dl, (T*)dx, s); return hip_rc();
-    case 32: bwd_direct_roles<T, 32>(P, roles, (const T*)x, (const T*)nbA, (const T*)nbB, g, dl, (T*)dx, s); return hip_rc();
-    case 64: bwd_direct_roles<T, 64>(P, roles, (const T*)x, (const T*)nbA, (const T*)nbB, g, dl, (T*)dx, s); return hip_rc();
-    case 4: bwd_direct_roles<T, 4>(P, roles, (const T*)x, (const T*)nbA, (const T*)nbB, g, dl, (T*)dx, s); return hip_rc();
-    case 8: bwd_direct_roles<T, 8>(P, roles, (const T*)x, (const T*)nbA, (const T*)nbB, g, dl, (T*)dx, s); return hip_rc();
-    default: break;
-  }
+  if (with_width<16, 32, 64, 4, 8>(P.D, [&](auto d) {
+        bwd_direct_roles<T, d.value>(P, roles, (const T*)x, (const T*)nbA, (const T*)nbB, g, dl, (T*)dx, s);
+        return true;
+      }))
+    return hip_rc();
   // any other width: the runtime-D kernel; the REPLICATE border keeps the specialised kernels
   if (P.border == PEA_BORDER_REPLICATE) return PEA_E_UNSUPPORTED;
   const size_t lds = (size_t)2 * P.K * kBlock * sizeof(float);
   const dim3 grid((unsigned)(P.tiles_per_xcd * kXcd)), blk(kBlock);
-#define PEA_ANYD(RA_, RB_)                                                                                           \
-  {                                                                                                                  \
-    constexpr auto kern = k_bwd_direct_anyd<T, RA_, RB_>;                                                            \
-    const int rc = allow_lds<kern>(lds);                                                                             \
-    if (rc) return rc;                                                                                               \
-    hipLaunchKernelGGL(kern, grid, blk, lds, s, P, (const T*)x, (const T*)nbA, (const T*)nbB, g, dl, (T*)dx);        \
-  }
-  if (roles == 3) PEA_ANYD(true, true) else if (roles == 1) PEA_ANYD(true, false) else PEA_ANYD(false, true)
-#undef PEA_ANYD
-  return hip_rc();
+  auto go = [&](auto ra, auto rb) {  // (a failed allow_lds: its error code, not the pending one)
+    constexpr auto kern = k_bwd_direct_anyd<T, ra.value, rb.value>;
+    if (const int rc = allow_lds<kern>(lds)) return rc;
+    hipLaunchKernelGGL(kern, grid, blk, lds, s, P, (const T*)x, (const T*)nbA, (const T*)nbB, g, dl, (T*)dx);
+    return hip_rc();
+  };
+  if (roles == 3) return go(std::true_type{}, std::true_type{});
+  if (roles == 1) return go(std::true_type{}, std::false_type{});
+  return go(std::false_type{}, std::true_type{});
 }
 }  // namespace
 
 void direct_fwd(const KParams& P, const FwdArgs& A, hipStream_t s) {
-  if (A.train && A.lact) {  // the loss on the activated map (PEA_FLAG_LOSS_ACT): the catch-all of every descriptor
-    if (A.mf32) {
-      if (A.dtype == PEA_F16) fwd_direct<__half, true, float, true>(P, A, s);
-      else if (A.dtype == PEA_BF16) fwd_direct<__bf16, true, float, true>(P, A, s);
-      else fwd_direct<float, true, float, true>(P, A, s);
-    } else {
-      if (A.dtype == PEA_F16) fwd_direct<__half, true, uint8_t, true>(P, A, s);
-      else if (A.dtype == PEA_BF16) fwd_direct<__bf16, true, uint8_t, true>(P, A, s);
-      else fwd_direct<float, true, uint8_t, true>(P, A, s);
-    }
-    return;
-  }
-  if (A.train && A.mf32) {  // an f32 mask (PEA_FLAG_MASK_F32): training only
-    if (A.dtype == PEA_F16) fwd_direct<__half, true, float>(P, A, s);
-    else if (A.dtype == PEA_BF16) fwd_direct<__bf16, true, float>(P, A, s);
-    else fwd_direct<float, true, float>(P, A, s);
-    return;
-  }
-  if (A.dtype == PEA_F16) { if (A.train) fwd_direct<__half, true>(P, A, s); else fwd_direct<__half, false>(P, A, s); }
-  else if (A.dtype == PEA_BF16) { if (A.train) fwd_direct<__bf16, true>(P, A, s); else fwd_direct<__bf16, false>(P, A, s); }
-  else { if (A.train) fwd_direct<float, true>(P, A, s); else fwd_direct<float, false>(P, A, s); }
+  with_storage(A.dtype, [&](auto st) {
+    using T = typename decltype(st)::type;
+    if (!A.train) return fwd_direct<T, false>(P, A, s);
+    // an f32 mask (PEA_FLAG_MASK_F32) and the loss on the activated map (PEA_FLAG_LOSS_ACT: the catch-all of every descriptor): training only
+    with_mask_form(A.mf32, A.lact, [&](auto mt, auto lact) { fwd_direct<T, true, typename decltype(mt)::type, lact.value>(P, A, s); });
+  });
 }
 
 int direct_bwd(const KParams& P, int dtype, int roles, const void* x, const void* nbA, const void* nbB, const float* g,
                const float* dl, void* dx, hipStream_t s) {
-  if (dtype == PEA_F16) return bwd_direct<__half>(P, roles, x, nbA, nbB, g, dl, dx, s);
-  if (dtype == PEA_BF16) return bwd_direct<__bf16>(P, roles, x, nbA, nbB, g, dl, dx, s);
-  return bwd_direct<float>(P, roles, x, nbA, nbB, g, dl, dx, s);
+  return with_storage(dtype, [&](auto st) { return bwd_direct<typename decltype(st)::type>(P, roles, x, nbA, nbB, g, dl, dx, s); });
 }
 
 }  // namespace pea

@@ -2,16 +2,11 @@
 // One translation unit of libpea_hip.so (pea_host.h).
 #include "pea_plan.h"
 #include "pea_fused_labels.h"
+#include "pea_dispatch.h"
 
 namespace pea {
 
 namespace {
-
-#define PEA_LAUNCH(kern, grid, blk, lds, s, ...)              \
-  {                                                           \
-    if (allow_lds<kern>(lds)) return false;                   \
-    hipLaunchKernelGGL(kern, grid, blk, lds, s, __VA_ARGS__); \
-  }
 
 // same tile plan as the tiled backward
 template <typename T, int D_T, bool RB>
@@ -24,14 +19,10 @@ bool try_fused_labels(const KParams& P, const T* x, const T* nb, const int32_t* 
   const size_t lds = Lds<D_T, c.PLQ>::kBytes + (size_t)(c.TH * c.TW / 64) * P.K * sizeof(float);
   if (lds > (size_t)kLdsMax) return false;
   const dim3 grid((unsigned)(Q.tiles_per_xcd * kXcd)), blk(c.TH * c.TW);
-  if (P.border == PEA_BORDER_CIRCULAR) {
-    constexpr auto kern = k_fused_labels<T, D_T, c.TH, c.TW, c.PLQ, false, RB>;
-    PEA_LAUNCH(kern, grid, blk, lds, s, P, Q, x, nb, labels, wtab, lflags, affs, st, dl, dx)
-  } else {
-    constexpr auto kern = k_fused_labels<T, D_T, c.TH, c.TW, c.PLQ, true, RB>;
-    PEA_LAUNCH(kern, grid, blk, lds, s, P, Q, x, nb, labels, wtab, lflags, affs, st, dl, dx)
-  }
-  return true;
+  return with_bool(P.border != PEA_BORDER_CIRCULAR, [&](auto crop) {
+    return launch<k_fused_labels<T, D_T, c.TH, c.TW, c.PLQ, crop.value, RB>>(grid, blk, lds, s, P, Q, x, nb, labels, wtab, lflags, affs,
+                                                                             st, dl, dx);
+  });
 }
 
 // self + detached-EMA cross loss from labels in one launch (k_fused_labels_dual): both plans must split the stencil
@@ -56,14 +47,10 @@ bool try_fused_labels_dual(const KParams& P, const KParams& P2, const T* x, cons
   const size_t lds = Lds<D_T, c.PLQ>::kBytes + 2 * (size_t)(c.TH * c.TW / 64) * P.K * sizeof(float);
   if (lds > (size_t)kLdsMax) return false;
   const dim3 grid((unsigned)(Q.tiles_per_xcd * kXcd)), blk(c.TH * c.TW);
-  if (P.border == PEA_BORDER_CIRCULAR) {
-    constexpr auto kern = k_fused_labels_dual<T, D_T, c.TH, c.TW, c.PLQ, false>;
-    PEA_LAUNCH(kern, grid, blk, lds, s, P, Q, Q2, C2, x, ema, labels, wtab, lflags, affs, st, st2, dl, dl2, dx)
-  } else {
-    constexpr auto kern = k_fused_labels_dual<T, D_T, c.TH, c.TW, c.PLQ, true>;
-    PEA_LAUNCH(kern, grid, blk, lds, s, P, Q, Q2, C2, x, ema, labels, wtab, lflags, affs, st, st2, dl, dl2, dx)
-  }
-  return true;
+  return with_bool(P.border != PEA_BORDER_CIRCULAR, [&](auto crop) {
+    return launch<k_fused_labels_dual<T, D_T, c.TH, c.TW, c.PLQ, crop.value>>(grid, blk, lds, s, P, Q, Q2, C2, x, ema, labels, wtab, lflags,
+                                                                              affs, st, st2, dl, dl2, dx);
+  });
 }
 
 GParams gparams(const PeaDesc* desc, unsigned flags) {
@@ -81,31 +68,26 @@ GParams gparams(const PeaDesc* desc, unsigned flags) {
 bool labels_step(const KParams& P, int dtype, const void* e, const void* e_other, const int32_t* labels, const float* wtab,
                  unsigned lflags, float* affs, LossState* st, const float* dl, void* de, hipStream_t s) {
   if ((P.D != 16 && P.D != 32) || env().force_direct) return false;
-#define PEA_LAB(TT, DD)                                                                                                       \
-  {                                                                                                                           \
-    const TT *x = (const TT*)e, *nb = (const TT*)e_other;                                                                     \
-    return nb ? try_fused_labels<TT, DD, false>(P, x, nb, labels, wtab, lflags, affs, st, dl, (TT*)de, s)                     \
-              : try_fused_labels<TT, DD, true>(P, x, x, labels, wtab, lflags, affs, st, dl, (TT*)de, s);                      \
-  }
-  if (dtype == PEA_F16) {
-    if (P.D == 16) PEA_LAB(__half, 16) else PEA_LAB(__half, 32)
-  } else if (dtype == PEA_BF16) {
-    if (P.D == 16) PEA_LAB(__bf16, 16) else PEA_LAB(__bf16, 32)
-  } else {
-    if (P.D == 16) PEA_LAB(float, 16) else PEA_LAB(float, 32)
-  }
-#undef PEA_LAB
+  return with_storage(dtype, [&](auto st_) {
+    using T = typename decltype(st_)::type;
+    const T *x = (const T*)e, *nb = (const T*)e_other;
+    return with_width<16, 32>(P.D, [&](auto d) {
+      return nb ? try_fused_labels<T, d.value, false>(P, x, nb, labels, wtab, lflags, affs, st, dl, (T*)de, s)
+                : try_fused_labels<T, d.value, true>(P, x, x, labels, wtab, lflags, affs, st, dl, (T*)de, s);
+    });
+  });
 }
 
 bool labels_step_dual(const KParams& P, const KParams& P2, int dtype, const void* e, const void* ema, const int32_t* labels,
                       const float* wtab, unsigned lflags, float* affs, LossState* st, LossState* st2, const float* dl,
                       const float* dl2, void* de, hipStream_t s) {
   if ((P.D != 16 && P.D != 32) || env().force_direct) return false;
-#define PEA_LD(T_, D_) try_fused_labels_dual<T_, D_>(P, P2, (const T_*)e, (const T_*)ema, labels, wtab, lflags, affs, st, st2, dl, dl2, (T_*)de, s)
-  if (dtype == PEA_F16) return P.D == 16 ? PEA_LD(__half, 16) : PEA_LD(__half, 32);
-  if (dtype == PEA_BF16) return P.D == 16 ? PEA_LD(__bf16, 16) : PEA_LD(__bf16, 32);
-  return P.D == 16 ? PEA_LD(float, 16) : PEA_LD(float, 32);
-#undef PEA_LD
+  return with_storage(dtype, [&](auto st_) {
+    using T = typename decltype(st_)::type;
+    return with_width<16, 32>(P.D, [&](auto d) {
+      return try_fused_labels_dual<T, d.value>(P, P2, (const T*)e, (const T*)ema, labels, wtab, lflags, affs, st, st2, dl, dl2, (T*)de, s);
+    });
+  });
 }
 
 // pea_gen_targets: one count per (image, channel); pea_label_weights: one partial per (image, channel, workgroup)

@@ -5,16 +5,11 @@
 
 #include "pea_plan.h"
 #include "pea_chunked.h"
+#include "pea_dispatch.h"
 
 namespace pea {
 
 namespace {
-
-#define PEA_LAUNCH(kern, grid, blk, lds, s, ...)              \
-  {                                                           \
-    if (allow_lds<kern>(lds)) return false;                   \
-    hipLaunchKernelGGL(kern, grid, blk, lds, s, __VA_ARGS__); \
-  }
 
 // REPLICATE tables are generic (embedding_loss_norm6: diagonals, z steps, reach 27): where the forward's one-sided region serves fewer
 // than half of the offsets from LDS the global-memory forward is faster (shift_func(17) at 24 x 1024^2: 2 near of 17, 4.06 against
@@ -31,33 +26,8 @@ struct FwdT {  // typed view of FwdArgs
   bool mf32;  // m holds f32 (training): the kernels' MT = float forms
   bool lact;  // training: the loss on the activated map (PEA_FLAG_LOSS_ACT): the kernels' LACT forms
 };
-// launch a forward's u8-mask form `kern`, or -- training with an f32 mask -- its f32-mask form (KF: the parenthesised kernel,
-// instantiated where the launcher's constexpr kMF says so; the launcher has declined the call where it does not)
-#define PEA_LAUNCH_M(kern, KF, grid, blk, lds, s, P, Q, e, eo, ...)                                                        \
-  if (TRAIN && A.mf32) {                                                                                                   \
-    if constexpr (kMF) {                                                                                                   \
-      constexpr auto kernm = KF;                                                                                           \
-      PEA_LAUNCH(kernm, grid, blk, lds, s, P, Q, e, eo, A.t, A.w, (const float*)(const void*)A.m, __VA_ARGS__)             \
-    }                                                                                                                      \
-  } else {                                                                                                                 \
-    PEA_LAUNCH(kern, grid, blk, lds, s, P, Q, e, eo, A.t, A.w, A.m, __VA_ARGS__)                                           \
-  }
-
-// the same for the forwards that also have PEA_FLAG_LOSS_ACT forms (KL: u8 mask, instantiated wherever TRAIN; KLF: f32 mask, where kMF)
-#define PEA_LAUNCH_ML(kern, KF, KL, KLF, grid, blk, lds, s, P, Q, e, eo, ...)                                              \
-  if (TRAIN && A.lact) {                                                                                                   \
-    if constexpr (TRAIN) {                                                                                                 \
-      if (A.mf32) {                                                                                                        \
-        if constexpr (kMF) {                                                                                               \
-          constexpr auto kernlf = KLF;                                                                                     \
-          PEA_LAUNCH(kernlf, grid, blk, lds, s, P, Q, e, eo, A.t, A.w, (const float*)(const void*)A.m, __VA_ARGS__)        \
-        }                                                                                                                  \
-      } else {                                                                                                             \
-        constexpr auto kernl = KL;                                                                                         \
-        PEA_LAUNCH(kernl, grid, blk, lds, s, P, Q, e, eo, A.t, A.w, A.m, __VA_ARGS__)                                      \
-      }                                                                                                                    \
-    }                                                                                                                      \
-  } else PEA_LAUNCH_M(kern, KF, grid, blk, lds, s, P, Q, e, eo, __VA_ARGS__)
+// The (mask type, LOSS_ACT) forms of a forward that are built: the u8 mask on the raw map always; PEA_FLAG_LOSS_ACT forms wherever
+// TRAIN; f32-mask forms where the launcher's constexpr kMF says so (the launcher has declined the call where a form is not built)
 
 // forward with the LDS-transposed, dwordx4 epilogue (k_fwd_tiled_v): 16x32 tiles, the dot products laid over the dead region,
 // two workgroups of 8 waves per CU.  The training forward wherever the LDS-DMA kernel (k_fwd_xdma) does not apply.
@@ -80,19 +50,17 @@ bool try_fwd_v(const KParams& P, const FwdT& A, float* inv_out, hipStream_t s) {
   if (rep_mostly_far(P, Q)) return false;
   const T *e = (const T*)A.e, *eo = (const T*)A.eo;
   const dim3 grid((unsigned)(Q.tiles_per_xcd * kXcd)), blk(c.TH * c.TW);
-#define PEA_FV(CROP_, SELF_)                                                                                  \
-  {                                                                                                           \
-    constexpr auto kern = k_fwd_tiled_v<T, D_T, c.TH, c.TW, c.PLQ, true, CROP_, TRAIN, SELF_>;                \
-    PEA_LAUNCH_ML(kern, (k_fwd_tiled_v<T, D_T, c.TH, c.TW, c.PLQ, true, CROP_, TRAIN, SELF_, float>),           \
-                  (k_fwd_tiled_v<T, D_T, c.TH, c.TW, c.PLQ, true, CROP_, TRAIN, SELF_, uint8_t, true>),         \
-                  (k_fwd_tiled_v<T, D_T, c.TH, c.TW, c.PLQ, true, CROP_, TRAIN, SELF_, float, true>),           \
-                  grid, blk, lds, s, P, Q, e, eo, A.affs, A.gout, A.st, inv_out)                                \
-  }
-  const bool crop = P.border != PEA_BORDER_CIRCULAR;
-  if (eo == e) { if (crop) PEA_FV(true, true) else PEA_FV(false, true) }
-  else { if (crop) PEA_FV(true, false) else PEA_FV(false, false) }
-#undef PEA_FV
-  return true;
+  return with_bool(P.border != PEA_BORDER_CIRCULAR, [&](auto crop) {
+    return with_bool(eo == e, [&](auto self) {
+      return with_mask_form(A.mf32, A.lact, [&](auto mt, auto lact) {
+        using MT = typename decltype(mt)::type;
+        if constexpr ((std::is_same<MT, uint8_t>::value || kMF) && (TRAIN || !lact.value))
+          return launch<k_fwd_tiled_v<T, D_T, c.TH, c.TW, c.PLQ, true, crop.value, TRAIN, self.value, MT, lact.value>>(
+              grid, blk, lds, s, P, Q, e, eo, A.t, A.w, (const MT*)(const void*)A.m, A.affs, A.gout, A.st, inv_out);
+        else return false;
+      });
+    });
+  });
 }
 
 template <typename T, int D_T, bool TRAIN>
@@ -109,19 +77,17 @@ bool try_fwd_tiled(const KParams& P, const FwdT& A, float* inv_out, hipStream_t 
   const size_t lds = Lds<D_T, c.PLQ>::kBytes + (TRAIN ? (size_t)(NT / 64) * P.K * sizeof(float) : 0);
   const T *e = (const T*)A.e, *eo = (const T*)A.eo;
   const dim3 grid((unsigned)(Q.tiles_per_xcd * kXcd)), blk(NT);
-#define PEA_FT(CROP_, SELF_)                                                                                  \
-  {                                                                                                           \
-    constexpr auto kern = k_fwd_tiled<T, D_T, c.TH, c.TW, c.PLQ, CROP_, TRAIN, SELF_>;                        \
-    PEA_LAUNCH_ML(kern, (k_fwd_tiled<T, D_T, c.TH, c.TW, c.PLQ, CROP_, TRAIN, SELF_, float>),                   \
-                  (k_fwd_tiled<T, D_T, c.TH, c.TW, c.PLQ, CROP_, TRAIN, SELF_, uint8_t, true>),                 \
-                  (k_fwd_tiled<T, D_T, c.TH, c.TW, c.PLQ, CROP_, TRAIN, SELF_, float, true>),                   \
-                  grid, blk, lds, s, P, Q, e, eo, A.affs, A.gout, A.st, inv_out)                                \
-  }
-  const bool crop = P.border != PEA_BORDER_CIRCULAR;
-  if (eo == e) { if (crop) PEA_FT(true, true) else PEA_FT(false, true) }
-  else { if (crop) PEA_FT(true, false) else PEA_FT(false, false) }
-#undef PEA_FT
-  return true;
+  return with_bool(P.border != PEA_BORDER_CIRCULAR, [&](auto crop) {
+    return with_bool(eo == e, [&](auto self) {
+      return with_mask_form(A.mf32, A.lact, [&](auto mt, auto lact) {
+        using MT = typename decltype(mt)::type;
+        if constexpr ((std::is_same<MT, uint8_t>::value || kMF) && (TRAIN || !lact.value))
+          return launch<k_fwd_tiled<T, D_T, c.TH, c.TW, c.PLQ, crop.value, TRAIN, self.value, MT, lact.value>>(
+              grid, blk, lds, s, P, Q, e, eo, A.t, A.w, (const MT*)(const void*)A.m, A.affs, A.gout, A.st, inv_out);
+        else return false;
+      });
+    });
+  });
 }
 
 // D = 64: channels through LDS in two chunks of 32 (k_fwd_tiled_chunked, the D = 32 region geometry);
@@ -140,22 +106,18 @@ bool try_fwd_chunked(const KParams& P, const FwdT& A, hipStream_t s) {
   if (lds > (size_t)kLdsMax) return false;
   const T *e = (const T*)A.e, *eo = (const T*)A.eo;
   const dim3 grid((unsigned)(Q.tiles_per_xcd * kXcd)), blk(c.TH * c.TW);
-#define PEA_FC(CROP_, SELF_)                                                                                  \
-  {                                                                                                           \
-    constexpr auto kern = k_fwd_tiled_chunked<T, D_T, DC, c.TH, c.TW, c.PLQ, CROP_, TRAIN, SELF_>;            \
-    PEA_LAUNCH_M(kern, (k_fwd_tiled_chunked<T, D_T, DC, c.TH, c.TW, c.PLQ, CROP_, TRAIN, SELF_, float>),        \
-                 grid, blk, lds, s, P, Q, e, eo, A.affs, A.gout, A.st)                           \
-  }
-  const bool crop = P.border != PEA_BORDER_CIRCULAR;
-  if (eo == e) {
-    if (crop) PEA_FC(true, true) else PEA_FC(false, true)
-  } else {
-    // a second operand under the 128-VGPR budget of DC = 16 spills: not instantiated (the caller keeps the one-region kernels)
-    if constexpr (DC > 16) { if (crop) PEA_FC(true, false) else PEA_FC(false, false) }
-    else return false;
-  }
-#undef PEA_FC
-  return true;
+  return with_bool(P.border != PEA_BORDER_CIRCULAR, [&](auto crop) {
+    return with_bool(eo == e, [&](auto self) {
+      return with_bool(A.mf32, [&](auto mf) {
+        using MT = std::conditional_t<mf.value, float, uint8_t>;
+        // a second operand under the 128-VGPR budget of DC = 16 spills: not instantiated (the caller keeps the one-region kernels)
+        if constexpr ((self.value || DC > 16) && (kMF || !mf.value))
+          return launch<k_fwd_tiled_chunked<T, D_T, DC, c.TH, c.TW, c.PLQ, crop.value, TRAIN, self.value, MT>>(
+              grid, blk, lds, s, P, Q, e, eo, A.t, A.w, (const MT*)(const void*)A.m, A.affs, A.gout, A.st);
+        else return false;
+      });
+    });
+  });
 }
 
 template <typename T, bool TRAIN>
@@ -189,14 +151,9 @@ bool try_bwd_tiled(const KParams& P, const T* x, const T* nb, const float* g, co
   if (!plan_tiles_cached(P, c, !(RA && !RB), &Q, true)) return false;
   const size_t lds = Lds<D_T, c.PLQ>::kBytes;
   const dim3 grid((unsigned)(Q.tiles_per_xcd * kXcd)), blk(c.TH * c.TW);
-  if (P.border == PEA_BORDER_CIRCULAR) {
-    constexpr auto kern = k_bwd_tiled<T, D_T, c.TH, c.TW, c.PLQ, false, RA, RB>;
-    PEA_LAUNCH(kern, grid, blk, lds, s, P, Q, x, nb, g, dl, dx)
-  } else {
-    constexpr auto kern = k_bwd_tiled<T, D_T, c.TH, c.TW, c.PLQ, true, RA, RB>;
-    PEA_LAUNCH(kern, grid, blk, lds, s, P, Q, x, nb, g, dl, dx)
-  }
-  return true;
+  return with_bool(P.border != PEA_BORDER_CIRCULAR, [&](auto crop) {
+    return launch<k_bwd_tiled<T, D_T, c.TH, c.TW, c.PLQ, crop.value, RA, RB>>(grid, blk, lds, s, P, Q, x, nb, g, dl, dx);
+  });
 }
 
 template <typename T, int D_T>
@@ -213,19 +170,18 @@ bool tiled_fwd(const KParams& P, const FwdArgs& A, hipStream_t s, bool* wrote_in
   *wrote_inv = false;
   if (env().force_direct) return false;
   const FwdT T_ = {A.e, A.eo, A.t, A.w, A.m, A.affs, A.gout, A.st, A.inv_out, A.train && A.mf32, A.train && A.lact};
-  if (A.dtype == PEA_F16) return A.train ? fwd_any<__half, true>(P, T_, s, wrote_inv) : fwd_any<__half, false>(P, T_, s, wrote_inv);
-  if (A.dtype == PEA_BF16) return A.train ? fwd_any<__bf16, true>(P, T_, s, wrote_inv) : fwd_any<__bf16, false>(P, T_, s, wrote_inv);
-  return A.train ? fwd_any<float, true>(P, T_, s, wrote_inv) : fwd_any<float, false>(P, T_, s, wrote_inv);
+  return with_storage(A.dtype, [&](auto st) {
+    return with_bool(A.train, [&](auto train) { return fwd_any<typename decltype(st)::type, train.value>(P, T_, s, wrote_inv); });
+  });
 }
 
 bool tiled_bwd(const KParams& P, int dtype, int roles, const void* x, const void* nbA, const void* nbB, const float* g,
                const float* dl, void* dx, hipStream_t s) {
   if (env().force_direct || (P.D != 16 && P.D != 32)) return false;
-  if (dtype == PEA_F16)
-    return P.D == 16 ? bwd_roles<__half, 16>(P, roles, x, nbA, nbB, g, dl, dx, s) : bwd_roles<__half, 32>(P, roles, x, nbA, nbB, g, dl, dx, s);
-  if (dtype == PEA_BF16)
-    return P.D == 16 ? bwd_roles<__bf16, 16>(P, roles, x, nbA, nbB, g, dl, dx, s) : bwd_roles<__bf16, 32>(P, roles, x, nbA, nbB, g, dl, dx, s);
-  return P.D == 16 ? bwd_roles<float, 16>(P, roles, x, nbA, nbB, g, dl, dx, s) : bwd_roles<float, 32>(P, roles, x, nbA, nbB, g, dl, dx, s);
+  return with_storage(dtype, [&](auto st) {
+    return with_width<16, 32>(
+        P.D, [&](auto d) { return bwd_roles<typename decltype(st)::type, d.value>(P, roles, x, nbA, nbB, g, dl, dx, s); });
+  });
 }
 
 }  // namespace pea

@@ -31,39 +31,24 @@ bool fwd_self(const KParams& P, const FwdArgs& A, hipStream_t s) {
   if (la && z3) return false;
   const XParams& C = X.C;
   const dim3 grid((unsigned)(C.tiles_per_xcd * kXcd)), blk(kXdmaTH * kXdmaTW);
-#define PEA_XFK(CROP_, PSU_, WPE_, MT_, LACT_)                                                                              \
-  {                                                                                                                         \
-    constexpr auto kern = k_fwd_xdma<D_T, kXdmaTH, kXdmaTW, PSU_, CROP_, true, 0, false, WPE_, false, MT_, LACT_>;          \
-    PEA_LAUNCH(kern, grid, blk, X.lds, s, P, C, e, t, w, (const MT_*)(const void*)A.m, A.affs, A.gout, A.st, A.inv_out,     \
-               (const float*)nullptr, (float*)nullptr, LabArgs{})                                                           \
-  }
-#define PEA_XF(CROP_, PSU_, ZF_, WPE_)                                                                                      \
-  if (mf || la) {                                                                                                           \
-    if constexpr (TRAIN && ZF_ == 0) {                                                                                      \
-      if (!la) PEA_XFK(CROP_, PSU_, WPE_, float, false)                                                                     \
-      else if (mf) PEA_XFK(CROP_, PSU_, WPE_, float, true)                                                                  \
-      else PEA_XFK(CROP_, PSU_, WPE_, uint8_t, true)                                                                        \
-    }                                                                                                                       \
-  } else {                                                                                                                  \
-    constexpr auto kern = k_fwd_xdma<D_T, kXdmaTH, kXdmaTW, PSU_, CROP_, TRAIN, ZF_, false, WPE_>;                          \
-    PEA_LAUNCH(kern, grid, blk, X.lds, s, P, C, e, t, w, A.m, A.affs, A.gout, A.st, A.inv_out, (const float*)nullptr,       \
-               (float*)nullptr, LabArgs{})                                                                                  \
-  }
-  const bool crop = P.border != PEA_BORDER_CIRCULAR;
+  // the f32-mask and LOSS_ACT forms are built for 2D training only (TRAIN, ZF = 0): every other call with them was declined above
+  auto go = [&](auto psu, auto zf, auto wpe) {
+    return with_bool(P.border != PEA_BORDER_CIRCULAR, [&](auto crop) {
+      return with_mask_form(mf, la, [&](auto mt, auto lact) {
+        using MT = typename decltype(mt)::type;
+        if constexpr ((std::is_same<MT, uint8_t>::value && !lact.value) || (TRAIN && zf.value == 0))
+          return launch<k_fwd_xdma<D_T, kXdmaTH, kXdmaTW, psu.value, crop.value, TRAIN, zf.value, false, wpe.value, false, MT, lact.value>>(
+              grid, blk, X.lds, s, P, C, e, t, w, (const MT*)(const void*)A.m, A.affs, A.gout, A.st, A.inv_out, (const float*)nullptr,
+              (float*)nullptr, LabArgs{});
+        else return false;
+      });
+    });
+  };
   if constexpr (D_T == 16) {
-    if (z3) {
-      if (crop) PEA_XF(true, kXdmaPSU3F, kXZ / 2, 4) else PEA_XF(false, kXdmaPSU3F, kXZ / 2, 4)
-      return true;
-    }
+    if (z3) return go(Int<kXdmaPSU3F>{}, Int<kXZ / 2>{}, Int<4>{});
   }
-  if (wg3) {
-    if (crop) PEA_XF(true, kXdmaPSUF, 0, 6) else PEA_XF(false, kXdmaPSUF, 0, 6)
-  } else {
-    if (crop) PEA_XF(true, kXdmaPSU, 0, 4) else PEA_XF(false, kXdmaPSU, 0, 4)
-  }
-#undef PEA_XF
-#undef PEA_XFK
-  return true;
+  if (wg3) return go(Int<kXdmaPSUF>{}, Int<0>{}, Int<6>{});
+  return go(Int<kXdmaPSU>{}, Int<0>{}, Int<4>{});
 }
 
 template <int D_T>
@@ -82,21 +67,16 @@ bool bwd_self(const KParams& P, const float* x, const float* inv, const float* g
   constexpr int XP = D_T > 32 ? 8 : kXP;  // pairs per axis the instantiation keeps in registers
   if (C.npx > (z3 ? 8 : XP) || C.npy > (z3 ? 8 : XP)) return false;
   const dim3 grid((unsigned)(C.tiles_per_xcd * kXcd)), blk(kXdmaTH * kXdmaTW);
-#define PEA_XB(CROP_, XP_, PSU_, ZP_)                                                             \
-  {                                                                                               \
-    constexpr auto kern = k_bwd_xdma<D_T, kXdmaTH, kXdmaTW, PSU_, CROP_, XP_, kAuxNT, ZP_>;       \
-    PEA_LAUNCH(kern, grid, blk, X.lds, s, P, C, x, inv, g, dl, dx, OtherArgs{}, DualArgs{})       \
-  }
-  const bool crop = P.border != PEA_BORDER_CIRCULAR;
+  auto go = [&](auto xp, auto psu, auto zp) {
+    return with_bool(P.border != PEA_BORDER_CIRCULAR, [&](auto crop) {
+      return launch<k_bwd_xdma<D_T, kXdmaTH, kXdmaTW, psu.value, crop.value, xp.value, kAuxNT, zp.value>>(grid, blk, X.lds, s, P, C, x, inv, g,
+                                                                                                       dl, dx, OtherArgs{}, DualArgs{});
+    });
+  };
   if constexpr (D_T == 16) {
-    if (z3) {
-      if (crop) PEA_XB(true, 8, kXdmaPSU3, kXZ) else PEA_XB(false, 8, kXdmaPSU3, kXZ)
-      return true;
-    }
+    if (z3) return go(Int<8>{}, Int<kXdmaPSU3>{}, Int<kXZ>{});
   }
-  if (crop) PEA_XB(true, XP, kXdmaPSU, 0) else PEA_XB(false, XP, kXdmaPSU, 0)
-#undef PEA_XB
-  return true;
+  return go(Int<XP>{}, Int<kXdmaPSU>{}, Int<0>{});
 }
 
 }  // namespace
@@ -109,16 +89,9 @@ bool xdma_fwd_self(const KParams& P, const FwdArgs& A, hipStream_t s) {
   if (A.dtype == PEA_F16 || A.dtype == PEA_BF16) {  // 16-bit storage: pea_xdma_h16.h
     return xdma_h_fwd_self(P, A, s);  // pea_k_xdma_h.hip
   }
-  if (!A.train) {
-    if (P.D == 16) return fwd_self<16, false>(P, A, s);
-    if (P.D == 32) return fwd_self<32, false>(P, A, s);
-    if (P.D == 64) return fwd_self<64, false>(P, A, s);
-    return false;
-  }
-  if (P.D == 16) return fwd_self<16, true>(P, A, s);
-  if (P.D == 32) return fwd_self<32, true>(P, A, s);
-  if (P.D == 64) return fwd_self<64, true>(P, A, s);
-  return false;
+  return with_width<16, 32, 64>(P.D, [&](auto d) {
+    return with_bool(A.train, [&](auto train) { return fwd_self<d.value, train.value>(P, A, s); });
+  });
 }
 
 // the full-resolution pair of the 2D training loops as one forward launch (pea_xdma_dual.h): 2D, D = 16, f32, axis-aligned stencil
@@ -142,24 +115,18 @@ bool xdma_fwd_dual(const KParams& P, const KParams& P2, const FwdArgs& A, const 
   DA.e2 = e2; DA.gout2 = A2.gout; DA.inv_other_out = A2.inv_out; DA.st2 = A2.st;
   for (int i = 0; i < kXK; ++i) DA.gs2[i] = i < P2.K ? P2.gscale[i] : 0.f;
   const dim3 grid((unsigned)(X.C.tiles_per_xcd * kXcd)), blk(kXdmaTH * kXdmaTW);
-  const bool crop = P.border != PEA_BORDER_CIRCULAR;
-#define PEA_XFD(CROP_, NB_)                                                                                                \
-  {                                                                                                                        \
-    const size_t lds = (size_t)(NB_ == 3 ? 3 : 2) * 4 * kXdmaPSUF * 256;                                                   \
-    if (A.mf32) {                                                                                                          \
-      constexpr auto kern = k_fwd_xdma_dual<kXdmaTH, kXdmaTW, kXdmaPSUF, CROP_, NB_, float>;                               \
-      PEA_LAUNCH(kern, grid, blk, lds, s, P, X.C, e, A.t, A.w, (const float*)(const void*)A.m, A.affs, A.gout, A.st,       \
-                 A.inv_out, DA)                                                                                            \
-    } else {                                                                                                               \
-      constexpr auto kern = k_fwd_xdma_dual<kXdmaTH, kXdmaTW, kXdmaPSUF, CROP_, NB_>;                                      \
-      PEA_LAUNCH(kern, grid, blk, lds, s, P, X.C, e, A.t, A.w, A.m, A.affs, A.gout, A.st, A.inv_out, DA)                   \
-    }                                                                                                                      \
-  }
   // (NB = 4: the ring of two four-plane buffers handed over in halves; the whole-buffer hand-off -- NB = 2, +2.6 % -- and the ring of
   //  three at one workgroup per CU -- NB = 3, +21 % -- were switches until round 6 and are no longer compiled: EXPERIMENTS.md)
-  if (crop) PEA_XFD(true, 4) else PEA_XFD(false, 4)
-#undef PEA_XFD
-  return true;
+  constexpr int NB = 4;
+  const size_t lds = (size_t)2 * 4 * kXdmaPSUF * 256;
+  return with_bool(P.border != PEA_BORDER_CIRCULAR, [&](auto crop) {
+    return with_bool(A.mf32, [&](auto mf) {
+      using MT = std::conditional_t<mf.value, float, uint8_t>;
+      return launch<k_fwd_xdma_dual<kXdmaTH, kXdmaTW, kXdmaPSUF, crop.value, NB, MT>>(grid, blk, lds, s, P, X.C, e, A.t, A.w,
+                                                                                      (const MT*)(const void*)A.m, A.affs, A.gout, A.st,
+                                                                                      A.inv_out, DA);
+    });
+  });
 }
 
 // the cross loss with a second operand: D = 16, f32, axis-aligned stencil; 2D images (either border) and 3D volumes whose stencil
@@ -175,23 +142,14 @@ static bool fwd_other_wide(const KParams& P, const FwdArgs& A, hipStream_t s) {
   if (!plan(P, kXdmaPSUF, 1, &X) || X.C.nfz > 0 || P.K > kXP || P.Z != 1) return false;
   const size_t lds = X.lds + (size_t)6 * 2048;  // + the own tiles: three buffers x two channels x 2 KB
   const dim3 grid((unsigned)(X.C.tiles_per_xcd * kXcd)), blk(kXdmaTH * kXdmaTW);
-#define PEA_XFW(CROP_, MT_, LACT_)                                                                                       \
-  {                                                                                                                      \
-    constexpr auto kern = k_fwd_xdma<D_T, kXdmaTH, kXdmaTW, kXdmaPSUF, CROP_, true, 0, true, 4, false, MT_, LACT_>;      \
-    PEA_LAUNCH(kern, grid, blk, lds, s, P, X.C, e_other, A.t, A.w, (const MT_*)(const void*)A.m, A.affs, A.gout, A.st,   \
-               A.inv_out, e, A.inv_out + (size_t)P.B * P.S, LabArgs{})                                                   \
-  }
-  const bool crop = P.border != PEA_BORDER_CIRCULAR;
-  if (A.lact) {  // the loss on the activated map (PEA_FLAG_LOSS_ACT)
-    if (A.mf32) { if (crop) PEA_XFW(true, float, true) else PEA_XFW(false, float, true) }
-    else { if (crop) PEA_XFW(true, uint8_t, true) else PEA_XFW(false, uint8_t, true) }
-  } else if (A.mf32) {
-    if (crop) PEA_XFW(true, float, false) else PEA_XFW(false, float, false)
-  } else {
-    if (crop) PEA_XFW(true, uint8_t, false) else PEA_XFW(false, uint8_t, false)
-  }
-#undef PEA_XFW
-  return true;
+  return with_bool(P.border != PEA_BORDER_CIRCULAR, [&](auto crop) {
+    return with_mask_form(A.mf32, A.lact, [&](auto mt, auto lact) {  // lact: the loss on the activated map (PEA_FLAG_LOSS_ACT)
+      using MT = typename decltype(mt)::type;
+      return launch<k_fwd_xdma<D_T, kXdmaTH, kXdmaTW, kXdmaPSUF, crop.value, true, 0, true, 4, false, MT, lact.value>>(
+          grid, blk, lds, s, P, X.C, e_other, A.t, A.w, (const MT*)(const void*)A.m, A.affs, A.gout, A.st, A.inv_out, e,
+          A.inv_out + (size_t)P.B * P.S, LabArgs{});
+    });
+  });
 }
 
 bool xdma_fwd_other(const KParams& P, const FwdArgs& A, hipStream_t s) {
@@ -205,8 +163,7 @@ bool xdma_fwd_other(const KParams& P, const FwdArgs& A, hipStream_t s) {
     return false;
   if ((P.tbs | P.wbs | P.mbs) & 3) return false;
   if (A.mf32 && misaligned(A.m, 16)) return false;  // (the f32 mask's quads are dwordx4 loads)
-  if (P.D == 32) return fwd_other_wide<32>(P, A, s);
-  if (P.D == 64) return fwd_other_wide<64>(P, A, s);
+  if (P.D != 16) return with_width<32, 64>(P.D, [&](auto d) { return fwd_other_wide<d.value>(P, A, s); });
   XPlan X;
   // (three workgroups per CU do not fit here: the own pixel's 16 registers on top of the accumulators spill at 80 VGPRs)
   bool z3 = false;
@@ -217,32 +174,20 @@ bool xdma_fwd_other(const KParams& P, const FwdArgs& A, hipStream_t s) {
   if (P.K > (z3 ? kXP + 2 : kXP)) return false;
   if (z3 && (A.mf32 || A.lact)) return false;  // (the f32-mask and the PEA_FLAG_LOSS_ACT forms are 2D)
   const dim3 grid((unsigned)(X.C.tiles_per_xcd * kXcd)), blk(kXdmaTH * kXdmaTW);
-  const bool crop = P.border != PEA_BORDER_CIRCULAR;
-#define PEA_XFO(CROP_, PSU_, ZF_)                                                                                           \
-  {                                                                                                                         \
-    constexpr auto kern = k_fwd_xdma<16, kXdmaTH, kXdmaTW, PSU_, CROP_, true, ZF_, true>;                                   \
-    PEA_LAUNCH(kern, grid, blk, X.lds, s, P, X.C, e_other, A.t, A.w, A.m, A.affs, A.gout, A.st, A.inv_out, e,               \
-               A.inv_out + (size_t)P.B * P.S, LabArgs{})                                                                    \
-  }
-#define PEA_XFOM(CROP_, MT_, LACT_)                                                                                         \
-  {                                                                                                                         \
-    constexpr auto kern = k_fwd_xdma<16, kXdmaTH, kXdmaTW, kXdmaPSU, CROP_, true, 0, true, 4, false, MT_, LACT_>;           \
-    PEA_LAUNCH(kern, grid, blk, X.lds, s, P, X.C, e_other, A.t, A.w, (const MT_*)(const void*)A.m, A.affs, A.gout, A.st,    \
-               A.inv_out, e, A.inv_out + (size_t)P.B * P.S, LabArgs{})                                                      \
-  }
-  if (A.lact) {  // the loss on the activated map (PEA_FLAG_LOSS_ACT)
-    if (A.mf32) { if (crop) PEA_XFOM(true, float, true) else PEA_XFOM(false, float, true) }
-    else { if (crop) PEA_XFOM(true, uint8_t, true) else PEA_XFOM(false, uint8_t, true) }
-  } else if (A.mf32) {
-    if (crop) PEA_XFOM(true, float, false) else PEA_XFOM(false, float, false)
-  } else if (z3) {
-    if (crop) PEA_XFO(true, kXdmaPSU3F, kXZ / 2) else PEA_XFO(false, kXdmaPSU3F, kXZ / 2)
-  } else {
-    if (crop) PEA_XFO(true, kXdmaPSU, 0) else PEA_XFO(false, kXdmaPSU, 0)
-  }
-#undef PEA_XFO
-#undef PEA_XFOM
-  return true;
+  // the f32-mask and the loss on the activated map (PEA_FLAG_LOSS_ACT) are 2D forms (ZF = 0): z3 with them was declined above
+  auto go = [&](auto psu, auto zf) {
+    return with_bool(P.border != PEA_BORDER_CIRCULAR, [&](auto crop) {
+      return with_mask_form(A.mf32, A.lact, [&](auto mt, auto lact) {
+        using MT = typename decltype(mt)::type;
+        if constexpr ((std::is_same<MT, uint8_t>::value && !lact.value) || zf.value == 0)
+          return launch<k_fwd_xdma<16, kXdmaTH, kXdmaTW, psu.value, crop.value, true, zf.value, true, 4, false, MT, lact.value>>(
+              grid, blk, X.lds, s, P, X.C, e_other, A.t, A.w, (const MT*)(const void*)A.m, A.affs, A.gout, A.st, A.inv_out, e,
+              A.inv_out + (size_t)P.B * P.S, LabArgs{});
+        else return false;
+      });
+    });
+  };
+  return z3 ? go(Int<kXdmaPSU3F>{}, Int<kXZ / 2>{}) : go(Int<kXdmaPSU>{}, Int<0>{});
 }
 
 // the labels-in forward (k_fwd_xdma<.., LAB>): self loss, 2D, f32, axis-aligned stencil, K <= kXP; g_out and inv_out are required
@@ -256,16 +201,11 @@ static bool fwd_labels(const KParams& P, const FwdArgs& A, const LabArgs& LA, hi
   if (!plan(P, kXdmaPSUF, 1, &X) || X.C.nfz > 0 || P.K > kXP || P.Z != 1) return false;
   const size_t lds = X.lds + (size_t)kXdmaPSUF * 256;  // + the label plane
   const dim3 grid((unsigned)(X.C.tiles_per_xcd * kXcd)), blk(kXdmaTH * kXdmaTW);
-  if (P.border != PEA_BORDER_CIRCULAR) {
-    constexpr auto kern = k_fwd_xdma<D_T, kXdmaTH, kXdmaTW, kXdmaPSUF, true, true, 0, false, 6, true>;
-    PEA_LAUNCH(kern, grid, blk, lds, s, P, X.C, e, (const float*)nullptr, (const float*)nullptr, (const uint8_t*)nullptr, A.affs, A.gout,
-               A.st, A.inv_out, (const float*)nullptr, (float*)nullptr, LA)
-  } else {
-    constexpr auto kern = k_fwd_xdma<D_T, kXdmaTH, kXdmaTW, kXdmaPSUF, false, true, 0, false, 6, true>;
-    PEA_LAUNCH(kern, grid, blk, lds, s, P, X.C, e, (const float*)nullptr, (const float*)nullptr, (const uint8_t*)nullptr, A.affs, A.gout,
-               A.st, A.inv_out, (const float*)nullptr, (float*)nullptr, LA)
-  }
-  return true;
+  return with_bool(P.border != PEA_BORDER_CIRCULAR, [&](auto crop) {
+    return launch<k_fwd_xdma<D_T, kXdmaTH, kXdmaTW, kXdmaPSUF, crop.value, true, 0, false, 6, true>>(
+        grid, blk, lds, s, P, X.C, e, (const float*)nullptr, (const float*)nullptr, (const uint8_t*)nullptr, A.affs, A.gout, A.st, A.inv_out,
+        (const float*)nullptr, (float*)nullptr, LA);
+  });
 }
 
 // would xdma_fwd_labels + xdma_bwd_self take this descriptor (16-byte aligned tensors assumed)?
@@ -279,9 +219,7 @@ bool xdma_labels_supported(const KParams& P, int dtype) {
 bool xdma_fwd_labels(const KParams& P, const FwdArgs& A, const int32_t* labels, const float* wtab, unsigned lflags, hipStream_t s) {
   if (!env().fwd_xdma || !env().bwd_xdma || env().force_direct || A.dtype != PEA_F32 || !A.gout || !A.inv_out) return false;
   const LabArgs LA = {labels, wtab, lflags};
-  if (P.D == 16) return fwd_labels<16>(P, A, LA, s);
-  if (P.D == 32) return fwd_labels<32>(P, A, LA, s);
-  return false;
+  return with_width<16, 32>(P.D, [&](auto d) { return fwd_labels<d.value>(P, A, LA, s); });
 }
 
 // the cross backward (self loss, f32 storage, axis-aligned stencil): needs the 1 / norm plane; with the raw affinity map too
@@ -296,10 +234,7 @@ bool xdma_bwd_self(const KParams& P, const float* x, const float* inv, const flo
     done = xdma_pf_bwd_self(P, x, inv, g, affs, dl, dx, s);  // pea_k_xdma_pf.hip
     if (done) return true;
   }
-  if (P.D == 16) return bwd_self<16>(P, x, inv, g, dl, dx, s);
-  if (P.D == 32) return bwd_self<32>(P, x, inv, g, dl, dx, s);
-  if (P.D == 64) return bwd_self<64>(P, x, inv, g, dl, dx, s);
-  return false;
+  return with_width<16, 32, 64>(P.D, [&](auto d) { return bwd_self<d.value>(P, x, inv, g, dl, dx, s); });
 }
 
 // backward, role A only (the second operand is detached): de (+)= dloss * d loss / d e.  2D (either border) and 3D volumes with z steps
@@ -322,19 +257,13 @@ bool xdma_bwd_other(const KParams& P, const float* e, const float* e_other, cons
   const dim3 grid((unsigned)(X.C.tiles_per_xcd * kXcd)), blk(kXdmaTH * kXdmaTW);
   OtherArgs O;
   O.own = e; O.own_inv = inv2; O.accumulate = accumulate ? 1 : 0;
-  const bool crop = P.border != PEA_BORDER_CIRCULAR;
-#define PEA_XBO(CROP_, XP_, PSU_, ZP_)                                                                                      \
-  {                                                                                                                         \
-    constexpr auto kern = k_bwd_xdma<16, kXdmaTH, kXdmaTW, PSU_, CROP_, XP_, kAuxNT, ZP_, true>;                            \
-    PEA_LAUNCH(kern, grid, blk, X.lds, s, P, X.C, e_other, inv2 + (size_t)P.B * P.S, g, dl, de, O, DualArgs{})              \
-  }
-  if (z3) {
-    if (crop) PEA_XBO(true, 8, kXdmaPSU3, kXZ / 2) else PEA_XBO(false, 8, kXdmaPSU3, kXZ / 2)
-  } else {
-    if (crop) PEA_XBO(true, kXP, kXdmaPSU, 0) else PEA_XBO(false, kXP, kXdmaPSU, 0)
-  }
-#undef PEA_XBO
-  return true;
+  auto go = [&](auto xp, auto psu, auto zp) {
+    return with_bool(P.border != PEA_BORDER_CIRCULAR, [&](auto crop) {
+      return launch<k_bwd_xdma<16, kXdmaTH, kXdmaTW, psu.value, crop.value, xp.value, kAuxNT, zp.value, true>>(
+          grid, blk, X.lds, s, P, X.C, e_other, inv2 + (size_t)P.B * P.S, g, dl, de, O, DualArgs{});
+    });
+  };
+  return z3 ? go(Int<8>{}, Int<kXdmaPSU3>{}, Int<kXZ / 2>{}) : go(Int<kXP>{}, Int<kXdmaPSU>{}, Int<0>{});
 }
 
 // the pair's backward in one launch (k_bwd_xdma<.., DUAL>): 2D, D = 16, f32, circular border
@@ -349,16 +278,16 @@ bool xdma_bwd_dual(const KParams& P, const float* e, const float* ema, const flo
   Q.C2 = X2.C;
   Q.ema = ema; Q.inv_other = inv_other; Q.g_cross = g_cross; Q.dloss_cross = dl_cross;
   const dim3 grid((unsigned)(X.C.tiles_per_xcd * kXcd)), blk(kXdmaTH * kXdmaTW);
-  constexpr auto kern = k_bwd_xdma<16, kXdmaTH, kXdmaTW, kXdmaPSU, false, kXP, kAuxNT, 0, false, true>;
-  PEA_LAUNCH(kern, grid, blk, X.lds, s, P, X.C, e, inv, g, dl, de, OtherArgs{}, Q)
-  return true;
+  return launch<k_bwd_xdma<16, kXdmaTH, kXdmaTW, kXdmaPSU, false, kXP, kAuxNT, 0, false, true>>(grid, blk, X.lds, s, P, X.C, e, inv, g, dl, de,
+                                                                                              OtherArgs{}, Q);
 }
 
 void launch_inv_norm(const KParams& P, int dtype, const void* e, float* inv, hipStream_t s) {
   const dim3 grid((unsigned)(P.tiles_per_xcd * kXcd)), blk(kBlock);
-  if (dtype == PEA_F16) hipLaunchKernelGGL(k_inv_norm<__half>, grid, blk, 0, s, P, (const __half*)e, inv);
-  else if (dtype == PEA_BF16) hipLaunchKernelGGL(k_inv_norm<__bf16>, grid, blk, 0, s, P, (const __bf16*)e, inv);
-  else hipLaunchKernelGGL(k_inv_norm<float>, grid, blk, 0, s, P, (const float*)e, inv);
+  with_storage(dtype, [&](auto st) {
+    using T = typename decltype(st)::type;
+    hipLaunchKernelGGL(k_inv_norm<T>, grid, blk, 0, s, P, (const T*)e, inv);
+  });
 }
 
 // pea_cross_supported: would the cross kernels take this descriptor?  mode 0: forward, 1: backward (self loss),

@@ -35,47 +35,36 @@ bool fwd_self_h(const KParams& P, const FwdArgs& A, hipStream_t s) {
   // the loss on the activated map (PEA_FLAG_LOSS_ACT): likewise the 16-bit working buffer's kernel with one slot count, either mask type
   const bool la = TRAIN && A.lact;
   if (la && !(kBf16<T> || env().h16_hw)) return false;
+  const bool crop = P.border != PEA_BORDER_CIRCULAR;
   if (kBf16<T> || env().h16_hw) {  // half-precision working buffer, v_dot2 gather: 48 VGPRs and 30 KB -- four workgroups per CU (five: 173 against 168 us)
     const size_t ldsh = (size_t)4 * kXdmaPSUF * 256;
-    if constexpr (TRAIN) {
-      if (mf || la) {
-#define PEA_HFM(CROP_, MT_, LACT_)                                                                                        \
-  {                                                                                                                       \
-    /* (LOSS_ACT with an f32 mask and a cropped border takes 65 VGPRs: three workgroups per CU instead of a spill at four) */ \
-    constexpr int WPE_ = (LACT_ && CROP_ && std::is_same<MT_, float>::value) ? 6 : 8;                                     \
-    constexpr auto kern = k_fwd_xdma_h<D_T, kXdmaTH, kXdmaTW, kXdmaPSUF, CROP_, true, WPE_, true, kXP, false, T, MT_, LACT_>; \
-    PEA_LAUNCH(kern, grid, blk, ldsh, s, P, X.C, e, A.t, A.w, (const MT_*)(const void*)A.m, A.affs, A.gout, A.st,         \
-               A.inv_out, (const T*)nullptr, (float*)nullptr)                                                             \
+    return with_bool(crop, [&](auto crop) {
+      return with_mask_form(mf, la, [&](auto mt, auto lact) {
+        using MT = typename decltype(mt)::type;
+        if constexpr (std::is_same<MT, uint8_t>::value && !lact.value) {
+          // (D = 64 with at most eight offsets -- BASELINE configs[4] -- walks eight slots instead of ten)
+          return with_bool(D_T == 64 && X.C.nf <= 8, [&](auto few) {
+            constexpr int NXP = few.value && D_T == 64 ? 8 : kXP;
+            return launch<k_fwd_xdma_h<D_T, kXdmaTH, kXdmaTW, kXdmaPSUF, crop.value, TRAIN, 8, true, NXP, false, T>>(
+                grid, blk, ldsh, s, P, X.C, e, A.t, A.w, A.m, A.affs, A.gout, A.st, A.inv_out, (const T*)nullptr, (float*)nullptr);
+          });
+        } else if constexpr (TRAIN) {
+          // (LOSS_ACT with an f32 mask and a cropped border takes 65 VGPRs: three workgroups per CU instead of a spill at four)
+          constexpr int WPE = (lact.value && crop.value && std::is_same<MT, float>::value) ? 6 : 8;
+          return launch<k_fwd_xdma_h<D_T, kXdmaTH, kXdmaTW, kXdmaPSUF, crop.value, true, WPE, true, kXP, false, T, MT, lact.value>>(
+              grid, blk, ldsh, s, P, X.C, e, A.t, A.w, (const MT*)(const void*)A.m, A.affs, A.gout, A.st, A.inv_out, (const T*)nullptr,
+              (float*)nullptr);
+        } else {
+          return false;
+        }
+      });
+    });
   }
-        const bool crop = P.border != PEA_BORDER_CIRCULAR;
-        if (!la) { if (crop) PEA_HFM(true, float, false) else PEA_HFM(false, float, false) }
-        else if (mf) { if (crop) PEA_HFM(true, float, true) else PEA_HFM(false, float, true) }
-        else { if (crop) PEA_HFM(true, uint8_t, true) else PEA_HFM(false, uint8_t, true) }
-#undef PEA_HFM
-        return true;
-      }
-    }
-    // (D = 64 with at most eight offsets -- BASELINE configs[4] -- walks eight slots instead of ten)
-#define PEA_HF(CROP_, NXP_)                                                                                          \
-  {                                                                                                                  \
-    constexpr auto kern = k_fwd_xdma_h<D_T, kXdmaTH, kXdmaTW, kXdmaPSUF, CROP_, TRAIN, 8, true, NXP_, false, T>;     \
-    PEA_LAUNCH(kern, grid, blk, ldsh, s, P, X.C, e, A.t, A.w, A.m, A.affs, A.gout, A.st, A.inv_out, (const T*)nullptr, (float*)nullptr) \
-  }
-    const bool crop = P.border != PEA_BORDER_CIRCULAR;
-    if (D_T == 64 && X.C.nf <= 8) { if (crop) PEA_HF(true, (D_T == 64 ? 8 : kXP)) else PEA_HF(false, (D_T == 64 ? 8 : kXP)) }
-    else { if (crop) PEA_HF(true, kXP) else PEA_HF(false, kXP) }
-#undef PEA_HF
-    return true;
-  }
-  if constexpr (!kBf16<T>) {
-    if (P.border != PEA_BORDER_CIRCULAR) {
-      constexpr auto kern = k_fwd_xdma_h<D_T, kXdmaTH, kXdmaTW, kXdmaPSUF, true, TRAIN, 6>;
-      PEA_LAUNCH(kern, grid, blk, lds, s, P, X.C, e, A.t, A.w, A.m, A.affs, A.gout, A.st, A.inv_out, (const __half*)nullptr, (float*)nullptr)
-    } else {
-      constexpr auto kern = k_fwd_xdma_h<D_T, kXdmaTH, kXdmaTW, kXdmaPSUF, false, TRAIN, 6>;
-      PEA_LAUNCH(kern, grid, blk, lds, s, P, X.C, e, A.t, A.w, A.m, A.affs, A.gout, A.st, A.inv_out, (const __half*)nullptr, (float*)nullptr)
-    }
-  }
+  if constexpr (!kBf16<T>)
+    return with_bool(crop, [&](auto crop) {
+      return launch<k_fwd_xdma_h<D_T, kXdmaTH, kXdmaTW, kXdmaPSUF, crop.value, TRAIN, 6>>(
+          grid, blk, lds, s, P, X.C, e, A.t, A.w, A.m, A.affs, A.gout, A.st, A.inv_out, (const __half*)nullptr, (float*)nullptr);
+    });
   return true;
 }
 
@@ -96,25 +85,23 @@ bool bwd_self_h(const KParams& P, const T* x, const float* inv, const float* g, 
       //  eight pairs per axis instead of ten: an unused pair costs its LDS read and its two FMAs all the same)
       constexpr int XPS = D_T == 64 ? 8 : kXP;
       const bool few = D_T == 64 && X.C.npx <= 8 && X.C.npy <= 8;
-#define PEA_HPF(CROP_, PSU_, WPE_)                                                                   \
-  {                                                                                                  \
-    if ((kBf16<T> || env().h16_hw) && few) {                                                         \
-      constexpr auto kern = k_bwd_xdma_h<D_T, kXdmaTH, kXdmaTW, PSU_, CROP_, XPS, true, WPE_, true, false, T>;  \
-      PEA_LAUNCH(kern, grid, blk, (size_t)5 * PSU_ * 256, s, P, X.C, x, inv, g, affs, dl, dx, (const T*)nullptr, (const float*)nullptr) \
-    } else if (kBf16<T> || env().h16_hw) {                                                           \
-      constexpr auto kern = k_bwd_xdma_h<D_T, kXdmaTH, kXdmaTW, PSU_, CROP_, kXP, true, WPE_, true, false, T>;  \
-      PEA_LAUNCH(kern, grid, blk, (size_t)5 * PSU_ * 256, s, P, X.C, x, inv, g, affs, dl, dx, (const T*)nullptr, (const float*)nullptr) \
-    } else if constexpr (!kBf16<T>) {                                                                \
-      constexpr auto kern = k_bwd_xdma_h<D_T, kXdmaTH, kXdmaTW, PSU_, CROP_, kXP, true, WPE_>;        \
-      PEA_LAUNCH(kern, grid, blk, (size_t)5 * PSU_ * 256, s, P, X.C, x, inv, g, affs, dl, dx, (const T*)nullptr, (const float*)nullptr) \
-    }                                                                                                \
-  }
       // (87 VGPRs: the conversion's temporaries keep it above the 80 a third workgroup would need; small planes all the same --
       //  less LDS per workgroup never hurts the other kernels sharing the CU in a multi-stream section)
-      if (small) { if (crop) PEA_HPF(true, kXdmaPSUHS, 4) else PEA_HPF(false, kXdmaPSUHS, 4) }
-      else { if (crop) PEA_HPF(true, kXdmaPSUH, 4) else PEA_HPF(false, kXdmaPSUH, 4) }
-#undef PEA_HPF
-      return true;
+      auto go = [&](auto psu) {
+        const size_t lds = (size_t)5 * psu.value * 256;
+        return with_bool(crop, [&](auto crop) {
+          if (kBf16<T> || env().h16_hw)
+            return with_bool(few, [&](auto few) {
+              return launch<k_bwd_xdma_h<D_T, kXdmaTH, kXdmaTW, psu.value, crop.value, (few.value ? XPS : kXP), true, 4, true, false, T>>(
+                  grid, blk, lds, s, P, X.C, x, inv, g, affs, dl, dx, (const T*)nullptr, (const float*)nullptr);
+            });
+          if constexpr (!kBf16<T>)
+            return launch<k_bwd_xdma_h<D_T, kXdmaTH, kXdmaTW, psu.value, crop.value, kXP, true, 4>>(
+                grid, blk, lds, s, P, X.C, x, inv, g, affs, dl, dx, (const T*)nullptr, (const float*)nullptr);
+          else return true;
+        });
+      };
+      return small ? go(Int<kXdmaPSUHS>{}) : go(Int<kXdmaPSUH>{});
     }
    }
   }
@@ -123,14 +110,10 @@ bool bwd_self_h(const KParams& P, const T* x, const float* inv, const float* g, 
   if (X.C.npx > XP || X.C.npy > XP) return false;
   const size_t lds = (size_t)5 * kXdmaPSUH * 256;
   const dim3 grid((unsigned)(X.C.tiles_per_xcd * kXcd));
-  if (crop) {
-    constexpr auto kern = k_bwd_xdma_h<D_T, kXdmaTH, kXdmaTW, kXdmaPSUH, true, XP, false, 4, false, false, T>;
-    PEA_LAUNCH(kern, grid, blk, lds, s, P, X.C, x, inv, g, (const float*)nullptr, dl, dx, (const T*)nullptr, (const float*)nullptr)
-  } else {
-    constexpr auto kern = k_bwd_xdma_h<D_T, kXdmaTH, kXdmaTW, kXdmaPSUH, false, XP, false, 4, false, false, T>;
-    PEA_LAUNCH(kern, grid, blk, lds, s, P, X.C, x, inv, g, (const float*)nullptr, dl, dx, (const T*)nullptr, (const float*)nullptr)
-  }
-  return true;
+  return with_bool(crop, [&](auto crop) {
+    return launch<k_bwd_xdma_h<D_T, kXdmaTH, kXdmaTW, kXdmaPSUH, crop.value, XP, false, 4, false, false, T>>(
+        grid, blk, lds, s, P, X.C, x, inv, g, (const float*)nullptr, dl, dx, (const T*)nullptr, (const float*)nullptr);
+  });
 }
 
 // ---- 16-bit storage, the cross loss with a detached second operand (k_fwd_xdma_h<.., OTHER>, k_bwd_xdma_h<.., PF, HW, OTHER>): 2D, X % 8 == 0
@@ -145,31 +128,19 @@ bool fwd_other_h(const KParams& P, const FwdArgs& A, hipStream_t s) {
   const size_t lds = (size_t)4 * kXdmaPSUF * 256 + 6 * 1024;  // working plane + ring + the own tiles
   const dim3 grid((unsigned)(X.C.tiles_per_xcd * kXcd)), blk(kXdmaTH * kXdmaTW);
   float* inv_other = A.inv_out + (size_t)P.B * P.S;
-  if (A.mf32 || A.lact) {  // an f32 mask: dwordx4 mask quads; PEA_FLAG_LOSS_ACT: the loss on the activated map -- one slot count (kXP)
-    if (A.mf32 && misaligned(A.m, 16)) return false;
-#define PEA_HFOM(CROP_, MT_, LACT_)                                                                                      \
-  {                                                                                                                      \
-    constexpr auto kern = k_fwd_xdma_h<D_T, kXdmaTH, kXdmaTW, kXdmaPSUF, CROP_, true, 6, true, kXP, true, T, MT_, LACT_>; \
-    PEA_LAUNCH(kern, grid, blk, lds, s, P, X.C, eo, A.t, A.w, (const MT_*)(const void*)A.m, A.affs, A.gout, A.st,        \
-               A.inv_out, e, inv_other)                                                                                  \
-  }
-    const bool crop = P.border != PEA_BORDER_CIRCULAR;
-    if (!A.lact) { if (crop) PEA_HFOM(true, float, false) else PEA_HFOM(false, float, false) }
-    else if (A.mf32) { if (crop) PEA_HFOM(true, float, true) else PEA_HFOM(false, float, true) }
-    else { if (crop) PEA_HFOM(true, uint8_t, true) else PEA_HFOM(false, uint8_t, true) }
-#undef PEA_HFOM
-    return true;
-  }
-#define PEA_HFO(CROP_, NXP_)                                                                                                  \
-  {                                                                                                                          \
-    constexpr auto kern = k_fwd_xdma_h<D_T, kXdmaTH, kXdmaTW, kXdmaPSUF, CROP_, true, 6, true, NXP_, true, T>;                \
-    PEA_LAUNCH(kern, grid, blk, lds, s, P, X.C, eo, A.t, A.w, A.m, A.affs, A.gout, A.st, A.inv_out, e, inv_other)             \
-  }
-  const bool crop = P.border != PEA_BORDER_CIRCULAR;
-  if (D_T == 64 && X.C.nf <= 8) { if (crop) PEA_HFO(true, (D_T == 64 ? 8 : kXP)) else PEA_HFO(false, (D_T == 64 ? 8 : kXP)) }
-  else { if (crop) PEA_HFO(true, kXP) else PEA_HFO(false, kXP) }
-#undef PEA_HFO
-  return true;
+  if (A.mf32 && misaligned(A.m, 16)) return false;  // an f32 mask: dwordx4 mask quads
+  return with_bool(P.border != PEA_BORDER_CIRCULAR, [&](auto crop) {
+    return with_mask_form(A.mf32, A.lact, [&](auto mt, auto lact) {
+      using MT = typename decltype(mt)::type;
+      // an f32 mask; PEA_FLAG_LOSS_ACT: the loss on the activated map -- one slot count (kXP); else D = 64 with at most eight offsets walks eight
+      constexpr bool kPlain = std::is_same<MT, uint8_t>::value && !lact.value;
+      return with_bool(kPlain && D_T == 64 && X.C.nf <= 8, [&](auto few) {
+        constexpr int NXP = kPlain && few.value && D_T == 64 ? 8 : kXP;
+        return launch<k_fwd_xdma_h<D_T, kXdmaTH, kXdmaTW, kXdmaPSUF, crop.value, true, 6, true, NXP, true, T, MT, lact.value>>(
+            grid, blk, lds, s, P, X.C, eo, A.t, A.w, (const MT*)(const void*)A.m, A.affs, A.gout, A.st, A.inv_out, e, inv_other);
+      });
+    });
+  });
 }
 
 template <typename T, int D_T>
@@ -185,81 +156,53 @@ bool bwd_other_h(const KParams& P, const T* e, const T* eo, const float* inv2, c
   const float* inv_other = inv2 + (size_t)P.B * P.S;
   constexpr int XPS = D_T == 64 ? 8 : kXP;
   const bool few = D_T == 64 && X.C.npx <= 8 && X.C.npy <= 8;
-#define PEA_HBO(CROP_, XP_)                                                                                                   \
-  {                                                                                                                          \
-    constexpr auto kern = k_bwd_xdma_h<D_T, kXdmaTH, kXdmaTW, kXdmaPSUF, CROP_, XP_, true, 4, true, true, T>;                 \
-    PEA_LAUNCH(kern, grid, blk, lds, s, P, X.C, eo, inv_other, g, affs, dl, de, e, inv2)                                      \
-  }
-  const bool crop = P.border != PEA_BORDER_CIRCULAR;
-  if (few) { if (crop) PEA_HBO(true, XPS) else PEA_HBO(false, XPS) }
-  else { if (crop) PEA_HBO(true, kXP) else PEA_HBO(false, kXP) }
-#undef PEA_HBO
-  return true;
-}
-
-template <typename T>
-bool fwd_other_t(const KParams& P, const FwdArgs& A, hipStream_t s) {
-  if (P.D == 16) return fwd_other_h<T, 16>(P, A, s);
-  if (P.D == 32) return fwd_other_h<T, 32>(P, A, s);
-  if (P.D == 64) return fwd_other_h<T, 64>(P, A, s);
-  return false;
-}
-
-template <typename T>
-bool bwd_other_t(const KParams& P, const void* e, const void* e_other, const float* inv2, const float* g, const float* affs,
-                 const float* dl, void* de, hipStream_t s) {
-  if (P.D == 16) return bwd_other_h<T, 16>(P, (const T*)e, (const T*)e_other, inv2, g, affs, dl, (T*)de, s);
-  if (P.D == 32) return bwd_other_h<T, 32>(P, (const T*)e, (const T*)e_other, inv2, g, affs, dl, (T*)de, s);
-  if (P.D == 64) return bwd_other_h<T, 64>(P, (const T*)e, (const T*)e_other, inv2, g, affs, dl, (T*)de, s);
-  return false;
-}
-
-template <typename T>
-bool fwd_self_t(const KParams& P, const FwdArgs& A, hipStream_t s) {
-  if (P.D == 16) return A.train ? fwd_self_h<T, 16, true>(P, A, s) : fwd_self_h<T, 16, false>(P, A, s);
-  if (P.D == 32) return A.train ? fwd_self_h<T, 32, true>(P, A, s) : fwd_self_h<T, 32, false>(P, A, s);
-  if (P.D == 64) return A.train ? fwd_self_h<T, 64, true>(P, A, s) : fwd_self_h<T, 64, false>(P, A, s);
-  return false;
-}
-
-template <typename T>
-bool bwd_self_t(const KParams& P, const void* x, const float* inv, const float* g, const float* affs, const float* dl, void* dx,
-                hipStream_t s) {
-  if (P.D == 16) return bwd_self_h<T, 16>(P, (const T*)x, inv, g, affs, dl, (T*)dx, s);
-  if (P.D == 32) return bwd_self_h<T, 32>(P, (const T*)x, inv, g, affs, dl, (T*)dx, s);
-  if (P.D == 64) return bwd_self_h<T, 64>(P, (const T*)x, inv, g, affs, dl, (T*)dx, s);
-  return false;
+  return with_bool(P.border != PEA_BORDER_CIRCULAR, [&](auto crop) {
+    return with_bool(few, [&](auto few) {
+      return launch<k_bwd_xdma_h<D_T, kXdmaTH, kXdmaTW, kXdmaPSUF, crop.value, (few.value ? XPS : kXP), true, 4, true, true, T>>(
+          grid, blk, lds, s, P, X.C, eo, inv_other, g, affs, dl, de, e, inv2);
+    });
+  });
 }
 
 }  // namespace
 
-
 bool xdma_h_fwd_other(const KParams& P, const FwdArgs& A, hipStream_t s) {
-  if (A.dtype == PEA_BF16) return fwd_other_t<__bf16>(P, A, s);
-  if (!env().h16_hw) return false;
-  return fwd_other_t<__half>(P, A, s);
+  if (A.dtype != PEA_BF16 && !env().h16_hw) return false;
+  return with_bool(A.dtype == PEA_BF16, [&](auto bf) {
+    using T = std::conditional_t<bf.value, __bf16, __half>;
+    return with_width<16, 32, 64>(P.D, [&](auto d) { return fwd_other_h<T, d.value>(P, A, s); });
+  });
 }
 
 bool xdma_h_bwd_other(const KParams& P, int dtype, const void* e, const void* e_other, const float* inv2, const float* g, const float* affs,
                       const float* dl, void* de, hipStream_t s) {
   if (!env().bwd_pf || !affs || (P.flags & kActMask)) return false;
-  if (dtype == PEA_BF16) return bwd_other_t<__bf16>(P, e, e_other, inv2, g, affs, dl, de, s);
-  if (!env().h16_hw) return false;
-  return bwd_other_t<__half>(P, e, e_other, inv2, g, affs, dl, de, s);
+  if (dtype != PEA_BF16 && !env().h16_hw) return false;
+  return with_bool(dtype == PEA_BF16, [&](auto bf) {
+    using T = std::conditional_t<bf.value, __bf16, __half>;
+    return with_width<16, 32, 64>(
+        P.D, [&](auto d) { return bwd_other_h<T, d.value>(P, (const T*)e, (const T*)e_other, inv2, g, affs, dl, (T*)de, s); });
+  });
 }
 
 // entry points used by pea_k_xdma.hip's dispatchers
 bool xdma_h_fwd_self(const KParams& P, const FwdArgs& A, hipStream_t s) {
-  return A.dtype == PEA_BF16 ? fwd_self_t<__bf16>(P, A, s) : fwd_self_t<__half>(P, A, s);
+  return with_bool(A.dtype == PEA_BF16, [&](auto bf) {
+    using T = std::conditional_t<bf.value, __bf16, __half>;
+    return with_width<16, 32, 64>(P.D, [&](auto d) {
+      return with_bool(A.train, [&](auto train) { return fwd_self_h<T, d.value, train.value>(P, A, s); });
+    });
+  });
 }
-
 
 bool xdma_bwd_self_h(const KParams& P, int dtype, const void* x, const float* inv, const float* g, const float* affs, const float* dl,
                      void* dx, hipStream_t s) {
   if (!inv || !env().bwd_xdma || env().force_direct) return false;
-  if (dtype == PEA_BF16) return bwd_self_t<__bf16>(P, x, inv, g, affs, dl, dx, s);
-  if (env().h16_hw == 2 && env().bwd_pf && xdma_hq_bwd_self(P, x, inv, g, affs, dl, dx, s)) return true;  // pea_k_xdma_hq.hip
-  return bwd_self_t<__half>(P, x, inv, g, affs, dl, dx, s);
+  if (dtype != PEA_BF16 && env().h16_hw == 2 && env().bwd_pf && xdma_hq_bwd_self(P, x, inv, g, affs, dl, dx, s)) return true;  // pea_k_xdma_hq.hip
+  return with_bool(dtype == PEA_BF16, [&](auto bf) {
+    using T = std::conditional_t<bf.value, __bf16, __half>;
+    return with_width<16, 32, 64>(P.D, [&](auto d) { return bwd_self_h<T, d.value>(P, (const T*)x, inv, g, affs, dl, (T*)dx, s); });
+  });
 }
 
 }  // namespace pea

@@ -1,8 +1,8 @@
 // pea_k_xdma_plan.h -- what the two translation units of the LDS-DMA cross kernels share (pea_k_xdma.hip: f32 storage;
-// pea_k_xdma_h.hip: f16 storage and the projection-first backward): tile shape, plane sizes, the memoised plan, the launch macro.
+// pea_k_xdma_h.hip: f16 storage and the projection-first backward): tile shape, plane sizes, the memoised plan.
 // (One file took 75 s to compile, the longest of the library; each of the two is an independent hipcc job.)
 #pragma once
-#include "pea_host.h"
+#include "pea_dispatch.h"
 #include "pea_xdma.h"
 
 namespace pea {
@@ -36,12 +36,6 @@ bool plan(const KParams& P, int psu, int mode, XPlan* out, int th = kXdmaTH, int
     return true;
   });
 }
-
-#define PEA_LAUNCH(kern, grid, blk, lds, s, ...)              \
-  {                                                           \
-    if (allow_lds<kern>(lds)) return false;                   \
-    hipLaunchKernelGGL(kern, grid, blk, lds, s, __VA_ARGS__); \
-  }
 
 }  // namespace
 }  // namespace pea

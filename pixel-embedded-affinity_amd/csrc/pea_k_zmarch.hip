@@ -1,6 +1,6 @@
 // pea_k_zmarch.hip -- launchers of the z-march kernels (pea_zmarch.h): 3D volumes whose axis-aligned stencil steps along z
 // (embedding_loss_norm5 / norm1, scripts_ac3ac4/loss/loss_embedding_mse.py:7-27, 143-194).  One translation unit of libpea_hip.so.
-#include "pea_host.h"
+#include "pea_dispatch.h"
 #include "pea_zmarch.h"
 
 namespace pea {
@@ -71,12 +71,6 @@ bool plan(const KParams& P, int mode, ZPlan* out) {
   });
 }
 
-#define PEA_LAUNCH(kern, grid, blk, lds, s, ...)              \
-  {                                                           \
-    if (allow_lds<kern>(lds)) return false;                   \
-    hipLaunchKernelGGL(kern, grid, blk, lds, s, __VA_ARGS__); \
-  }
-
 }  // namespace
 
 // forward / inference of the self loss on a 3D volume (f32, D = 16, CROP_ZERO, every z offset in {-1 .. -4}); true = launched
@@ -91,17 +85,13 @@ bool zmarch_fwd(const KParams& P, const FwdArgs& A, hipStream_t s) {
   ZPlan Z;
   if (!plan(P, 1, &Z)) return false;
   const dim3 grid((unsigned)(Z.C.tiles_per_xcd * kXcd)), blk(kTH * kTW);
-#define PEA_ZF(TRAIN_, NXP_)                                                                                                      \
-  {                                                                                                                               \
-    constexpr auto kern = k_fwd_zm<kTH, kTW, kPSUF, TRAIN_, NXP_>;                                                                \
-    PEA_LAUNCH(kern, grid, blk, Z.lds, s, P, Z.C, Z.M, e, A.train ? A.t : nullptr, A.train ? A.w : nullptr,                       \
-               A.train ? A.m : nullptr, A.affs, A.train ? A.gout : nullptr, A.train ? A.st : nullptr, A.train ? A.inv_out : nullptr) \
-  }
-  const bool few = Z.C.nf <= 8;  // the reference's 3D tables have at most eight in-plane offsets
-  if (A.train) { if (few) PEA_ZF(true, 8) else PEA_ZF(true, kXP) }
-  else { if (few) PEA_ZF(false, 8) else PEA_ZF(false, kXP) }
-#undef PEA_ZF
-  return true;
+  return with_bool(A.train, [&](auto train) {
+    return with_bool(Z.C.nf <= 8, [&](auto few) {  // the reference's 3D tables have at most eight in-plane offsets
+      return launch<k_fwd_zm<kTH, kTW, kPSUF, train.value, (few.value ? 8 : kXP)>>(
+          grid, blk, Z.lds, s, P, Z.C, Z.M, e, A.train ? A.t : nullptr, A.train ? A.w : nullptr, A.train ? A.m : nullptr, A.affs,
+          A.train ? A.gout : nullptr, A.train ? A.st : nullptr, A.train ? A.inv_out : nullptr);
+    });
+  });
 }
 
 // would zmarch_bwd take this descriptor (given the 1 / norm plane and the raw affinity map)?
@@ -119,9 +109,8 @@ bool zmarch_bwd(const KParams& P, const float* x, const float* inv, const float*
   ZPlan Z;
   if (!plan(P, 0, &Z)) return false;
   const dim3 grid((unsigned)(Z.C.tiles_per_xcd * kXcd)), blk(kTH * kTW);
-  constexpr auto kern = k_bwd_zm<kTH, kTW, kPSUB, 4>;  // (the ring depth the plan sized its LDS for)
-  PEA_LAUNCH(kern, grid, blk, Z.lds, s, P, Z.C, Z.M, x, inv, g, affs, dl, dx)
-  return true;
+  // (4: the ring depth the plan sized its LDS for)
+  return launch<k_bwd_zm<kTH, kTW, kPSUB, 4>>(grid, blk, Z.lds, s, P, Z.C, Z.M, x, inv, g, affs, dl, dx);
 }
 
 }  // namespace pea
