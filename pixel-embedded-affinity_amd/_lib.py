@@ -13,6 +13,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 SO_PATH = os.environ.get("PEA_HIP_LIB") or os.path.join(CSRC, "libpea_hip.so")  # PEA_HIP_LIB: debugging override
 HEADER = os.path.join(HERE, "..", "include", "pea.h")
+HEADER_INFER = os.path.join(HERE, "..", "include", "pea_infer.h")
 
 PEA_ABI_VERSION = 2
 PEA_MAX_K = 32
@@ -32,6 +33,8 @@ EXPORTS = ("pea_version", "pea_strerror", "pea_desc_validate", "pea_workspace_by
            "pea_targets_workspace_bytes", "pea_gen_targets", "pea_stitch_add", "pea_stitch_finalize",
            "pea_label_weights", "pea_affinity_fwd_bwd_labels", "pea_affinity_fwd_bwd_labels_ex", "pea_labels_scratch_bytes",
            "pea_affinity_fwd_bwd_labels_dual")
+# the entry points of include/pea_infer.h (the fused 3D window inference); include/pea.h and EXPORTS stay as they are
+EXPORTS_INFER = ("pea_infer_stitch_supported", "pea_affinity_infer_stitch")
 
 
 class PeaLibraryError(RuntimeError):
@@ -74,7 +77,7 @@ def build(force=False, verbose=False, jobs=None):
 
 def _build_locked(force, verbose, jobs):
     srcs = sources()
-    hdrs = [HEADER] + [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".h")]
+    hdrs = [HEADER, HEADER_INFER] + [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".h")]
     newest_hdr = max(os.path.getmtime(h) for h in hdrs)
     if not force and os.path.exists(SO_PATH) and os.path.getmtime(SO_PATH) >= max([newest_hdr] + [os.path.getmtime(x) for x in srcs]):
         return SO_PATH
@@ -138,7 +141,7 @@ def lib():
         L = ctypes.CDLL(SO_PATH)
     except OSError as ex:
         raise PeaLibraryError("cannot load %s: %s" % (SO_PATH, ex))
-    for name in EXPORTS:
+    for name in EXPORTS + EXPORTS_INFER:
         if not hasattr(L, name):
             raise PeaLibraryError("%s does not export %s" % (SO_PATH, name))
     vp, dp = ctypes.c_void_p, ctypes.POINTER(PeaDesc)
@@ -207,6 +210,10 @@ def lib():
     L.pea_head_fwd.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_size_t, vp, vp, vp, vp, vp]
     L.pea_head_bwd.restype = ctypes.c_int
     L.pea_head_bwd.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_size_t, vp, vp, vp, vp, vp, vp, vp, ctypes.c_size_t, vp]
+    L.pea_infer_stitch_supported.restype = ctypes.c_int
+    L.pea_infer_stitch_supported.argtypes = [dp, ctypes.c_int]
+    L.pea_affinity_infer_stitch.restype = ctypes.c_int
+    L.pea_affinity_infer_stitch.argtypes = [dp, vp, ctypes.c_int, vp, vp, vp] + [ctypes.c_int] * 6 + [vp]
     if L.pea_version() != PEA_ABI_VERSION:
         raise PeaLibraryError("ABI mismatch: library %d, binding %d" % (L.pea_version(), PEA_ABI_VERSION))
     _lib = L

@@ -1,7 +1,8 @@
 """3D inference stitcher on the device: Provider_valid.reset_output / get_weight / add_vol / get_results of
 scripts_ac3ac4/data/provider_valid.py:291-349 (model_type 'superhuman') without the per-window D2H copy and numpy
 accumulation (scripts_ac3ac4/inference.py:166, main.py:302).  The Gaussian blend weights are computed exactly as the
-reference does (numpy, float32 linspace / meshgrid) once on the host; everything per window runs in pea_stitch_add.
+reference does (numpy, float32 linspace / meshgrid) once on the host; everything per window runs in pea_stitch_add -- or, from the
+embedding itself, in pea_affinity_infer_stitch (add_embedding: affinities, border fill, relu and blend in one launch per window).
 """
 import ctypes
 
@@ -9,6 +10,9 @@ import numpy as np
 import torch
 
 from .. import _lib
+from ..affinity_op import AffinitySpec, _embedding_arg, _on_device, _ptr, _stream, affinity_infer, make_desc
+from ..utils.affinity_ours import NORM5_SHIFTS, axis_offsets_3d
+from ..utils.postproc import fill_border_relu_
 
 
 def get_weight(out_size, sigma=0.2, mu=0.0):
@@ -19,6 +23,27 @@ def get_weight(out_size, sigma=0.2, mu=0.0):
     dd = np.sqrt(zz * zz + yy * yy + xx * xx)
     weight = 1e-6 + np.exp(-((dd - mu) ** 2 / (2.0 * sigma ** 2)))
     return weight[np.newaxis, ...]
+
+
+_SPECS = {}
+
+
+def _mode_spec(embedding_mode):
+    """the spec of inf_embedding_loss_norm1 / _norm5 (loss/loss_embedding_mse_3d.py), built once: a window costs tens of microseconds"""
+    spec = _SPECS.get(embedding_mode)
+    if spec is None:
+        shifts = NORM5_SHIFTS if embedding_mode == 5 else (1, 1, 1)
+        spec = _SPECS[embedding_mode] = AffinitySpec(3, axis_offsets_3d(shifts), None, _lib.BORDER_CROP_ZERO, _lib.NORM_CROPPED, 1e-12)
+    return spec
+
+
+def _with_relu(spec):
+    """`spec` with PEA_FLAG_RELU_AFFS, remembered on the spec itself"""
+    r = getattr(spec, "_relu_twin", None)
+    if r is None or (r.offsets, r.lam, r.border, r.norm, r.eps, r.act) != (spec.offsets, spec.lam, spec.border, spec.norm, spec.eps,
+                                                                            spec.act | _lib.FLAG_RELU_AFFS):
+        r = spec._relu_twin = AffinitySpec(spec.ndim, spec.offsets, spec.lam, spec.border, spec.norm, spec.eps, True, spec.act)
+    return r
 
 
 class VolumeStitcher(object):
@@ -51,6 +76,45 @@ class VolumeStitcher(object):
             _lib.check(_lib.lib().pea_stitch_add(p(self.out_affs), p(self.weight_map), p(v), p(self.weight_vol), self.C, Z, Y, X,
                                                  oz, oy, ox, int(pos[0]), int(pos[1]), int(pos[2]),
                                                  ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)), "pea_stitch_add")
+
+    def add_embedding(self, embedding, pos, embedding_mode=5, shift=1, relu=True, spec=None, fused=False):
+        """scripts_ac3ac4/inference.py:150-166 from the embedding on: inf_embedding_loss_norm1 / _norm5 (embedding_mode 1 / 5; `spec`
+        overrides it), the border fill of channels 0..2 by `shift` (:160-163; 0 = none), F.relu (:164) and add_vol (:166).
+        embedding [B, D, oz, oy, ox] on the GPU, f32 / f16 / bf16; pos = one (z0, y0, x0) or B of them.  Batch items are issued as B
+        calls in order (overlapping windows read-modify-write the same voxels: one launch never holds two).  fused=True: one launch
+        per window (pea_affinity_infer_stitch) where the library fuses the descriptor; elsewhere, and with fused=False, the three
+        calls affinity_infer, fill_border_relu_, add_vol.  fused=False is the default until profiles/infer_stitch_ab.py has shown
+        the one-launch form faster on an MI355X."""
+        e = _embedding_arg(embedding, "embedding").detach()
+        if e.dim() != 5 or tuple(e.shape[2:]) != self.out_size:
+            raise ValueError("embedding must be [B, D] + %s, got %s" % (self.out_size, tuple(e.shape)))
+        if e.device != self.weight_vol.device:
+            raise ValueError("embedding is on %s, the stitcher on %s" % (e.device, self.weight_vol.device))
+        B = e.shape[0]
+        pos = np.asarray(pos, dtype=np.int64)
+        pos = np.broadcast_to(pos, (B, 3)) if pos.ndim == 1 else pos
+        if pos.shape != (B, 3):
+            raise ValueError("pos must be (z0, y0, x0) or one per batch item, got shape %s" % (pos.shape,))
+        if spec is None:
+            if embedding_mode not in (1, 5):
+                raise NotImplementedError("embedding_mode must be 1 or 5 (or pass spec)")
+            spec = _mode_spec(embedding_mode)
+        if spec.K != self.C:
+            raise ValueError("the spec has %d channels, the stitcher %d" % (spec.K, self.C))
+        fspec = _with_relu(spec) if relu and not spec.relu else spec  # F.relu rides in the descriptor's activation bits
+        L = _lib.lib()
+        Z, Y, X = self.shape
+        with _on_device(e.device):
+            for b in range(B):
+                eb = e[b:b + 1]
+                d = make_desc(fspec, eb)
+                if fused and L.pea_infer_stitch_supported(ctypes.byref(d), int(shift)):
+                    _lib.check(L.pea_affinity_infer_stitch(ctypes.byref(d), _ptr(eb), int(shift), _ptr(self.weight_vol), _ptr(self.out_affs),
+                                                           _ptr(self.weight_map), Z, Y, X, int(pos[b][0]), int(pos[b][1]), int(pos[b][2]),
+                                                           _stream()), "pea_affinity_infer_stitch")
+                else:
+                    pred = fill_border_relu_(affinity_infer(eb, None, spec), shift=shift, relu=relu)
+                    self.add_vol(pred[0], pos[b])
 
     def get_results(self, valid_padding):
         """provider_valid.py:337-349: out / weight_map, cropped by valid_padding (a view of the device tensor)"""
