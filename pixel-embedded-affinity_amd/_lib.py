@@ -14,9 +14,11 @@ CSRC = os.path.join(HERE, "csrc")
 SO_PATH = os.environ.get("PEA_HIP_LIB") or os.path.join(CSRC, "libpea_hip.so")  # PEA_HIP_LIB: debugging override
 HEADER = os.path.join(HERE, "..", "include", "pea.h")
 HEADER_INFER = os.path.join(HERE, "..", "include", "pea_infer.h")
+HEADER_MULTI = os.path.join(HERE, "..", "include", "pea_multi.h")
 
 PEA_ABI_VERSION = 2
 PEA_MAX_K = 32
+PEA_MULTI_MAX_N, PEA_MULTI_MAX_K = 4, 12  # include/pea_multi.h
 E_UNSUPPORTED = -3
 BORDER_CIRCULAR, BORDER_CROP_ZERO, BORDER_REPLICATE = 0, 1, 2
 F32, F16, BF16 = 0, 1, 2
@@ -35,6 +37,8 @@ EXPORTS = ("pea_version", "pea_strerror", "pea_desc_validate", "pea_workspace_by
            "pea_affinity_fwd_bwd_labels_dual")
 # the entry points of include/pea_infer.h (the fused 3D window inference); include/pea.h and EXPORTS stay as they are
 EXPORTS_INFER = ("pea_infer_stitch_supported", "pea_affinity_infer_stitch")
+# the entry points of include/pea_multi.h (up to four self losses per launch: the deep-supervision scales)
+EXPORTS_MULTI = ("pea_multi_supported", "pea_affinity_fwd_multi", "pea_affinity_bwd_multi")
 
 
 class PeaLibraryError(RuntimeError):
@@ -50,6 +54,18 @@ class PeaDesc(ctypes.Structure):
                 ("offsets", (ctypes.c_int32 * 3) * PEA_MAX_K), ("lam", ctypes.c_float * PEA_MAX_K),
                 ("target_bstride", ctypes.c_int64), ("weight_bstride", ctypes.c_int64),
                 ("mask_bstride", ctypes.c_int64)]
+
+
+class PeaMultiFwd(ctypes.Structure):
+    """mirror of `struct PeaMultiFwd` in include/pea_multi.h"""
+    _fields_ = [("desc", ctypes.POINTER(PeaDesc)), ("e", ctypes.c_void_p), ("target", ctypes.c_void_p), ("weight", ctypes.c_void_p),
+                ("mask", ctypes.c_void_p), ("affs", ctypes.c_void_p), ("g_out", ctypes.c_void_p), ("loss_out", ctypes.c_void_p)]
+
+
+class PeaMultiBwd(ctypes.Structure):
+    """mirror of `struct PeaMultiBwd` in include/pea_multi.h"""
+    _fields_ = [("desc", ctypes.POINTER(PeaDesc)), ("e", ctypes.c_void_p), ("g", ctypes.c_void_p), ("dloss", ctypes.c_void_p),
+                ("de", ctypes.c_void_p)]
 
 
 HIPCC_FLAGS = ["-O3", "--offload-arch=gfx950", "-std=c++17", "-fPIC"]
@@ -77,7 +93,7 @@ def build(force=False, verbose=False, jobs=None):
 
 def _build_locked(force, verbose, jobs):
     srcs = sources()
-    hdrs = [HEADER, HEADER_INFER] + [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".h")]
+    hdrs = [HEADER, HEADER_INFER, HEADER_MULTI] + [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".h")]
     newest_hdr = max(os.path.getmtime(h) for h in hdrs)
     if not force and os.path.exists(SO_PATH) and os.path.getmtime(SO_PATH) >= max([newest_hdr] + [os.path.getmtime(x) for x in srcs]):
         return SO_PATH
@@ -141,7 +157,7 @@ def lib():
         L = ctypes.CDLL(SO_PATH)
     except OSError as ex:
         raise PeaLibraryError("cannot load %s: %s" % (SO_PATH, ex))
-    for name in EXPORTS + EXPORTS_INFER:
+    for name in EXPORTS + EXPORTS_INFER + EXPORTS_MULTI:
         if not hasattr(L, name):
             raise PeaLibraryError("%s does not export %s" % (SO_PATH, name))
     vp, dp = ctypes.c_void_p, ctypes.POINTER(PeaDesc)
@@ -214,6 +230,12 @@ def lib():
     L.pea_infer_stitch_supported.argtypes = [dp, ctypes.c_int]
     L.pea_affinity_infer_stitch.restype = ctypes.c_int
     L.pea_affinity_infer_stitch.argtypes = [dp, vp, ctypes.c_int, vp, vp, vp] + [ctypes.c_int] * 6 + [vp]
+    L.pea_multi_supported.restype = ctypes.c_int
+    L.pea_multi_supported.argtypes = [ctypes.POINTER(dp), ctypes.c_int]
+    L.pea_affinity_fwd_multi.restype = ctypes.c_int
+    L.pea_affinity_fwd_multi.argtypes = [ctypes.POINTER(PeaMultiFwd), ctypes.c_int, vp, ctypes.c_size_t, vp]
+    L.pea_affinity_bwd_multi.restype = ctypes.c_int
+    L.pea_affinity_bwd_multi.argtypes = [ctypes.POINTER(PeaMultiBwd), ctypes.c_int, vp]
     if L.pea_version() != PEA_ABI_VERSION:
         raise PeaLibraryError("ABI mismatch: library %d, binding %d" % (L.pea_version(), PEA_ABI_VERSION))
     _lib = L

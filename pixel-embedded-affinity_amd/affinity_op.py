@@ -320,6 +320,131 @@ class FusedAffinityMSE(torch.autograd.Function):
         return de, de_o, None, None, None, None
 
 
+class MultiUnsupported(NotImplementedError):
+    """the table of losses is outside the fused set of include/pea_multi.h (pea_multi_supported == 0): nothing was launched, the
+    *_multi wrappers and the sections make the single calls instead -- same results"""
+
+
+_MULTI_OK = {}
+
+
+def multi_supported(descs):
+    """pea_multi_supported for a list of memoised descriptors, remembered by their identities (host-only, but it validates each
+    descriptor again: more host time than the launch it decides about)"""
+    key = tuple(id(d) for d in descs)
+    hit = _MULTI_OK.get(key)
+    if hit is None or any(a is not b for a, b in zip(hit[1], descs)):  # (the entry keeps its descriptors alive: no id is reused)
+        arr = (ctypes.POINTER(PeaDesc) * len(descs))(*[ctypes.pointer(d) for d in descs])
+        r = bool(_lib.lib().pea_multi_supported(arr, len(descs)))
+        with _CROSS_LOCK:
+            if len(_MULTI_OK) > 256:
+                _MULTI_OK.clear()
+            _MULTI_OK[key] = hit = (r, list(descs))
+    return hit[0]
+
+
+def multi_backward(descs, e_cs, gs, dlosses):
+    """de_j = dloss_j * d loss_j / d e_j of n self losses as ONE launch (pea_affinity_bwd_multi); dlosses: device scalars (or None = 1)"""
+    n = len(descs)
+    des = [torch.empty_like(e_c) for e_c in e_cs]
+    table = (_lib.PeaMultiBwd * n)()
+    for j in range(n):
+        a = table[j]
+        a.desc, a.e, a.g, a.de = ctypes.pointer(descs[j]), e_cs[j].data_ptr(), gs[j].data_ptr(), des[j].data_ptr()
+        a.dloss = None if dlosses[j] is None else dlosses[j].data_ptr()
+    rc = _lib.lib().pea_affinity_bwd_multi(table, n, _stream())
+    if rc == _lib.E_UNSUPPORTED:
+        raise MultiUnsupported("pea_affinity_bwd_multi: the table is outside the fused set")
+    _lib.check(rc, "pea_affinity_bwd_multi")
+    return des
+
+
+class MultiAffinityMSE(torch.autograd.Function):
+    """n self losses with the fused WeightedMSE as ONE node -- the four deep-supervision scales of a training step
+    (scripts_cvppp/main.py:284-287, scripts_ac3ac4/main.py:227-230): one forward launch over every tile of every scale, one loss
+    finish, one backward launch (include/pea_multi.h) instead of three launches per scale.
+
+        loss_0 .. loss_{n-1}, affs_0 .. affs_{n-1}, per_offset_0 .. per_offset_{n-1} = f(specs, tensors, need_affs, pre, *embeddings)
+
+    specs: n AffinitySpecs; tensors: n (target, weight, mask) triples as FusedAffinityMSE takes them; need_affs=False: the maps are
+    not written (empty tensors come back).  pre: None -- the backward launch is made by backward(), with autograd's grad_outputs as
+    the per-loss dloss -- or (rows, dlosses) for a caller that OWNS the weighting and the backward (the section nodes, which call
+    forward() directly inside their own forward): n loss rows [1 + K] to write into and the n per-loss weights as device scalars;
+    the backward launch is then enqueued right behind the forward and its gradients are left in ctx.grads.
+    Raises MultiUnsupported, before anything is launched, where the table is outside the fused set."""
+
+    @staticmethod
+    def forward(ctx, specs, tensors, need_affs, pre, *embs):
+        ctx.set_materialize_grads(False)
+        n = len(embs)
+        if not (len(specs) == len(tensors) == n):
+            raise ValueError("one spec and one (target, weight, mask) triple per embedding")
+        e_cs = [_embedding_arg(e, "embedding") for e in embs]
+        dev = e_cs[0].device
+        descs, twm = [], []
+        for spec, e_c, (t, w, m) in zip(specs, e_cs, tensors):
+            kshape = _affs_shape(e_c, spec.K)
+            t, ts = _batch_strided(t, "target", torch.float32, kshape)
+            w, ws = _batch_strided(w, "weightmap", torch.float32, kshape)
+            m, ms, mflag = mask_arg(m, kshape)
+            for x in (e_c, t, w, m):
+                if x is not None and x.device != dev:
+                    raise RuntimeError("all operands must live on %s" % dev)
+            descs.append(make_desc(spec, e_c, ts, ws, ms, mflag))
+            twm.append((t, w, m, kshape))
+        if not 1 <= n <= _lib.PEA_MULTI_MAX_N or not multi_supported(descs):
+            raise MultiUnsupported("the table is outside the fused set of include/pea_multi.h")
+        with _on_device(dev):
+            if pre is None:
+                rows = torch.empty((n, 1 + max(sp.K for sp in specs)), dtype=torch.float32, device=dev).unbind(0)
+            else:
+                rows = pre[0]
+            train = pre is not None or any(e.requires_grad for e in embs)
+            gs = [torch.empty(a[3], dtype=torch.float32, device=dev) for a in twm]  # (g_out is required by the C call)
+            affs = [torch.empty(a[3] if need_affs else (0,), dtype=torch.float32, device=dev) for a in twm]
+            work, wsb = workspace(dev, descs[0], n)
+            table = (_lib.PeaMultiFwd * n)()
+            for j in range(n):
+                a, (t, w, m, _) = table[j], twm[j]
+                a.desc, a.e, a.target, a.weight = ctypes.pointer(descs[j]), e_cs[j].data_ptr(), t.data_ptr(), w.data_ptr()
+                a.mask = None if m is None else m.data_ptr()
+                a.affs = affs[j].data_ptr() if need_affs else None
+                a.g_out, a.loss_out = gs[j].data_ptr(), rows[j].data_ptr()
+            rc = _lib.lib().pea_affinity_fwd_multi(table, n, _ptr(work), wsb, _stream())
+            if rc == _lib.E_UNSUPPORTED:  # (nothing was launched)
+                raise MultiUnsupported("pea_affinity_fwd_multi: the table is outside the fused set")
+            _lib.check(rc, "pea_affinity_fwd_multi")
+            ctx.grads = multi_backward(descs, e_cs, gs, pre[1]) if pre is not None else None
+        ctx.descs, ctx.n = descs, n
+        if pre is None and train:
+            ctx.save_for_backward(*(e_cs + gs))
+        losses = [rows[j][0] for j in range(n)]
+        parts = [rows[j][1:1 + specs[j].K] for j in range(n)]
+        ctx.mark_non_differentiable(*(affs + parts))
+        return tuple(losses) + tuple(affs) + tuple(parts)
+
+    @staticmethod
+    def backward(ctx, *grads):
+        n = ctx.n
+        none = (None, None, None, None) + (None,) * n
+        if ctx.grads is not None:
+            raise RuntimeError("MultiAffinityMSE with pre=(rows, dlosses) belongs to a caller that owns the backward")
+        # one launch over the losses that take part in this backward (a sub-table of a fused table is fused)
+        live = [j for j in range(n) if grads[j] is not None and ctx.needs_input_grad[4 + j]]
+        if not live:
+            return none
+        saved = ctx.saved_tensors
+        e_cs, gs = saved[:n], saved[n:]
+        dev = e_cs[0].device
+        with _on_device(dev):
+            dls = [grads[j].to(device=dev, dtype=torch.float32).contiguous() for j in live]
+            des = multi_backward([ctx.descs[j] for j in live], [e_cs[j] for j in live], [gs[j] for j in live], dls)
+        out = [None] * n
+        for j, de in zip(live, des):
+            out[j] = de
+        return (None, None, None, None) + tuple(out)
+
+
 _ONES = {}
 
 

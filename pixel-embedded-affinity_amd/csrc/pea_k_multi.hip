@@ -1,0 +1,519 @@
+// pea_k_multi.hip -- up to four self losses per launch (include/pea_multi.h): the deep-supervision scales of the training loops
+// (scripts_cvppp/main.py:284-287: embedding_loss on emd1..emd4 at 1/2 .. 1/16 resolution; scripts_ac3ac4/main.py:227-230: four
+// embedding_loss_norm1 calls) as one forward, one loss finish and one backward instead of three launches per scale.
+//
+// The table of the launch -- per entry its pointers and the few descriptor fields the bodies read, offsets as int16 -- travels BY
+// VALUE in the kernel arguments (KParams is ~900 bytes: four of them do not fit the 4 KB segment): no device-side table and no copy
+// from host memory on the stream, so the calls can be captured into a HIP graph.  A workgroup serves one tile (256 consecutive
+// pixels of one batch item) of one entry and finds the entry from the prefix of tile counts; the host puts the entry with the most
+// tiles first.  The tiles are then walked XCD-aware like logical_tile() walks one image: every XCD takes a contiguous range of the
+// concatenated tile list, so the rows a tile's neighbours live in are mostly rows its own XCD loads anyway.
+//
+// Gather-from-global form, the arithmetic of k_fwd_direct / k_bwd_direct (pea_direct.h): one lane per pixel, the own pixel's D
+// channels in registers, every neighbour vector read from global memory with its norm accumulated while the channels stream in,
+// a = dot * (1 / max(|e(p)|, eps)) * (1 / max(|e(q)|, eps)), the clamp branch of F.normalize (I / eps) where |e| < eps.  The largest
+// table of the reference (B = 8 x 16 x 272^2 and below, f32) is 38 MB of embeddings: L2 / Infinity Cache resident.
+// The body is a template of D (16 / 32), the mask type (none / u8 / f32) and the border; a table whose entries agree on the three
+// (the four scales of one training loop do) takes the kernel instantiated for them, any other the kernel that branches per
+// workgroup (the branch is uniform: a workgroup has one entry).
+// Loss partials: per offset a wave reduction and a fixed-order sum of the four waves, then loss_accumulate() into the entry's own
+// state block (integer adds: order-independent, exact); k_loss_finish_multi is k_loss_finish (pea_loss.h) with a workgroup per entry.
+#include <algorithm>
+
+#include "../../include/pea_multi.h"
+#include "pea_dispatch.h"
+
+using namespace pea;
+
+namespace {
+
+constexpr int kMaxN = PEA_MULTI_MAX_N, kMaxK = PEA_MULTI_MAX_K;
+enum { kMaskNone = 0, kMaskU8 = 1, kMaskF32 = 2 };
+
+struct MGeom {  // what the bodies read of an entry's descriptor
+  int S, Z, Y, X, K, D, border;
+  int chunks;  // workgroups per batch item = ceil(S / kBlock)
+  int tile0;   // the entry's first tile in the launch's tile order
+  float eps;
+  int16_t off[kMaxK][3];
+};
+struct MFwdEntry {
+  MGeom g;
+  int mtype;     // kMask*
+  unsigned act;  // activation bits of the affs output
+  float gscale[kMaxK];      // 2 * lambda_i / N_i
+  long long tbs, wbs, mbs;  // batch strides (elements) of target / weight / mask
+  const float* e;
+  const float* t;
+  const float* w;
+  const void* m;
+  float* affs;
+  float* gout;
+  LossState* st;
+};
+struct MBwdEntry {
+  MGeom g;
+  const float* e;
+  const float* gin;
+  const float* dloss;
+  float* de;
+};
+struct MFinEntry {
+  LossState* st;
+  float* loss_out;
+  int K, pad;
+  float inv_n[kMaxK], lam[kMaxK];
+};
+template <typename ENT>
+struct MTable {
+  int n, tiles, tiles_per_xcd, pad;
+  ENT en[kMaxN];
+};
+struct MFinTable {
+  MFinEntry en[kMaxN];
+};
+static_assert(sizeof(MTable<MFwdEntry>) <= 4096 - 64, "the forward's table must fit the kernel-argument segment");
+static_assert(sizeof(MTable<MBwdEntry>) <= 4096 - 64 && sizeof(MFinTable) <= 4096 - 64, "the tables must fit the kernel-argument segment");
+
+// neighbour of (z, y, x) displaced by o: flat index, or -1 (CROP_ZERO, outside).  neighbour() of pea_common.h with the border known
+template <int BORDER>
+__device__ __forceinline__ int neighbour_of(const MGeom& G, int z, int y, int x, int oz, int oy, int ox) {
+  int zz = z + oz, yy = y + oy, xx = x + ox;
+  if constexpr (BORDER == PEA_BORDER_CIRCULAR) {  // the host guarantees |o| < dim
+    zz += (zz < 0) ? G.Z : 0; zz -= (zz >= G.Z) ? G.Z : 0;
+    yy += (yy < 0) ? G.Y : 0; yy -= (yy >= G.Y) ? G.Y : 0;
+    xx += (xx < 0) ? G.X : 0; xx -= (xx >= G.X) ? G.X : 0;
+  } else if ((unsigned)zz >= (unsigned)G.Z || (unsigned)yy >= (unsigned)G.Y || (unsigned)xx >= (unsigned)G.X) {
+    return -1;
+  }
+  return (zz * G.Y + yy) * G.X + xx;
+}
+
+// the launch's tile of this workgroup (XCD-aware, as logical_tile) and the entry it belongs to; false: past the last tile
+template <typename ENT>
+__device__ __forceinline__ bool find_entry(const MTable<ENT>& T, int& idx, int& tile) {
+  const int t = ((int)blockIdx.x % kXcd) * T.tiles_per_xcd + (int)blockIdx.x / kXcd;
+  if (t >= T.tiles) return false;
+  idx = 0;
+  for (int i = 1; i < T.n; ++i)
+    if (t >= T.en[i].g.tile0) idx = i;
+  tile = t - T.en[idx].g.tile0;
+  return true;
+}
+
+// f(Int<v>{}) for the value a workgroup's entry has: SEL >= 0 when the whole table agrees on it, else a uniform branch over A, B(, C)
+template <int SEL, int A, int B, int C = B, typename F>
+__device__ __forceinline__ void with_value(int v, F&& f) {
+  if constexpr (SEL >= 0) f(Int<SEL>{});
+  else if (v == A) f(Int<A>{});
+  else if (C == B || v == B) f(Int<B>{});
+  else f(Int<C>{});
+}
+
+// ------------------------------------------------------------------------------------------------
+// forward: affs (nullable), g = d loss / d affs, the tile's loss partials
+// ------------------------------------------------------------------------------------------------
+template <int D, int MT, int BORDER>
+__device__ __forceinline__ void fwd_body(const MFwdEntry& E, int tile, float (*s_part)[kBlock / 64]) {
+  const MGeom& G = E.g;
+  const int b = tile / G.chunks;
+  const int p = (tile - b * G.chunks) * kBlock + (int)threadIdx.x;
+  const bool live = p < G.S;
+  const size_t S = (size_t)G.S;
+  const float* eb = E.e + (size_t)b * D * S;
+  const size_t kb = (size_t)b * G.K * S;
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+
+  int x = 0, y = 0, z = 0;
+  float ec[D];
+  float inv_p = 0.f;
+  if (live) {
+    const int yx = G.Y * G.X;
+    z = p / yx;
+    const int r = p - z * yx;
+    y = r / G.X;
+    x = r - y * G.X;
+    float ss = 0.f;
+#pragma unroll
+    for (int c = 0; c < D; ++c) {
+      ec[c] = eb[c * S + p];
+      ss = fmaf(ec[c], ec[c], ss);
+    }
+    inv_p = inv_norm(ss, G.eps);
+  }
+
+  for (int i = 0; i < G.K; ++i) {
+    float contrib = 0.f;
+    if (live) {
+      const int q = neighbour_of<BORDER>(G, z, y, x, G.off[i][0], G.off[i][1], G.off[i][2]);
+      float a = 0.f;
+      if (q >= 0) {
+        float dot = 0.f, sq = 0.f;
+#pragma unroll
+        for (int c = 0; c < D; ++c) {
+          const float v = eb[c * S + q];
+          dot = fmaf(ec[c], v, dot);
+          sq = fmaf(v, v, sq);
+        }
+        a = dot * inv_p * inv_norm(sq, G.eps);
+      }
+      const size_t in = (size_t)i * S + p;
+      if (E.affs) E.affs[kb + in] = act_affs(a, E.act);
+      float g = 0.f;
+      if (q >= 0) {
+        float m = 1.f;
+        if constexpr (MT == kMaskU8) m = (float)((const uint8_t*)E.m)[(size_t)b * E.mbs + in];
+        if constexpr (MT == kMaskF32) m = ((const float*)E.m)[(size_t)b * E.mbs + in];
+        const float r = a * m - E.t[(size_t)b * E.tbs + in] * m;
+        const float wr = E.w[(size_t)b * E.wbs + in] * r;
+        contrib = wr * r;
+        g = E.gscale[i] * wr * m;
+      }
+      E.gout[kb + in] = g;
+    }
+    const float v = wave_sum(contrib);
+    if (lane == 0) s_part[i][wave] = v;
+  }
+  __syncthreads();
+  if ((int)threadIdx.x < G.K) {
+    const float* r = s_part[threadIdx.x];
+    loss_accumulate(E.st, tile, (int)threadIdx.x, (r[0] + r[1]) + (r[2] + r[3]));
+  }
+}
+
+// DS / MS / BS: the table's common D / mask type / border, or -1: read from the workgroup's entry
+template <int DS, int MS, int BS>
+__global__ __launch_bounds__(kBlock) void k_fwd_multi(const MTable<MFwdEntry> T) {
+  __shared__ float s_part[kMaxK][kBlock / 64];
+  int idx, tile;
+  if (!find_entry(T, idx, tile)) return;  // the whole workgroup together
+  const MFwdEntry& E = T.en[idx];
+  with_value<DS, 16, 32>(E.g.D, [&](auto d) {
+    with_value<MS, kMaskNone, kMaskU8, kMaskF32>(E.mtype, [&](auto m) {
+      with_value<BS, PEA_BORDER_CIRCULAR, PEA_BORDER_CROP_ZERO>(E.g.border, [&](auto bd) {
+        fwd_body<decltype(d)::value, decltype(m)::value, decltype(bd)::value>(E, tile, s_part);
+      });
+    });
+  });
+}
+
+// k_loss_finish (pea_loss.h) with one workgroup per entry: lane = 16 * j + s holds slot s of offset 4 * wave + j; reads the
+// accumulators, writes loss_out, puts the state back to zero.  A kernel boundary lies between the adds and these plain loads.
+__global__ __launch_bounds__(64 * ((kMaxK + 3) / 4)) void k_loss_finish_multi(const MFinTable T) {
+  __shared__ double s_l[kMaxK];
+  const MFinEntry& E = T.en[blockIdx.x];
+  LossState* __restrict__ st = E.st;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, s = lane & (kLossSlots - 1), j = lane >> 4;
+  const bool good = st->magic == kLossMagic;
+  const int k = 4 * wave + j;
+  const bool on = k < E.K;
+  u64 v0 = 0, v1 = 0, v2 = 0;
+  unsigned fl = 0;
+  if (on) {
+    u64* a = st->acc[s][k];
+    v0 = a[0]; v1 = a[1]; v2 = a[2];
+    a[0] = 0; a[1] = 0; a[2] = 0;
+    if (s == 0) { fl = st->flags[k]; st->flags[k] = 0; }
+  }
+#pragma unroll
+  for (int o = 1; o < kLossSlots; o <<= 1) {
+    v0 += __shfl_xor(v0, o, 64);
+    v1 += __shfl_xor(v1, o, 64);
+    v2 += __shfl_xor(v2, o, 64);
+    fl |= __shfl_xor(fl, o, 64);
+  }
+  double Li = on ? loss_value(v0, v1, v2, fl) * (double)E.inv_n[on ? k : 0] : 0.0;
+  if (!good) Li = __builtin_nan("");  // the state block was never initialised (pea_workspace_init): say so
+  if (on && s == 0) {
+    E.loss_out[1 + k] = (float)Li;
+    s_l[k] = Li;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    double tot = 0.0;
+    for (int i = 0; i < E.K; ++i) tot += (double)E.lam[i] * s_l[i];
+    E.loss_out[0] = (float)tot;
+  }
+}
+
+// ------------------------------------------------------------------------------------------------
+// backward, gather form: G(p) = sum_i g_i(p) nhat(p + o_i) + g_i(p - o_i) nhat(p - o_i),
+//   de(p) = dloss * (G - ehat <ehat, G>) / n(p)        (G / eps when |e(p)| < eps)
+// ------------------------------------------------------------------------------------------------
+template <int D, int BORDER>
+__device__ __forceinline__ void bwd_body(const MBwdEntry& E, int tile) {
+  const MGeom& Gm = E.g;
+  const int b = tile / Gm.chunks;
+  const int p = (tile - b * Gm.chunks) * kBlock + (int)threadIdx.x;
+  if (p >= Gm.S) return;
+  const size_t S = (size_t)Gm.S;
+  const float* xb = E.e + (size_t)b * D * S;
+  const float* gb = E.gin + (size_t)b * Gm.K * S;
+  const float dl = E.dloss ? E.dloss[0] : 1.f;
+
+  const int yx = Gm.Y * Gm.X;
+  const int z = p / yx;
+  const int r0 = p - z * yx;
+  const int y = r0 / Gm.X;
+  const int x = r0 - y * Gm.X;
+
+  float xc[D], G[D];
+  float ss = 0.f;
+#pragma unroll
+  for (int c = 0; c < D; ++c) {
+    xc[c] = xb[c * S + p];
+    ss = fmaf(xc[c], xc[c], ss);
+    G[c] = 0.f;
+  }
+  const float nrm = sqrtf(ss);
+  const float inv_p = 1.0f / fmaxf(nrm, Gm.eps);
+
+  for (int i = 0; i < Gm.K; ++i) {
+    const int oz = Gm.off[i][0], oy = Gm.off[i][1], ox = Gm.off[i][2];
+#pragma unroll
+    for (int role = 0; role < 2; ++role) {
+      const int sg = role == 0 ? 1 : -1;
+      const int q = neighbour_of<BORDER>(Gm, z, y, x, sg * oz, sg * oy, sg * ox);
+      if (q < 0) continue;
+      float v[D], sq = 0.f;
+#pragma unroll
+      for (int c = 0; c < D; ++c) {
+        v[c] = xb[c * S + q];
+        sq = fmaf(v[c], v[c], sq);
+      }
+      // the loss term lives at the first operand's pixel: p for role A, the neighbour for role B
+      const float g = gb[(size_t)i * S + (role == 0 ? p : q)] * inv_norm(sq, Gm.eps);
+#pragma unroll
+      for (int c = 0; c < D; ++c) G[c] = fmaf(g, v[c], G[c]);
+    }
+  }
+
+  float proj = 0.f;
+#pragma unroll
+  for (int c = 0; c < D; ++c) proj = fmaf(xc[c] * inv_p, G[c], proj);
+  if (nrm < Gm.eps) proj = 0.f;  // clamp_min branch of F.normalize: d ehat / d e = I / eps
+  float* db = E.de + (size_t)b * D * S;
+  const float sc = dl * inv_p;
+#pragma unroll
+  for (int c = 0; c < D; ++c) db[c * S + p] = (G[c] - xc[c] * inv_p * proj) * sc;
+}
+
+template <int DS, int BS>
+__global__ __launch_bounds__(kBlock) void k_bwd_multi(const MTable<MBwdEntry> T) {
+  int idx, tile;
+  if (!find_entry(T, idx, tile)) return;
+  const MBwdEntry& E = T.en[idx];
+  with_value<DS, 16, 32>(E.g.D, [&](auto d) {
+    with_value<BS, PEA_BORDER_CIRCULAR, PEA_BORDER_CROP_ZERO>(E.g.border, [&](auto bd) {
+      bwd_body<decltype(d)::value, decltype(bd)::value>(E, tile);
+    });
+  });
+}
+
+// ------------------------------------------------------------------------------------------------
+// host: the fused set, descriptor -> table entry
+// ------------------------------------------------------------------------------------------------
+bool fuses(const PeaDesc* d) {
+  if (d->dtype != PEA_F32 || (d->D != 16 && d->D != 32) || d->K > kMaxK) return false;
+  if (d->border != PEA_BORDER_CIRCULAR && d->border != PEA_BORDER_CROP_ZERO) return false;
+  if (d->flags & PEA_FLAG_LOSS_ACT) return false;
+  const long long S = (long long)d->dims[0] * d->dims[1] * d->dims[2];
+  if (S * std::max(d->D, d->K) > 0x7fffffffLL) return false;
+  for (int i = 0; i < d->K; ++i)
+    for (int a = 0; a < 3; ++a)
+      if (d->offsets[i][a] < -32768 || d->offsets[i][a] > 32767) return false;
+  return true;
+}
+
+MGeom make_geom(const PeaDesc* d) {
+  MGeom g;
+  memset(&g, 0, sizeof(g));
+  g.Z = d->dims[0]; g.Y = d->dims[1]; g.X = d->dims[2]; g.K = d->K; g.D = d->D;
+  g.S = g.Z * g.Y * g.X;
+  g.border = d->border; g.eps = d->eps;
+  g.chunks = (g.S + kBlock - 1) / kBlock;
+  for (int i = 0; i < d->K; ++i)
+    for (int a = 0; a < 3; ++a) g.off[i][a] = (int16_t)d->offsets[i][a];
+  return g;
+}
+
+// N_i of include/pea.h
+double normaliser(const PeaDesc* d, int i) {
+  if (d->norm == PEA_NORM_BX) return (double)d->B * d->dims[2];
+  if (d->norm == PEA_NORM_FULL) return (double)d->B * d->dims[0] * d->dims[1] * d->dims[2];
+  double n = d->B;
+  for (int a = 0; a < 3; ++a) n *= (double)(d->dims[a] - abs(d->offsets[i][a]));
+  return n;
+}
+
+// entry order of the launch: most tiles first (stable), so the tail of every XCD's range is the small images
+void tile_order(const PeaDesc* const* descs, int n, int* order) {
+  long long tiles[kMaxN];
+  for (int i = 0; i < n; ++i) {
+    const long long S = (long long)descs[i]->dims[0] * descs[i]->dims[1] * descs[i]->dims[2];
+    tiles[i] = (S + kBlock - 1) / kBlock * descs[i]->B;
+    order[i] = i;
+  }
+  std::stable_sort(order, order + n, [&](int a, int b) { return tiles[a] > tiles[b]; });
+}
+
+// the whole table: every descriptor valid and in the fused set, and the tiles of all entries fit one grid
+bool table_fuses(const PeaDesc* const* descs, int n) {
+  if (n < 1 || n > kMaxN || !descs) return false;
+  long long tiles = 0;
+  for (int i = 0; i < n; ++i) {
+    if (!descs[i] || pea_desc_validate(descs[i]) != PEA_OK || !fuses(descs[i])) return false;
+    const long long S = (long long)descs[i]->dims[0] * descs[i]->dims[1] * descs[i]->dims[2];
+    tiles += (S + kBlock - 1) / kBlock * descs[i]->B;  // (each term < 2^31: pea_desc_validate)
+  }
+  return tiles <= 0x7fffff00LL;
+}
+
+// tile0 of every entry (entries already in launch order, g.chunks set; B[i]: their batch sizes), the totals -> the grid
+template <typename ENT>
+dim3 place_tiles(MTable<ENT>& T, const int* B) {
+  int t0 = 0;
+  for (int i = 0; i < T.n; ++i) {
+    T.en[i].g.tile0 = t0;
+    t0 += B[i] * T.en[i].g.chunks;
+  }
+  T.tiles = t0;
+  T.tiles_per_xcd = (t0 + kXcd - 1) / kXcd;
+  return dim3((unsigned)(T.tiles_per_xcd * kXcd));
+}
+
+// the value all n entries share, or -1
+template <typename GET>
+int common(int n, GET&& get) {
+  const int v = get(0);
+  for (int i = 1; i < n; ++i)
+    if (get(i) != v) return -1;
+  return v;
+}
+
+}  // namespace
+
+extern "C" {
+
+int pea_multi_supported(const PeaDesc* const* descs, int n) { return table_fuses(descs, n) ? 1 : 0; }
+
+int pea_affinity_fwd_multi(const PeaMultiFwd* entries, int n, void* workspace, size_t workspace_bytes, void* stream) {
+  if (n < 1 || n > kMaxN) return PEA_E_DESC;
+  if (!entries) return PEA_E_NULL;
+  const PeaDesc* descs[kMaxN];
+  for (int i = 0; i < n; ++i) {
+    const PeaMultiFwd& A = entries[i];
+    const int rc = pea_desc_validate(A.desc);  // (PEA_E_NULL for a missing descriptor)
+    if (rc) return rc;
+    if (!A.e || !A.target || !A.weight || !A.g_out || !A.loss_out) return PEA_E_NULL;
+    if (misaligned(A.e, dtype_bytes(A.desc->dtype)) || misaligned(A.affs, 4) || misaligned(A.g_out, 4) || misaligned(A.target, 4) ||
+        misaligned(A.weight, 4) || misaligned(A.loss_out, 4) || ((A.desc->flags & PEA_FLAG_MASK_F32) && misaligned(A.mask, 4)))
+      return PEA_E_ALIGN;
+    descs[i] = A.desc;
+  }
+  if (misaligned(workspace, 8)) return PEA_E_ALIGN;
+  if (!workspace || workspace_bytes / sizeof(LossState) < (size_t)n) return PEA_E_WORKSPACE;
+  if (!table_fuses(descs, n)) return PEA_E_UNSUPPORTED;
+
+  int order[kMaxN], B[kMaxN];
+  tile_order(descs, n, order);
+  MTable<MFwdEntry> T;
+  MFinTable F;
+  memset(&T, 0, sizeof(T));
+  memset(&F, 0, sizeof(F));
+  T.n = n;
+  LossState* states = (LossState*)workspace;
+  for (int j = 0; j < n; ++j) {
+    const int i = order[j];  // entry i of the caller is entry j of the launch; its loss state stays state i
+    const PeaMultiFwd& A = entries[i];
+    const PeaDesc* d = A.desc;
+    MFwdEntry& E = T.en[j];
+    E.g = make_geom(d);
+    B[j] = d->B;
+    E.mtype = !A.mask ? kMaskNone : (d->flags & PEA_FLAG_MASK_F32) ? kMaskF32 : kMaskU8;
+    E.act = d->flags & kActMask;
+    const long long dense = (long long)d->K * E.g.S;
+    E.tbs = d->target_bstride ? d->target_bstride : dense;
+    E.wbs = d->weight_bstride ? d->weight_bstride : dense;
+    E.mbs = d->mask_bstride ? d->mask_bstride : dense;
+    E.e = (const float*)A.e; E.t = A.target; E.w = A.weight; E.m = A.mask; E.affs = A.affs; E.gout = A.g_out;
+    E.st = states + i;
+    MFinEntry& Fe = F.en[i];
+    Fe.st = states + i; Fe.loss_out = A.loss_out; Fe.K = d->K;
+    for (int k = 0; k < d->K; ++k) {  // the values make_params (pea_abi.hip) gives the single calls
+      const double nk = normaliser(d, k);
+      E.gscale[k] = (float)(2.0 * (double)d->lambda[k] / nk);
+      Fe.inv_n[k] = (float)(1.0 / nk);
+      Fe.lam[k] = d->lambda[k];
+    }
+  }
+  const dim3 grid = place_tiles(T, B), blk(kBlock);
+  hipStream_t s = (hipStream_t)stream;
+  const int cd = common(n, [&](int j) { return T.en[j].g.D; }), cm = common(n, [&](int j) { return T.en[j].mtype; }),
+            cb = common(n, [&](int j) { return T.en[j].g.border; });
+  if (cd >= 0 && cm >= 0 && cb >= 0) {
+    with_width<16, 32>(cd, [&](auto dw) {
+      return with_width<kMaskNone, kMaskU8, kMaskF32>(cm, [&](auto mt) {
+        return with_width<PEA_BORDER_CIRCULAR, PEA_BORDER_CROP_ZERO>(cb, [&](auto bd) {
+          return launch<k_fwd_multi<decltype(dw)::value, decltype(mt)::value, decltype(bd)::value>>(grid, blk, 0, s, T);
+        });
+      });
+    });
+  } else {
+    launch<k_fwd_multi<-1, -1, -1>>(grid, blk, 0, s, T);
+  }
+  int rc = hip_rc();
+  if (!rc) {
+    hipLaunchKernelGGL(k_loss_finish_multi, dim3((unsigned)n), dim3(64 * ((kMaxK + 3) / 4)), 0, s, F);
+    rc = hip_rc();
+  }
+  if (rc) {  // (run_fwd of pea_abi.hip: the states must be zero between calls, and only the finish puts them back)
+    launch_loss_state_init(states, n, s);
+    (void)hipGetLastError();
+  }
+  return rc;
+}
+
+int pea_affinity_bwd_multi(const PeaMultiBwd* entries, int n, void* stream) {
+  if (n < 1 || n > kMaxN) return PEA_E_DESC;
+  if (!entries) return PEA_E_NULL;
+  const PeaDesc* descs[kMaxN];
+  for (int i = 0; i < n; ++i) {
+    const PeaMultiBwd& A = entries[i];
+    const int rc = pea_desc_validate(A.desc);
+    if (rc) return rc;
+    if (!A.e || !A.g || !A.de) return PEA_E_NULL;
+    const size_t es = dtype_bytes(A.desc->dtype);
+    if (misaligned(A.e, es) || misaligned(A.de, es) || misaligned(A.g, 4) || misaligned(A.dloss, 4)) return PEA_E_ALIGN;
+    descs[i] = A.desc;
+  }
+  if (!table_fuses(descs, n)) return PEA_E_UNSUPPORTED;
+
+  int order[kMaxN], B[kMaxN];
+  tile_order(descs, n, order);
+  MTable<MBwdEntry> T;
+  memset(&T, 0, sizeof(T));
+  T.n = n;
+  for (int j = 0; j < n; ++j) {
+    const PeaMultiBwd& A = entries[order[j]];
+    MBwdEntry& E = T.en[j];
+    E.g = make_geom(A.desc);
+    B[j] = A.desc->B;
+    E.e = (const float*)A.e; E.gin = A.g; E.dloss = A.dloss; E.de = (float*)A.de;
+  }
+  const dim3 grid = place_tiles(T, B), blk(kBlock);
+  hipStream_t s = (hipStream_t)stream;
+  const int cd = common(n, [&](int j) { return T.en[j].g.D; }), cb = common(n, [&](int j) { return T.en[j].g.border; });
+  if (cd >= 0 && cb >= 0) {
+    with_width<16, 32>(cd, [&](auto dw) {
+      return with_width<PEA_BORDER_CIRCULAR, PEA_BORDER_CROP_ZERO>(cb, [&](auto bd) {
+        return launch<k_bwd_multi<decltype(dw)::value, decltype(bd)::value>>(grid, blk, 0, s, T);
+      });
+    });
+  } else {
+    launch<k_bwd_multi<-1, -1>>(grid, blk, 0, s, T);
+  }
+  return hip_rc();
+}
+
+}  // extern "C"

@@ -15,9 +15,9 @@ import torch
 
 from .. import _lib
 from .. import affinity_op as op
-from ..loss.loss_embedding_mse import ema_embedding_loss, embedding_loss
+from ..loss.loss_embedding_mse import ema_embedding_loss, embedding_loss, embedding_loss_multi
 from ..loss.loss_embedding_mse_3d import (ema_embedding_loss_norm1, ema_embedding_loss_norm5, embedding_loss_norm1,
-                                          embedding_loss_norm5)
+                                          embedding_loss_norm1_multi, embedding_loss_norm5)
 from ..utils.postproc import fill_border_relu_, relu_
 
 
@@ -77,9 +77,15 @@ class _TensorSection(torch.autograd.Function):
     """cvppp_loss_section's six losses as ONE autograd node on the tensor path: per loss one forward launch (saving g)
     and one backward launch whose dloss is the loss' weight; the EMA cross gradient is added to the self gradient with one
     add.  Same reasons as _LabelsSection: nothing per loss is left to autograd."""
+    batched = False  # _TensorSectionBatched: the four deep-supervision scales through op.MultiAffinityMSE
 
     @staticmethod
-    def forward(ctx, specs, weights, ema_embedding, tensors, *embs):
+    def forward(ctx, *args):
+        return _TensorSection.run(ctx, _TensorSection, *args)
+
+    @staticmethod
+    def run(ctx, cls, specs, weights, ema_embedding, tensors, *embs):
+        """the forward of node `cls` (this one or _TensorSectionBatched)"""
         ctx.set_materialize_grads(False)
         dev = embs[0].device
         L = _lib.lib()
@@ -170,7 +176,7 @@ class _TensorSection(torch.autograd.Function):
             #      shape allows (pea_affinity_bwd_dual_ex with the 1 / norm planes the two forwards wrote: 2D, D = 16, axis-aligned
             #      stencil), else the tiled two-phase kernel, else two launches and an add
             jx = ncall - 1
-            small = []
+            small = None
             fork = _side_stream(dev)  # (the fork point: the small scales wait for nothing this section launches)
             e0 = op._embedding_arg(embs[0], "embedding")
             ema_c = op._embedding_arg(ema_embedding, "ema_embedding").to(e0.dtype)
@@ -183,13 +189,18 @@ class _TensorSection(torch.autograd.Function):
                 dxx, gx, _, invx, rawx = forward_one(jx, e0, ema_c, False, 2 if inv0 is not None else 0)
                 inv_other = None if invx is None else invx[1]
             with fork:  # the deep-supervision scales, on their own stream beside the full-resolution pair
-                for j in range(1, jx):
-                    e_c = op._embedding_arg(embs[j], "embedding")
-                    # (the 1 / norm plane goes along wherever the cross backward takes the scale -- 272^2 down to 68^2 -- : round 4 kept
-                    #  the small scales on the tiled backward "because their grids are launch-sized"; measured in round 5 the cross
-                    #  backward is worth 36 us of the section, profiles/r5_section_small.txt.  No raw map: D = 16 reads none.)
-                    d, g, _, inv, raw = forward_one(j, e_c, None, False, 1)
-                    small.append(backward_one(j, d, e_c, None, g, inv, raw=raw))
+                if cls.batched:  # the four scales as one forward, one loss finish and one backward launch (include/pea_multi.h)
+                    small = _small_scales_batched(specs[1:jx], tensors[1:jx], embs[1:jx], [rows[j] for j in range(1, jx)],
+                                                  [wdev[j:j + 1] for j in range(1, jx)])
+                if small is None:
+                    small = []
+                    for j in range(1, jx):
+                        e_c = op._embedding_arg(embs[j], "embedding")
+                        # (the 1 / norm plane goes along wherever the cross backward takes the scale -- 272^2 down to 68^2 -- : round 4
+                        #  kept the small scales on the tiled backward "because their grids are launch-sized"; measured in round 5 the
+                        #  cross backward is worth 36 us of the section, profiles/r5_section_small.txt.  No raw map: D = 16 reads none.)
+                        d, g, _, inv, raw = forward_one(j, e_c, None, False, 1)
+                        small.append(backward_one(j, d, e_c, None, g, inv, raw=raw))
             de0 = torch.empty_like(e0)
             rc = L.pea_affinity_bwd_dual_ex(ctypes.byref(d0), op._ptr(e0), op._ptr(ema_c), op._ptr(g0), op._ptr(gx), op._ptr(inv0),
                                             op._ptr(inv_other), op._ptr(wdev[0:1]), op._ptr(wdev[jx:jx + 1]),
@@ -208,11 +219,29 @@ class _TensorSection(torch.autograd.Function):
             losses = rows[:, 0]
             total = _section_total(L, rows, wdev, ncall)
         ctx.grads, ctx.n_embs = grads, len(embs)
-        _stash_again(ctx, _TensorSection, (specs, weights, ema_embedding, tensors) + tuple(embs))
+        _stash_again(ctx, cls, (specs, weights, ema_embedding, tensors) + tuple(embs))
         ctx.mark_non_differentiable(pred, losses)
         return total, pred, losses
 
     backward = staticmethod(lambda ctx, dtotal, _dp, _dl: _section_backward(ctx, dtotal))
+
+
+class _TensorSectionBatched(_TensorSection):
+    """_TensorSection with the four deep-supervision scales as ONE forward, one loss finish and one backward launch
+    (include/pea_multi.h) instead of three launches per scale: the same stream, the same `rows` / `wdev` slots"""
+    batched = True
+    forward = staticmethod(lambda ctx, *args: _TensorSection.run(ctx, _TensorSectionBatched, *args))
+
+
+def _small_scales_batched(specs, tensors, embs, rows, dlosses):
+    """the deep-supervision self losses of a section as op.MultiAffinityMSE: loss rows into `rows`, gradients weighted by the device
+    scalars `dlosses` -> the gradients, or None where the table is outside the fused set (nothing launched: the caller's loop runs)"""
+    stub = _Rerun()
+    try:
+        op.MultiAffinityMSE.forward(stub, specs, tensors, False, (rows, dlosses), *embs)
+    except op.MultiUnsupported:
+        return None
+    return stub.grads
 
 
 _ACC_DESC = {}
@@ -381,7 +410,7 @@ def _section_parts(losses, weights, self_emb, cross_emb):
 
 
 def cvppp_loss_section(embedding, emds, ema_embedding, target, weightmap, affs_mask, downs, criterion, offsets, nb_half,
-                       affs0_weight=1, dis_mode='ours', deep_weight=1, self_emb=1.0, cross_emb=1.0, relu_pred=False):
+                       affs0_weight=1, dis_mode='ours', deep_weight=1, self_emb=1.0, cross_emb=1.0, relu_pred=False, batched=False):
     """scripts_cvppp/main.py:284-310 (and scripts_bbbc/main.py:279-305): five self losses over the deep-supervision
     scales + the EMA cross loss at full resolution.
 
@@ -396,7 +425,11 @@ def cvppp_loss_section(embedding, emds, ema_embedding, target, weightmap, affs_m
 
     relu_pred=True: pred comes back already clamped at 0 -- the kernel that writes the map applies the reference's next
     statement, `pred = F.relu(pred)` (:312), on the way out, so that line (finish_pred_2d_) and its pass over
-    [B,K,H,W] are dropped; nothing else reads pred in the training loop."""
+    [B,K,H,W] are dropped; nothing else reads pred in the training loop.
+
+    batched=True: the four deep-supervision scales run as ONE forward, one loss finish and one backward launch (include/pea_multi.h,
+    op.MultiAffinityMSE) instead of three launches per scale -- on the same side stream; where the library does not fuse the table
+    (pea_multi_supported == 0) the per-scale launches run as before.  Same results to rounding (profiles/multi_scale_ab.json)."""
     if getattr(criterion, 'pea_fused', False) and not ema_embedding.requires_grad:
         specs, weights = _section_specs(offsets, nb_half, affs0_weight, dis_mode, deep_weight, self_emb, cross_emb)
         specs[0].relu = specs[-1].relu = bool(relu_pred)  # (the cross loss writes no map; its descriptor must match)
@@ -405,24 +438,29 @@ def cvppp_loss_section(embedding, emds, ema_embedding, target, weightmap, affs_m
             k = nb_half * (4 - j)
             m = down[:, 2 * k:3 * k]
             tensors.append((down[:, 0:k], down[:, k:2 * k], m))  # (a float mask third goes to the kernels as it is: PEA_FLAG_MASK_F32)
-        loss, pred, losses = _TensorSection.apply(specs, weights, ema_embedding, tensors, embedding, *emds)
+        node = _TensorSectionBatched if batched else _TensorSection
+        loss, pred, losses = node.apply(specs, weights, ema_embedding, tensors, embedding, *emds)
         return loss, pred, _section_parts(losses, weights, self_emb, cross_emb)
     loss, pred, parts = cvppp_loss_section_composed(embedding, emds, ema_embedding, target, weightmap, affs_mask, downs, criterion,
-                                                    offsets, nb_half, affs0_weight, dis_mode, deep_weight, self_emb, cross_emb)
+                                                    offsets, nb_half, affs0_weight, dis_mode, deep_weight, self_emb, cross_emb, batched)
     # (out of place: the composed path's `pred` may be saved for its loss' backward -- the projection-first kernel reads the raw map)
     return loss, (torch.relu(pred) if relu_pred else pred), parts
 
 
 def cvppp_loss_section_composed(embedding, emds, ema_embedding, target, weightmap, affs_mask, downs, criterion, offsets, nb_half,
-                                affs0_weight=1, dis_mode='ours', deep_weight=1, self_emb=1.0, cross_emb=1.0):
-    """the same section call by call, statement for statement as scripts_cvppp/main.py:284-310 (any criterion)"""
+                                affs0_weight=1, dis_mode='ours', deep_weight=1, self_emb=1.0, cross_emb=1.0, batched=False):
+    """the same section call by call, statement for statement as scripts_cvppp/main.py:284-310 (any criterion).
+    batched=True: the four embedding_loss calls of :284-287 as one embedding_loss_multi call (one autograd node, one launch each way)"""
     dwf = deep_weight_factor(deep_weight)
-    losses = []
-    for j, (emd, down) in enumerate(zip(emds, downs)):
-        k = nb_half * (4 - j)
-        l, _, _ = embedding_loss(emd, down[:, 0:k], down[:, k:2 * k], down[:, 2 * k:3 * k], criterion, offsets[:k],
-                                 affs0_weight=affs0_weight, mode=dis_mode)
-        losses.append(l)
+    if batched:
+        losses = [l for l, _, _ in _deep_losses_2d(emds, downs, criterion, offsets, nb_half, affs0_weight, dis_mode)]
+    else:
+        losses = []
+        for j, (emd, down) in enumerate(zip(emds, downs)):
+            k = nb_half * (4 - j)
+            l, _, _ = embedding_loss(emd, down[:, 0:k], down[:, k:2 * k], down[:, 2 * k:3 * k], criterion, offsets[:k],
+                                     affs0_weight=affs0_weight, mode=dis_mode)
+            losses.append(l)
     loss_embedding, pred, _ = embedding_loss(embedding, target, weightmap, affs_mask, criterion, offsets,
                                              affs0_weight=affs0_weight, mode=dis_mode)
     loss_embedding_cross, _ = ema_embedding_loss(embedding, ema_embedding, target, weightmap, affs_mask, criterion, offsets,
@@ -435,6 +473,15 @@ def cvppp_loss_section_composed(embedding, emds, ema_embedding, target, weightma
     loss = loss_embedding_total + loss_embedding_cross_total
     parts = {"loss_embedding": loss_embedding, "loss_emd": loss_emd, "loss_embedding_cross": loss_embedding_cross}
     return loss, pred, parts
+
+
+def _deep_losses_2d(emds, downs, criterion, offsets, nb_half, affs0_weight, dis_mode):
+    """embedding_loss on emd1..emd4 with the packed thirds of down1..down4 and offsets[:8], [:6], [:4], [:2]
+    (scripts_cvppp/main.py:284-287) as one embedding_loss_multi call"""
+    ks = [nb_half * (4 - j) for j in range(len(emds))]
+    return embedding_loss_multi(list(emds), [d[:, 0:k] for d, k in zip(downs, ks)], [d[:, k:2 * k] for d, k in zip(downs, ks)],
+                                [d[:, 2 * k:3 * k] for d, k in zip(downs, ks)], criterion, [offsets[:k] for k in ks],
+                                affs0_weight=affs0_weight, mode=dis_mode, need_affs=False)
 
 
 def _specs_3d(embedding_mode, affs0_weight):
@@ -451,7 +498,7 @@ def _specs_3d(embedding_mode, affs0_weight):
 
 
 def ac3ac4_loss_section(embedding, emds, ema_embedding, target, weightmap, downs, criterion, embedding_mode=5, affs0_weight=1,
-                        finish_pred=False):
+                        finish_pred=False, batched=False):
     """scripts_ac3ac4/main.py:219-231: full-resolution self + EMA cross loss (norm1 or norm5) and four norm1 losses on
     the deep-supervision heads; downs = (down1, .., down4) packed [B, 6, z, y, x] = (target[:3] | weight[3:]),
     paired emd1<->down4 .. emd4<->down1 as in the reference.  Returns (loss, pred before the border fill / relu);
@@ -461,7 +508,9 @@ def ac3ac4_loss_section(embedding, emds, ema_embedding, target, weightmap, downs
     finish_pred=True: pred comes back FINISHED -- the reference's next five statements (:233-237: border fill of the three shift-1
     channels, F.relu) applied: where no backward kernel reads the raw map (the reference's training crops) the forward clamps the
     map on the way out and only the border slices are touched afterwards (pea_fill_border_relu with relu = 0: 5 us instead of a pass
-    over [B,12,Z,Y,X]); else one fill + relu pass.  Do not call finish_pred_3d_ again (it would be harmless: both are idempotent)."""
+    over [B,12,Z,Y,X]); else one fill + relu pass.  Do not call finish_pred_3d_ again (it would be harmless: both are idempotent).
+
+    batched=True: the four norm1 losses of the deep-supervision heads as one launch each way, as in cvppp_loss_section."""
     if getattr(criterion, 'pea_fused', False) and not ema_embedding.requires_grad and embedding_mode in (1, 5):
         specs, weights = _specs_3d(embedding_mode, affs0_weight)
         tensors = [(target, weightmap, None)] + [(d[:, :3], d[:, 3:], None) for d in downs[::-1]]
@@ -470,11 +519,12 @@ def ac3ac4_loss_section(embedding, emds, ema_embedding, target, weightmap, downs
             # (the z-march backward of large volumes reads the forward's RAW map: pea_cross_supported mode 3)
             clamped = not op.cross_supported(op.make_desc(specs[0], op._embedding_arg(embedding, "embedding")), 3)
             specs[0].relu = clamped
-        loss, pred, _ = _TensorSection.apply(specs, weights, ema_embedding, tensors, embedding, *emds)
+        loss, pred, _ = (_TensorSectionBatched if batched else _TensorSection).apply(specs, weights, ema_embedding, tensors, embedding, *emds)
         if finish_pred:
             fill_border_relu_(pred, shift=1, relu=not clamped)
         return loss, pred
-    loss, pred = ac3ac4_loss_section_composed(embedding, emds, ema_embedding, target, weightmap, downs, criterion, embedding_mode, affs0_weight)
+    loss, pred = ac3ac4_loss_section_composed(embedding, emds, ema_embedding, target, weightmap, downs, criterion, embedding_mode, affs0_weight,
+                                              batched)
     return loss, (finish_pred_3d_(pred.detach().clone()) if finish_pred else pred)
 
 
@@ -491,8 +541,10 @@ def ac3ac4_loss_section_from_labels(embedding, emds, ema_embedding, labels, labe
     return loss, pred
 
 
-def ac3ac4_loss_section_composed(embedding, emds, ema_embedding, target, weightmap, downs, criterion, embedding_mode=5, affs0_weight=1):
-    """the same section call by call, statement for statement as scripts_ac3ac4/main.py:219-231 (any criterion)"""
+def ac3ac4_loss_section_composed(embedding, emds, ema_embedding, target, weightmap, downs, criterion, embedding_mode=5, affs0_weight=1,
+                                 batched=False):
+    """the same section call by call, statement for statement as scripts_ac3ac4/main.py:219-231 (any criterion).
+    batched=True: the four embedding_loss_norm1 calls of :227-230 as one embedding_loss_norm1_multi call"""
     if embedding_mode == 1:
         loss_embedding, pred = embedding_loss_norm1(embedding, target, weightmap, criterion, affs0_weight=affs0_weight)
         loss_embedding_cross, _ = ema_embedding_loss_norm1(embedding, ema_embedding, target, weightmap, criterion,
@@ -504,8 +556,12 @@ def ac3ac4_loss_section_composed(embedding, emds, ema_embedding, target, weightm
     else:
         raise NotImplementedError
     loss = loss_embedding + loss_embedding_cross
-    for emd, down in zip(emds, downs[::-1]):
-        l, _ = embedding_loss_norm1(emd, down[:, :3], down[:, 3:], criterion, affs0_weight=affs0_weight)
+    if batched:
+        deep = embedding_loss_norm1_multi(list(emds), [d[:, :3] for d in downs[::-1]], [d[:, 3:] for d in downs[::-1]], criterion,
+                                          affs0_weight=affs0_weight, need_affs=False)
+    else:
+        deep = [embedding_loss_norm1(emd, down[:, :3], down[:, 3:], criterion, affs0_weight=affs0_weight) for emd, down in zip(emds, downs[::-1])]
+    for l, _ in deep:
         loss = loss + l
     return loss, pred
 
@@ -516,11 +572,12 @@ def finish_pred_3d_(pred, shift=1):
 
 
 def cvppp_validation_section(embedding, emds, target, weightmap, affs_mask, downs, criterion, offsets, nb_half,
-                             affs0_weight=1, dis_mode='ours', test_mode=False):
+                             affs0_weight=1, dis_mode='ours', test_mode=False, batched=False):
     """The validation / test caller of scripts_cvppp/inference.py:179-193 (and the validation branch of main.py:380-395):
     under no_grad, either embedding2affs alone (mode == 'test') or the five self losses -- unweighted sum, as the reference
     adds them at :190 -- and the full-resolution map; `pred` comes back as F.relu(pred) (:193).  Returns (loss or None,
-    pred); the caller adds its own loss_mask term.  emds = (emd1, .., emd4), downs = (down1, .., down4) as in training."""
+    pred); the caller adds its own loss_mask term.  emds = (emd1, .., emd4), downs = (down1, .., down4) as in training.
+    batched=True: the four small losses as one embedding_loss_multi call (one forward launch and one loss finish for the four)."""
     with torch.no_grad():
         if test_mode:
             from ..loss.loss_embedding_mse import embedding2affs
@@ -528,11 +585,15 @@ def cvppp_validation_section(embedding, emds, target, weightmap, affs_mask, down
         total = None
         fork = _side_stream(embedding.device)
         with fork:  # the small scales beside the full-resolution call, as in training
-            for j, (emd, down) in enumerate(zip(emds, downs)):
-                k = nb_half * (4 - j)
-                l, _, _ = embedding_loss(emd, down[:, 0:k], down[:, k:2 * k], down[:, 2 * k:3 * k], criterion, offsets[:k],
-                                         affs0_weight=affs0_weight, mode=dis_mode)
-                total = l if total is None else total + l
+            if batched:
+                for l, _, _ in _deep_losses_2d(emds, downs, criterion, offsets, nb_half, affs0_weight, dis_mode):
+                    total = l if total is None else total + l
+            else:
+                for j, (emd, down) in enumerate(zip(emds, downs)):
+                    k = nb_half * (4 - j)
+                    l, _, _ = embedding_loss(emd, down[:, 0:k], down[:, k:2 * k], down[:, 2 * k:3 * k], criterion, offsets[:k],
+                                             affs0_weight=affs0_weight, mode=dis_mode)
+                    total = l if total is None else total + l
         loss_embedding, pred, _ = embedding_loss(embedding, target, weightmap, affs_mask, criterion, offsets,
                                                  affs0_weight=affs0_weight, mode=dis_mode)
         fork.join()

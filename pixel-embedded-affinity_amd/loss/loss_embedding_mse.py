@@ -21,7 +21,7 @@ import torch
 
 from .. import _lib
 from ..affinity_op import (AffinityMap, activation_flags, AffinitySpec, FusedAffinityMSE, LabelsAffinityMSE, LabelsStepUnsupported, LossList,
-                           affinity_infer)
+                           MultiAffinityMSE, MultiUnsupported, affinity_infer)
 
 
 def _eps(mode):
@@ -56,6 +56,28 @@ def embedding_loss(embedding, target, weightmap, mask, criterion, offsets, affs0
     else:
         loss, affs, parts = _foreign_criterion(embedding, None, target, weightmap, mask, criterion, offsets, lam, mode)
     return loss, affs, LossList(parts)
+
+
+def embedding_loss_multi(embeddings, targets, weightmaps, masks, criterion, offsets_list, affs0_weight=1, mode='ours', need_affs=False):
+    """[embedding_loss(embeddings[j], targets[j], weightmaps[j], masks[j], criterion, offsets_list[j], affs0_weight, mode) for j]
+    -> a list of (loss, affs, all_loss) -- the four deep-supervision calls of scripts_cvppp/main.py:284-287 (and of the validation
+    loop, inference.py:185-188) -- as ONE forward, one loss finish and one backward launch where the fused criterion is used and
+    the table is in the fused set of include/pea_multi.h (up to four losses, float32 embeddings, D = 16 / 32, at most 12 offsets);
+    anything else, and any other criterion, takes the single calls.  need_affs=False (what those callers want: they throw the small
+    maps away): affs is None and, on the fused path, never written."""
+    n = len(embeddings)
+    if not (len(targets) == len(weightmaps) == len(masks) == len(offsets_list) == n):
+        raise ValueError("one target, weightmap, mask and offset list per embedding")
+    if _fused(criterion):
+        specs = [_spec(offs, [1.0] * len(offs), mode) for offs in offsets_list]
+        try:
+            out = MultiAffinityMSE.apply(specs, list(zip(targets, weightmaps, masks)), bool(need_affs), None, *embeddings)
+            return [(out[j], out[n + j] if need_affs else None, LossList(out[2 * n + j])) for j in range(n)]
+        except MultiUnsupported:
+            pass
+    out = [embedding_loss(e, t, w, m, criterion, offs, affs0_weight=affs0_weight, mode=mode)
+           for e, t, w, m, offs in zip(embeddings, targets, weightmaps, masks, offsets_list)]
+    return [(l, a if need_affs else None, parts) for l, a, parts in out]
 
 
 def embedding2affs(embedding, offsets, mode='ours', activation=None):

@@ -12,7 +12,8 @@ Semantics kept from the reference (file:line there):
 """
 
 from .. import _lib
-from ..affinity_op import AffinityMap, AffinitySpec, FusedAffinityMSE, LabelsAffinityMSE, LabelsStepUnsupported, affinity_infer
+from ..affinity_op import (AffinityMap, AffinitySpec, FusedAffinityMSE, LabelsAffinityMSE, LabelsStepUnsupported, MultiAffinityMSE,
+                           MultiUnsupported, affinity_infer)
 from ..utils.affinity_ours import NORM5_SHIFTS, axis_offsets_3d
 
 
@@ -44,6 +45,28 @@ def _run(embedding, ema_embedding, target, weightmap, criterion, shifts, affs0_w
 def embedding_loss_norm1(embedding, target, weightmap, criterion, affs0_weight=1, shift=1, fill=True):
     """-> (loss, affs [B,3,Z,Y,X]) -- reference :7-27"""
     return _run(embedding, None, target, weightmap, criterion, [shift] * 3, affs0_weight, 1)
+
+
+def embedding_loss_norm1_multi(embeddings, targets, weightmaps, criterion, affs0_weight=1, shift=1, need_affs=True):
+    """[embedding_loss_norm1(embeddings[j], targets[j], weightmaps[j], criterion, affs0_weight, shift) for j] -> a list of
+    (loss, affs) -- the four deep-supervision calls of scripts_ac3ac4/main.py:227-230 -- as ONE forward, one loss finish and one
+    backward launch with the fused criterion (include/pea_multi.h: up to four losses, float32 embeddings, D = 16 / 32); anything
+    else takes the single calls.  shift: one value, or one per embedding.  need_affs=False: affs is None (never written on the
+    fused path)."""
+    n = len(embeddings)
+    if not (len(targets) == len(weightmaps) == n):
+        raise ValueError("one target and weightmap per embedding")
+    shifts = list(shift) if isinstance(shift, (list, tuple)) else [shift] * n
+    if getattr(criterion, 'pea_fused', False):
+        specs = [_spec([s] * 3, affs0_weight, 1) for s in shifts]
+        try:
+            out = MultiAffinityMSE.apply(specs, [(t, w, None) for t, w in zip(targets, weightmaps)], bool(need_affs), None, *embeddings)
+            return [(out[j], out[n + j] if need_affs else None) for j in range(n)]
+        except MultiUnsupported:
+            pass
+    out = [embedding_loss_norm1(e, t, w, criterion, affs0_weight=affs0_weight, shift=s)
+           for e, t, w, s in zip(embeddings, targets, weightmaps, shifts)]
+    return [(l, a if need_affs else None) for l, a in out]
 
 
 def ema_embedding_loss_norm1(embedding, ema_embedding, target, weightmap, criterion, affs0_weight=1, shift=1, fill=True):
