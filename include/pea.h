@@ -106,6 +106,15 @@ extern "C" {
 #define PEA_E_UNSUPPORTED (-3) /* valid but not implemented combination */
 #define PEA_E_WORKSPACE (-4)   /* workspace too small / missing */
 #define PEA_E_ALIGN (-5)       /* pointer not aligned to its element size */
+/* The alignment contract (tests/test_gpu_alignment.py, tests/test_align_host.py hold the library to it).  A data pointer only has to
+ * be aligned to its element size -- 4 bytes for f32 / int32 tensors, 2 for f16 / bf16 embeddings, 1 for a u8 mask, 8 for a state
+ * block, 16 for the labels scratch -- anything less returns PEA_E_ALIGN before anything is launched.  An f32 mask
+ * (PEA_FLAG_MASK_F32) is an f32 pointer: 4 bytes.  ANY element-aligned pointer and ANY non-negative batch stride of target / weight /
+ * mask is served, with the same results (to rounding) and without a write outside the tensors handed over.  16-byte alignment and
+ * batch strides that are multiples of four elements only SELECT the faster kernels (dwordx4 loads, LDS-DMA, quad stores): a call
+ * that misses them in one pointer takes the next kernel family, and pea_cross_supported, which sees no pointers, assumes them.  The
+ * two places where no slower family exists say so in their own words: pea_affinity_fwd_dual_ex / pea_affinity_bwd_dual_ex and
+ * PEA_FLAG_ACCUMULATE_DE return PEA_E_UNSUPPORTED -- before anything is launched -- for pointers their one kernel cannot take. */
 
 typedef struct PeaDesc {
   int32_t abi;     /* must equal PEA_ABI_VERSION */

@@ -181,7 +181,7 @@ int pea_affinity_fwd_ex(const PeaDesc* desc, const void* e, const void* e_other,
   const size_t es = dtype_bytes(desc->dtype);
   if (misaligned(e, es) || misaligned(e_other, es) || misaligned(affs, 4) || misaligned(g_out, 4) ||
       misaligned(target, 4) || misaligned(weight, 4) || misaligned(loss_out, 4) || misaligned(workspace, 8) ||
-      misaligned(inv_norm_out, 4))
+      misaligned(inv_norm_out, 4) || ((desc->flags & PEA_FLAG_MASK_F32) && misaligned(mask, 4)))  // (an f32 mask is an f32 pointer)
     return PEA_E_ALIGN;
   const KParams P = make_params(desc);
   if (!workspace || workspace_bytes < kStateBytes) return PEA_E_WORKSPACE;
@@ -226,7 +226,8 @@ int pea_affinity_fwd_dual_ex(const PeaDesc* desc, const PeaDesc* desc_cross, con
   if (!same) return PEA_E_DESC;
   if (misaligned(e, 4) || misaligned(ema, 4) || misaligned(affs, 4) || misaligned(g_out, 4) || misaligned(g_cross_out, 4) ||
       misaligned(target, 4) || misaligned(weight, 4) || misaligned(loss_out, 4) || misaligned(loss_cross_out, 4) ||
-      misaligned(workspace, 8) || misaligned(workspace_cross, 8) || misaligned(inv_norm_out, 4) || misaligned(inv_norm_other_out, 4))
+      misaligned(workspace, 8) || misaligned(workspace_cross, 8) || misaligned(inv_norm_out, 4) || misaligned(inv_norm_other_out, 4) ||
+      ((desc->flags & PEA_FLAG_MASK_F32) && misaligned(mask, 4)))
     return PEA_E_ALIGN;
   if (!workspace || !workspace_cross || workspace == workspace_cross || workspace_bytes < kStateBytes) return PEA_E_WORKSPACE;
   if (e == ema) return PEA_E_UNSUPPORTED;  // (an aliased second operand is a self loss twice: the two calls handle it)
