@@ -12,7 +12,7 @@ Import name: the directory is not a valid Python identifier, so load it through
 from . import _lib
 from ._lib import PeaLibraryError, build
 from .affinity_op import (AffinityMap, AffinitySpec, FusedAffinityMSE, Graphed, LabelsAffinityMSE, MultiAffinityMSE, affinity_infer, backward,
-                          check_label_ranges, graphed)
+                          check_label_ranges, graphed, unflip)
 from .loss.loss import WeightedMSE
 from .loss.loss_embedding_mse import (ema_embedding_loss, ema_embedding_loss_from_labels, embedding2affs, embedding_loss,
                                       embedding_loss_from_labels, embedding_loss_multi)
@@ -54,5 +54,5 @@ __all__ = [
     "embedding2affs_half_clamp", "embedding_loss_clamp", "embedding2affs_clamp", "embedding_loss_normalized",
     "ema_embedding_loss_normalized", "embedding2affs_normalized",
     "embedding_loss_norm6", "ema_embedding_loss_norm6", "EmbeddingHead", "OutConv", "head_conv3d_block", "cvppp_label_weight_tables", "cvppp_validation_section",
-    "MultiAffinityMSE", "embedding_loss_multi", "embedding_loss_norm1_multi",
+    "MultiAffinityMSE", "embedding_loss_multi", "embedding_loss_norm1_multi", "unflip", "convert_consistency_flip",
 ]

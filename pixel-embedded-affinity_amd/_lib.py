@@ -15,6 +15,7 @@ SO_PATH = os.environ.get("PEA_HIP_LIB") or os.path.join(CSRC, "libpea_hip.so")  
 HEADER = os.path.join(HERE, "..", "include", "pea.h")
 HEADER_INFER = os.path.join(HERE, "..", "include", "pea_infer.h")
 HEADER_MULTI = os.path.join(HERE, "..", "include", "pea_multi.h")
+HEADER_FLIP = os.path.join(HERE, "..", "include", "pea_flip.h")
 
 PEA_ABI_VERSION = 2
 PEA_MAX_K = 32
@@ -26,6 +27,7 @@ NORM_BX, NORM_CROPPED, NORM_FULL = 0, 1, 2
 FLAG_RELU_AFFS, FLAG_ONE_MINUS, FLAG_HALF_SHIFT, FLAG_CLAMP01, FLAG_ACCUMULATE_DE = 1, 2, 4, 8, 16  # activation of the affs output (include/pea.h)
 FLAG_MASK_F32 = 32  # the mask of the training forwards holds f32 values (include/pea.h PEA_FLAG_MASK_F32)
 FLAG_LOSS_ACT = 64  # the loss of the training forwards is taken on the activated map (include/pea.h PEA_FLAG_LOSS_ACT)
+RULES_U8, RULES_I32, RULES_I64, RULES_F32 = 0, 1, 2, 3  # element type of the rules table (include/pea_flip.h PEA_RULES_*)
 TGT_PADDING, TGT_BOTH_FOREGROUND, TGT_MASK_INSIDE, TGT_ACCUMULATE = 1, 2, 4, 8
 
 EXPORTS = ("pea_version", "pea_strerror", "pea_desc_validate", "pea_workspace_bytes", "pea_workspace_init", "pea_reload_env",
@@ -39,6 +41,8 @@ EXPORTS = ("pea_version", "pea_strerror", "pea_desc_validate", "pea_workspace_by
 EXPORTS_INFER = ("pea_infer_stitch_supported", "pea_affinity_infer_stitch")
 # the entry points of include/pea_multi.h (up to four self losses per launch: the deep-supervision scales)
 EXPORTS_MULTI = ("pea_multi_supported", "pea_affinity_fwd_multi", "pea_affinity_bwd_multi")
+# the entry point of include/pea_flip.h (the per-sample un-flip of the EMA embedding, rules read on the device)
+EXPORTS_FLIP = ("pea_consistency_unflip",)
 
 
 class PeaLibraryError(RuntimeError):
@@ -93,7 +97,7 @@ def build(force=False, verbose=False, jobs=None):
 
 def _build_locked(force, verbose, jobs):
     srcs = sources()
-    hdrs = [HEADER, HEADER_INFER, HEADER_MULTI] + [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".h")]
+    hdrs = [HEADER, HEADER_INFER, HEADER_MULTI, HEADER_FLIP] + [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".h")]
     newest_hdr = max(os.path.getmtime(h) for h in hdrs)
     if not force and os.path.exists(SO_PATH) and os.path.getmtime(SO_PATH) >= max([newest_hdr] + [os.path.getmtime(x) for x in srcs]):
         return SO_PATH
@@ -157,7 +161,7 @@ def lib():
         L = ctypes.CDLL(SO_PATH)
     except OSError as ex:
         raise PeaLibraryError("cannot load %s: %s" % (SO_PATH, ex))
-    for name in EXPORTS + EXPORTS_INFER + EXPORTS_MULTI:
+    for name in EXPORTS + EXPORTS_INFER + EXPORTS_MULTI + EXPORTS_FLIP:
         if not hasattr(L, name):
             raise PeaLibraryError("%s does not export %s" % (SO_PATH, name))
     vp, dp = ctypes.c_void_p, ctypes.POINTER(PeaDesc)
@@ -236,6 +240,8 @@ def lib():
     L.pea_affinity_fwd_multi.argtypes = [ctypes.POINTER(PeaMultiFwd), ctypes.c_int, vp, ctypes.c_size_t, vp]
     L.pea_affinity_bwd_multi.restype = ctypes.c_int
     L.pea_affinity_bwd_multi.argtypes = [ctypes.POINTER(PeaMultiBwd), ctypes.c_int, vp]
+    L.pea_consistency_unflip.restype = ctypes.c_int
+    L.pea_consistency_unflip.argtypes = [ctypes.c_int] * 6 + [vp, vp, vp, ctypes.c_int, ctypes.c_int, vp]
     if L.pea_version() != PEA_ABI_VERSION:
         raise PeaLibraryError("ABI mismatch: library %d, binding %d" % (L.pea_version(), PEA_ABI_VERSION))
     _lib = L

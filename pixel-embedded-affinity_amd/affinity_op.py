@@ -242,6 +242,58 @@ def affinity_infer(e, e_other, spec):
     return affs
 
 
+# element type of a rules table -> PEA_RULES_* (include/pea_flip.h); every other dtype is converted once on the device
+UNFLIP_DTYPES = tuple(_DTYPE_CODE)  # what pea_consistency_unflip moves: the embedding's storage dtypes
+_RULES_CODE = {torch.uint8: _lib.RULES_U8, torch.int32: _lib.RULES_I32, torch.int64: _lib.RULES_I64, torch.float32: _lib.RULES_F32}
+
+
+def check_unflip_shapes(t_shape, rules_shape):
+    """the shapes unflip() and harness.train_step.convert_consistency_flip accept: a [B, C, H, W] or [B, C, Z, H, W] tensor with
+    [B, 3] rules (x-flip, y-flip, xy-transpose), or a [B, C, Z, H, W] tensor with [B, 4] rules (z-flip, x-flip, y-flip, xy-transpose)"""
+    t_shape, rules_shape = tuple(t_shape), tuple(rules_shape)
+    if len(t_shape) not in (4, 5):
+        raise ValueError("the tensor must be [B,C,H,W] or [B,C,Z,H,W], got shape %s" % (t_shape,))
+    if len(rules_shape) != 2 or rules_shape[1] not in (3, 4):
+        raise ValueError("rules must be [B,3] or [B,4], got shape %s" % (rules_shape,))
+    if rules_shape[1] == 4 and len(t_shape) != 5:
+        raise ValueError("[B,4] rules (z-flip, x-flip, y-flip, xy-transpose) need a [B,C,Z,H,W] tensor, got shape %s" % (t_shape,))
+    if rules_shape[0] != t_shape[0]:
+        raise ValueError("rules has %d rows for a batch of %d" % (rules_shape[0], t_shape[0]))
+
+
+def unflip(t, rules):
+    """pea_consistency_unflip (include/pea_flip.h): the per-sample inverse of the EMA branch's flips / transpose in ONE launch, the
+    rules read on the device (no host synchronisation: the call can be captured into a HIP graph and replayed on new rules).
+    t [B,C,H,W] or [B,C,Z,H,W] f32 / f16 / bf16 on a ROCm device; rules a tensor on the same device, [B,3] = (x-flip, y-flip,
+    xy-transpose) or, for a volume, [B,4] = (z-flip, x-flip, y-flip, xy-transpose); a rule is set when it is nonzero.
+    Returns a NEW, detached, contiguous tensor: a bit-exact copy.  A sample whose transpose rule is set on a non-square plane comes
+    back all NaN (the host cannot see the rules)."""
+    _require_gpu(t, "tensor")
+    if t.dtype not in _DTYPE_CODE:
+        raise TypeError("the tensor must be float32, float16 or bfloat16, got %s" % t.dtype)
+    _require_gpu(rules, "rules")
+    check_unflip_shapes(t.shape, rules.shape)
+    if rules.device != t.device:
+        raise RuntimeError("rules is on %s, the tensor on %s" % (rules.device, t.device))
+    t = t.detach()
+    if not t.is_contiguous():
+        t = t.contiguous()
+    if rules.dtype == torch.bool:
+        rules = rules.view(torch.uint8)
+    elif rules.dtype not in _RULES_CODE:
+        rules = rules.to(torch.float32 if rules.is_floating_point() else torch.int64)
+    rules = rules.detach()
+    if not rules.is_contiguous():
+        rules = rules.contiguous()
+    Z = t.shape[2] if t.dim() == 5 else 1
+    with _on_device(t.device):
+        out = torch.empty(t.shape, dtype=t.dtype, device=t.device)
+        _lib.check(_lib.lib().pea_consistency_unflip(t.shape[0], t.shape[1], Z, t.shape[-2], t.shape[-1], _DTYPE_CODE[t.dtype], _ptr(t),
+                                                     _ptr(out), _ptr(rules), _RULES_CODE[rules.dtype], rules.shape[1], _stream()),
+                   "pea_consistency_unflip")
+    return out
+
+
 class FusedAffinityMSE(torch.autograd.Function):
     """loss, affs, per_offset_losses = f(e, e_other, target, weight, mask): the WeightedMSE criterion fused into the affinity
     forward.  One forward launch (saving g = d loss / d affs and, for the self loss, the 1 / norm plane of e) and one backward

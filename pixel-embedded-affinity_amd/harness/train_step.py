@@ -20,29 +20,55 @@ import torch
 import torch.nn.functional as F
 
 from ..loss.loss import WeightedMSE
+from ..affinity_op import UNFLIP_DTYPES, check_unflip_shapes, unflip
 from ..utils.affinity_ours import multi_offset
 from .loss_section import cvppp_loss_section, cvppp_loss_section_from_labels
 
 
-def convert_consistency_flip(ema_embedding, rules):
-    """per-sample inverse of the EMA branch's flips (rules[b] = (x-flip, y-flip, xy-transpose), drawn by the data provider);
-    returns a DETACHED tensor, as the reference's convert_consistency_flip does (data_consistency.py:36)"""
-    out = ema_embedding.detach().clone()
-    if rules is None:
-        return out
-    # one host copy of the whole table, cast the way the reference does (rules.data.cpu().numpy().astype(np.uint8), :37)
-    r = (rules.detach().cpu().numpy() if torch.is_tensor(rules) else np.asarray(rules)).astype(np.uint8)
+def _torch_unflip(out, r):
+    """the reference's composition on views (simple_augment_reverse_torch: transpose, y-flip, x-flip[, z-flip]) and one torch.stack;
+    r: host uint8 [B, 3] = (x-flip, y-flip, xy-transpose) or [B, 4] = (z-flip, x-flip, y-flip, xy-transpose)"""
+    o = r.shape[1] - 3  # the AC3/AC4 table puts the z-flip FIRST (scripts_ac3ac4/utils/consistency_aug.py:58-77)
     parts = []
     for b in range(out.shape[0]):
         t = out[b]
-        if r[b][2]:
+        if r[b][o + 2]:
             t = t.transpose(-1, -2)
-        if r[b][1]:
+        if r[b][o + 1]:
             t = t.flip(-2)
-        if r[b][0]:
+        if r[b][o]:
             t = t.flip(-1)
+        if o and r[b][0]:
+            t = t.flip(-3)
         parts.append(t)
     return torch.stack(parts, dim=0)  # (a transposed view cannot be written back over its own storage)
+
+
+def convert_consistency_flip(ema_embedding, rules):
+    """per-sample inverse of the EMA branch's flips, drawn by the data provider: rules[b] = (x-flip, y-flip, xy-transpose) for a
+    [B,C,H,W] tensor (on a [B,C,Z,H,W] tensor: applied to every z slice), or rules[b] = (z-flip, x-flip, y-flip, xy-transpose) for a
+    [B,C,Z,H,W] tensor (scripts_ac3ac4/utils/consistency_aug.py:217-228).  Returns a DETACHED tensor, as the reference's
+    convert_consistency_flip does (data_consistency.py:36).
+    A tensor on a ROCm device takes pea_consistency_unflip (affinity_op.unflip): one launch, the rules read on the device, no host
+    synchronisation -- rules that live on the host (list, array, CPU tensor) are uploaded asynchronously through a pinned block of
+    torch's caching host allocator (a NEW block is a hipHostMalloc, which can stall the device: the upload is free of that only once
+    the allocator's cache is warm, i.e. after the first steps; a loop that wants no such hazard at all hands over device rules);
+    under graph capture they must already be a device tensor, which a replay then reads afresh.  A CPU tensor, and a device tensor
+    of a dtype the kernel does not move (anything but float32 / float16 / bfloat16), takes the torch composition."""
+    if rules is None:
+        return ema_embedding.detach().clone()
+    if ema_embedding.is_cuda and ema_embedding.dtype in UNFLIP_DTYPES:
+        if not (torch.is_tensor(rules) and rules.is_cuda):
+            if torch.cuda.is_current_stream_capturing():
+                raise RuntimeError("convert_consistency_flip under graph capture needs rules that are a device tensor (a static input)")
+            r = rules.detach() if torch.is_tensor(rules) else torch.as_tensor(np.asarray(rules))
+            check_unflip_shapes(ema_embedding.shape, r.shape)
+            rules = r.contiguous().pin_memory().to(ema_embedding.device, non_blocking=True)
+        return unflip(ema_embedding, rules)
+    # cast the way the reference does (rules.data.cpu().numpy().astype(np.uint8), :37)
+    r = (rules.detach().cpu().numpy() if torch.is_tensor(rules) else np.asarray(rules)).astype(np.uint8)
+    check_unflip_shapes(ema_embedding.shape, r.shape)
+    return _torch_unflip(ema_embedding.detach(), r)
 
 
 def label_pyramid(labels):
