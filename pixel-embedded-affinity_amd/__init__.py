@@ -11,11 +11,11 @@ Import name: the directory is not a valid Python identifier, so load it through
 """
 from . import _lib
 from ._lib import PeaLibraryError, build
-from .affinity_op import (AffinityMap, AffinitySpec, FusedAffinityMSE, Graphed, LabelsAffinityMSE, MultiAffinityMSE, affinity_infer, backward,
+from .affinity_op import (AffinityMap, AffinitySpec, FusedAffinityMSE, Graphed, LabelsAffinityMSE, MultiAffinityMSE, MultiLabelsAffinityMSE, affinity_infer, backward,
                           check_label_ranges, graphed, unflip)
 from .loss.loss import WeightedMSE
 from .loss.loss_embedding_mse import (ema_embedding_loss, ema_embedding_loss_from_labels, embedding2affs, embedding_loss,
-                                      embedding_loss_from_labels, embedding_loss_multi)
+                                      embedding_loss_from_labels, embedding_loss_from_labels_multi, embedding_loss_multi)
 from .loss import loss_embedding, loss_embedding_exp, loss_embedding_norm
 from .loss.loss_embedding import (ema_embedding_loss as ema_embedding_loss_half_clamp, embedding2affs as embedding2affs_half_clamp,
                                   embedding_loss as embedding_loss_half_clamp)
@@ -24,7 +24,8 @@ from .loss.loss_embedding_norm import (ema_embedding_loss as ema_embedding_loss_
                                        embedding_loss as embedding_loss_normalized)
 from .loss.loss_embedding_mse_3d import (ema_embedding_loss_norm1, ema_embedding_loss_norm5, ema_embedding_loss_norm5_from_labels,
                                          ema_embedding_loss_norm6, embedding_loss_norm6,
-                                         embedding_loss_norm1, embedding_loss_norm1_from_labels, embedding_loss_norm1_multi, embedding_loss_norm5,
+                                         embedding_loss_norm1, embedding_loss_norm1_from_labels, embedding_loss_norm1_from_labels_multi, embedding_loss_norm1_multi,
+                                         embedding_loss_norm5,
                                          embedding_loss_norm5_from_labels, inf_embedding_loss_norm1, inf_embedding_loss_norm5)
 from .utils.affinity_ours import gen_offsets, multi_offset
 from .utils.postproc import fill_border_relu_, relu_
@@ -55,4 +56,5 @@ __all__ = [
     "ema_embedding_loss_normalized", "embedding2affs_normalized",
     "embedding_loss_norm6", "ema_embedding_loss_norm6", "EmbeddingHead", "OutConv", "head_conv3d_block", "cvppp_label_weight_tables", "cvppp_validation_section",
     "MultiAffinityMSE", "embedding_loss_multi", "embedding_loss_norm1_multi", "unflip", "convert_consistency_flip",
+    "MultiLabelsAffinityMSE", "embedding_loss_from_labels_multi", "embedding_loss_norm1_from_labels_multi",
 ]

@@ -16,6 +16,7 @@ HEADER = os.path.join(HERE, "..", "include", "pea.h")
 HEADER_INFER = os.path.join(HERE, "..", "include", "pea_infer.h")
 HEADER_MULTI = os.path.join(HERE, "..", "include", "pea_multi.h")
 HEADER_FLIP = os.path.join(HERE, "..", "include", "pea_flip.h")
+HEADER_MULTI_LABELS = os.path.join(HERE, "..", "include", "pea_multi_labels.h")
 
 PEA_ABI_VERSION = 2
 PEA_MAX_K = 32
@@ -43,6 +44,8 @@ EXPORTS_INFER = ("pea_infer_stitch_supported", "pea_affinity_infer_stitch")
 EXPORTS_MULTI = ("pea_multi_supported", "pea_affinity_fwd_multi", "pea_affinity_bwd_multi")
 # the entry point of include/pea_flip.h (the per-sample un-flip of the EMA embedding, rules read on the device)
 EXPORTS_FLIP = ("pea_consistency_unflip",)
+# the entry points of include/pea_multi_labels.h (up to four self losses per launch straight from label images)
+EXPORTS_MULTI_LABELS = ("pea_multi_labels_supported", "pea_multi_labels_scratch_bytes", "pea_affinity_fwd_bwd_labels_multi")
 
 
 class PeaLibraryError(RuntimeError):
@@ -72,6 +75,13 @@ class PeaMultiBwd(ctypes.Structure):
                 ("de", ctypes.c_void_p)]
 
 
+class PeaMultiLabels(ctypes.Structure):
+    """mirror of `struct PeaMultiLabels` in include/pea_multi_labels.h"""
+    _fields_ = [("desc", ctypes.POINTER(PeaDesc)), ("e", ctypes.c_void_p), ("labels", ctypes.c_void_p), ("label_dims", ctypes.c_int32 * 3),
+                ("label_step", ctypes.c_int32 * 3), ("wtab", ctypes.c_void_p), ("affs", ctypes.c_void_p), ("loss_out", ctypes.c_void_p),
+                ("dloss", ctypes.c_void_p), ("de", ctypes.c_void_p)]
+
+
 HIPCC_FLAGS = ["-O3", "--offload-arch=gfx950", "-std=c++17", "-fPIC"]
 OBJ_DIR = os.path.join(CSRC, "build")
 
@@ -97,7 +107,7 @@ def build(force=False, verbose=False, jobs=None):
 
 def _build_locked(force, verbose, jobs):
     srcs = sources()
-    hdrs = [HEADER, HEADER_INFER, HEADER_MULTI, HEADER_FLIP] + [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".h")]
+    hdrs = [HEADER, HEADER_INFER, HEADER_MULTI, HEADER_FLIP, HEADER_MULTI_LABELS] + [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".h")]
     newest_hdr = max(os.path.getmtime(h) for h in hdrs)
     if not force and os.path.exists(SO_PATH) and os.path.getmtime(SO_PATH) >= max([newest_hdr] + [os.path.getmtime(x) for x in srcs]):
         return SO_PATH
@@ -161,7 +171,7 @@ def lib():
         L = ctypes.CDLL(SO_PATH)
     except OSError as ex:
         raise PeaLibraryError("cannot load %s: %s" % (SO_PATH, ex))
-    for name in EXPORTS + EXPORTS_INFER + EXPORTS_MULTI + EXPORTS_FLIP:
+    for name in EXPORTS + EXPORTS_INFER + EXPORTS_MULTI + EXPORTS_FLIP + EXPORTS_MULTI_LABELS:
         if not hasattr(L, name):
             raise PeaLibraryError("%s does not export %s" % (SO_PATH, name))
     vp, dp = ctypes.c_void_p, ctypes.POINTER(PeaDesc)
@@ -240,6 +250,13 @@ def lib():
     L.pea_affinity_fwd_multi.argtypes = [ctypes.POINTER(PeaMultiFwd), ctypes.c_int, vp, ctypes.c_size_t, vp]
     L.pea_affinity_bwd_multi.restype = ctypes.c_int
     L.pea_affinity_bwd_multi.argtypes = [ctypes.POINTER(PeaMultiBwd), ctypes.c_int, vp]
+    L.pea_multi_labels_supported.restype = ctypes.c_int
+    L.pea_multi_labels_supported.argtypes = [ctypes.POINTER(PeaMultiLabels), ctypes.c_int, ctypes.c_uint]
+    L.pea_multi_labels_scratch_bytes.restype = ctypes.c_size_t
+    L.pea_multi_labels_scratch_bytes.argtypes = [ctypes.POINTER(PeaMultiLabels), ctypes.c_int]
+    L.pea_affinity_fwd_bwd_labels_multi.restype = ctypes.c_int
+    L.pea_affinity_fwd_bwd_labels_multi.argtypes = [ctypes.POINTER(PeaMultiLabels), ctypes.c_int, ctypes.c_uint, vp, ctypes.c_size_t, vp,
+                                                    ctypes.c_size_t, vp]
     L.pea_consistency_unflip.restype = ctypes.c_int
     L.pea_consistency_unflip.argtypes = [ctypes.c_int] * 6 + [vp, vp, vp, ctypes.c_int, ctypes.c_int, vp]
     if L.pea_version() != PEA_ABI_VERSION:

@@ -723,6 +723,185 @@ class LabelsStepUnsupported(NotImplementedError):
     target / mask / weight tensors on the GPU (pea_gen_targets) and take the tensor path -- same results."""
 
 
+class MultiLabelsUnsupported(NotImplementedError):
+    """the table of labels-in losses is outside the fused set of include/pea_multi_labels.h (pea_multi_labels_supported == 0): nothing
+    was launched, the *_from_labels_multi wrappers and the sections make the single calls on materialised label images instead"""
+
+
+def label_sources(embs, ndim, labels, label_steps=None):
+    """-> [(label tensor, (sz, sy, sx))] per embedding.  labels: a list with one label tensor per embedding, or ONE tensor all of
+    them sample; label_steps: per embedding None, an int (the in-plane step: z keeps 1) or a tuple of ndim (or 3) steps.  A step of
+    None is label size / embedding size, which must divide exactly on every axis (there OpenCV's nearest rule, src = floor(dst / f),
+    is the plain stride); ValueError otherwise, and for a step that reads past the label image."""
+    n = len(embs)
+    shared = isinstance(labels, torch.Tensor)
+    if not shared and len(labels) != n:
+        raise ValueError("one label tensor per embedding (or one tensor for all)")
+    if label_steps is not None and len(label_steps) != n:
+        raise ValueError("one label step per embedding")
+    out = []
+    for j, e in enumerate(embs):
+        lab = labels if shared else labels[j]
+        if not isinstance(lab, torch.Tensor):
+            raise TypeError("labels must be a torch.Tensor (or a list of them)")
+        dims = _spatial(e, ndim)
+        if lab.dtype.is_floating_point or lab.dim() != ndim + 1 or lab.shape[0] != e.shape[0]:
+            raise ValueError("labels must be an integer tensor [B, %s] with the embedding's batch size, got %s for embedding %s"
+                             % ("H, W" if ndim == 2 else "Z, Y, X", tuple(lab.shape), tuple(e.shape)))
+        ldims = [1] * (3 - ndim) + list(lab.shape[1:])
+        step = None if label_steps is None else label_steps[j]
+        if step is None:
+            if any(l % d for l, d in zip(ldims, dims)):
+                raise ValueError("label image %s is no integer multiple of the embedding's %s: pass nearest-downsampled label images "
+                                 "(label_downs / one label tensor per embedding) instead" % (tuple(ldims[3 - ndim:]), tuple(dims[3 - ndim:])))
+            step = [l // d for l, d in zip(ldims, dims)]
+        elif isinstance(step, int):
+            step = [1, step, step]
+        else:
+            step = [1] * (3 - len(step)) + [int(v) for v in step]
+        if any(v < 1 for v in step) or any((d - 1) * v + 1 > l for d, v, l in zip(dims, step, ldims)):
+            raise ValueError("label step %s reads outside the label image %s for an embedding of %s" % (tuple(step), tuple(ldims), tuple(dims)))
+        out.append((lab, tuple(step)))
+    return out
+
+
+def materialise_labels(lab, e, ndim, step):
+    """the label image an embedding sees, as a tensor of its own: labels[b][z * sz][y * sy][x * sx]"""
+    dims = _spatial(e, ndim)
+    if all(v == 1 for v in step) and list(lab.shape[1:]) == dims[3 - ndim:]:
+        return lab
+    v = lab.unsqueeze(1) if ndim == 2 else lab
+    v = v[:, ::step[0], ::step[1], ::step[2]][:, :dims[0], :dims[1], :dims[2]]
+    return (v.squeeze(1) if ndim == 2 else v).contiguous()
+
+
+_MULTI_LABELS_OK = {}
+
+
+def multi_labels_call(specs, e_cs, sources, flags, tables, need_affs, rows, dlosses):
+    """ONE pea_affinity_fwd_bwd_labels_multi call (include/pea_multi_labels.h): loss rows into `rows`, de_j = dlosses[j] (device
+    scalars, or None = 1) * d loss_j / d e_j -> (affs list, de list).  Raises MultiLabelsUnsupported before anything is launched."""
+    n = len(e_cs)
+    L = _lib.lib()
+    dev = e_cs[0].device
+    if not 1 <= n <= _lib.PEA_MULTI_MAX_N:
+        raise MultiLabelsUnsupported("at most %d losses per call" % _lib.PEA_MULTI_MAX_N)
+    descs, labs, conv = [], [], {}
+    for spec, e_c, (lab, step) in zip(specs, e_cs, sources):
+        if e_c.device != dev or lab.device != dev:
+            raise RuntimeError("all operands must live on %s" % dev)
+        if not labels_offsets_in_range(spec, e_c):
+            raise MultiLabelsUnsupported("an offset is as long as the image (see labels_offsets_in_range)")
+        descs.append(make_desc(spec, e_c))
+        if id(lab) not in conv:  # (one tensor sampled by every entry is converted and range-checked once)
+            conv[id(lab)] = _labels_int32(lab)
+        labs.append(conv[id(lab)])
+    table = (_lib.PeaMultiLabels * n)()
+    for j in range(n):
+        a, lab, step = table[j], labs[j], sources[j][1]
+        a.desc, a.e, a.labels = ctypes.pointer(descs[j]), e_cs[j].data_ptr(), lab.data_ptr()
+        a.label_dims[:] = [1] * (4 - lab.dim()) + list(lab.shape[1:])
+        a.label_step[:] = step
+    key = tuple(id(d) for d in descs) + tuple(tuple(a.label_dims) + tuple(a.label_step) for a in table) + (flags,)
+    hit = _MULTI_LABELS_OK.get(key)
+    if hit is None or any(x is not y for x, y in zip(hit[1], descs)):  # (the entry keeps its descriptors alive: no id is reused)
+        with _CROSS_LOCK:
+            if len(_MULTI_LABELS_OK) > 256:
+                _MULTI_LABELS_OK.clear()
+            _MULTI_LABELS_OK[key] = hit = (bool(L.pea_multi_labels_supported(table, n, flags)), list(descs))
+    if not hit[0]:
+        raise MultiLabelsUnsupported("the table is outside the fused set of include/pea_multi_labels.h")
+    with _on_device(dev):
+        affs = [torch.empty(_affs_shape(e_c, sp.K) if need_affs else (0,), dtype=torch.float32, device=dev) for e_c, sp in zip(e_cs, specs)]
+        des = [torch.empty_like(e_c) for e_c in e_cs]
+        for j in range(n):
+            a = table[j]
+            if tables is not None and tables[j] is not None:
+                wtab = tables[j]
+                if wtab.numel() != e_cs[j].shape[0] * specs[j].K * 2 or wtab.dtype != torch.float32 or wtab.device != dev:
+                    raise ValueError("weight table %d does not fit this batch / stencil" % j)
+                if not wtab.is_contiguous():
+                    raise ValueError("weight table %d must be contiguous" % j)
+                a.wtab = wtab.data_ptr()
+            a.affs = affs[j].data_ptr() if need_affs else None
+            a.loss_out, a.de = rows[j].data_ptr(), des[j].data_ptr()
+            a.dloss = None if dlosses is None or dlosses[j] is None else dlosses[j].data_ptr()
+        sb = int(L.pea_multi_labels_scratch_bytes(table, n))
+        scratch = torch.empty(max(sb, 4) // 4, dtype=torch.int32, device=dev)
+        work, wsb = workspace(dev, descs[0], n)
+        rc = L.pea_affinity_fwd_bwd_labels_multi(table, n, flags, _ptr(work), wsb, _ptr(scratch), sb, _stream())
+    if rc == _lib.E_UNSUPPORTED:  # (nothing was launched)
+        raise MultiLabelsUnsupported("pea_affinity_fwd_bwd_labels_multi: the table is outside the fused set")
+    _lib.check(rc, "pea_affinity_fwd_bwd_labels_multi")
+    return affs, des
+
+
+class MultiLabelsAffinityMSE(torch.autograd.Function):
+    """n self losses straight from label images as ONE node and ONE library call (include/pea_multi_labels.h): a count launch for the
+    class-balance tables, one fused forward + backward launch over every tile of every scale, one loss finish.
+
+        loss_0 .., affs_0 .., per_offset_0 .. = f(specs, sources, flags, need_affs, tables, pre, *embeddings)
+
+    specs: n AffinitySpecs; sources: label_sources(...) -- per loss (label tensor, (sz, sy, sx)), a tensor of its own or one all
+    losses sample with a step; flags: _lib.TGT_*; tables: None or per loss None / a [B, K, 2] table of pea_label_weights.
+    pre: None -- the gradients are computed for grad_output = 1 and backward() hands them out scaled by autograd's grad_outputs -- or
+    (rows, dlosses) for a caller that owns the weighting and the backward (the section node): loss rows to write into and per-loss
+    weights as device scalars; the gradients are then left in ctx.grads.  Raises MultiLabelsUnsupported before anything is launched."""
+
+    @staticmethod
+    def forward(ctx, specs, sources, flags, need_affs, tables, pre, *embs):
+        ctx.set_materialize_grads(False)
+        n = len(embs)
+        if not (len(specs) == len(sources) == n):
+            raise ValueError("one spec and one label source per embedding")
+        e_cs = [_embedding_arg(e, "embedding") for e in embs]
+        dev = e_cs[0].device
+        with _on_device(dev):
+            if pre is None:
+                rows = torch.empty((n, 1 + max(sp.K for sp in specs)), dtype=torch.float32, device=dev).unbind(0)
+                affs, des = multi_labels_call(specs, e_cs, sources, flags, tables, need_affs, rows, None)
+                ctx.des, ctx.grads = des, None
+                ctx.args = (specs, [st for _, st in sources], flags)
+                ctx.n_tab = 0 if tables is None else n
+                tabs = [] if tables is None else [t if t is not None else torch.empty(0, device=dev) for t in tables]
+                ctx.save_for_backward(*(e_cs + [lab for lab, _ in sources] + tabs))
+            else:
+                rows = pre[0]
+                affs, ctx.grads = multi_labels_call(specs, e_cs, sources, flags, tables, need_affs, rows, pre[1])
+        ctx.n = n
+        losses = [rows[j][0] for j in range(n)]
+        parts = [rows[j][1:1 + specs[j].K] for j in range(n)]
+        ctx.mark_non_differentiable(*(affs + parts))
+        return tuple(losses) + tuple(affs) + tuple(parts)
+
+    @staticmethod
+    def backward(ctx, *grads):
+        n = ctx.n
+        none = (None,) * 6 + (None,) * n
+        if ctx.grads is not None:
+            raise RuntimeError("MultiLabelsAffinityMSE with pre=(rows, dlosses) belongs to a caller that owns the backward")
+        live = [j for j in range(n) if grads[j] is not None and ctx.needs_input_grad[6 + j]]
+        if not live:
+            return none
+        if ctx.des is None:  # a second backward over a retained graph: the call once more on the saved inputs
+            saved = ctx.saved_tensors
+            specs, steps, flags = ctx.args
+            e_cs, labs = list(saved[:n]), saved[n:2 * n]
+            tables = [t if t.numel() else None for t in saved[2 * n:]] if ctx.n_tab else None
+            with _on_device(e_cs[0].device):
+                rows = torch.empty((n, 1 + max(sp.K for sp in specs)), dtype=torch.float32, device=e_cs[0].device).unbind(0)
+                _, ctx.des = multi_labels_call(specs, e_cs, list(zip(labs, steps)), flags, tables, False, rows, None)
+        des, ctx.des = ctx.des, None
+        out = [None] * n
+        with _on_device(des[0].device):
+            for j in live:  # (the buffers were written for grad_output = 1: rescaled in place, untouched where that is exactly 1)
+                de = des[j]
+                dl = grads[j].to(device=de.device, dtype=torch.float32).contiguous()
+                _lib.check(_lib.lib().pea_scale_inplace(_ptr(de), _lib.F32, de.numel(), _ptr(dl), _stream()), "pea_scale_inplace")
+                out[j] = de
+        return (None,) * 6 + tuple(out)
+
+
 class LabelsAffinityMSE(torch.autograd.Function):
     """loss, affs, per_offset_losses = f(e, e_other, labels): the training step straight from the label image
     (pea_label_weights + pea_affinity_fwd_bwd_labels): target / mask / weight are evaluated inside the kernel and

@@ -18,25 +18,15 @@
 // workgroup (the branch is uniform: a workgroup has one entry).
 // Loss partials: per offset a wave reduction and a fixed-order sum of the four waves, then loss_accumulate() into the entry's own
 // state block (integer adds: order-independent, exact); k_loss_finish_multi is k_loss_finish (pea_loss.h) with a workgroup per entry.
-#include <algorithm>
-
-#include "../../include/pea_multi.h"
-#include "pea_dispatch.h"
+#include "pea_multi_common.h"
 
 using namespace pea;
+using namespace pea::multi;
 
 namespace {
 
-constexpr int kMaxN = PEA_MULTI_MAX_N, kMaxK = PEA_MULTI_MAX_K;
 enum { kMaskNone = 0, kMaskU8 = 1, kMaskF32 = 2 };
 
-struct MGeom {  // what the bodies read of an entry's descriptor
-  int S, Z, Y, X, K, D, border;
-  int chunks;  // workgroups per batch item = ceil(S / kBlock)
-  int tile0;   // the entry's first tile in the launch's tile order
-  float eps;
-  int16_t off[kMaxK][3];
-};
 struct MFwdEntry {
   MGeom g;
   int mtype;     // kMask*
@@ -58,57 +48,8 @@ struct MBwdEntry {
   const float* dloss;
   float* de;
 };
-struct MFinEntry {
-  LossState* st;
-  float* loss_out;
-  int K, pad;
-  float inv_n[kMaxK], lam[kMaxK];
-};
-template <typename ENT>
-struct MTable {
-  int n, tiles, tiles_per_xcd, pad;
-  ENT en[kMaxN];
-};
-struct MFinTable {
-  MFinEntry en[kMaxN];
-};
 static_assert(sizeof(MTable<MFwdEntry>) <= 4096 - 64, "the forward's table must fit the kernel-argument segment");
-static_assert(sizeof(MTable<MBwdEntry>) <= 4096 - 64 && sizeof(MFinTable) <= 4096 - 64, "the tables must fit the kernel-argument segment");
-
-// neighbour of (z, y, x) displaced by o: flat index, or -1 (CROP_ZERO, outside).  neighbour() of pea_common.h with the border known
-template <int BORDER>
-__device__ __forceinline__ int neighbour_of(const MGeom& G, int z, int y, int x, int oz, int oy, int ox) {
-  int zz = z + oz, yy = y + oy, xx = x + ox;
-  if constexpr (BORDER == PEA_BORDER_CIRCULAR) {  // the host guarantees |o| < dim
-    zz += (zz < 0) ? G.Z : 0; zz -= (zz >= G.Z) ? G.Z : 0;
-    yy += (yy < 0) ? G.Y : 0; yy -= (yy >= G.Y) ? G.Y : 0;
-    xx += (xx < 0) ? G.X : 0; xx -= (xx >= G.X) ? G.X : 0;
-  } else if ((unsigned)zz >= (unsigned)G.Z || (unsigned)yy >= (unsigned)G.Y || (unsigned)xx >= (unsigned)G.X) {
-    return -1;
-  }
-  return (zz * G.Y + yy) * G.X + xx;
-}
-
-// the launch's tile of this workgroup (XCD-aware, as logical_tile) and the entry it belongs to; false: past the last tile
-template <typename ENT>
-__device__ __forceinline__ bool find_entry(const MTable<ENT>& T, int& idx, int& tile) {
-  const int t = ((int)blockIdx.x % kXcd) * T.tiles_per_xcd + (int)blockIdx.x / kXcd;
-  if (t >= T.tiles) return false;
-  idx = 0;
-  for (int i = 1; i < T.n; ++i)
-    if (t >= T.en[i].g.tile0) idx = i;
-  tile = t - T.en[idx].g.tile0;
-  return true;
-}
-
-// f(Int<v>{}) for the value a workgroup's entry has: SEL >= 0 when the whole table agrees on it, else a uniform branch over A, B(, C)
-template <int SEL, int A, int B, int C = B, typename F>
-__device__ __forceinline__ void with_value(int v, F&& f) {
-  if constexpr (SEL >= 0) f(Int<SEL>{});
-  else if (v == A) f(Int<A>{});
-  else if (C == B || v == B) f(Int<B>{});
-  else f(Int<C>{});
-}
+static_assert(sizeof(MTable<MBwdEntry>) <= 4096 - 64, "the tables must fit the kernel-argument segment");
 
 // ------------------------------------------------------------------------------------------------
 // forward: affs (nullable), g = d loss / d affs, the tile's loss partials
@@ -197,45 +138,6 @@ __global__ __launch_bounds__(kBlock) void k_fwd_multi(const MTable<MFwdEntry> T)
   });
 }
 
-// k_loss_finish (pea_loss.h) with one workgroup per entry: lane = 16 * j + s holds slot s of offset 4 * wave + j; reads the
-// accumulators, writes loss_out, puts the state back to zero.  A kernel boundary lies between the adds and these plain loads.
-__global__ __launch_bounds__(64 * ((kMaxK + 3) / 4)) void k_loss_finish_multi(const MFinTable T) {
-  __shared__ double s_l[kMaxK];
-  const MFinEntry& E = T.en[blockIdx.x];
-  LossState* __restrict__ st = E.st;
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, s = lane & (kLossSlots - 1), j = lane >> 4;
-  const bool good = st->magic == kLossMagic;
-  const int k = 4 * wave + j;
-  const bool on = k < E.K;
-  u64 v0 = 0, v1 = 0, v2 = 0;
-  unsigned fl = 0;
-  if (on) {
-    u64* a = st->acc[s][k];
-    v0 = a[0]; v1 = a[1]; v2 = a[2];
-    a[0] = 0; a[1] = 0; a[2] = 0;
-    if (s == 0) { fl = st->flags[k]; st->flags[k] = 0; }
-  }
-#pragma unroll
-  for (int o = 1; o < kLossSlots; o <<= 1) {
-    v0 += __shfl_xor(v0, o, 64);
-    v1 += __shfl_xor(v1, o, 64);
-    v2 += __shfl_xor(v2, o, 64);
-    fl |= __shfl_xor(fl, o, 64);
-  }
-  double Li = on ? loss_value(v0, v1, v2, fl) * (double)E.inv_n[on ? k : 0] : 0.0;
-  if (!good) Li = __builtin_nan("");  // the state block was never initialised (pea_workspace_init): say so
-  if (on && s == 0) {
-    E.loss_out[1 + k] = (float)Li;
-    s_l[k] = Li;
-  }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    double tot = 0.0;
-    for (int i = 0; i < E.K; ++i) tot += (double)E.lam[i] * s_l[i];
-    E.loss_out[0] = (float)tot;
-  }
-}
-
 // ------------------------------------------------------------------------------------------------
 // backward, gather form: G(p) = sum_i g_i(p) nhat(p + o_i) + g_i(p - o_i) nhat(p - o_i),
 //   de(p) = dloss * (G - ehat <ehat, G>) / n(p)        (G / eps when |e(p)| < eps)
@@ -310,87 +212,6 @@ __global__ __launch_bounds__(kBlock) void k_bwd_multi(const MTable<MBwdEntry> T)
   });
 }
 
-// ------------------------------------------------------------------------------------------------
-// host: the fused set, descriptor -> table entry
-// ------------------------------------------------------------------------------------------------
-bool fuses(const PeaDesc* d) {
-  if (d->dtype != PEA_F32 || (d->D != 16 && d->D != 32) || d->K > kMaxK) return false;
-  if (d->border != PEA_BORDER_CIRCULAR && d->border != PEA_BORDER_CROP_ZERO) return false;
-  if (d->flags & PEA_FLAG_LOSS_ACT) return false;
-  const long long S = (long long)d->dims[0] * d->dims[1] * d->dims[2];
-  if (S * std::max(d->D, d->K) > 0x7fffffffLL) return false;
-  for (int i = 0; i < d->K; ++i)
-    for (int a = 0; a < 3; ++a)
-      if (d->offsets[i][a] < -32768 || d->offsets[i][a] > 32767) return false;
-  return true;
-}
-
-MGeom make_geom(const PeaDesc* d) {
-  MGeom g;
-  memset(&g, 0, sizeof(g));
-  g.Z = d->dims[0]; g.Y = d->dims[1]; g.X = d->dims[2]; g.K = d->K; g.D = d->D;
-  g.S = g.Z * g.Y * g.X;
-  g.border = d->border; g.eps = d->eps;
-  g.chunks = (g.S + kBlock - 1) / kBlock;
-  for (int i = 0; i < d->K; ++i)
-    for (int a = 0; a < 3; ++a) g.off[i][a] = (int16_t)d->offsets[i][a];
-  return g;
-}
-
-// N_i of include/pea.h
-double normaliser(const PeaDesc* d, int i) {
-  if (d->norm == PEA_NORM_BX) return (double)d->B * d->dims[2];
-  if (d->norm == PEA_NORM_FULL) return (double)d->B * d->dims[0] * d->dims[1] * d->dims[2];
-  double n = d->B;
-  for (int a = 0; a < 3; ++a) n *= (double)(d->dims[a] - abs(d->offsets[i][a]));
-  return n;
-}
-
-// entry order of the launch: most tiles first (stable), so the tail of every XCD's range is the small images
-void tile_order(const PeaDesc* const* descs, int n, int* order) {
-  long long tiles[kMaxN];
-  for (int i = 0; i < n; ++i) {
-    const long long S = (long long)descs[i]->dims[0] * descs[i]->dims[1] * descs[i]->dims[2];
-    tiles[i] = (S + kBlock - 1) / kBlock * descs[i]->B;
-    order[i] = i;
-  }
-  std::stable_sort(order, order + n, [&](int a, int b) { return tiles[a] > tiles[b]; });
-}
-
-// the whole table: every descriptor valid and in the fused set, and the tiles of all entries fit one grid
-bool table_fuses(const PeaDesc* const* descs, int n) {
-  if (n < 1 || n > kMaxN || !descs) return false;
-  long long tiles = 0;
-  for (int i = 0; i < n; ++i) {
-    if (!descs[i] || pea_desc_validate(descs[i]) != PEA_OK || !fuses(descs[i])) return false;
-    const long long S = (long long)descs[i]->dims[0] * descs[i]->dims[1] * descs[i]->dims[2];
-    tiles += (S + kBlock - 1) / kBlock * descs[i]->B;  // (each term < 2^31: pea_desc_validate)
-  }
-  return tiles <= 0x7fffff00LL;
-}
-
-// tile0 of every entry (entries already in launch order, g.chunks set; B[i]: their batch sizes), the totals -> the grid
-template <typename ENT>
-dim3 place_tiles(MTable<ENT>& T, const int* B) {
-  int t0 = 0;
-  for (int i = 0; i < T.n; ++i) {
-    T.en[i].g.tile0 = t0;
-    t0 += B[i] * T.en[i].g.chunks;
-  }
-  T.tiles = t0;
-  T.tiles_per_xcd = (t0 + kXcd - 1) / kXcd;
-  return dim3((unsigned)(T.tiles_per_xcd * kXcd));
-}
-
-// the value all n entries share, or -1
-template <typename GET>
-int common(int n, GET&& get) {
-  const int v = get(0);
-  for (int i = 1; i < n; ++i)
-    if (get(i) != v) return -1;
-  return v;
-}
-
 }  // namespace
 
 extern "C" {
@@ -438,14 +259,8 @@ int pea_affinity_fwd_multi(const PeaMultiFwd* entries, int n, void* workspace, s
     E.mbs = d->mask_bstride ? d->mask_bstride : dense;
     E.e = (const float*)A.e; E.t = A.target; E.w = A.weight; E.m = A.mask; E.affs = A.affs; E.gout = A.g_out;
     E.st = states + i;
-    MFinEntry& Fe = F.en[i];
-    Fe.st = states + i; Fe.loss_out = A.loss_out; Fe.K = d->K;
-    for (int k = 0; k < d->K; ++k) {  // the values make_params (pea_abi.hip) gives the single calls
-      const double nk = normaliser(d, k);
-      E.gscale[k] = (float)(2.0 * (double)d->lambda[k] / nk);
-      Fe.inv_n[k] = (float)(1.0 / nk);
-      Fe.lam[k] = d->lambda[k];
-    }
+    fill_finish(F.en[i], d, states + i, A.loss_out);
+    for (int k = 0; k < d->K; ++k) E.gscale[k] = (float)(2.0 * (double)d->lambda[k] / normaliser(d, k));  // as make_params (pea_abi.hip)
   }
   const dim3 grid = place_tiles(T, B), blk(kBlock);
   hipStream_t s = (hipStream_t)stream;
@@ -464,7 +279,7 @@ int pea_affinity_fwd_multi(const PeaMultiFwd* entries, int n, void* workspace, s
   }
   int rc = hip_rc();
   if (!rc) {
-    hipLaunchKernelGGL(k_loss_finish_multi, dim3((unsigned)n), dim3(64 * ((kMaxK + 3) / 4)), 0, s, F);
+    launch_loss_finish_multi(F, n, s);
     rc = hip_rc();
   }
   if (rc) {  // (run_fwd of pea_abi.hip: the states must be zero between calls, and only the finish puts them back)

@@ -282,7 +282,7 @@ def _stash_again(ctx, cls, args):
         if isinstance(x, dict):
             return ("D", [(k, enc(v)) for k, v in x.items()])
         if isinstance(x, _LabelCfg):
-            return ("C", enc([x.labels, x.lflags, x.gen_flags, x.has_mask, x.tables]))
+            return ("C", enc([x.labels, x.lflags, x.gen_flags, x.has_mask, x.tables, x.steps, x.batched]))
         return ("V", x)
 
     ctx.again = (cls, enc(tuple(args)))
@@ -528,15 +528,22 @@ def ac3ac4_loss_section(embedding, emds, ema_embedding, target, weightmap, downs
     return loss, (finish_pred_3d_(pred.detach().clone()) if finish_pred else pred)
 
 
-def ac3ac4_loss_section_from_labels(embedding, emds, ema_embedding, labels, label_downs, criterion, embedding_mode=5, affs0_weight=1):
+def ac3ac4_loss_section_from_labels(embedding, emds, ema_embedding, labels, label_downs=None, criterion=None, embedding_mode=5,
+                                    affs0_weight=1, batched=False):
     """ac3ac4_loss_section from the segmentation: labels [B,Z,Y,X] and label_downs = (seg of down1, .., seg of down4) replace
-    target / weightmap / down1..4 (seg_to_aff(pad='') + weight_binary_ratio are evaluated inside the kernels)."""
+    target / weightmap / down1..4 (seg_to_aff(pad='') + weight_binary_ratio are evaluated inside the kernels).
+    label_downs=None: the four heads sample `labels` itself in-plane with the step Y / y, X / x (exact division, z unchanged: what the
+    provider's slice-wise nearest resize yields; ValueError otherwise).  batched=True: the four norm1 losses as ONE
+    pea_affinity_fwd_bwd_labels_multi call (include/pea_multi_labels.h) on the side stream, with or without label_downs."""
+    if criterion is None:
+        raise TypeError("ac3ac4_loss_section_from_labels() needs a criterion")
     if not getattr(criterion, 'pea_fused', False):
         raise NotImplementedError("the labels-in section fuses WeightedMSE")
     if ema_embedding.requires_grad:
         raise NotImplementedError("the EMA operand must be detached (convert_consistency_flip)")
     specs, weights = _specs_3d(embedding_mode, affs0_weight)
-    label_cfg = _LabelCfg([labels] + list(label_downs[::-1]), _lib.TGT_BOTH_FOREGROUND, _lib.TGT_BOTH_FOREGROUND, False, None)
+    label_cfg = _section_label_cfg(3, labels, None if label_downs is None else list(label_downs[::-1]), emds, batched,
+                                   _lib.TGT_BOTH_FOREGROUND, _lib.TGT_BOTH_FOREGROUND, False, None)
     loss, pred, _ = _LabelsSection.apply(specs, weights, ema_embedding, label_cfg, embedding, *emds)
     return loss, pred
 
@@ -608,10 +615,13 @@ def finish_pred_2d_(pred):
 class _LabelCfg(object):
     """what the labels-in section needs besides the embeddings: the label images (full resolution first), the target flags
     of the fused kernels / of pea_gen_targets (the fallback for scales smaller than a tile), whether a mask exists, and
-    optionally the class-balance tables computed ahead"""
+    optionally the class-balance tables computed ahead.  steps: None -- every scale has a label image of its own -- or per scale
+    the (sz, sy, sx) with which it samples its entry of `labels` (then usually the full-resolution image again).  batched: the
+    deep-supervision scales as ONE pea_affinity_fwd_bwd_labels_multi call (include/pea_multi_labels.h)"""
 
-    def __init__(self, labels, lflags, gen_flags, has_mask, tables):
+    def __init__(self, labels, lflags, gen_flags, has_mask, tables, steps=None, batched=False):
         self.labels, self.lflags, self.gen_flags, self.has_mask, self.tables = labels, lflags, gen_flags, has_mask, tables
+        self.steps, self.batched = steps, bool(batched)
 
 
 class _LabelsSection(torch.autograd.Function):
@@ -629,6 +639,7 @@ class _LabelsSection(torch.autograd.Function):
         L = _lib.lib()
         labels_list, lflags, gen_flags, has_mask = label_cfg.labels, label_cfg.lflags, label_cfg.gen_flags, label_cfg.has_mask
         tables = label_cfg.tables  # precomputed by *_label_weight_tables (off the critical path), or None
+        steps = label_cfg.steps
         ncall = len(specs)
         kmax = max(sp.K for sp in specs)
         with op._on_device(dev):
@@ -637,7 +648,8 @@ class _LabelsSection(torch.autograd.Function):
 
             def prep(j):
                 e_c = op._embedding_arg(embs[j], "embedding")
-                lab = op._labels_int32(labels_list[j])
+                lab = labels_list[j] if steps is None else op.materialise_labels(labels_list[j], e_c, specs[j].ndim, steps[j])
+                lab = op._labels_int32(lab)
                 d = op.make_desc(specs[j], e_c)
                 cb = L.pea_targets_workspace_bytes(ctypes.byref(d))
                 counts = torch.empty(max(cb, 4) // 4, dtype=torch.int32, device=dev)
@@ -696,11 +708,19 @@ class _LabelsSection(torch.autograd.Function):
             else:
                 _lib.check(rc, "pea_affinity_fwd_bwd_labels_dual")
             with fork:  # the deep-supervision scales, on their own stream beside the full-resolution pair (enqueued behind it: _side_stream)
-                for j in range(1, jx):
-                    e_c, lab, d, wtab, counts, cb = prep(j)
-                    de = torch.empty_like(e_c)
-                    one(j, e_c, None, lab, d, wtab, counts, cb, None, de, False)
-                    small.append(de)
+                batched = None
+                if label_cfg.batched:  # one count launch, one fused forward + backward launch, one loss finish for the four scales
+                    batched = _small_labels_batched(specs[1:jx], embs[1:jx], labels_list[1:jx], None if steps is None else steps[1:jx],
+                                                    lflags, None if tables is None else tables[1:jx], [rows[j] for j in range(1, jx)],
+                                                    [wdev[j:j + 1] for j in range(1, jx)])
+                if batched is not None:
+                    small = batched
+                else:
+                    for j in range(1, jx):
+                        e_c, lab, d, wtab, counts, cb = prep(j)
+                        de = torch.empty_like(e_c)
+                        one(j, e_c, None, lab, d, wtab, counts, cb, None, de, False)
+                        small.append(de)
             grads = [de0] + small
             fork.join()
             losses = rows[:, 0]
@@ -711,6 +731,34 @@ class _LabelsSection(torch.autograd.Function):
         return total, pred, losses
 
     backward = staticmethod(lambda ctx, dtotal, _dp, _dl: _section_backward(ctx, dtotal))
+
+
+def _small_labels_batched(specs, embs, labels, steps, lflags, tables, rows, dlosses):
+    """the deep-supervision self losses of a labels-in section as ONE pea_affinity_fwd_bwd_labels_multi call: loss rows into `rows`,
+    gradients weighted by the device scalars `dlosses` -> the gradients, or None where the table is outside the fused set (nothing
+    launched: the caller's loop runs)"""
+    e_cs = [op._embedding_arg(e, "embedding") for e in embs]
+    sources = op.label_sources(e_cs, specs[0].ndim, list(labels), steps)
+    try:
+        _, des = op.multi_labels_call(specs, e_cs, sources, lflags, tables, False, rows, dlosses)
+    except op.MultiLabelsUnsupported:
+        return None
+    return des
+
+
+def _section_label_cfg(ndim, labels, label_downs, emds, batched, lflags, gen_flags, has_mask, tables):
+    """the _LabelCfg of a labels-in section.  label_downs=None: the deep-supervision scales sample `labels` itself with the step
+    label size / embedding size (must divide exactly: there OpenCV's nearest rule is the plain stride; ValueError otherwise; 3D:
+    in-plane only) -- batched: inside the kernels; else the strided views are made contiguous here and the per-scale path runs."""
+    if label_downs is not None:
+        return _LabelCfg([labels] + list(label_downs), lflags, gen_flags, has_mask, tables, None, batched)
+    sources = op.label_sources(emds, ndim, labels, None)
+    if ndim == 3 and any(st[0] != 1 for _, st in sources):
+        raise ValueError("the deep-supervision scales of the 3D section keep the z extent of `labels`: pass label_downs for these shapes")
+    if batched:
+        return _LabelCfg([labels] * (1 + len(emds)), lflags, gen_flags, has_mask, tables, [(1, 1, 1)] + [st for _, st in sources], True)
+    downs = [op.materialise_labels(labels, e, ndim, st) for e, (_, st) in zip(emds, sources)]
+    return _LabelCfg([labels] + downs, lflags, gen_flags, has_mask, tables, None, False)
 
 
 _WEIGHT_CACHE = {}
@@ -726,15 +774,21 @@ def _weights_on(dev, weights):
     return t
 
 
-def cvppp_label_weight_tables(labels, label_downs, offsets, nb_half, dis_mode='ours'):
+def cvppp_label_weight_tables(labels, label_downs=None, offsets=None, nb_half=None, dis_mode='ours'):
     """The class-balance weight tables (weight_binary_ratio per image and channel, scripts_cvppp/data/data_segmentation.py:
     205-228) of the five scales, straight from the label images.  They depend on the labels only: call this as soon as the
     label batch is on the GPU -- e.g. before the backbone's forward -- and hand the result to
     cvppp_loss_section_from_labels(weight_tables=...), which then starts with the loss kernels instead of the count
-    reductions (33 us at full resolution on the critical path otherwise)."""
+    reductions (33 us at full resolution on the critical path otherwise).  label_downs=None: labels[:, ::2, ::2] .. [:, ::16, ::16]."""
+    if offsets is None or nb_half is None:
+        raise TypeError("cvppp_label_weight_tables() needs offsets and nb_half")
     specs, _ = _section_specs(offsets, nb_half, 1, dis_mode, 1, 1.0, 1.0)
     flags = _lib.TGT_PADDING | _lib.TGT_MASK_INSIDE
     L = _lib.lib()
+    if label_downs is None:  # the reference's fx = 1/2 .. 1/16 nearest resize: a plain stride where the size divides
+        if labels.shape[-2] % 16 or labels.shape[-1] % 16:
+            raise ValueError("label image %s is no multiple of 16: pass the four nearest-downsampled label_downs" % (tuple(labels.shape[1:]),))
+        label_downs = [labels[:, ::2 << j, ::2 << j].contiguous() for j in range(4)]
     tables = []
     for j, lab in enumerate([labels] + list(label_downs)):
         op._require_gpu(lab, "labels")
@@ -751,22 +805,29 @@ def cvppp_label_weight_tables(labels, label_downs, offsets, nb_half, dis_mode='o
     return tables
 
 
-def cvppp_loss_section_from_labels(embedding, emds, ema_embedding, labels, label_downs, criterion, offsets, nb_half,
+def cvppp_loss_section_from_labels(embedding, emds, ema_embedding, labels, label_downs=None, criterion=None, offsets=None, nb_half=None,
                                    affs0_weight=1, dis_mode='ours', deep_weight=1, self_emb=1.0, cross_emb=1.0, relu_pred=False,
-                                   weight_tables=None):
+                                   weight_tables=None, batched=False):
     """cvppp_loss_section without any target / weight / mask tensor: `labels` [B,H,W] and `label_downs` = the four
     nearest-downsampled label images (scripts_cvppp/data/data_provider.py:199-208) replace target, weightmap, affs_mask
     and down1..down4 (gen_affs_ours(padding=True) + weight_binary_ratio are evaluated inside the kernels).  The six
     losses run as one autograd node (_LabelsSection).  Returns (loss, pred, parts) like cvppp_loss_section; the entries
     of parts are the weighted per-loss values (device scalars, no gradient of their own).  relu_pred: as there.
-    weight_tables: the result of cvppp_label_weight_tables for this label batch, computed earlier in the step."""
+    weight_tables: the result of cvppp_label_weight_tables for this label batch, computed earlier in the step.
+    label_downs=None: the four scales sample `labels` itself with the step H / h, W / w, which must divide exactly -- there the
+    loader's cv2.resize(.., INTER_NEAREST) is the plain stride labels[:, ::s, ::s]; ValueError otherwise.
+    batched=True: the four deep-supervision losses as ONE pea_affinity_fwd_bwd_labels_multi call (include/pea_multi_labels.h: one
+    count launch, one fused forward + backward launch, one loss finish) on the side stream instead of four to five launches per scale,
+    with or without label_downs; where the library does not fuse the table the per-scale launches run as before."""
+    if criterion is None or offsets is None or nb_half is None:
+        raise TypeError("cvppp_loss_section_from_labels() needs criterion, offsets and nb_half")
     if not getattr(criterion, 'pea_fused', False):
         raise NotImplementedError("the labels-in section fuses WeightedMSE; use cvppp_loss_section for another criterion")
     if ema_embedding.requires_grad:
         raise NotImplementedError("the EMA operand must be detached (convert_consistency_flip)")
     specs, weights = _section_specs(offsets, nb_half, affs0_weight, dis_mode, deep_weight, self_emb, cross_emb)
     specs[0].relu = specs[-1].relu = bool(relu_pred)
-    label_cfg = _LabelCfg([labels] + list(label_downs), _lib.TGT_PADDING | _lib.TGT_MASK_INSIDE, _lib.TGT_PADDING, True,
-                          None if weight_tables is None else list(weight_tables))  # gen_affs_ours(padding=True) + its mask
+    label_cfg = _section_label_cfg(2, labels, label_downs, emds, batched, _lib.TGT_PADDING | _lib.TGT_MASK_INSIDE, _lib.TGT_PADDING, True,
+                                   None if weight_tables is None else list(weight_tables))  # gen_affs_ours(padding=True) + its mask
     loss, pred, losses = _LabelsSection.apply(specs, weights, ema_embedding, label_cfg, embedding, *emds)
     return loss, pred, _section_parts(losses, weights, self_emb, cross_emb)

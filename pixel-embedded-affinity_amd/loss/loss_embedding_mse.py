@@ -21,7 +21,8 @@ import torch
 
 from .. import _lib
 from ..affinity_op import (AffinityMap, activation_flags, AffinitySpec, FusedAffinityMSE, LabelsAffinityMSE, LabelsStepUnsupported, LossList,
-                           MultiAffinityMSE, MultiUnsupported, affinity_infer)
+                           MultiAffinityMSE, MultiLabelsAffinityMSE, MultiLabelsUnsupported, MultiUnsupported, affinity_infer, label_sources,
+                           materialise_labels)
 
 
 def _eps(mode):
@@ -130,3 +131,37 @@ def ema_embedding_loss_from_labels(embedding, ema_embedding, labels, criterion, 
     lam = [float(affs0_weight) if i < 2 else 1.0 for i in range(len(offsets))]
     loss, affs, _ = _from_labels(embedding, ema_embedding, labels, criterion, offsets, lam, mode, need_affs)
     return loss, affs
+
+
+def embedding_loss_from_labels_multi(embeddings, labels, criterion, offsets_list, label_steps=None, need_affs=False, weight_tables=None,
+                                     affs0_weight=1, mode='ours'):
+    """[embedding_loss_from_labels(embeddings[j], labels of scale j, criterion, offsets_list[j], need_affs=need_affs) for j] -> a list of
+    (loss, affs, all_loss) -- the four deep-supervision losses of scripts_cvppp/main.py:284-287 straight from label images -- as ONE
+    library call (include/pea_multi_labels.h: a count launch, one fused forward + backward launch, one loss finish).
+    labels: a list with one label tensor [B,h,w] per embedding, or ONE tensor [B,H,W] that every embedding samples with a step --
+    label_steps[j] (an int or (sy, sx)); None: H / h and W / w, which must divide exactly (ValueError otherwise).  Such a strided view
+    is what the reference's loader makes with cv2.resize(label, fx=1/2 .. 1/16, INTER_NEAREST), data_provider.py:200-203.
+    weight_tables: per embedding None or the [B,K,2] table of pea_label_weights for its (materialised) label image.
+    A table outside the fused set (bf16 / f16 embeddings, D other than 16 / 32, more than four losses or twelve offsets) and any
+    foreign criterion run the single calls on materialised label images -- embedding_loss_from_labels, or, for a foreign criterion
+    (which that call refuses), gen_targets + embedding_loss -- same results."""
+    n = len(embeddings)
+    if len(offsets_list) != n or (weight_tables is not None and len(weight_tables) != n):
+        raise ValueError("one offset list (and weight table) per embedding")
+    sources = label_sources(embeddings, 2, labels, label_steps)
+    if _fused(criterion):
+        specs = [_spec(offs, [1.0] * len(offs), mode) for offs in offsets_list]
+        try:
+            out = MultiLabelsAffinityMSE.apply(specs, sources, _FLAGS_2D, bool(need_affs), weight_tables, None, *embeddings)
+            return [(out[j], out[n + j], LossList(out[2 * n + j])) for j in range(n)]
+        except MultiLabelsUnsupported:
+            pass
+        return [embedding_loss_from_labels(e, materialise_labels(lab, e, 2, step), criterion, offs, affs0_weight=affs0_weight, mode=mode,
+                                           need_affs=need_affs)
+                for e, (lab, step), offs in zip(embeddings, sources, offsets_list)]
+    from ..utils.targets import gen_targets
+    out = []
+    for e, (lab, step), offs in zip(embeddings, sources, offsets_list):
+        t, m, w = gen_targets(materialise_labels(lab, e, 2, step), offs, padding=True)
+        out.append(embedding_loss(e, t, w, m, criterion, offs, affs0_weight=affs0_weight, mode=mode))
+    return out

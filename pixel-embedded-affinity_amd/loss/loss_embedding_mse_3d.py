@@ -13,7 +13,8 @@ Semantics kept from the reference (file:line there):
 
 from .. import _lib
 from ..affinity_op import (AffinityMap, AffinitySpec, FusedAffinityMSE, LabelsAffinityMSE, LabelsStepUnsupported, MultiAffinityMSE,
-                           MultiUnsupported, affinity_infer)
+                           MultiLabelsAffinityMSE, MultiLabelsUnsupported, MultiUnsupported, affinity_infer, label_sources,
+                           materialise_labels)
 from ..utils.affinity_ours import NORM5_SHIFTS, axis_offsets_3d
 
 
@@ -144,6 +145,32 @@ def _run_labels(embedding, ema_embedding, labels, criterion, shifts, affs0_weigh
 
 def embedding_loss_norm1_from_labels(embedding, labels, criterion, affs0_weight=1, shift=1):
     return _run_labels(embedding, None, labels, criterion, [shift] * 3, affs0_weight, 1)
+
+
+def embedding_loss_norm1_from_labels_multi(embeddings, labels, criterion, label_steps=None, affs0_weight=1, shift=1, need_affs=True,
+                                           weight_tables=None):
+    """[embedding_loss_norm1_from_labels(embeddings[j], segmentation of scale j, criterion, affs0_weight, shift) for j] -> a list of
+    (loss, affs) -- the four deep-supervision losses of scripts_ac3ac4/main.py:227-230 straight from the segmentation -- as ONE
+    library call (include/pea_multi_labels.h).  labels: one tensor [B,z,y,x] per embedding, or ONE tensor [B,Z,Y,X] every embedding
+    samples with a step -- label_steps[j]: an int (in-plane, z keeps 1: the reference downsamples slice by slice,
+    data_provider_labeled_deep.py:225-232) or (sz, sy, sx); None: label size / embedding size, which must divide exactly.
+    shift: one value, or one per embedding.  need_affs=False: the maps are not written (empty tensors come back).  Anything outside
+    the fused set runs the single calls on materialised label images."""
+    n = len(embeddings)
+    shifts = list(shift) if isinstance(shift, (list, tuple)) else [shift] * n
+    if len(shifts) != n or (weight_tables is not None and len(weight_tables) != n):
+        raise ValueError("one shift (and weight table) per embedding")
+    sources = label_sources(embeddings, 3, labels, label_steps)
+    if not getattr(criterion, 'pea_fused', False):
+        raise NotImplementedError("the labels-in step fuses WeightedMSE; for another criterion use gen_targets + the tensor API")
+    specs = [_spec([s] * 3, affs0_weight, 1) for s in shifts]
+    try:
+        out = MultiLabelsAffinityMSE.apply(specs, sources, _FLAGS_3D, bool(need_affs), weight_tables, None, *embeddings)
+        return [(out[j], out[n + j]) for j in range(n)]
+    except MultiLabelsUnsupported:
+        pass
+    return [embedding_loss_norm1_from_labels(e, materialise_labels(lab, e, 3, step), criterion, affs0_weight=affs0_weight, shift=s)
+            for e, (lab, step), s in zip(embeddings, sources, shifts)]
 
 
 def embedding_loss_norm5_from_labels(embedding, labels, criterion, affs0_weight=1):
