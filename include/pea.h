@@ -147,11 +147,21 @@ int pea_desc_validate(const PeaDesc *desc);
 
 /* The workspace of the training forward (pea_affinity_fwd / _fwd_ex / _fwd_bwd_labels): a STATE block of pea_workspace_bytes(desc)
  * bytes (the same ~16 KB for every descriptor; 8-byte aligned) into which the workgroups add their loss partials as 128-bit
- * fixed-point integers with integer atomics (csrc/pea_loss.h): the sum does not depend on the order of arrival, is exact, and
- * bit-reproducible.  Contract:
+ * fixed-point integers (LSB 2^-64) with integer atomics (csrc/pea_loss.h): the sum does not depend on the order of arrival and is
+ * bit-reproducible.  What it holds of each workgroup's f32 partial v of an offset (tests/test_gpu_loss_reduction.py):
+ *   - 2^-41 <= |v| < 2^60: v is added exactly.  More precisely the bits of v below 2^-64 are dropped toward zero (an f32 has 24 of
+ *     them), and a partial with |v| < 2^-64 counts as zero: weights scaled down until an offset's partials fall below 2^-64 give a
+ *     truncated and in the end a zero loss where a float sum would not;
+ *   - |v| >= 2^60, or v not finite, is not summed: it makes that offset's L_i +inf (v >= 2^60 or +inf), -inf (v <= -2^60 or -inf) or
+ *     NaN (v NaN, or both signs among the offset's partials; any NaN gives NaN), whatever the other partials hold, and the total
+ *     follows (lambda_i L_i summed in float64);
+ *   - negative weights are summed with their sign (two's complement): -W gives the loss of W negated, bit for bit;
+ *   - no rounding happens between the partials and the final float64, which is then rounded once to the f32 of loss_out.
+ * Contract:
  *   - call pea_workspace_init(workspace, bytes, stream) ONCE after allocating it (it may hold several states back to back:
  *     pea_affinity_fwd_bwd_labels_dual takes two);
- *   - every call leaves the block ready for the next one (it is zero between calls), so one block can serve every later call
+ *   - every call leaves the block ready for the next one (it is zero between calls: the finish clears the non-finite flags like
+ *     the digits, so an inf or NaN loss does not reach the next call), so one block can serve every later call
  *     ON THE SAME STREAM, of any descriptor; calls that may run concurrently (different streams) need a block each;
  *   - a block that was never initialised yields NaN losses (never a silently wrong number). */
 size_t pea_workspace_bytes(const PeaDesc *desc);

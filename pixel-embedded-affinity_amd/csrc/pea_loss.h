@@ -1,4 +1,4 @@
-// pea_loss.h -- the loss reduction: order-independent, exact, and off the critical path.
+// pea_loss.h -- the loss reduction: order-independent, exact inside a stated window, and off the critical path.
 //
 // L_i = sum_{b,p} w_i (a_i m_i - t_i m_i)^2 / N_i  (WeightedMSE, scripts_cvppp/loss/loss.py:106-124) is a sum over every pixel of
 // the batch; a forward kernel holds one f32 partial per (workgroup, offset).  Rounds 1-2 wrote those partials to a [K][ntiles]
@@ -9,7 +9,11 @@
 // partial is converted exactly to a 128-bit fixed-point number (LSB 2^-64) and its three digits (low 32 bits, middle 32 bits,
 // upper 64 bits, two's complement) are added to three u64 words.  Integer addition is associative and commutative, so the sum is
 // the same in every arrival order -- bit-reproducible like the fixed-order tree it replaces, and independent of the grid too --
-// and exact: no rounding happens between the f32 partial and the final f64.  A digit word takes 2^32 additions before it can wrap.
+// and exact for partials with 2^-41 <= |v| < 2^60: no rounding happens between the f32 partial and the final f64.  Outside that
+// window (include/pea.h states it; tests/test_gpu_loss_reduction.py pins it): the bits of v below 2^-64 are dropped toward zero and
+// |v| < 2^-64 counts as zero; |v| >= 2^60, an infinity or a NaN is not summed but remembered in flags[k], and the finish reports that
+// offset as +inf, -inf or NaN (both signs, or any NaN: NaN) and clears the flag like the digits.  Negative partials are added in
+// two's complement, so the sign is summed like everything else.  A digit word takes 2^32 additions before it can wrap.
 // The table is sharded kLossSlots ways by tile number so that no address sees more than ntiles / 16 adds.
 //
 // What is left for the end is 16 x K x 3 words: k_loss_finish, one launch of ONE wave, reads the table, writes loss_out and
@@ -41,7 +45,7 @@ static_assert(sizeof(LossState) % 64 == 0, "states are laid out back to back in 
 typedef unsigned long long u64;
 #define PEA_ATOM_ADD(p, v) (void)__hip_atomic_fetch_add((p), (v), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)
 
-// one workgroup's partial of offset k: st->acc[tile % 16][k] += v * 2^64 (exactly; |v| < 2^60, smaller than 2^-64 counts as 0)
+// one workgroup's partial of offset k: st->acc[tile % 16][k] += trunc(v * 2^64) (|v| < 2^60; exact from 2^-41 up, smaller than 2^-64 is 0)
 __device__ __forceinline__ void loss_accumulate(LossState* __restrict__ st, int tile, int k, float v) {
   const unsigned u = __builtin_bit_cast(unsigned, v);
   const int e = (int)((u >> 23) & 0xffu);
