@@ -35,7 +35,7 @@ from .harness.handoff import AffsCollector
 from .harness.head_loss import HeadAffinityMSE, head_embedding_loss
 from .harness.train_step import CvpppTrainStep, convert_consistency_flip, label_pyramid, make_optimizer
 from .model.unet2d_residual import ResidualUNet2D_deep
-from .model.head import EmbeddingHead, OutConv, head_conv3d_block
+from .model.head import EmbeddingHead, OutConv, head16_supported, head_conv3d_block
 from .harness.loss_section import (ac3ac4_loss_section, ac3ac4_loss_section_composed, ac3ac4_loss_section_from_labels,
                                    cvppp_loss_section, cvppp_loss_section_composed,
                                    cvppp_loss_section_from_labels, cvppp_label_weight_tables, cvppp_validation_section,
@@ -54,7 +54,7 @@ __all__ = [
     "loss_embedding", "loss_embedding_exp", "loss_embedding_norm", "embedding_loss_half_clamp", "ema_embedding_loss_half_clamp",
     "embedding2affs_half_clamp", "embedding_loss_clamp", "embedding2affs_clamp", "embedding_loss_normalized",
     "ema_embedding_loss_normalized", "embedding2affs_normalized",
-    "embedding_loss_norm6", "ema_embedding_loss_norm6", "EmbeddingHead", "OutConv", "head_conv3d_block", "cvppp_label_weight_tables", "cvppp_validation_section",
+    "embedding_loss_norm6", "ema_embedding_loss_norm6", "EmbeddingHead", "OutConv", "head_conv3d_block", "head16_supported", "cvppp_label_weight_tables", "cvppp_validation_section",
     "MultiAffinityMSE", "embedding_loss_multi", "embedding_loss_norm1_multi", "unflip", "convert_consistency_flip",
     "MultiLabelsAffinityMSE", "embedding_loss_from_labels_multi", "embedding_loss_norm1_from_labels_multi",
 ]

@@ -17,6 +17,7 @@ HEADER_INFER = os.path.join(HERE, "..", "include", "pea_infer.h")
 HEADER_MULTI = os.path.join(HERE, "..", "include", "pea_multi.h")
 HEADER_FLIP = os.path.join(HERE, "..", "include", "pea_flip.h")
 HEADER_MULTI_LABELS = os.path.join(HERE, "..", "include", "pea_multi_labels.h")
+HEADER_HEAD16 = os.path.join(HERE, "..", "include", "pea_head16.h")
 
 PEA_ABI_VERSION = 2
 PEA_MAX_K = 32
@@ -46,6 +47,8 @@ EXPORTS_MULTI = ("pea_multi_supported", "pea_affinity_fwd_multi", "pea_affinity_
 EXPORTS_FLIP = ("pea_consistency_unflip",)
 # the entry points of include/pea_multi_labels.h (up to four self losses per launch straight from label images)
 EXPORTS_MULTI_LABELS = ("pea_multi_labels_supported", "pea_multi_labels_scratch_bytes", "pea_affinity_fwd_bwd_labels_multi")
+# the entry points of include/pea_head16.h (the embedding head on f16 / bf16 features)
+EXPORTS_HEAD16 = ("pea_head_supported_t", "pea_head_fwd_t", "pea_head_bwd_t")
 
 
 class PeaLibraryError(RuntimeError):
@@ -107,7 +110,7 @@ def build(force=False, verbose=False, jobs=None):
 
 def _build_locked(force, verbose, jobs):
     srcs = sources()
-    hdrs = [HEADER, HEADER_INFER, HEADER_MULTI, HEADER_FLIP, HEADER_MULTI_LABELS] + [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".h")]
+    hdrs = [HEADER, HEADER_INFER, HEADER_MULTI, HEADER_FLIP, HEADER_MULTI_LABELS, HEADER_HEAD16] + [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".h")]
     newest_hdr = max(os.path.getmtime(h) for h in hdrs)
     if not force and os.path.exists(SO_PATH) and os.path.getmtime(SO_PATH) >= max([newest_hdr] + [os.path.getmtime(x) for x in srcs]):
         return SO_PATH
@@ -171,7 +174,7 @@ def lib():
         L = ctypes.CDLL(SO_PATH)
     except OSError as ex:
         raise PeaLibraryError("cannot load %s: %s" % (SO_PATH, ex))
-    for name in EXPORTS + EXPORTS_INFER + EXPORTS_MULTI + EXPORTS_FLIP + EXPORTS_MULTI_LABELS:
+    for name in EXPORTS + EXPORTS_INFER + EXPORTS_MULTI + EXPORTS_FLIP + EXPORTS_MULTI_LABELS + EXPORTS_HEAD16:
         if not hasattr(L, name):
             raise PeaLibraryError("%s does not export %s" % (SO_PATH, name))
     vp, dp = ctypes.c_void_p, ctypes.POINTER(PeaDesc)
@@ -259,6 +262,13 @@ def lib():
                                                     ctypes.c_size_t, vp]
     L.pea_consistency_unflip.restype = ctypes.c_int
     L.pea_consistency_unflip.argtypes = [ctypes.c_int] * 6 + [vp, vp, vp, ctypes.c_int, ctypes.c_int, vp]
+    L.pea_head_supported_t.restype = ctypes.c_int
+    L.pea_head_supported_t.argtypes = [ctypes.c_int] * 4
+    L.pea_head_fwd_t.restype = ctypes.c_int
+    L.pea_head_fwd_t.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_size_t, vp, ctypes.c_int, vp, vp, vp, ctypes.c_int, vp]
+    L.pea_head_bwd_t.restype = ctypes.c_int
+    L.pea_head_bwd_t.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_size_t, vp, ctypes.c_int, vp, vp, ctypes.c_int, vp, vp, vp, vp,
+                                 ctypes.c_size_t, vp]
     if L.pea_version() != PEA_ABI_VERSION:
         raise PeaLibraryError("ABI mismatch: library %d, binding %d" % (L.pea_version(), PEA_ABI_VERSION))
     _lib = L
