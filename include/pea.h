@@ -38,6 +38,24 @@
  *   N_i     = B * X                      (PEA_NORM_BX: the 2D WeightedMSE quirk, pred is [B,H,W])
  *           = B * prod(dims - |o_i|)     (PEA_NORM_CROPPED: 3D, pred is the cropped [B,1,Z',Y',X'])
  *           = B * Z * Y * X              (PEA_NORM_FULL)
+ *
+ * Non-finite embeddings (tests/test_nonfinite_host.py; tests/test_gpu_nonfinite.py holds the kernel families its header lists to
+ * this).  The formulas above are evaluated in IEEE arithmetic, as torch evaluates the reference's, so a NaN or +-inf in any channel of e(q) or e_other(q)
+ * reaches exactly the outputs whose formula reads that pixel and nothing else:
+ *   affs     a_i(p) is NaN exactly for the EXISTING pairs (p, p + o_i) that contain q -- existing as the border mode says: wrapped
+ *            (CIRCULAR), clamped (REPLICATE: a border q is the neighbour of every pixel the clamp folds onto it), or no pair
+ *            (CROP_ZERO).  Cropped-away positions stay exactly 0 (the activation of 0 where activation bits are set), also those
+ *            of q itself.  Every activation bit keeps NaN (F.relu and torch.clamp do; the kernels select, they do not call
+ *            fmaxf / fminf, which would answer 0).
+ *   loss, g  L_i and the total are NaN whenever offset i has such a pair, also where w = 0 or m = 0 there (0 * NaN); g_i is NaN on
+ *            those pairs.  The one exception: with PEA_FLAG_LOSS_ACT | PEA_FLAG_CLAMP01 g_i is 0 on them (the slope test u == v is
+ *            false for NaN, as in torch.clamp's backward); de at the neighbours of q is then unspecified (NaN or finite).
+ *   de       de / de_other are NaN in all D channels at every pixel whose formula reads a NaN g or the non-finite pixel itself; the
+ *            16-bit stores keep NaN (they never turn it into inf).
+ *   the rest every output element outside these sets is bit-identical to the same call on the finite embedding; the value of the
+ *            1 / norm plane at a non-finite pixel is unspecified; the state block is zero afterwards, as after any call.
+ * A NaN loss is therefore a reliable sign of a non-finite embedding, and the map shows where.  Not covered: a FINITE embedding whose
+ * squared norm overflows f32 -- the library and torch's f32 F.normalize both get |e| = inf and ehat = 0 there, silently.
  */
 #ifndef PEA_H_
 #define PEA_H_
@@ -287,7 +305,9 @@ int pea_weighted_sum(const float *rows, int stride, const float *w, int n, float
 /* Caller epilogue of the 3D path, in place on affs [B,K,Z,Y,X] (scripts_ac3ac4/main.py:233-237, 296-300;
  * scripts_ac3ac4/inference.py:160-164): pred[:,0,:s] = pred[:,0,s:2s] (z), pred[:,1,:,:s] = pred[:,1,:,s:2s] (y),
  * pred[:,2,:,:,:s] = pred[:,2,:,:,s:2s] (x) for s = shift (0 = skip), then F.relu when relu != 0.  Also the plain
- * F.relu(pred) of the 2D callers (scripts_cvppp/main.py:312) with shift = 0. */
+ * F.relu(pred) of the 2D callers (scripts_cvppp/main.py:312) with shift = 0.  relu keeps NaN, like F.relu.  The source slices must
+ * exist: PEA_E_DESC when shift > 0 and 2 * shift exceeds Z, or Y with K >= 2, or X with K >= 3 (a channel that is not there asks
+ * nothing of its axis: K = 1, Z = 4, Y = X = 3, shift = 2 is served). */
 int pea_fill_border_relu(float *affs, int B, int K, int Z, int Y, int X, int shift, int relu, void *stream);
 
 /* ---- the step feeding the path: label image -> target / mask / class-balance weight ----

@@ -199,7 +199,13 @@ __global__ __launch_bounds__(kBoxTH* kBoxTW, 4) void k_fwd_box(const KParams P, 
       w4 = __builtin_bit_cast(f4, __builtin_amdgcn_raw_buffer_load_b128(mkbuf(weight + (size_t)b * P.wbs + (size_t)k * S), vo, 0u, kAuxNT));
       if (has_m) m4 = __builtin_amdgcn_raw_buffer_load_b32(mkbuf(mask + (size_t)b * P.mbs + (size_t)k * S), vo == kOOB ? kOOB : vo >> 2, 0u, kAuxNT);
     }
-    const f4 a4 = *(const f4*)(sA + C.slot[k] * TP + l4);
+    f4 a4 = *(const f4*)(sA + C.slot[k] * TP + l4);
+    const int oz = P.off[k][0], oy = P.off[k][1], ox = P.off[k][2];
+    const bool rowok = !CROP || ((unsigned)(z + oz) < (unsigned)P.Z && (unsigned)(gy + oy) < (unsigned)P.Y);
+    if (CROP) {  // a cropped-away pair is exactly 0: its staged neighbour is 0, but 0 * e(p) is NaN for a non-finite own pixel
+#pragma unroll
+      for (int j = 0; j < 4; ++j) a4[j] = rowok && (unsigned)(gx + j + ox) < (unsigned)P.X ? a4[j] : 0.f;
+    }
     if (has_a) {
       f4 o = a4;
       if (af) { o.x = act_affs(o.x, af); o.y = act_affs(o.y, af); o.z = act_affs(o.z, af); o.w = act_affs(o.w, af); }
@@ -209,8 +215,6 @@ __global__ __launch_bounds__(kBoxTH* kBoxTW, 4) void k_fwd_box(const KParams P, 
       float acc = 0.f;
       f4 g4;
       const float gs = C.gs[k];
-      const int oz = P.off[k][0], oy = P.off[k][1], ox = P.off[k][2];
-      const bool rowok = !CROP || ((unsigned)(z + oz) < (unsigned)P.Z && (unsigned)(gy + oy) < (unsigned)P.Y);
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
         const float m = (float)((m4 >> (8 * j)) & 0xffu);

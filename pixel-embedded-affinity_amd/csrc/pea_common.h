@@ -85,24 +85,31 @@ __device__ __forceinline__ int neighbour(const KParams& P, int z, int y, int x, 
 
 // activation of the affs output (include/pea.h PEA_FLAG_*): flags are wave-uniform, the common case (0) is one scalar branch
 constexpr unsigned kActMask = PEA_FLAG_RELU_AFFS | PEA_FLAG_ONE_MINUS | PEA_FLAG_HALF_SHIFT | PEA_FLAG_CLAMP01;
+// relu and clamp as SELECTS, not fmaxf / fminf: C's fmaxf(NaN, 0) is 0, F.relu and torch.clamp keep NaN -- and a NaN affinity is the only
+// sign of a non-finite embedding that a caller gets (include/pea.h, "Non-finite embeddings").  Every comparison with NaN is false, so
+// NaN falls through; every other value compares equal to what fmaxf / fminf gave (-0.0 stays -0.0, as in torch).
+__device__ __forceinline__ float relu_keep_nan(float a) { return a < 0.f ? 0.f : a; }
+__device__ __forceinline__ float clamp_keep_nan(float v, float lo, float hi) { return v < lo ? lo : (v > hi ? hi : v); }
 __device__ __forceinline__ float act_affs(float a, unsigned af) {
   if (af == 0) return a;
   if (af & PEA_FLAG_HALF_SHIFT) a = (a + 1.0f) * 0.5f;
-  if (af & PEA_FLAG_RELU_AFFS) a = fmaxf(a, 0.f);
-  if (af & PEA_FLAG_CLAMP01) a = fminf(fmaxf(a, 0.f), 1.0f);
+  if (af & PEA_FLAG_RELU_AFFS) a = relu_keep_nan(a);
+  if (af & PEA_FLAG_CLAMP01) a = clamp_keep_nan(a, 0.f, 1.0f);
   if (af & PEA_FLAG_ONE_MINUS) a = 1.0f - a;
   return a;
 }
 
 // PEA_FLAG_LOSS_ACT (the LACT instantiations of the training forwards): the loss is taken on u = act_affs(a, af), af = HALF_SHIFT and /
 // or CLAMP01 (pea_desc_validate admits nothing else).  The flags are wave-uniform, so the activation is four scalars and no branch:
-//   v = a * sc + of,  u = min(max(v, lo), hi)      (sc, of) = (1/2, 1/2) for the half shift, (lo, hi) = (0, 1) for the clamp, else infinite
+//   v = a * sc + of,  u = v < lo ? lo : v > hi ? hi : v   (sc, of) = (1/2, 1/2) for the half shift, (lo, hi) = (0, 1) for the clamp, else infinite
 // -- the same bits act_affs stores ((a + 1) / 2 and a / 2 + 1/2 round alike: halving is exact) -- and the slope du / da is sc where the
 // clamp left v alone (u == v: torch.clamp's backward is INCLUSIVE at both edges), 0 where it did not.  The forward folds the slope
 // into g (act_g), so the backward kernels do not know about activations.  The epilogues keep v, not u, across their stores (u is two
-// instructions away from v; keeping both spilled in the 64-VGPR forwards).
+// instructions away from v; keeping both spilled in the 64-VGPR forwards).  A NaN v (a non-finite embedding) stays NaN in u, so the loss
+// is NaN; u == v is then false and g is `gz`: 0 with the clamp (what torch.clamp's backward gives at a NaN input), NaN without it (the
+// half shift alone has no branch: g = 2 w m r s / N is NaN like r).
 struct ActK {
-  float sc, of, lo, hi;
+  float sc, of, lo, hi, gz;
 };
 __device__ __forceinline__ ActK act_consts(unsigned af) {
   ActK k;
@@ -110,12 +117,13 @@ __device__ __forceinline__ ActK act_consts(unsigned af) {
   k.of = (af & PEA_FLAG_HALF_SHIFT) ? 0.5f : 0.f;
   k.lo = (af & PEA_FLAG_CLAMP01) ? 0.f : -__builtin_inff();
   k.hi = (af & PEA_FLAG_CLAMP01) ? 1.0f : __builtin_inff();
+  k.gz = (af & PEA_FLAG_CLAMP01) ? 0.f : __builtin_nanf("");
   return k;
 }
 __device__ __forceinline__ float act_v(float a, const ActK& k) { return fmaf(a, k.sc, k.of); }
-__device__ __forceinline__ float act_u(float v, const ActK& k) { return fminf(fmaxf(v, k.lo), k.hi); }
+__device__ __forceinline__ float act_u(float v, const ActK& k) { return clamp_keep_nan(v, k.lo, k.hi); }
 // g of a term whose raw-cosine form is gs_sc * wr * m, gs_sc = gscale * ActK::sc (exact: sc is a power of two)
-__device__ __forceinline__ float act_g(float u, float v, float gs_sc, float wr, float m) { return u == v ? gs_sc * wr * m : 0.f; }
+__device__ __forceinline__ float act_g(float u, float v, float gs_sc, float wr, float m, const ActK& k) { return u == v ? gs_sc * wr * m : k.gz; }
 
 __device__ __forceinline__ float inv_norm(float ss, float eps) { return 1.0f / fmaxf(sqrtf(ss), eps); }
 

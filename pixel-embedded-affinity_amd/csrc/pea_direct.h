@@ -97,7 +97,7 @@ __global__ __launch_bounds__(kBlock) void k_fwd_direct(const KParams P, const T*
           const float r = u * m - target[(size_t)b * P.tbs + in] * m;
           const float wr = weight[(size_t)b * P.wbs + in] * r;
           contrib = wr * r;
-          g = LACT ? act_g(u, v, gsc, wr, m) : P.gscale[i] * wr * m;
+          g = LACT ? act_g(u, v, gsc, wr, m, act_consts(P.flags & kActMask)) : P.gscale[i] * wr * m;
         }
         if (gout) gout[kb + in] = g;
       }

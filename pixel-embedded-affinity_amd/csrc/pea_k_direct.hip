@@ -211,10 +211,10 @@ __global__ __launch_bounds__(256) void k_relu_inplace(float* __restrict__ a, siz
   const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
   if (i < n4) {
     f4 v = ((f4*)a)[i];
-    v.x = fmaxf(v.x, 0.f); v.y = fmaxf(v.y, 0.f); v.z = fmaxf(v.z, 0.f); v.w = fmaxf(v.w, 0.f);
+    v.x = relu_keep_nan(v.x); v.y = relu_keep_nan(v.y); v.z = relu_keep_nan(v.z); v.w = relu_keep_nan(v.w);
     ((f4*)a)[i] = v;
   }
-  if (i < n - 4 * n4) a[4 * n4 + i] = fmaxf(a[4 * n4 + i], 0.f);
+  if (i < n - 4 * n4) a[4 * n4 + i] = relu_keep_nan(a[4 * n4 + i]);
 }
 
 __global__ __launch_bounds__(256) void k_fill_border_relu(float* __restrict__ affs, int B, int K, int Z, int Y, int X, int shift,
@@ -232,7 +232,7 @@ __global__ __launch_bounds__(256) void k_fill_border_relu(float* __restrict__ af
     if (a < shift) src = i + (size_t)shift * stride;  // pred[..., :shift] = pred[..., shift:2*shift]
   }
   float v = affs[src];
-  if (relu) v = fmaxf(v, 0.f);
+  if (relu) v = relu_keep_nan(v);
   if (src != i || relu) affs[i] = v;
 }
 
@@ -259,7 +259,7 @@ __global__ __launch_bounds__(256) void k_fill_border_relu_v4(float* __restrict__
     for (int j = 0; j < 4; ++j)
       if (x + j < shift) v[j] = affs[i + j + shift];
   }
-  v.x = fmaxf(v.x, 0.f); v.y = fmaxf(v.y, 0.f); v.z = fmaxf(v.z, 0.f); v.w = fmaxf(v.w, 0.f);
+  v.x = relu_keep_nan(v.x); v.y = relu_keep_nan(v.y); v.z = relu_keep_nan(v.z); v.w = relu_keep_nan(v.w);
   *(f4*)(affs + i) = v;
 }
 
@@ -278,7 +278,7 @@ __global__ __launch_bounds__(256) void k_fill_border_only(float* __restrict__ af
   const size_t dst = ((b * K + c) * Z + z) * (size_t)Y * X + (size_t)y * X + x;
   (void)S;
   float v = affs[dst + (size_t)shift * stride];
-  if (relu) v = fmaxf(v, 0.f);
+  if (relu) v = relu_keep_nan(v);
   affs[dst] = v;
 }
 
@@ -353,7 +353,8 @@ int pea_scale_inplace(void* buf, int dtype, size_t n, const float* scale, void* 
 int pea_fill_border_relu(float* affs, int B, int K, int Z, int Y, int X, int shift, int relu, void* stream) {
   if (!affs) return PEA_E_NULL;
   if (B < 1 || K < 1 || Z < 1 || Y < 1 || X < 1 || shift < 0) return PEA_E_DESC;
-  if (shift > 0 && K >= 3 && (2 * shift > Z || 2 * shift > Y || 2 * shift > X)) return PEA_E_DESC;
+  // channel c < min(K, 3) reads slices [shift, 2 * shift) of axis c: they must exist (a channel that is not there asks nothing of its axis)
+  if (shift > 0 && (2 * shift > Z || (K >= 2 && 2 * shift > Y) || (K >= 3 && 2 * shift > X))) return PEA_E_DESC;
   if (misaligned(affs, 4)) return PEA_E_ALIGN;
   const size_t n = (size_t)B * K * Z * Y * X, blocks = (n + 255) / 256;
   if (blocks > 0x7fffffffULL) return PEA_E_UNSUPPORTED;

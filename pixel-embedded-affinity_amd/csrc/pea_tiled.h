@@ -367,7 +367,7 @@ __device__ __forceinline__ void fwd_finish(const FwdU U, int K, float* s_part, c
   if (TRAIN) {
     const float r = u * m - t * m;
     const float wr = valid ? w * r : 0.f;
-    if (U.has_g) bs32(hi ? U.gB1 : U.gB, LACT ? act_g(u, v, e.gscale * AK.sc, wr, m) : e.gscale * wr * m, pb, so);
+    if (U.has_g) bs32(hi ? U.gB1 : U.gB, LACT ? act_g(u, v, e.gscale * AK.sc, wr, m, AK) : e.gscale * wr * m, pb, so);
     const float red = wave_sum63(wr * r);
     if ((threadIdx.x & 63) == 63) s_part[(threadIdx.x >> 6) * K + e.i] = red;
   }
@@ -756,7 +756,7 @@ __global__ __launch_bounds__(TH* TW, (D_T > 16 ? 2 : 4)) void k_fwd_tiled_v(cons
           const bool inz = (unsigned)(z + ioz[it]) < (unsigned)P.Z;
           wr = (inside && inz) ? wr : 0.f;
         }
-        g4[j] = LACT ? act_g(u, v4[j], en.gscale * AK.sc, wr, m) : en.gscale * wr * m;
+        g4[j] = LACT ? act_g(u, v4[j], en.gscale * AK.sc, wr, m, AK) : en.gscale * wr * m;
         acc = fmaf(wr, r, acc);
       }
       if (has_g) bs128<false>(gB, g4, ivo[it], so);

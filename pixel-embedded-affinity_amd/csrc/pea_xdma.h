@@ -71,7 +71,7 @@ struct XParams {
   int QV, QA;     // quads (4 x-adjacent pixels) in VF; in VF + strips.  Blocks of 64 quads go round the waves.
   int tiles_y, tiles_x, tiles_per_plane, ntiles, tiles_per_xcd;
   int npx, npy;
-  int xd[kXP], yd[kXP];    // pixel displacement of the neighbour along x / y  (0 for unused pairs)
+  int xd[kXP], yd[kXP];    // pixel displacement of the neighbour along x / y  (unused pairs: the first used one's, plan_xdma)
   int xm[kXP];             // strip coordinate mask of the x pair: d < 0 ? SW - 1 : TW - 1
   int xgi[kXP], ygi[kXP];  // g channel
   int xgo[kXP], ygo[kXP];  // role A: 0 (g at p); role B: -o (g at p - o)
@@ -465,14 +465,20 @@ __global__ __launch_bounds__(TH* TW, 4) void k_bwd_xdma(const KParams P, const X
   PEA_XG_DWORDS()
 #undef PEA_XG_DWORDS
   // z pairs: g and the neighbour's 1 / norm (another plane, same (y, x): scalar plane offsets); a pair whose plane does not
-  // exist gets the coefficient 0 and reads plane z itself
+  // exist, and a spare slot, gets the coefficient 0 and reads plane z itself: the lane's own pixel of the staged tensor.  In the
+  // role-A instantiation (OTHER) that is the second operand's pixel p, which de(p) does not read, and 0 * NaN would put a non-finite
+  // ema pixel into it (include/pea.h, "Non-finite embeddings"): there such a slot gathers at an out-of-range offset (zok) and reads 0.
+  // The self-loss instantiation keeps 0 * e(p): harmless ONLY because a non-finite e(p) puts de(p) inside the footprint anyway (its
+  // own projection reads e(p)).  That does not hold for any role whose staged tensor is not the differentiated one: do not copy it.
   float cz[ZP > 0 ? ZP : 1];
   unsigned zso[ZP > 0 ? ZP : 1];  // byte offset of the neighbour's plane (scalar)
+  bool zok[ZP > 0 ? ZP : 1];      // uniform
 #pragma unroll
   for (int k = 0; k < ZP; ++k) {
     bool okq, okg;
     const int zq = wrap1<CROP>(z + C.zd[k], P.Z, okq), zg = wrap1<CROP>(z + C.zgo[k], P.Z, okg);
     const bool ok = okq && okg && k < C.npz;
+    zok[k] = ok;
     zso[k] = (unsigned)(ok ? zq : z) * YX * 4u;
     const float gk = bl32(gB, pe, (unsigned)(ok ? zg : z) * YX * 4u + (unsigned)C.zgi[k] * ecs);
     const float iq = bl32(iB, pe, zso[k]);
@@ -516,8 +522,9 @@ __global__ __launch_bounds__(TH* TW, 4) void k_bwd_xdma(const KParams P, const X
 #define PEA_XZLOAD(ch)                                                                  \
   {                                                                                     \
     _Pragma("unroll") for (int k = 0; k < ZP; ++k) {                                    \
-      zv[(ch) & 1][k].x = bl32(xB, pe, zso[k] + (unsigned)(2 * (ch)) * ecs);            \
-      zv[(ch) & 1][k].y = bl32(xB, pe, zso[k] + (unsigned)(2 * (ch) + 1) * ecs);        \
+      const unsigned zpe = (!OTHER || zok[k]) ? pe : kOOB; /* self: e(p), see zok */   \
+      zv[(ch) & 1][k].x = bl32(xB, zpe, zso[k] + (unsigned)(2 * (ch)) * ecs);           \
+      zv[(ch) & 1][k].y = bl32(xB, zpe, zso[k] + (unsigned)(2 * (ch) + 1) * ecs);       \
     }                                                                                   \
   }
   PEA_XZLOAD(0)
@@ -1080,7 +1087,7 @@ __global__ __launch_bounds__(TH* TW, WPE) void k_fwd_xdma(const KParams P, const
           const int q = (ax_ == 1 ? igx[it] + j : ax_ == 0 ? igy[it] : z) + od_;
           wr = (unsigned)q < (unsigned)(ax_ == 1 ? P.X : ax_ == 0 ? P.Y : P.Z) ? wr : 0.f;
         }
-        g4[j] = LACT ? act_g(u, v4[j], gs * AK.sc, wr, m) : gs * wr * m;
+        g4[j] = LACT ? act_g(u, v4[j], gs * AK.sc, wr, m, AK) : gs * wr * m;
         acc = fmaf(wr, r, acc);
       }
       if (has_g) bs128<false>(gB, g4, ivo[it], so);
@@ -1155,6 +1162,17 @@ inline bool plan_xdma(const KParams& P, int TH, int TW, int psu, XParams* out, s
       C.yd[C.npy] = oy; C.ygi[C.npy] = i; C.ygo[C.npy] = 0; ++C.npy;
       if (!role_a) { C.yd[C.npy] = -oy; C.ygi[C.npy] = i; C.ygo[C.npy] = -oy; ++C.npy; }
     }
+  }
+  // The backward kernels walk all kXP slots of an axis; a slot beyond npx / npy has the coefficient 0 (its g load is out of range) and
+  // still multiplies the LDS value at its displacement.  Displacement 0 is the lane's own pixel of the STAGED tensor: in the role-A
+  // kernels that is the second operand's pixel p, which no formula of de(p) reads, and 0 * NaN = NaN would put a non-finite ema pixel
+  // into a gradient that must not see it (include/pea.h, "Non-finite embeddings").  So the spare slots repeat the first used slot's
+  // displacement: a neighbour that de(p) reads anyway.  (Finite data: + 0 * finite either way, the same bits.)  An axis without any
+  // offset has no such neighbour: those stencils stay with the tiled kernels.
+  if (role_a && (C.npx == 0 || C.npy == 0)) return false;
+  if (!fwd) {
+    for (int k = C.npx; k < kXP && C.npx > 0; ++k) C.xd[k] = C.xd[0];
+    for (int k = C.npy; k < kXP && C.npy > 0; ++k) C.yd[k] = C.yd[0];
   }
   const bool has_z = C.npz > 0 || C.nfz > 0;
   if (has_z && P.Z > 1) C.zrun = P.Z;

@@ -632,7 +632,7 @@ __global__ __launch_bounds__(TH* TW, WPE) void k_fwd_xdma_h(const KParams P, con
           const int q = (ax_ == 1 ? igx[it] + j : igy[it]) + od_;
           wr = (unsigned)q < (unsigned)(ax_ == 1 ? P.X : P.Y) ? wr : 0.f;
         }
-        g4[j] = LACT ? act_g(u, v4[j], gs * AK.sc, wr, m) : gs * wr * m;
+        g4[j] = LACT ? act_g(u, v4[j], gs * AK.sc, wr, m, AK) : gs * wr * m;
         acc = fmaf(wr, r, acc);
       }
       if (has_g) bs128<false>(gB, g4, ivo[it], so);

@@ -62,9 +62,13 @@ def cosine_loss(E, other, T, W, M, offsets3, lam, eps, border, norm, dloss=None,
         loss, parts, maps = 0.0, [], []
         for i, o in enumerate(offsets3):
             ys, ok = shifted(yn, o, border)
-            a = (xn * ys).sum(1) * ok
+            # selects, not "* ok": a pair that does not exist is 0 and has no gradient whatever the clamped index read (NaN * 0 is NaN)
+            ys = torch.where(ok, ys, torch.zeros_like(ys))
+            a = (xn * ys).sum(1)
+            a = torch.where(ok, a, torch.zeros_like(a))
             m = 1.0 if M is None else M[:, i].double()
-            r = (a * m - T[:, i].double() * m) * ok
+            r = a * m - T[:, i].double() * m
+            r = torch.where(ok, r, torch.zeros_like(r))
             Li = (W[:, i].double() * r * r).sum() / normaliser(norm, B, dims, o)
             loss = loss + float(lam[i]) * Li
             parts.append(Li.detach())

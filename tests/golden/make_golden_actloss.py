@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """Generate tests/golden/gal_*.npz: the reference's three loss modules that take the loss on the ACTIVATED affinity map, run as
-they are.
+they are; and tests/golden/gnf_2d.npz: the same modules and the raw-cosine one on an embedding with a NaN / an inf in it
+(`python tests/golden/make_golden_actloss.py nonfinite` writes that file alone).
 
 Run in the build container only (needs /root/reference; the GPU box has neither):
     python tests/golden/make_golden_actloss.py
@@ -125,7 +126,39 @@ def case(name, module, seed, B, D, H, W, ema=False, affs0_weight=1, mode=None, f
                                                            100.0 * near.sum() / near.size))
 
 
+def nonfinite_case(name="gnf_2d"):
+    """One NaN / one +inf channel value in a small embedding through embedding_loss of the raw-cosine module (loss_embedding_mse.py) and
+    of the two clamp modules: where the reference's map, loss and gradient are NaN (tests/test_nonfinite_host.py).  No edge rule is
+    needed: only NaN positions and the values away from them are compared, with the same module's clean run."""
+    rng = np.random.default_rng(31)
+    mods = dict(MODULES, loss_embedding_mse=load("ref_le_mse", "scripts_cvppp/loss/loss_embedding_mse.py"))
+    B, D, H, W = 2, 4, 6, 10
+    offsets = refaff.multi_offset([1, 3], neighbor=8)
+    e = rng.standard_normal((B, D, H, W)).astype(np.float32)
+    t, w, m = targets_2d(rng, B, H, W, offsets, cell=3, n=3)
+    out = dict(offsets=np.array(offsets, np.int32), e=e, target=t, weight=w, mask=m, q_nan=np.array([0, 2, 7], np.int32),
+               q_inf=np.array([0, 0, 0], np.int32), channel=np.int32(1))
+    for module in ("loss_embedding_mse", "loss_embedding", "loss_embedding_exp"):
+        for tag, val in (("clean", None), ("nan", np.nan), ("inf", np.inf)):
+            x = e.copy()
+            if val is not None:
+                q = out["q_" + tag]
+                x[0, 1, q[1], q[2]] = val
+            et = T(x).requires_grad_(True)
+            res = mods[module].embedding_loss(et, T(t), T(w), T(m), criterion, offsets)
+            res[0].backward()
+            out["loss_%s_%s" % (module, tag)] = np.float32(res[0].item())
+            out["affs_%s_%s" % (module, tag)] = res[1].detach().numpy()
+            out["grad_%s_%s" % (module, tag)] = et.grad.numpy()
+    path = os.path.join(OUT, name + ".npz")
+    np.savez_compressed(path, **{k: np.asarray(x) for k, x in out.items()})
+    print("%-24s %7.1f KB" % (name, os.path.getsize(path) / 1024))
+
+
 if __name__ == "__main__":
+    if sys.argv[1:] == ["nonfinite"]:  # the one fixture alone (the gal_* files are not rewritten)
+        nonfinite_case()
+        sys.exit(0)
     case("gal_emb_self", "loss_embedding", 11, 2, 16, 40, 72)
     case("gal_emb_ema_w", "loss_embedding", 12, 2, 16, 32, 48, ema=True, affs0_weight=0.5)
     case("gal_exp_self_w", "loss_embedding_exp", 13, 2, 16, 40, 72, affs0_weight=2.0)
@@ -135,3 +168,4 @@ if __name__ == "__main__":
     case("gal_norm_ema_cos", "loss_embedding_norm", 17, 2, 16, 32, 48, ema=True, mode="cos")
     case("gal_norm_ema_l2_w", "loss_embedding_norm", 18, 2, 16, 32, 48, ema=True, mode="l2", affs0_weight=0.25)
     case("gal_emb_self_fmask", "loss_embedding", 19, 2, 16, 40, 72, float_mask=True, affs0_weight=1.5)
+    nonfinite_case()
