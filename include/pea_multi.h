@@ -22,11 +22,18 @@
  *
  * The fused set.  pea_multi_supported(descs, n) == 1 exactly when
  *   - 1 <= n <= PEA_MULTI_MAX_N and every descriptor passes pea_desc_validate (so |offset| < the dimension it steps along),
- *   - dtype is PEA_F32, D is 16 or 32, K <= PEA_MULTI_MAX_K,
+ *   - dtype is PEA_F32, PEA_F16 or PEA_BF16 and THE SAME for all n entries (a table of f32 and 16-bit entries, or of f16 and bf16
+ *     ones, is outside the set: the launch is instantiated per storage type), D is 16 or 32, K <= PEA_MULTI_MAX_K,
  *   - the border is PEA_BORDER_CIRCULAR or PEA_BORDER_CROP_ZERO, PEA_FLAG_LOSS_ACT is not set,
  *   - S * max(D, K) per batch item (S = Z * Y * X) fits int32, as for the kernels of pea.h,
  *   - every offset component fits int16 (the table of the launch stores them so; no image of a deep-supervision scale is 32768 wide).
  * For any other table the two calls return PEA_E_UNSUPPORTED and the caller makes the n single calls.
+ *
+ * 16-bit storage (what the embedding heads emit under autocast: include/pea_head16.h).  e is read and de is written in the
+ * descriptor's dtype, one element per lane: e and de want the alignment of ONE element (2 bytes) and nothing of S, as pea.h
+ * states for every entry point.  Everything between the load and the store is the f32 arithmetic of the f32 table, in the same
+ * order: affs, g_out and loss_out carry the bits the f32 call gives on the upcast embedding, and de is that call's de rounded
+ * once to nearest even (NaN stays NaN).  target, weight, mask, affs, g_out, loss_out, dloss and the loss states stay f32.
  */
 #ifndef PEA_MULTI_H_
 #define PEA_MULTI_H_
@@ -42,7 +49,7 @@ extern "C" {
 
 typedef struct PeaMultiFwd { /* one self loss: the arguments of pea_affinity_fwd for it */
   const PeaDesc *desc;
-  const void *e;        /* [B, D, Z, Y, X] f32 */
+  const void *e;        /* [B, D, Z, Y, X] in desc->dtype (f32 / f16 / bf16) */
   const float *target;  /* [B, K, Z, Y, X], batch stride desc->target_bstride */
   const float *weight;  /* likewise, desc->weight_bstride */
   const uint8_t *mask;  /* NULL, u8, or f32 with PEA_FLAG_MASK_F32 (passed as for pea_affinity_fwd); desc->mask_bstride */
@@ -53,10 +60,10 @@ typedef struct PeaMultiFwd { /* one self loss: the arguments of pea_affinity_fwd
 
 typedef struct PeaMultiBwd { /* the arguments of pea_affinity_bwd for it */
   const PeaDesc *desc;
-  const void *e;       /* [B, D, Z, Y, X] f32 */
+  const void *e;       /* [B, D, Z, Y, X] in desc->dtype (f32 / f16 / bf16) */
   const float *g;      /* [B, K, Z, Y, X]: what the forward wrote to g_out, or any upstream gradient d criterion / d affs */
   const float *dloss;  /* device scalar or NULL = 1 */
-  void *de;            /* [B, D, Z, Y, X] f32 */
+  void *de;            /* [B, D, Z, Y, X] in desc->dtype, like e */
 } PeaMultiBwd;
 
 /* host-only: 1 when the table is in the fused set (above), else 0 (also for a NULL or invalid descriptor).  No GPU needed. */

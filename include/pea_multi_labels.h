@@ -27,13 +27,18 @@
  *
  * The fused set.  pea_multi_labels_supported(entries, n, flags) == 1 exactly when
  *   - 1 <= n <= PEA_MULTI_MAX_N and every descriptor passes pea_desc_validate,
- *   - dtype is PEA_F32, D is 16 or 32, K <= PEA_MULTI_MAX_K, the border is PEA_BORDER_CIRCULAR or PEA_BORDER_CROP_ZERO,
+ *   - dtype is PEA_F32, PEA_F16 or PEA_BF16 and THE SAME for all n entries (as in pea_multi.h: mixed tables are outside the set),
+ *     D is 16 or 32, K <= PEA_MULTI_MAX_K, the border is PEA_BORDER_CIRCULAR or PEA_BORDER_CROP_ZERO,
  *     neither PEA_FLAG_LOSS_ACT nor PEA_FLAG_MASK_F32 is set,
  *   - flags holds nothing but PEA_TGT_PADDING, PEA_TGT_BOTH_FOREGROUND, PEA_TGT_MASK_INSIDE,
  *   - every label_step >= 1 and (dims[a] - 1) * label_step[a] + 1 <= label_dims[a] on every axis (no sampled index leaves the image),
  *   - B * LZ * LY * LX and S * max(D, K) fit int32, every offset component fits int16,
  *   - the tiles (256 voxels) of all entries fit one grid.
  * For any other table the call returns PEA_E_UNSUPPORTED and the caller makes the n single calls on materialised label images.
+ *
+ * 16-bit storage: as in pea_multi.h.  e is read and de is written in the descriptor's dtype (element alignment: 2 bytes, any S);
+ * the arithmetic in between is that of the f32 table, so affs and loss_out carry the bits of the f32 call on the upcast embedding
+ * and de is that call's de rounded once to nearest even (NaN stays NaN).  labels, wtab, affs, loss_out and dloss keep their types.
  */
 #ifndef PEA_MULTI_LABELS_H_
 #define PEA_MULTI_LABELS_H_
@@ -46,7 +51,7 @@ extern "C" {
 
 typedef struct PeaMultiLabels { /* one self loss evaluated from labels */
   const PeaDesc *desc;          /* geometry of THIS scale, D, K, offsets, lambda, norm, eps, border, activation bits of affs */
-  const void *e;                /* [B, D, Z, Y, X] f32 */
+  const void *e;                /* [B, D, Z, Y, X] in desc->dtype (f32 / f16 / bf16) */
   const int32_t *labels;        /* [B, LZ, LY, LX] int32, dense */
   int32_t label_dims[3];        /* LZ, LY, LX */
   int32_t label_step[3];        /* label of voxel (z,y,x) of this scale = labels[b][z*sz][y*sy][x*sx]; {1,1,1}: an image of its own */
@@ -54,7 +59,7 @@ typedef struct PeaMultiLabels { /* one self loss evaluated from labels */
   float *affs;                  /* [B, K, Z, Y, X], nullable */
   float *loss_out;              /* [1 + K] */
   const float *dloss;           /* device scalar or NULL = 1 */
-  void *de;                     /* [B, D, Z, Y, X] f32 */
+  void *de;                     /* [B, D, Z, Y, X] in desc->dtype, like e */
 } PeaMultiLabels;
 
 /* host-only: 1 when the table is in the fused set (above), else 0 (also for NULL entries or a NULL / invalid descriptor).  No
@@ -71,9 +76,9 @@ size_t pea_multi_labels_scratch_bytes(const PeaMultiLabels *entries, int n);
  * looked at when at least one entry has wtab == NULL -- if every entry brings a table no count launch is made and scratch may be NULL.
  * Returns n < 1 or n > PEA_MULTI_MAX_N: PEA_E_DESC; PEA_E_NULL for missing entries; then per entry, in table order, the
  * descriptor's own code (PEA_E_NULL where it is missing; PEA_E_DESC also for PEA_FLAG_MASK_F32, as the labels-in calls of pea.h),
- * PEA_E_NULL (e, labels, loss_out or de missing), PEA_E_ALIGN (element alignment: 4 bytes); then PEA_E_ALIGN for `workspace`
- * (8 bytes) or `scratch` (4); PEA_E_WORKSPACE for a missing or short workspace or scratch; PEA_E_UNSUPPORTED where
- * pea_multi_labels_supported is 0.
+ * PEA_E_NULL (e, labels, loss_out or de missing), PEA_E_ALIGN (element alignment: 4 bytes, 2 for e / de of a 16-bit entry);
+ * then PEA_E_ALIGN for `workspace` (8 bytes) or `scratch` (4); PEA_E_WORKSPACE for a missing or short workspace or scratch;
+ * PEA_E_UNSUPPORTED where pea_multi_labels_supported is 0.
  * Two entries whose output buffers (affs, loss_out, de) overlap are the CALLER'S error, as in pea_multi.h. */
 int pea_affinity_fwd_bwd_labels_multi(const PeaMultiLabels *entries, int n, unsigned flags, void *workspace, size_t workspace_bytes,
                                       void *scratch, size_t scratch_bytes, void *stream);

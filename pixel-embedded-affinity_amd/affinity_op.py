@@ -373,8 +373,11 @@ class FusedAffinityMSE(torch.autograd.Function):
 
 
 class MultiUnsupported(NotImplementedError):
-    """the table of losses is outside the fused set of include/pea_multi.h (pea_multi_supported == 0): nothing was launched, the
-    *_multi wrappers and the sections make the single calls instead -- same results"""
+    """the table of losses is outside the fused set of include/pea_multi.h (pea_multi_supported == 0: D other than 16 / 32, more than
+    four losses or twelve offsets, a REPLICATE border, a loss on the activated map -- or embeddings of different dtypes: float32,
+    float16 and bfloat16 tables are all fused, a table that mixes them is not), or it is a 16-bit table too large for the batched
+    launch to pay (multi16_pays): nothing was launched, the *_multi wrappers and the sections make the single calls instead -- same
+    results"""
 
 
 _MULTI_OK = {}
@@ -395,8 +398,31 @@ def multi_supported(descs):
     return hit[0]
 
 
+# The tensor-form batched launches on 16-bit storage pay while the table is launch-sized.  Measured on an MI355X with bf16 embeddings
+# (profiles/multi16_ab.json, cvppp_loss_section, gain of batched=True in us per step): at B = 2, 772 tiles of 256 pixels, it wins
+# eager and ties graphed; at B = 8, 3088 tiles, it LOSES 40-60 us both ways -- there the call-by-call path runs the LDS-staged cross
+# kernels (k_fwd_xdma_h / k_bwd_xdma_h) and the scales are no longer launch-sized, while the gather body pays one 2-byte load per
+# lane and channel.  Nothing was measured in between, so the limit is the size up to which every workgroup of the launch is resident
+# at once and the launch is latency-bound like the measured 772: 256 CUs x 4 workgroups (k_bwd_multi needs up to 116 VGPRs: four
+# waves per SIMD, a workgroup puts one wave on each).  A 16-bit table above it is left to the single calls, so batched=True never
+# costs more than it did before the 16-bit kernels existed.  f32 tables are taken as before at every size.  The labels-in form is
+# not limited: at B = 8 it is as fast eager as the single calls on materialised label images which the same call ran before
+# (395-396 us against 398-464) and 3-5 us slower graphed (393-395 against 390), inside the 7-8 us spread of that leg.
+MULTI16_MAX_TILES = 1024
+
+
+def multi16_pays(descs):
+    """False for a table of 16-bit embeddings with more than MULTI16_MAX_TILES tiles (256 voxels of one batch item): op.MultiAffinityMSE
+    then raises MultiUnsupported and the wrappers / sections make the single calls, which were measured to be faster there"""
+    if descs[0].dtype == _lib.F32:
+        return True
+    tiles = sum(d.B * ((d.dims[0] * d.dims[1] * d.dims[2] + 255) // 256) for d in descs)
+    return tiles <= MULTI16_MAX_TILES
+
+
 def multi_backward(descs, e_cs, gs, dlosses):
-    """de_j = dloss_j * d loss_j / d e_j of n self losses as ONE launch (pea_affinity_bwd_multi); dlosses: device scalars (or None = 1)"""
+    """de_j = dloss_j * d loss_j / d e_j of n self losses as ONE launch (pea_affinity_bwd_multi); dlosses: device scalars (or None = 1).
+    de_j has the dtype of e_j (float32 / float16 / bfloat16, one for the whole table): a 16-bit de is the f32 result rounded once"""
     n = len(descs)
     des = [torch.empty_like(e_c) for e_c in e_cs]
     table = (_lib.PeaMultiBwd * n)()
@@ -423,6 +449,7 @@ class MultiAffinityMSE(torch.autograd.Function):
     the per-loss dloss -- or (rows, dlosses) for a caller that OWNS the weighting and the backward (the section nodes, which call
     forward() directly inside their own forward): n loss rows [1 + K] to write into and the n per-loss weights as device scalars;
     the backward launch is then enqueued right behind the forward and its gradients are left in ctx.grads.
+    Embeddings: float32, float16 or bfloat16, all n of ONE dtype; maps, loss rows and g stay float32, gradients take the embedding's dtype.
     Raises MultiUnsupported, before anything is launched, where the table is outside the fused set."""
 
     @staticmethod
@@ -446,6 +473,8 @@ class MultiAffinityMSE(torch.autograd.Function):
             twm.append((t, w, m, kshape))
         if not 1 <= n <= _lib.PEA_MULTI_MAX_N or not multi_supported(descs):
             raise MultiUnsupported("the table is outside the fused set of include/pea_multi.h")
+        if not multi16_pays(descs):
+            raise MultiUnsupported("a 16-bit table of more than %d tiles: the single calls are faster (multi16_pays)" % MULTI16_MAX_TILES)
         with _on_device(dev):
             if pre is None:
                 rows = torch.empty((n, 1 + max(sp.K for sp in specs)), dtype=torch.float32, device=dev).unbind(0)
@@ -780,7 +809,8 @@ _MULTI_LABELS_OK = {}
 
 def multi_labels_call(specs, e_cs, sources, flags, tables, need_affs, rows, dlosses):
     """ONE pea_affinity_fwd_bwd_labels_multi call (include/pea_multi_labels.h): loss rows into `rows`, de_j = dlosses[j] (device
-    scalars, or None = 1) * d loss_j / d e_j -> (affs list, de list).  Raises MultiLabelsUnsupported before anything is launched."""
+    scalars, or None = 1) * d loss_j / d e_j -> (affs list, de list; de_j in the dtype of e_j: float32 / float16 / bfloat16, one for
+    the whole table).  Raises MultiLabelsUnsupported before anything is launched."""
     n = len(e_cs)
     L = _lib.lib()
     dev = e_cs[0].device
@@ -897,7 +927,10 @@ class MultiLabelsAffinityMSE(torch.autograd.Function):
             for j in live:  # (the buffers were written for grad_output = 1: rescaled in place, untouched where that is exactly 1)
                 de = des[j]
                 dl = grads[j].to(device=de.device, dtype=torch.float32).contiguous()
-                _lib.check(_lib.lib().pea_scale_inplace(_ptr(de), _lib.F32, de.numel(), _ptr(dl), _stream()), "pea_scale_inplace")
+                # (a 16-bit de was rounded when it was stored: a grad_output that is no power of two rounds it a second time, as
+                #  LabelsAffinityMSE does -- within one ulp of the f32 product rounded once, tests/test_gpu_multi16.py)
+                _lib.check(_lib.lib().pea_scale_inplace(_ptr(de), _DTYPE_CODE[de.dtype], de.numel(), _ptr(dl), _stream()),
+                           "pea_scale_inplace")
                 out[j] = de
         return (None,) * 6 + tuple(out)
 

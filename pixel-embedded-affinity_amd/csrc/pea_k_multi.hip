@@ -16,6 +16,15 @@
 // The body is a template of D (16 / 32), the mask type (none / u8 / f32) and the border; a table whose entries agree on the three
 // (the four scales of one training loop do) takes the kernel instantiated for them, any other the kernel that branches per
 // workgroup (the branch is uniform: a workgroup has one entry).
+// Storage type T (float / __half / __bf16: what the embedding heads emit under autocast) is a template parameter too: e is loaded
+// through ld() and de stored through st() (one rounding to nearest even per stored 16-bit value, NaN kept; st_rounded keeps the
+// f32 result apart from the conversion), one element per lane, so nothing but the element's own alignment is asked of e / de / S.
+// Everything in between is f32 in the f32 order: affs, g and the loss carry the f32 kernel's bits on the upcast embedding.  All
+// entries of a table share T (table_fuses), so T never takes the per-workgroup branch: with_storage picks it on the host.
+// ALL common-D / mask / border specialisations are instantiated for the 16-bit types as well (3 x (13 + 5) kernels): the four
+// scales of a 16-bit training step agree on the three like the f32 ones and should not pay the branching kernel's registers
+// (86 against 50 VGPRs in the forward at D = 16).  Cost: this file compiles in 26 s instead of 8 s, pea_k_multi_labels.hip in
+// 11 s instead of 6 s; neither is the library's longest translation unit, a full parallel build took 189 s before and 180 s after.
 // Loss partials: per offset a wave reduction and a fixed-order sum of the four waves, then loss_accumulate() into the entry's own
 // state block (integer adds: order-independent, exact); k_loss_finish_multi is k_loss_finish (pea_loss.h) with a workgroup per entry.
 #include "pea_multi_common.h"
@@ -33,7 +42,7 @@ struct MFwdEntry {
   unsigned act;  // activation bits of the affs output
   float gscale[kMaxK];      // 2 * lambda_i / N_i
   long long tbs, wbs, mbs;  // batch strides (elements) of target / weight / mask
-  const float* e;
+  const void* e;  // [B, D, S] in the table's storage type
   const float* t;
   const float* w;
   const void* m;
@@ -43,10 +52,10 @@ struct MFwdEntry {
 };
 struct MBwdEntry {
   MGeom g;
-  const float* e;
+  const void* e;  // [B, D, S] in the table's storage type, and so is de
   const float* gin;
   const float* dloss;
-  float* de;
+  void* de;
 };
 static_assert(sizeof(MTable<MFwdEntry>) <= 4096 - 64, "the forward's table must fit the kernel-argument segment");
 static_assert(sizeof(MTable<MBwdEntry>) <= 4096 - 64, "the tables must fit the kernel-argument segment");
@@ -54,14 +63,14 @@ static_assert(sizeof(MTable<MBwdEntry>) <= 4096 - 64, "the tables must fit the k
 // ------------------------------------------------------------------------------------------------
 // forward: affs (nullable), g = d loss / d affs, the tile's loss partials
 // ------------------------------------------------------------------------------------------------
-template <int D, int MT, int BORDER>
+template <typename T, int D, int MT, int BORDER>
 __device__ __forceinline__ void fwd_body(const MFwdEntry& E, int tile, float (*s_part)[kBlock / 64]) {
   const MGeom& G = E.g;
   const int b = tile / G.chunks;
   const int p = (tile - b * G.chunks) * kBlock + (int)threadIdx.x;
   const bool live = p < G.S;
   const size_t S = (size_t)G.S;
-  const float* eb = E.e + (size_t)b * D * S;
+  const T* eb = (const T*)E.e + (size_t)b * D * S;
   const size_t kb = (size_t)b * G.K * S;
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
 
@@ -77,7 +86,7 @@ __device__ __forceinline__ void fwd_body(const MFwdEntry& E, int tile, float (*s
     float ss = 0.f;
 #pragma unroll
     for (int c = 0; c < D; ++c) {
-      ec[c] = eb[c * S + p];
+      ec[c] = ld(eb, c * S + p);
       ss = fmaf(ec[c], ec[c], ss);
     }
     inv_p = inv_norm(ss, G.eps);
@@ -92,7 +101,7 @@ __device__ __forceinline__ void fwd_body(const MFwdEntry& E, int tile, float (*s
         float dot = 0.f, sq = 0.f;
 #pragma unroll
         for (int c = 0; c < D; ++c) {
-          const float v = eb[c * S + q];
+          const float v = ld(eb, c * S + q);
           dot = fmaf(ec[c], v, dot);
           sq = fmaf(v, v, sq);
         }
@@ -123,16 +132,16 @@ __device__ __forceinline__ void fwd_body(const MFwdEntry& E, int tile, float (*s
 }
 
 // DS / MS / BS: the table's common D / mask type / border, or -1: read from the workgroup's entry
-template <int DS, int MS, int BS>
-__global__ __launch_bounds__(kBlock) void k_fwd_multi(const MTable<MFwdEntry> T) {
+template <typename T, int DS, int MS, int BS>
+__global__ __launch_bounds__(kBlock) void k_fwd_multi(const MTable<MFwdEntry> Tb) {
   __shared__ float s_part[kMaxK][kBlock / 64];
   int idx, tile;
-  if (!find_entry(T, idx, tile)) return;  // the whole workgroup together
-  const MFwdEntry& E = T.en[idx];
+  if (!find_entry(Tb, idx, tile)) return;  // the whole workgroup together
+  const MFwdEntry& E = Tb.en[idx];
   with_value<DS, 16, 32>(E.g.D, [&](auto d) {
     with_value<MS, kMaskNone, kMaskU8, kMaskF32>(E.mtype, [&](auto m) {
       with_value<BS, PEA_BORDER_CIRCULAR, PEA_BORDER_CROP_ZERO>(E.g.border, [&](auto bd) {
-        fwd_body<decltype(d)::value, decltype(m)::value, decltype(bd)::value>(E, tile, s_part);
+        fwd_body<T, decltype(d)::value, decltype(m)::value, decltype(bd)::value>(E, tile, s_part);
       });
     });
   });
@@ -142,14 +151,14 @@ __global__ __launch_bounds__(kBlock) void k_fwd_multi(const MTable<MFwdEntry> T)
 // backward, gather form: G(p) = sum_i g_i(p) nhat(p + o_i) + g_i(p - o_i) nhat(p - o_i),
 //   de(p) = dloss * (G - ehat <ehat, G>) / n(p)        (G / eps when |e(p)| < eps)
 // ------------------------------------------------------------------------------------------------
-template <int D, int BORDER>
+template <typename T, int D, int BORDER>
 __device__ __forceinline__ void bwd_body(const MBwdEntry& E, int tile) {
   const MGeom& Gm = E.g;
   const int b = tile / Gm.chunks;
   const int p = (tile - b * Gm.chunks) * kBlock + (int)threadIdx.x;
   if (p >= Gm.S) return;
   const size_t S = (size_t)Gm.S;
-  const float* xb = E.e + (size_t)b * D * S;
+  const T* xb = (const T*)E.e + (size_t)b * D * S;
   const float* gb = E.gin + (size_t)b * Gm.K * S;
   const float dl = E.dloss ? E.dloss[0] : 1.f;
 
@@ -163,7 +172,7 @@ __device__ __forceinline__ void bwd_body(const MBwdEntry& E, int tile) {
   float ss = 0.f;
 #pragma unroll
   for (int c = 0; c < D; ++c) {
-    xc[c] = xb[c * S + p];
+    xc[c] = ld(xb, c * S + p);
     ss = fmaf(xc[c], xc[c], ss);
     G[c] = 0.f;
   }
@@ -180,7 +189,7 @@ __device__ __forceinline__ void bwd_body(const MBwdEntry& E, int tile) {
       float v[D], sq = 0.f;
 #pragma unroll
       for (int c = 0; c < D; ++c) {
-        v[c] = xb[c * S + q];
+        v[c] = ld(xb, c * S + q);
         sq = fmaf(v[c], v[c], sq);
       }
       // the loss term lives at the first operand's pixel: p for role A, the neighbour for role B
@@ -194,20 +203,20 @@ __device__ __forceinline__ void bwd_body(const MBwdEntry& E, int tile) {
 #pragma unroll
   for (int c = 0; c < D; ++c) proj = fmaf(xc[c] * inv_p, G[c], proj);
   if (nrm < Gm.eps) proj = 0.f;  // clamp_min branch of F.normalize: d ehat / d e = I / eps
-  float* db = E.de + (size_t)b * D * S;
+  T* db = (T*)E.de + (size_t)b * D * S;
   const float sc = dl * inv_p;
 #pragma unroll
-  for (int c = 0; c < D; ++c) db[c * S + p] = (G[c] - xc[c] * inv_p * proj) * sc;
+  for (int c = 0; c < D; ++c) st_rounded(db, c * S + p, (G[c] - xc[c] * inv_p * proj) * sc);  // 16-bit: rounded once, NaN kept
 }
 
-template <int DS, int BS>
-__global__ __launch_bounds__(kBlock) void k_bwd_multi(const MTable<MBwdEntry> T) {
+template <typename T, int DS, int BS>
+__global__ __launch_bounds__(kBlock) void k_bwd_multi(const MTable<MBwdEntry> Tb) {
   int idx, tile;
-  if (!find_entry(T, idx, tile)) return;
-  const MBwdEntry& E = T.en[idx];
+  if (!find_entry(Tb, idx, tile)) return;
+  const MBwdEntry& E = Tb.en[idx];
   with_value<DS, 16, 32>(E.g.D, [&](auto d) {
     with_value<BS, PEA_BORDER_CIRCULAR, PEA_BORDER_CROP_ZERO>(E.g.border, [&](auto bd) {
-      bwd_body<decltype(d)::value, decltype(bd)::value>(E, tile);
+      bwd_body<T, decltype(d)::value, decltype(bd)::value>(E, tile);
     });
   });
 }
@@ -257,7 +266,7 @@ int pea_affinity_fwd_multi(const PeaMultiFwd* entries, int n, void* workspace, s
     E.tbs = d->target_bstride ? d->target_bstride : dense;
     E.wbs = d->weight_bstride ? d->weight_bstride : dense;
     E.mbs = d->mask_bstride ? d->mask_bstride : dense;
-    E.e = (const float*)A.e; E.t = A.target; E.w = A.weight; E.m = A.mask; E.affs = A.affs; E.gout = A.g_out;
+    E.e = A.e; E.t = A.target; E.w = A.weight; E.m = A.mask; E.affs = A.affs; E.gout = A.g_out;
     E.st = states + i;
     fill_finish(F.en[i], d, states + i, A.loss_out);
     for (int k = 0; k < d->K; ++k) E.gscale[k] = (float)(2.0 * (double)d->lambda[k] / normaliser(d, k));  // as make_params (pea_abi.hip)
@@ -266,17 +275,19 @@ int pea_affinity_fwd_multi(const PeaMultiFwd* entries, int n, void* workspace, s
   hipStream_t s = (hipStream_t)stream;
   const int cd = common(n, [&](int j) { return T.en[j].g.D; }), cm = common(n, [&](int j) { return T.en[j].mtype; }),
             cb = common(n, [&](int j) { return T.en[j].g.border; });
-  if (cd >= 0 && cm >= 0 && cb >= 0) {
-    with_width<16, 32>(cd, [&](auto dw) {
-      return with_width<kMaskNone, kMaskU8, kMaskF32>(cm, [&](auto mt) {
-        return with_width<PEA_BORDER_CIRCULAR, PEA_BORDER_CROP_ZERO>(cb, [&](auto bd) {
-          return launch<k_fwd_multi<decltype(dw)::value, decltype(mt)::value, decltype(bd)::value>>(grid, blk, 0, s, T);
+  with_storage(descs[0]->dtype, [&](auto tg) {  // (table_fuses: one storage type for the whole table)
+    using ST = typename decltype(tg)::type;
+    if (cd >= 0 && cm >= 0 && cb >= 0) {
+      return with_width<16, 32>(cd, [&](auto dw) {
+        return with_width<kMaskNone, kMaskU8, kMaskF32>(cm, [&](auto mt) {
+          return with_width<PEA_BORDER_CIRCULAR, PEA_BORDER_CROP_ZERO>(cb, [&](auto bd) {
+            return launch<k_fwd_multi<ST, decltype(dw)::value, decltype(mt)::value, decltype(bd)::value>>(grid, blk, 0, s, T);
+          });
         });
       });
-    });
-  } else {
-    launch<k_fwd_multi<-1, -1, -1>>(grid, blk, 0, s, T);
-  }
+    }
+    return launch<k_fwd_multi<ST, -1, -1, -1>>(grid, blk, 0, s, T);
+  });
   int rc = hip_rc();
   if (!rc) {
     launch_loss_finish_multi(F, n, s);
@@ -314,20 +325,22 @@ int pea_affinity_bwd_multi(const PeaMultiBwd* entries, int n, void* stream) {
     MBwdEntry& E = T.en[j];
     E.g = make_geom(A.desc);
     B[j] = A.desc->B;
-    E.e = (const float*)A.e; E.gin = A.g; E.dloss = A.dloss; E.de = (float*)A.de;
+    E.e = A.e; E.gin = A.g; E.dloss = A.dloss; E.de = A.de;
   }
   const dim3 grid = place_tiles(T, B), blk(kBlock);
   hipStream_t s = (hipStream_t)stream;
   const int cd = common(n, [&](int j) { return T.en[j].g.D; }), cb = common(n, [&](int j) { return T.en[j].g.border; });
-  if (cd >= 0 && cb >= 0) {
-    with_width<16, 32>(cd, [&](auto dw) {
-      return with_width<PEA_BORDER_CIRCULAR, PEA_BORDER_CROP_ZERO>(cb, [&](auto bd) {
-        return launch<k_bwd_multi<decltype(dw)::value, decltype(bd)::value>>(grid, blk, 0, s, T);
+  with_storage(descs[0]->dtype, [&](auto tg) {
+    using ST = typename decltype(tg)::type;
+    if (cd >= 0 && cb >= 0) {
+      return with_width<16, 32>(cd, [&](auto dw) {
+        return with_width<PEA_BORDER_CIRCULAR, PEA_BORDER_CROP_ZERO>(cb, [&](auto bd) {
+          return launch<k_bwd_multi<ST, decltype(dw)::value, decltype(bd)::value>>(grid, blk, 0, s, T);
+        });
       });
-    });
-  } else {
-    launch<k_bwd_multi<-1, -1>>(grid, blk, 0, s, T);
-  }
+    }
+    return launch<k_bwd_multi<ST, -1, -1>>(grid, blk, 0, s, T);
+  });
   return hip_rc();
 }
 

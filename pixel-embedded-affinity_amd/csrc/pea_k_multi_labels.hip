@@ -21,12 +21,16 @@
 // (pea_fused_labels.h) -- the same bits pea_label_weights writes.
 // Label reads with a step are uncoalesced (a wave's 64 labels of one row span 64 * sx * 4 bytes); the label images are 1.2 MB per
 // sample (544^2 int32) and L2-resident, every one of their cache lines is used by some scale, so they are not staged through LDS.
-// The body is a template of D and the border; the three target flags are uniform scalars of the launch (they live in SGPRs:
-// templating on them as well would multiply the instantiations by eight without freeing a vector register).  A table whose entries disagree on
-// D or the border takes <-1, -1>, which branches per workgroup (uniform: a workgroup has one entry).
+// The body is a template of the storage type T (float / __half / __bf16: ld() / st_rounded() around the unchanged f32 arithmetic,
+// one element per lane, one storage type per table chosen on the host -- as pea_k_multi.hip says, which also states the build cost
+// of instantiating every specialisation for the 16-bit types: 3 x 5 kernels here), of D and of the border; the three target flags
+// are uniform scalars of the launch (they live in SGPRs: templating on them as well would multiply the instantiations by eight
+// without freeing a vector register).  A table whose entries disagree on D or the border takes <-1, -1>, which branches per
+// workgroup (uniform: a workgroup has one entry).
 // Resources (hipcc -O3 --offload-arch=gfx950, -Rpass-analysis=kernel-resource-usage); no form spills to scratch (ScratchSize 0,
 // no SGPR / VGPR spill), LDS 288 bytes (loss partials + the image's table), 48 bytes in the count kernel:
-//   k_fwd_bwd_labels_multi<16, CIRCULAR> 84 VGPRs   <16, CROP_ZERO> 84   <32, CIRCULAR> 131   <32, CROP_ZERO> 131   <-1, -1> 130
+//   k_fwd_bwd_labels_multi<float, 16, CIRCULAR> 84 VGPRs   <16, CROP_ZERO> 84   <32, CIRCULAR> 131   <32, CROP_ZERO> 131   <-1, -1> 130
+//   <__half, ..> 84 / 81 / 131 / 131 / 130   <__bf16, ..> 83 / 79 / 131 / 129 / 130
 //   k_count_multi 11 VGPRs
 #include "../../include/pea_multi_labels.h"
 #include "pea_multi_common.h"
@@ -48,13 +52,13 @@ struct MLabEntry {
   unsigned act;          // activation bits of the affs output
   int pad;
   float gscale[kMaxK];   // 2 * lambda_i / N_i
-  const float* e;
+  const void* e;         // [B, D, S] in the table's storage type, and so is de
   const int32_t* lab;
   const float* wtab;     // the caller's table, or NULL: evaluated from cnt
   unsigned* cnt;         // [B, K] counts of this entry in the scratch (written by k_count_multi), or NULL
   float* affs;
   const float* dloss;
-  float* de;
+  void* de;
   LossState* st;
 };
 struct MCntEntry {
@@ -119,14 +123,14 @@ __global__ __launch_bounds__(kBlock) void k_count_multi(const MTable<MCntEntry> 
 // ------------------------------------------------------------------------------------------------
 // forward + backward
 // ------------------------------------------------------------------------------------------------
-template <int D, int BORDER>
+template <typename T, int D, int BORDER>
 __device__ __forceinline__ void lab_body(const MLabEntry& E, int tile, unsigned lflags, float (*s_part)[kBlock / 64], float (*s_w)[2]) {
   const MGeom& Gm = E.g;
   const int b = tile / Gm.chunks;
   const int p = (tile - b * Gm.chunks) * kBlock + (int)threadIdx.x;
   const bool live = p < Gm.S;
   const size_t S = (size_t)Gm.S;
-  const float* xb = E.e + (size_t)b * D * S;
+  const T* xb = (const T*)E.e + (size_t)b * D * S;
   const int32_t* lb = E.lab + (size_t)b * E.l.bs;
   float* ab = E.affs ? E.affs + (size_t)b * Gm.K * S : nullptr;
   const bool pad = lflags & PEA_TGT_PADDING, fg = lflags & PEA_TGT_BOTH_FOREGROUND, msk = lflags & PEA_TGT_MASK_INSIDE;
@@ -161,7 +165,7 @@ __device__ __forceinline__ void lab_body(const MLabEntry& E, int tile, unsigned 
     float ss = 0.f;
 #pragma unroll
     for (int c = 0; c < D; ++c) {
-      xc[c] = xb[c * S + p];
+      xc[c] = ld(xb, c * S + p);
       ss = fmaf(xc[c], xc[c], ss);
     }
     nrm = sqrtf(ss);
@@ -192,7 +196,7 @@ __device__ __forceinline__ void lab_body(const MLabEntry& E, int tile, unsigned 
           float v[D], sq = 0.f, dot = 0.f;
 #pragma unroll
           for (int c = 0; c < D; ++c) {
-            v[c] = xb[c * S + q];
+            v[c] = ld(xb, c * S + q);
             // (role B: the term lives at q, whose forward multiplies e(q)[c] * e(p)[c] -- the product commutes, the sum's order is c)
             dot = fmaf(xc[c], v[c], dot);
             sq = fmaf(v[c], v[c], sq);
@@ -219,10 +223,10 @@ __device__ __forceinline__ void lab_body(const MLabEntry& E, int tile, unsigned 
 #pragma unroll
     for (int c = 0; c < D; ++c) proj = fmaf(xc[c] * inv_p, G[c], proj);
     if (nrm < Gm.eps) proj = 0.f;  // clamp_min branch of F.normalize: d ehat / d e = I / eps
-    float* db = E.de + (size_t)b * D * S;
+    T* db = (T*)E.de + (size_t)b * D * S;
     const float sc = dl * inv_p;
 #pragma unroll
-    for (int c = 0; c < D; ++c) db[c * S + p] = (G[c] - xc[c] * inv_p * proj) * sc;
+    for (int c = 0; c < D; ++c) st_rounded(db, c * S + p, (G[c] - xc[c] * inv_p * proj) * sc);  // 16-bit: rounded once, NaN kept
   }
   __syncthreads();
   if ((int)threadIdx.x < Gm.K) {
@@ -232,16 +236,16 @@ __device__ __forceinline__ void lab_body(const MLabEntry& E, int tile, unsigned 
 }
 
 // DS / BS: the table's common D / border, or -1: read from the workgroup's entry
-template <int DS, int BS>
-__global__ __launch_bounds__(kBlock) void k_fwd_bwd_labels_multi(const MTable<MLabEntry> T, const unsigned lflags) {
+template <typename T, int DS, int BS>
+__global__ __launch_bounds__(kBlock) void k_fwd_bwd_labels_multi(const MTable<MLabEntry> Tb, const unsigned lflags) {
   __shared__ float s_part[kMaxK][kBlock / 64];
   __shared__ float s_w[kMaxK][2];
   int idx, tile;
-  if (!find_entry(T, idx, tile)) return;  // the whole workgroup together
-  const MLabEntry& E = T.en[idx];
+  if (!find_entry(Tb, idx, tile)) return;  // the whole workgroup together
+  const MLabEntry& E = Tb.en[idx];
   with_value<DS, 16, 32>(E.g.D, [&](auto d) {
     with_value<BS, PEA_BORDER_CIRCULAR, PEA_BORDER_CROP_ZERO>(E.g.border, [&](auto bd) {
-      lab_body<decltype(d)::value, decltype(bd)::value>(E, tile, lflags, s_part, s_w);
+      lab_body<T, decltype(d)::value, decltype(bd)::value>(E, tile, lflags, s_part, s_w);
     });
   });
 }
@@ -345,7 +349,7 @@ int pea_affinity_fwd_bwd_labels_multi(const PeaMultiLabels* entries, int n, unsi
     E.l = make_lab_geom(A);
     B[j] = d->B;
     E.act = d->flags & kActMask;
-    E.e = (const float*)A.e; E.lab = A.labels; E.wtab = A.wtab; E.affs = A.affs; E.dloss = A.dloss; E.de = (float*)A.de;
+    E.e = A.e; E.lab = A.labels; E.wtab = A.wtab; E.affs = A.affs; E.dloss = A.dloss; E.de = A.de;
     E.cnt = A.wtab ? nullptr : (unsigned*)scratch + cnt0[i];
     E.st = states + i;
     for (int k = 0; k < d->K; ++k) E.gscale[k] = (float)(2.0 * (double)d->lambda[k] / normaliser(d, k));  // as make_params (pea_abi.hip)
@@ -372,15 +376,17 @@ int pea_affinity_fwd_bwd_labels_multi(const PeaMultiLabels* entries, int n, unsi
   }
   const dim3 grid = place_tiles(T, B);
   const int cd = common(n, [&](int j) { return T.en[j].g.D; }), cb = common(n, [&](int j) { return T.en[j].g.border; });
-  if (cd >= 0 && cb >= 0) {
-    with_width<16, 32>(cd, [&](auto dw) {
-      return with_width<PEA_BORDER_CIRCULAR, PEA_BORDER_CROP_ZERO>(cb, [&](auto bd) {
-        return launch<k_fwd_bwd_labels_multi<decltype(dw)::value, decltype(bd)::value>>(grid, blk, 0, s, T, flags);
+  with_storage(descs[0]->dtype, [&](auto tg) {  // (table_fuses: one storage type for the whole table)
+    using ST = typename decltype(tg)::type;
+    if (cd >= 0 && cb >= 0) {
+      return with_width<16, 32>(cd, [&](auto dw) {
+        return with_width<PEA_BORDER_CIRCULAR, PEA_BORDER_CROP_ZERO>(cb, [&](auto bd) {
+          return launch<k_fwd_bwd_labels_multi<ST, decltype(dw)::value, decltype(bd)::value>>(grid, blk, 0, s, T, flags);
+        });
       });
-    });
-  } else {
-    launch<k_fwd_bwd_labels_multi<-1, -1>>(grid, blk, 0, s, T, flags);
-  }
+    }
+    return launch<k_fwd_bwd_labels_multi<ST, -1, -1>>(grid, blk, 0, s, T, flags);
+  });
   rc = hip_rc();
   if (!rc) {
     launch_loss_finish_multi(F, n, s);

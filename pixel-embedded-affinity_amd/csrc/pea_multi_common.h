@@ -1,7 +1,7 @@
 // pea_multi_common.h -- what the batched launches share (pea_k_multi.hip: the tensor form, include/pea_multi.h;
 // pea_k_multi_labels.hip: the labels-in form, include/pea_multi_labels.h): the per-entry geometry of the launch table, the walk from
 // a workgroup to (entry, tile), the uniform branch over an entry's D / border, the loss finish with a workgroup per entry, and the
-// host side that fills them (fused set, tile order, tile placement).
+// host side that fills them (fused set -- any of the three storage types, one per table --, tile order, tile placement).
 //
 // The table of a launch travels BY VALUE in the kernel arguments: no device-side table and no copy from host memory on the stream,
 // so the calls can be captured into a HIP graph.  A workgroup serves one tile (256 consecutive pixels of one batch item) of one entry
@@ -68,6 +68,16 @@ __device__ __forceinline__ bool find_entry(const MTable<ENT>& T, int& idx, int& 
   return true;
 }
 
+// st() of a value that exists as f32 BEFORE it is rounded to the storage type (the contract of include/pea.h: de16 = round(de32)).
+// Left alone the compiler folds the last multiply and the f16 conversion into one v_fma_mixlo_f16: a single rounding of the exact
+// product, one f16 ulp away from the rounded f32 result in a few of 100 000 values.  Only __half has such an instruction: the
+// f32 and the bf16 stores (a plain v_cvt_pk_bf16_f32 of the finished product) are left to the compiler.
+template <typename T>
+__device__ __forceinline__ void st_rounded(T* p, size_t i, float v) {
+  if constexpr (std::is_same<T, __half>::value) asm volatile("" : "+v"(v));
+  st(p, i, v);
+}
+
 // f(Int<v>{}) for the value a workgroup's entry has: SEL >= 0 when the whole table agrees on it, else a uniform branch over A, B(, C)
 template <int SEL, int A, int B, int C = B, typename F>
 __device__ __forceinline__ void with_value(int v, F&& f) {
@@ -123,8 +133,8 @@ inline void launch_loss_finish_multi(const MFinTable& F, int n, hipStream_t s) {
 // ------------------------------------------------------------------------------------------------
 // host: the fused set, descriptor -> table entry
 // ------------------------------------------------------------------------------------------------
-inline bool fuses(const PeaDesc* d) {
-  if (d->dtype != PEA_F32 || (d->D != 16 && d->D != 32) || d->K > kMaxK) return false;
+inline bool fuses(const PeaDesc* d) {  // (any of the three storage types: pea_desc_validate admits no other)
+  if ((d->D != 16 && d->D != 32) || d->K > kMaxK) return false;
   if (d->border != PEA_BORDER_CIRCULAR && d->border != PEA_BORDER_CROP_ZERO) return false;
   if (d->flags & PEA_FLAG_LOSS_ACT) return false;
   const long long S = (long long)d->dims[0] * d->dims[1] * d->dims[2];
@@ -176,12 +186,15 @@ inline void tile_order(const PeaDesc* const* descs, int n, int* order) {
   std::stable_sort(order, order + n, [&](int a, int b) { return tiles[a] > tiles[b]; });
 }
 
-// the whole table: every descriptor valid and in the fused set, and the tiles of all entries fit one grid
+// the whole table: every descriptor valid and in the fused set, ONE storage type for all entries (the kernels are instantiated
+// per storage type and chosen on the host: a table of f32 and 16-bit entries, or of f16 and bf16 ones, stays outside), and the
+// tiles of all entries fit one grid
 inline bool table_fuses(const PeaDesc* const* descs, int n) {
   if (n < 1 || n > kMaxN || !descs) return false;
   long long tiles = 0;
   for (int i = 0; i < n; ++i) {
     if (!descs[i] || pea_desc_validate(descs[i]) != PEA_OK || !fuses(descs[i])) return false;
+    if (descs[i]->dtype != descs[0]->dtype) return false;
     const long long S = (long long)descs[i]->dims[0] * descs[i]->dims[1] * descs[i]->dims[2];
     tiles += (S + kBlock - 1) / kBlock * descs[i]->B;  // (each term < 2^31: pea_desc_validate)
   }

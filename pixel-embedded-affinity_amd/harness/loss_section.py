@@ -429,7 +429,11 @@ def cvppp_loss_section(embedding, emds, ema_embedding, target, weightmap, affs_m
 
     batched=True: the four deep-supervision scales run as ONE forward, one loss finish and one backward launch (include/pea_multi.h,
     op.MultiAffinityMSE) instead of three launches per scale -- on the same side stream; where the library does not fuse the table
-    (pea_multi_supported == 0) the per-scale launches run as before.  Same results to rounding (profiles/multi_scale_ab.json)."""
+    (pea_multi_supported == 0) the per-scale launches run as before.  Same results to rounding (profiles/multi_scale_ab.json).
+    16-bit embeddings (what the heads emit under autocast) are fused like float32 ones as long as the four scales share one dtype
+    AND the table is launch-sized (op.MULTI16_MAX_TILES tiles of 256 pixels): measured with bf16 (profiles/multi16_ab.json) the one
+    launch gains 43 us of the eager section at B = 2 and ties graphed, and would lose 40-60 us at B = 8, where the per-scale launches
+    therefore run as before -- batched=True is never slower than batched=False beyond the spread of the runs."""
     if getattr(criterion, 'pea_fused', False) and not ema_embedding.requires_grad:
         specs, weights = _section_specs(offsets, nb_half, affs0_weight, dis_mode, deep_weight, self_emb, cross_emb)
         specs[0].relu = specs[-1].relu = bool(relu_pred)  # (the cross loss writes no map; its descriptor must match)
@@ -818,7 +822,8 @@ def cvppp_loss_section_from_labels(embedding, emds, ema_embedding, labels, label
     loader's cv2.resize(.., INTER_NEAREST) is the plain stride labels[:, ::s, ::s]; ValueError otherwise.
     batched=True: the four deep-supervision losses as ONE pea_affinity_fwd_bwd_labels_multi call (include/pea_multi_labels.h: one
     count launch, one fused forward + backward launch, one loss finish) on the side stream instead of four to five launches per scale,
-    with or without label_downs; where the library does not fuse the table the per-scale launches run as before."""
+    with or without label_downs; where the library does not fuse the table the per-scale launches run as before.  float32, float16
+    and bfloat16 embeddings are fused alike as long as the four scales share one dtype."""
     if criterion is None or offsets is None or nb_half is None:
         raise TypeError("cvppp_loss_section_from_labels() needs criterion, offsets and nb_half")
     if not getattr(criterion, 'pea_fused', False):

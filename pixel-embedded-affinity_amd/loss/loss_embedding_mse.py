@@ -63,7 +63,10 @@ def embedding_loss_multi(embeddings, targets, weightmaps, masks, criterion, offs
     """[embedding_loss(embeddings[j], targets[j], weightmaps[j], masks[j], criterion, offsets_list[j], affs0_weight, mode) for j]
     -> a list of (loss, affs, all_loss) -- the four deep-supervision calls of scripts_cvppp/main.py:284-287 (and of the validation
     loop, inference.py:185-188) -- as ONE forward, one loss finish and one backward launch where the fused criterion is used and
-    the table is in the fused set of include/pea_multi.h (up to four losses, float32 embeddings, D = 16 / 32, at most 12 offsets);
+    the table is in the fused set of include/pea_multi.h (up to four losses; float32, float16 or bfloat16 embeddings, all of ONE dtype;
+    D = 16 / 32, at most 12 offsets: 16-bit embeddings get their gradients in their own dtype, rounded once from the f32 result).
+    A 16-bit table of more than affinity_op.MULTI16_MAX_TILES tiles of 256 pixels runs the single calls: measured with bf16 at the
+    CVPPP shapes, the one launch wins at B = 2 (772 tiles) and loses 8 % of the section at B = 8 (3088 tiles, profiles/multi16_ab.json);
     anything else, and any other criterion, takes the single calls.  need_affs=False (what those callers want: they throw the small
     maps away): affs is None and, on the fused path, never written."""
     n = len(embeddings)
@@ -142,7 +145,10 @@ def embedding_loss_from_labels_multi(embeddings, labels, criterion, offsets_list
     label_steps[j] (an int or (sy, sx)); None: H / h and W / w, which must divide exactly (ValueError otherwise).  Such a strided view
     is what the reference's loader makes with cv2.resize(label, fx=1/2 .. 1/16, INTER_NEAREST), data_provider.py:200-203.
     weight_tables: per embedding None or the [B,K,2] table of pea_label_weights for its (materialised) label image.
-    A table outside the fused set (bf16 / f16 embeddings, D other than 16 / 32, more than four losses or twelve offsets) and any
+    float32, float16 and bfloat16 embeddings are fused alike as long as all n share ONE dtype, at every size (this form was measured
+    no slower than the single calls at B = 8 and faster at B = 2).  A 16-bit gradient is rounded when the call stores it and once
+    more when backward() rescales it by a grad_output that is no power of two: within one ulp of the f32 product.  A table outside
+    the fused set (embeddings of different dtypes, D other than 16 / 32, more than four losses or twelve offsets) and any
     foreign criterion run the single calls on materialised label images -- embedding_loss_from_labels, or, for a foreign criterion
     (which that call refuses), gen_targets + embedding_loss -- same results."""
     n = len(embeddings)

@@ -51,9 +51,10 @@ def embedding_loss_norm1(embedding, target, weightmap, criterion, affs0_weight=1
 def embedding_loss_norm1_multi(embeddings, targets, weightmaps, criterion, affs0_weight=1, shift=1, need_affs=True):
     """[embedding_loss_norm1(embeddings[j], targets[j], weightmaps[j], criterion, affs0_weight, shift) for j] -> a list of
     (loss, affs) -- the four deep-supervision calls of scripts_ac3ac4/main.py:227-230 -- as ONE forward, one loss finish and one
-    backward launch with the fused criterion (include/pea_multi.h: up to four losses, float32 embeddings, D = 16 / 32); anything
-    else takes the single calls.  shift: one value, or one per embedding.  need_affs=False: affs is None (never written on the
-    fused path)."""
+    backward launch with the fused criterion (include/pea_multi.h: up to four losses; float32, float16 or bfloat16 embeddings, all of
+    ONE dtype; D = 16 / 32); anything else takes the single calls.  shift: one value, or one per embedding.  need_affs=False: affs
+    is None (never written on the fused path).  16-bit tables too large for the batched launch to pay run call by call as well
+    (affinity_op.multi16_pays)."""
     n = len(embeddings)
     if not (len(targets) == len(weightmaps) == n):
         raise ValueError("one target and weightmap per embedding")
@@ -154,8 +155,9 @@ def embedding_loss_norm1_from_labels_multi(embeddings, labels, criterion, label_
     library call (include/pea_multi_labels.h).  labels: one tensor [B,z,y,x] per embedding, or ONE tensor [B,Z,Y,X] every embedding
     samples with a step -- label_steps[j]: an int (in-plane, z keeps 1: the reference downsamples slice by slice,
     data_provider_labeled_deep.py:225-232) or (sz, sy, sx); None: label size / embedding size, which must divide exactly.
-    shift: one value, or one per embedding.  need_affs=False: the maps are not written (empty tensors come back).  Anything outside
-    the fused set runs the single calls on materialised label images."""
+    shift: one value, or one per embedding.  need_affs=False: the maps are not written (empty tensors come back).  float32, float16
+    and bfloat16 embeddings are fused alike as long as all share ONE dtype; anything outside the fused set (mixed dtypes, D other than
+    16 / 32) runs the single calls on materialised label images."""
     n = len(embeddings)
     shifts = list(shift) if isinstance(shift, (list, tuple)) else [shift] * n
     if len(shifts) != n or (weight_tables is not None and len(weight_tables) != n):
