@@ -31,6 +31,7 @@ from .utils.affinity_ours import gen_offsets, multi_offset
 from .utils.postproc import fill_border_relu_, relu_
 from .utils.targets import gen_affs_ours, gen_targets, seg_to_aff
 from .harness.stitch import VolumeStitcher
+from .harness.metrics import AffinityMetrics, affinity_metrics
 from .harness.handoff import AffsCollector
 from .harness.head_loss import HeadAffinityMSE, head_embedding_loss
 from .harness.train_step import CvpppTrainStep, convert_consistency_flip, label_pyramid, make_optimizer
@@ -57,4 +58,5 @@ __all__ = [
     "embedding_loss_norm6", "ema_embedding_loss_norm6", "EmbeddingHead", "OutConv", "head_conv3d_block", "head16_supported", "cvppp_label_weight_tables", "cvppp_validation_section",
     "MultiAffinityMSE", "embedding_loss_multi", "embedding_loss_norm1_multi", "unflip", "convert_consistency_flip",
     "MultiLabelsAffinityMSE", "embedding_loss_from_labels_multi", "embedding_loss_norm1_from_labels_multi",
+    "affinity_metrics", "AffinityMetrics",
 ]

@@ -18,6 +18,7 @@ HEADER_MULTI = os.path.join(HERE, "..", "include", "pea_multi.h")
 HEADER_FLIP = os.path.join(HERE, "..", "include", "pea_flip.h")
 HEADER_MULTI_LABELS = os.path.join(HERE, "..", "include", "pea_multi_labels.h")
 HEADER_HEAD16 = os.path.join(HERE, "..", "include", "pea_head16.h")
+HEADER_METRICS = os.path.join(HERE, "..", "include", "pea_metrics.h")
 
 PEA_ABI_VERSION = 2
 PEA_MAX_K = 32
@@ -31,6 +32,8 @@ FLAG_MASK_F32 = 32  # the mask of the training forwards holds f32 values (includ
 FLAG_LOSS_ACT = 64  # the loss of the training forwards is taken on the activated map (include/pea.h PEA_FLAG_LOSS_ACT)
 RULES_U8, RULES_I32, RULES_I64, RULES_F32 = 0, 1, 2, 3  # element type of the rules table (include/pea_flip.h PEA_RULES_*)
 TGT_PADDING, TGT_BOTH_FOREGROUND, TGT_MASK_INSIDE, TGT_ACCUMULATE = 1, 2, 4, 8
+METRICS_COLS = 5  # mse, bce, tp, fp, fn (include/pea_metrics.h PEA_METRICS_COLS)
+MET_RELU, MET_DIVIDE, MET_STORE, MET_MASK_F32 = 1, 2, 4, 8  # include/pea_metrics.h PEA_MET_*
 
 EXPORTS = ("pea_version", "pea_strerror", "pea_desc_validate", "pea_workspace_bytes", "pea_workspace_init", "pea_reload_env",
            "pea_affinity_infer", "pea_affinity_fwd", "pea_affinity_bwd", "pea_affinity_fwd_ex", "pea_affinity_bwd_ex", "pea_affinity_bwd_ex2", "pea_inv_norm",
@@ -49,6 +52,8 @@ EXPORTS_FLIP = ("pea_consistency_unflip",)
 EXPORTS_MULTI_LABELS = ("pea_multi_labels_supported", "pea_multi_labels_scratch_bytes", "pea_affinity_fwd_bwd_labels_multi")
 # the entry points of include/pea_head16.h (the embedding head on f16 / bf16 features)
 EXPORTS_HEAD16 = ("pea_head_supported_t", "pea_head_fwd_t", "pea_head_bwd_t")
+# the entry points of include/pea_metrics.h (the validation pixel metrics: MSE, BCE and the F1 counts in one data launch)
+EXPORTS_METRICS = ("pea_metrics_validate", "pea_metrics_workspace_bytes", "pea_affs_metrics")
 
 
 class PeaLibraryError(RuntimeError):
@@ -85,6 +90,13 @@ class PeaMultiLabels(ctypes.Structure):
                 ("dloss", ctypes.c_void_p), ("de", ctypes.c_void_p)]
 
 
+class PeaMetricsDesc(ctypes.Structure):
+    """mirror of `struct PeaMetricsDesc` in include/pea_metrics.h"""
+    _fields_ = [("B", ctypes.c_int32), ("C", ctypes.c_int32), ("CP", ctypes.c_int32), ("dims", ctypes.c_int32 * 3),
+                ("pred_dims", ctypes.c_int32 * 3), ("origin", ctypes.c_int32 * 3), ("flags", ctypes.c_uint32),
+                ("clip_lo", ctypes.c_float), ("clip_hi", ctypes.c_float)]
+
+
 HIPCC_FLAGS = ["-O3", "--offload-arch=gfx950", "-std=c++17", "-fPIC"]
 OBJ_DIR = os.path.join(CSRC, "build")
 
@@ -110,7 +122,7 @@ def build(force=False, verbose=False, jobs=None):
 
 def _build_locked(force, verbose, jobs):
     srcs = sources()
-    hdrs = [HEADER, HEADER_INFER, HEADER_MULTI, HEADER_FLIP, HEADER_MULTI_LABELS, HEADER_HEAD16] + [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".h")]
+    hdrs = [HEADER, HEADER_INFER, HEADER_MULTI, HEADER_FLIP, HEADER_MULTI_LABELS, HEADER_HEAD16, HEADER_METRICS] + [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".h")]
     newest_hdr = max(os.path.getmtime(h) for h in hdrs)
     if not force and os.path.exists(SO_PATH) and os.path.getmtime(SO_PATH) >= max([newest_hdr] + [os.path.getmtime(x) for x in srcs]):
         return SO_PATH
@@ -174,7 +186,7 @@ def lib():
         L = ctypes.CDLL(SO_PATH)
     except OSError as ex:
         raise PeaLibraryError("cannot load %s: %s" % (SO_PATH, ex))
-    for name in EXPORTS + EXPORTS_INFER + EXPORTS_MULTI + EXPORTS_FLIP + EXPORTS_MULTI_LABELS + EXPORTS_HEAD16:
+    for name in EXPORTS + EXPORTS_INFER + EXPORTS_MULTI + EXPORTS_FLIP + EXPORTS_MULTI_LABELS + EXPORTS_HEAD16 + EXPORTS_METRICS:
         if not hasattr(L, name):
             raise PeaLibraryError("%s does not export %s" % (SO_PATH, name))
     vp, dp = ctypes.c_void_p, ctypes.POINTER(PeaDesc)
@@ -269,6 +281,12 @@ def lib():
     L.pea_head_bwd_t.restype = ctypes.c_int
     L.pea_head_bwd_t.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_size_t, vp, ctypes.c_int, vp, vp, ctypes.c_int, vp, vp, vp, vp,
                                  ctypes.c_size_t, vp]
+    L.pea_metrics_validate.restype = ctypes.c_int
+    L.pea_metrics_validate.argtypes = [ctypes.POINTER(PeaMetricsDesc)]
+    L.pea_metrics_workspace_bytes.restype = ctypes.c_size_t
+    L.pea_metrics_workspace_bytes.argtypes = []
+    L.pea_affs_metrics.restype = ctypes.c_int
+    L.pea_affs_metrics.argtypes = [ctypes.POINTER(PeaMetricsDesc), vp, vp, vp, vp, vp, vp, ctypes.c_size_t, vp]
     if L.pea_version() != PEA_ABI_VERSION:
         raise PeaLibraryError("ABI mismatch: library %d, binding %d" % (L.pea_version(), PEA_ABI_VERSION))
     _lib = L

@@ -583,12 +583,18 @@ def finish_pred_3d_(pred, shift=1):
 
 
 def cvppp_validation_section(embedding, emds, target, weightmap, affs_mask, downs, criterion, offsets, nb_half,
-                             affs0_weight=1, dis_mode='ours', test_mode=False, batched=False):
+                             affs0_weight=1, dis_mode='ours', test_mode=False, batched=False, metrics=False):
     """The validation / test caller of scripts_cvppp/inference.py:179-193 (and the validation branch of main.py:380-395):
     under no_grad, either embedding2affs alone (mode == 'test') or the five self losses -- unweighted sum, as the reference
     adds them at :190 -- and the full-resolution map; `pred` comes back as F.relu(pred) (:193).  Returns (loss or None,
     pred); the caller adds its own loss_mask term.  emds = (emd1, .., emd4), downs = (down1, .., down4) as in training.
-    batched=True: the four small losses as one embedding_loss_multi call (one forward launch and one loss finish for the four)."""
+    batched=True: the four small losses as one embedding_loss_multi call (one forward launch and one loss finish for the four).
+    metrics=True: the relu and the two validation metrics of main.py:395-397 -- valid_mse(pred * affs_mask, target * affs_mask) and
+    valid_bce(torch.clamp(pred, 0, 1) * affs_mask, target * affs_mask) -- as ONE launch (pea_affs_metrics with RELU | STORE,
+    include/pea_metrics.h) in place of finish_pred_2d_; returns (loss, pred, AffinityMetrics).  With test_mode=True there is no
+    target: ValueError."""
+    if metrics and test_mode:
+        raise ValueError("metrics=True needs the target: not with test_mode=True")
     with torch.no_grad():
         if test_mode:
             from ..loss.loss_embedding_mse import embedding2affs
@@ -608,6 +614,10 @@ def cvppp_validation_section(embedding, emds, target, weightmap, affs_mask, down
         loss_embedding, pred, _ = embedding_loss(embedding, target, weightmap, affs_mask, criterion, offsets,
                                                  affs0_weight=affs0_weight, mode=dis_mode)
         fork.join()
+        if metrics:
+            from .metrics import affinity_metrics
+            met = affinity_metrics(pred, target, affs_mask, relu=True, store=True, clip=(0.0, 1.0))
+            return total + loss_embedding, pred, met
         return total + loss_embedding, finish_pred_2d_(pred)
 
 

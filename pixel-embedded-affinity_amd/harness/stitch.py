@@ -123,8 +123,30 @@ class VolumeStitcher(object):
         with torch.cuda.device(self.device):
             _lib.check(_lib.lib().pea_stitch_finalize(p(self.out_affs), p(self.weight_map), self.C, Z * Y * X,
                                                       ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)), "pea_stitch_finalize")
+        return self._cropped(valid_padding)
+
+    def _cropped(self, valid_padding):
+        """the view get_results returns: out_affs cropped by valid_padding (provider_valid.py:341-348)"""
         vz, vy, vx = (int(v) for v in valid_padding)
         out = self.out_affs
         if vz:
             out = out[:, vz:-vz]
         return out[:, :, vy:-vy, vx:-vx] if (vy and vx) else out
+
+    def finish(self, valid_padding, gt_affs, channels=3, clip=(1e-6, 0.999999)):
+        """get_results AND the three scalars scripts_ac3ac4/main.py:339-351 logs on every save (whole_mse, whole_bce, whole_f1 of
+        out_affs[:channels] against gt_affs) in ONE data launch (pea_affs_metrics with DIVIDE | STORE, include/pea_metrics.h): the
+        division by the weight map is written back to the whole volume -- the bits of get_results -- while the first `channels`
+        channels of the cropped region are compared with gt_affs [channels, Z', Y', X'] (float32, on the GPU).  clip: the bounds of
+        np.clip at :345.  Returns (out, metrics): the view get_results returns and an AffinityMetrics; nothing is copied to the host."""
+        from .metrics import affinity_metrics
+        if not isinstance(gt_affs, torch.Tensor) or not gt_affs.is_cuda:
+            raise RuntimeError("VolumeStitcher.finish runs on an MI355X only (no CPU fallback): gt_affs must be a device tensor")
+        out = self._cropped(valid_padding)
+        if gt_affs.dim() != 4 or tuple(gt_affs.shape) != (int(channels),) + tuple(out.shape[1:]):
+            raise ValueError("gt_affs must be %s, got %s" % ((int(channels),) + tuple(out.shape[1:]), tuple(gt_affs.shape)))
+        vz, vy, vx = (int(v) for v in valid_padding)
+        origin = (vz, vy, vx) if (vy and vx) else (vz, 0, 0)
+        metrics = affinity_metrics(self.out_affs.unsqueeze(0), gt_affs.unsqueeze(0), None, store=True, weight_map=self.weight_map,
+                                   clip=(np.float32(clip[0]), np.float32(clip[1])), origin=origin, channels=int(channels))
+        return out, metrics
