@@ -255,7 +255,14 @@ int pea_inv_norm(const PeaDesc *desc, const void *e, float *inv_norm_out, void *
  * backward == 4: the same question for the cross loss with a detached second operand (e_other != NULL, de_other == NULL): 1 at
  * D = 32 / 64, f32, 2D -- there the role-A backward is the projection-first kernel k_bwd_xdma_pfo (csrc/pea_xdma_pf.h) and runs only
  * when `affs` (the cross loss' raw map) comes along; without it the tiled kernels run.  backward == 5: 1 when
- * pea_affinity_fwd_dual_ex runs the descriptor's self + cross forward pair as one launch. */
+ * pea_affinity_fwd_dual_ex runs the descriptor's self + cross forward pair as one launch.
+ * The stencil domain of the cross kernels, tested over all of it (tests/test_cross_stencils_host.py pins the answers,
+ * tests/test_gpu_cross_stencils.py holds the kernels to float64): every offset along ONE axis, of either sign, in any order, repeats
+ * allowed, one in-plane axis or both.  Ceilings: the forward takes 10 in-plane offsets (+ 4 along z in 3D); the self backward 5 per
+ * in-plane axis at D = 16 / 32 and 4 at D = 64 and in 3D, 4 along z; the role-A backward (mode 2) needs an offset on both in-plane axes.
+ * Reach: 32 pixels along x (33 is refused in every mode; reaching more than 16 BOTH ways needs X >= 96); along y what the LDS planes
+ * hold -- halo rows above plus below, with 32-pixel strip rows: 28 for the 16-bit, paired and labels-in forwards, 70 elsewhere (the
+ * self backward's halo is two-sided: 35 rows each way; the shipped tables reach 27). */
 int pea_cross_supported(const PeaDesc *desc, int backward);
 
 /* The FORWARD of the full-resolution pair of the 2D training loops in one launch: embedding_loss(e, target, weight, mask) and
