@@ -65,15 +65,7 @@ KParams make_params(const PeaDesc* d) {
   P.mbs = d->mask_bstride ? d->mask_bstride : dense;
   for (int i = 0; i < PEA_MAX_K; ++i) {
     const bool on = i < d->K;
-    double n = 1.0;
-    if (on) {
-      if (d->norm == PEA_NORM_BX) n = (double)d->B * d->dims[2];
-      else if (d->norm == PEA_NORM_FULL) n = (double)d->B * P.S;
-      else {
-        n = d->B;
-        for (int a = 0; a < 3; ++a) n *= (double)(d->dims[a] - abs(d->offsets[i][a]));
-      }
-    }
+    const double n = on ? normaliser(d, i) : 1.0;
     for (int a = 0; a < 3; ++a) P.off[i][a] = on ? d->offsets[i][a] : 0;
     P.lam[i] = on ? d->lambda[i] : 0.f;
     P.inv_n[i] = on ? (float)(1.0 / n) : 0.f;

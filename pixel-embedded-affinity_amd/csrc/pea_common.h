@@ -66,23 +66,6 @@ __device__ __forceinline__ void clamp_preimage(int c, int o, int n, int& lo, int
   else if (lo < 0 || lo > n - 1) { lo = 1; hi = 0; }
 }
 
-// neighbour of (z,y,x) displaced by o; returns flat index or -1 (CROP_ZERO, outside)
-__device__ __forceinline__ int neighbour(const KParams& P, int z, int y, int x, int oz, int oy, int ox) {
-  int zz = z + oz, yy = y + oy, xx = x + ox;
-  if (P.border == PEA_BORDER_CIRCULAR) {  // host guarantees |o| < dim
-    zz += (zz < 0) ? P.Z : 0; zz -= (zz >= P.Z) ? P.Z : 0;
-    yy += (yy < 0) ? P.Y : 0; yy -= (yy >= P.Y) ? P.Y : 0;
-    xx += (xx < 0) ? P.X : 0; xx -= (xx >= P.X) ? P.X : 0;
-  } else if (P.border == PEA_BORDER_REPLICATE) {  // index clamped into the volume: every pair exists
-    zz = min(max(zz, 0), P.Z - 1);
-    yy = min(max(yy, 0), P.Y - 1);
-    xx = min(max(xx, 0), P.X - 1);
-  } else if ((unsigned)zz >= (unsigned)P.Z || (unsigned)yy >= (unsigned)P.Y || (unsigned)xx >= (unsigned)P.X) {
-    return -1;
-  }
-  return (zz * P.Y + yy) * P.X + xx;
-}
-
 // activation of the affs output (include/pea.h PEA_FLAG_*): flags are wave-uniform, the common case (0) is one scalar branch
 constexpr unsigned kActMask = PEA_FLAG_RELU_AFFS | PEA_FLAG_ONE_MINUS | PEA_FLAG_HALF_SHIFT | PEA_FLAG_CLAMP01;
 // relu and clamp as SELECTS, not fmaxf / fminf: C's fmaxf(NaN, 0) is 0, F.relu and torch.clamp keep NaN -- and a NaN affinity is the only

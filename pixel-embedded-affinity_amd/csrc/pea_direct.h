@@ -2,9 +2,11 @@
 //
 // The direct kernels are the general fallback (any D in the forward, any offsets that no LDS tile can
 // hold): one lane = one pixel, D-loop in registers, every neighbour vector read from global memory
-// (coalesced row reads; the L2 norm of the neighbour is accumulated while its channels stream in).
+// (coalesced row reads; the L2 norm of the neighbour is accumulated while its channels stream in).  The per-pixel arithmetic of
+// the D-specialised paths is that of pea_gather.h; the kernels here add the tile walk, the loss reduction (s_acc, then wave_sum),
+// the REPLICATE pre-image loop, the runtime-D paths and the loss on the activated map.
 #pragma once
-#include "pea_loss.h"
+#include "pea_gather.h"
 
 namespace pea {
 
@@ -37,18 +39,10 @@ __global__ __launch_bounds__(kBlock) void k_fwd_direct(const KParams P, const T*
   float ec[D_T ? D_T : 1];
   float inv_p = 0.f;
   if (live) {
-    const int yx = P.Y * P.X;
-    z = p / yx;
-    const int r = p - z * yx;
-    y = r / P.X;
-    x = r - y * P.X;
+    split_voxel(P, p, z, y, x);
     float ss = 0.f;
-    if (D_T) {
-#pragma unroll
-      for (int c = 0; c < D_T; ++c) {
-        ec[c] = ld(eb, c * S + p);
-        ss = fmaf(ec[c], ec[c], ss);
-      }
+    if constexpr (D_T > 0) {
+      ss = load_vec(eb, S, p, ec);
     } else {
       for (int c = 0; c < D; ++c) {
         const float v = ld(eb, c * S + p);
@@ -64,22 +58,17 @@ __global__ __launch_bounds__(kBlock) void k_fwd_direct(const KParams P, const T*
       const int q = neighbour(P, z, y, x, P.off[i][0], P.off[i][1], P.off[i][2]);
       float a = 0.f;
       if (q >= 0) {
-        float dot = 0.f, sq = 0.f;
-        if (D_T) {
-#pragma unroll
-          for (int c = 0; c < D_T; ++c) {
-            const float v = ld(ob, c * S + q);
-            dot = fmaf(ec[c], v, dot);
-            sq = fmaf(v, v, sq);
-          }
+        if constexpr (D_T > 0) {
+          a = cosine_streamed(ec, inv_p, ob, S, q, P.eps);
         } else {
+          float dot = 0.f, sq = 0.f;
           for (int c = 0; c < D; ++c) {
             const float v = ld(ob, c * S + q);
             dot = fmaf(ld(eb, c * S + p), v, dot);
             sq = fmaf(v, v, sq);
           }
+          a = dot * inv_p * inv_norm(sq, P.eps);
         }
-        a = dot * inv_p * inv_norm(sq, P.eps);
       }
       const size_t in = (size_t)i * S + p;
       if (affs) affs[kb + in] = act_affs(a, P.flags & kActMask);
@@ -87,17 +76,17 @@ __global__ __launch_bounds__(kBlock) void k_fwd_direct(const KParams P, const T*
         float g = 0.f;
         if (q >= 0) {
           const float m = mask ? (float)mask[(size_t)b * P.mbs + in] : 1.f;
-          float u = a, v = a, gsc = P.gscale[i];
+          const float t = target[(size_t)b * P.tbs + in], w = weight[(size_t)b * P.wbs + in];
           if constexpr (LACT) {  // the loss on the activated value; its slope goes into g
             const ActK AK = act_consts(P.flags & kActMask);
-            v = act_v(a, AK);
-            u = act_u(v, AK);
-            gsc *= AK.sc;
+            const float v = act_v(a, AK), u = act_u(v, AK);
+            const float r = u * m - t * m;
+            const float wr = w * r;
+            contrib = wr * r;
+            g = act_g(u, v, P.gscale[i] * AK.sc, wr, m, AK);
+          } else {
+            g = raw_loss_term(a, t, w, m, P.gscale[i], contrib);
           }
-          const float r = u * m - target[(size_t)b * P.tbs + in] * m;
-          const float wr = weight[(size_t)b * P.wbs + in] * r;
-          contrib = wr * r;
-          g = LACT ? act_g(u, v, gsc, wr, m, act_consts(P.flags & kActMask)) : P.gscale[i] * wr * m;
         }
         if (gout) gout[kb + in] = g;
       }
@@ -140,21 +129,11 @@ __global__ __launch_bounds__(kBlock) void k_bwd_direct(const KParams P, const T*
   const float* gb = gin + (size_t)b * P.K * S;
   const float dl = dloss ? dloss[0] : 1.f;
 
-  const int yx = P.Y * P.X;
-  const int z = p / yx;
-  const int r0 = p - z * yx;
-  const int y = r0 / P.X;
-  const int x = r0 - y * P.X;
+  int z, y, x;
+  split_voxel(P, p, z, y, x);
 
-  float xc[D_T], G[D_T];
-  float ss = 0.f;
-#pragma unroll
-  for (int c = 0; c < D_T; ++c) {
-    xc[c] = ld(xb, c * S + p);
-    ss = fmaf(xc[c], xc[c], ss);
-    G[c] = 0.f;
-  }
-  const float nrm = sqrtf(ss);
+  float xc[D_T], G[D_T] = {};
+  const float nrm = sqrtf(load_vec(xb, S, p, xc));
   const float inv_p = 1.0f / fmaxf(nrm, P.eps);
 
   for (int i = 0; i < P.K; ++i) {
@@ -188,6 +167,9 @@ __global__ __launch_bounds__(kBlock) void k_bwd_direct(const KParams P, const T*
       }
       const int q = neighbour(P, z, y, x, sg * oz, sg * oy, sg * ox);
       if (q < 0) continue;
+      // gather_pair() of pea_gather.h, written out here and in the pre-image loop above: with either site a call, the D = 32
+      // instantiations that have role B lose a wave per SIMD (125 -> 140 and 160 -> 176 VGPRs in f32, 122 -> 138 in f16).  That
+      // these lines and gather_pair() agree bit for bit is therefore held by tests/test_gpu_gather_families.py, not by structure
       float v[D_T], sq = 0.f;
 #pragma unroll
       for (int c = 0; c < D_T; ++c) {
@@ -200,15 +182,7 @@ __global__ __launch_bounds__(kBlock) void k_bwd_direct(const KParams P, const T*
       for (int c = 0; c < D_T; ++c) G[c] = fmaf(g, v[c], G[c]);
     }
   }
-
-  float proj = 0.f;
-#pragma unroll
-  for (int c = 0; c < D_T; ++c) proj = fmaf(xc[c] * inv_p, G[c], proj);
-  if (nrm < P.eps) proj = 0.f;  // clamp_min branch of F.normalize: d ehat / d e = I / eps
-  T* db = dx + (size_t)b * D_T * S;
-  const float sc = dl * inv_p;
-#pragma unroll
-  for (int c = 0; c < D_T; ++c) st(db, c * S + p, (G[c] - xc[c] * inv_p * proj) * sc);
+  project_store<false>(dx + (size_t)b * D_T * S, S, p, xc, G, nrm, inv_p, P.eps, dl);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -234,11 +208,8 @@ __global__ __launch_bounds__(kBlock) void k_bwd_direct_anyd(const KParams P, con
   const T* xb = xt + (size_t)b * D * S;
   const float* gb = gin + (size_t)b * P.K * S;
   const float dl = dloss ? dloss[0] : 1.f;
-  const int yx = P.Y * P.X;
-  const int z = p / yx;
-  const int r0 = p - z * yx;
-  const int y = r0 / P.X;
-  const int x = r0 - y * P.X;
+  int z, y, x;
+  split_voxel(P, p, z, y, x);
 
   float ss = 0.f;
   for (int c = 0; c < D; ++c) {

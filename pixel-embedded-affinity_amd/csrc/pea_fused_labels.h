@@ -707,15 +707,9 @@ static __global__ __launch_bounds__(64) void k_weight_table(int S, int per_img, 
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) c += __shfl_down(c, o, 64);
   if (threadIdx.x == 0) {
-    float wpos = 1.f, wneg = 1.f;
-    if (c != 0 && c != (unsigned)S) {
-      double f = (double)c / (double)S;
-      f = fmin(fmax(f, 5e-2), 0.99);
-      if (f > 0.5) wneg = (float)(f / (1.0 - f));
-      else wpos = (float)((1.0 - f) / f);
-    }
-    wtab[2 * i] = wpos;
-    wtab[2 * i + 1] = wneg;
+    const ClassWeights cw = class_balance(c, S);
+    wtab[2 * i] = cw.pos;
+    wtab[2 * i + 1] = cw.neg;
   }
 }
 

@@ -19,6 +19,7 @@
 // arguments: launch<KERNEL>() and the with_bool / with_storage / with_width / with_mask_form callers of generic lambdas.
 #pragma once
 #include <stdint.h>
+#include <stdlib.h>
 #include <string.h>
 
 #include "pea_loss.h"
@@ -58,6 +59,14 @@ unsigned env_generation();  // = env().gen; a new one with every env_reload(): m
 inline bool misaligned(const void* p, size_t a) { return ((uintptr_t)p & (a - 1)) != 0; }
 // bytes per element of the embedding's storage dtype (validate() admits PEA_F32, PEA_F16 and PEA_BF16 only)
 inline size_t dtype_bytes(int dtype) { return dtype == PEA_F32 ? 4 : 2; }
+// N_i of include/pea.h: what the loss of offset i is divided by (1 / N_i in the loss finish, 2 lambda_i / N_i in g)
+inline double normaliser(const PeaDesc* d, int i) {
+  if (d->norm == PEA_NORM_BX) return (double)d->B * d->dims[2];
+  if (d->norm == PEA_NORM_FULL) return (double)d->B * d->dims[0] * d->dims[1] * d->dims[2];
+  double n = d->B;
+  for (int a = 0; a < 3; ++a) n *= (double)(d->dims[a] - abs(d->offsets[i][a]));
+  return n;
+}
 int& g_pending_error();  // per thread: an error met while preparing a launch (allow_lds), reported by the next hip_rc()
 inline int hip_rc() {
   int& pe = g_pending_error();

@@ -9,10 +9,10 @@
 // tiles first.  The tiles are then walked XCD-aware like logical_tile() walks one image: every XCD takes a contiguous range of the
 // concatenated tile list, so the rows a tile's neighbours live in are mostly rows its own XCD loads anyway.
 //
-// Gather-from-global form, the arithmetic of k_fwd_direct / k_bwd_direct (pea_direct.h): one lane per pixel, the own pixel's D
-// channels in registers, every neighbour vector read from global memory with its norm accumulated while the channels stream in,
-// a = dot * (1 / max(|e(p)|, eps)) * (1 / max(|e(q)|, eps)), the clamp branch of F.normalize (I / eps) where |e| < eps.  The largest
-// table of the reference (B = 8 x 16 x 272^2 and below, f32) is 38 MB of embeddings: L2 / Infinity Cache resident.
+// Gather-from-global form: the bodies compose the blocks of pea_gather.h, the same ones k_fwd_direct / k_bwd_direct (pea_direct.h)
+// are made of, so affs and g carry the single direct calls' bits, and so does de in f32 and bf16 (an f16 de lies within one f16 ulp:
+// st_rounded here, st there); only the loss partials are summed in an order of their own (below).  The largest table of the
+// reference (B = 8 x 16 x 272^2 and below, f32) is 38 MB of embeddings: L2 / Infinity Cache resident.
 // The body is a template of D (16 / 32), the mask type (none / u8 / f32) and the border; a table whose entries agree on the three
 // (the four scales of one training loop do) takes the kernel instantiated for them, any other the kernel that branches per
 // workgroup (the branch is uniform: a workgroup has one entry).
@@ -78,35 +78,15 @@ __device__ __forceinline__ void fwd_body(const MFwdEntry& E, int tile, float (*s
   float ec[D];
   float inv_p = 0.f;
   if (live) {
-    const int yx = G.Y * G.X;
-    z = p / yx;
-    const int r = p - z * yx;
-    y = r / G.X;
-    x = r - y * G.X;
-    float ss = 0.f;
-#pragma unroll
-    for (int c = 0; c < D; ++c) {
-      ec[c] = ld(eb, c * S + p);
-      ss = fmaf(ec[c], ec[c], ss);
-    }
-    inv_p = inv_norm(ss, G.eps);
+    split_voxel(G, p, z, y, x);
+    inv_p = inv_norm(load_vec(eb, S, p, ec), G.eps);
   }
 
   for (int i = 0; i < G.K; ++i) {
     float contrib = 0.f;
     if (live) {
-      const int q = neighbour_of<BORDER>(G, z, y, x, G.off[i][0], G.off[i][1], G.off[i][2]);
-      float a = 0.f;
-      if (q >= 0) {
-        float dot = 0.f, sq = 0.f;
-#pragma unroll
-        for (int c = 0; c < D; ++c) {
-          const float v = ld(eb, c * S + q);
-          dot = fmaf(ec[c], v, dot);
-          sq = fmaf(v, v, sq);
-        }
-        a = dot * inv_p * inv_norm(sq, G.eps);
-      }
+      const int q = neighbour<BORDER>(G, z, y, x, G.off[i][0], G.off[i][1], G.off[i][2]);
+      const float a = q >= 0 ? cosine_streamed(ec, inv_p, eb, S, q, G.eps) : 0.f;
       const size_t in = (size_t)i * S + p;
       if (E.affs) E.affs[kb + in] = act_affs(a, E.act);
       float g = 0.f;
@@ -114,10 +94,7 @@ __device__ __forceinline__ void fwd_body(const MFwdEntry& E, int tile, float (*s
         float m = 1.f;
         if constexpr (MT == kMaskU8) m = (float)((const uint8_t*)E.m)[(size_t)b * E.mbs + in];
         if constexpr (MT == kMaskF32) m = ((const float*)E.m)[(size_t)b * E.mbs + in];
-        const float r = a * m - E.t[(size_t)b * E.tbs + in] * m;
-        const float wr = E.w[(size_t)b * E.wbs + in] * r;
-        contrib = wr * r;
-        g = E.gscale[i] * wr * m;
+        g = raw_loss_term(a, E.t[(size_t)b * E.tbs + in], E.w[(size_t)b * E.wbs + in], m, E.gscale[i], contrib);
       }
       E.gout[kb + in] = g;
     }
@@ -162,21 +139,11 @@ __device__ __forceinline__ void bwd_body(const MBwdEntry& E, int tile) {
   const float* gb = E.gin + (size_t)b * Gm.K * S;
   const float dl = E.dloss ? E.dloss[0] : 1.f;
 
-  const int yx = Gm.Y * Gm.X;
-  const int z = p / yx;
-  const int r0 = p - z * yx;
-  const int y = r0 / Gm.X;
-  const int x = r0 - y * Gm.X;
+  int z, y, x;
+  split_voxel(Gm, p, z, y, x);
 
-  float xc[D], G[D];
-  float ss = 0.f;
-#pragma unroll
-  for (int c = 0; c < D; ++c) {
-    xc[c] = ld(xb, c * S + p);
-    ss = fmaf(xc[c], xc[c], ss);
-    G[c] = 0.f;
-  }
-  const float nrm = sqrtf(ss);
+  float xc[D], G[D] = {};
+  const float nrm = sqrtf(load_vec(xb, S, p, xc));
   const float inv_p = 1.0f / fmaxf(nrm, Gm.eps);
 
   for (int i = 0; i < Gm.K; ++i) {
@@ -184,29 +151,13 @@ __device__ __forceinline__ void bwd_body(const MBwdEntry& E, int tile) {
 #pragma unroll
     for (int role = 0; role < 2; ++role) {
       const int sg = role == 0 ? 1 : -1;
-      const int q = neighbour_of<BORDER>(Gm, z, y, x, sg * oz, sg * oy, sg * ox);
+      const int q = neighbour<BORDER>(Gm, z, y, x, sg * oz, sg * oy, sg * ox);
       if (q < 0) continue;
-      float v[D], sq = 0.f;
-#pragma unroll
-      for (int c = 0; c < D; ++c) {
-        v[c] = ld(xb, c * S + q);
-        sq = fmaf(v[c], v[c], sq);
-      }
       // the loss term lives at the first operand's pixel: p for role A, the neighbour for role B
-      const float g = gb[(size_t)i * S + (role == 0 ? p : q)] * inv_norm(sq, Gm.eps);
-#pragma unroll
-      for (int c = 0; c < D; ++c) G[c] = fmaf(g, v[c], G[c]);
+      gather_pair(G, xb, S, q, gb[(size_t)i * S + (role == 0 ? p : q)], Gm.eps);
     }
   }
-
-  float proj = 0.f;
-#pragma unroll
-  for (int c = 0; c < D; ++c) proj = fmaf(xc[c] * inv_p, G[c], proj);
-  if (nrm < Gm.eps) proj = 0.f;  // clamp_min branch of F.normalize: d ehat / d e = I / eps
-  T* db = (T*)E.de + (size_t)b * D * S;
-  const float sc = dl * inv_p;
-#pragma unroll
-  for (int c = 0; c < D; ++c) st_rounded(db, c * S + p, (G[c] - xc[c] * inv_p * proj) * sc);  // 16-bit: rounded once, NaN kept
+  project_store<true>((T*)E.de + (size_t)b * D * S, S, p, xc, G, nrm, inv_p, Gm.eps, dl);
 }
 
 template <typename T, int DS, int BS>
@@ -269,7 +220,7 @@ int pea_affinity_fwd_multi(const PeaMultiFwd* entries, int n, void* workspace, s
     E.e = A.e; E.t = A.target; E.w = A.weight; E.m = A.mask; E.affs = A.affs; E.gout = A.g_out;
     E.st = states + i;
     fill_finish(F.en[i], d, states + i, A.loss_out);
-    for (int k = 0; k < d->K; ++k) E.gscale[k] = (float)(2.0 * (double)d->lambda[k] / normaliser(d, k));  // as make_params (pea_abi.hip)
+    for (int k = 0; k < d->K; ++k) E.gscale[k] = (float)(2.0 * (double)d->lambda[k] / normaliser(d, k));
   }
   const dim3 grid = place_tiles(T, B), blk(kBlock);
   hipStream_t s = (hipStream_t)stream;

@@ -10,15 +10,15 @@
 // k_count_multi: a workgroup counts t_i != 0 per channel over its 256 voxels -- ballot per wave, LDS, then one u32 atomic per
 // (workgroup, channel) into scratch[entry][b][i].  Integer sums: the result does not depend on the order of arrival.
 //
-// k_fwd_bwd_labels_multi: gather-from-global form, the arithmetic of k_fwd_multi / k_bwd_multi: one lane per voxel p, its D channels
-// and its label in registers.  The backward of p needs g_i(p - o_i), which depends on cos(e(p - o_i), e(p)), two labels and two
+// k_fwd_bwd_labels_multi: gather-from-global form, composed of the blocks of pea_gather.h that k_fwd_multi / k_bwd_multi are made
+// of (so affs and de carry their bits on the same targets): one lane per voxel p, its D channels and its label in registers.  The backward of p needs g_i(p - o_i), which depends on cos(e(p - o_i), e(p)), two labels and two
 // table entries -- all of which the backward's gather reads anyway -- so no g map makes a round trip through memory.  Per offset
 //   role A: q = p + o_i, a = cos(e(p), e(q)), t / m / w from L'(p), L'(q): affs, the loss partial, G += g_A ehat(q)
 //   role B: q = p - o_i, the loss term lives at q: a (evaluated in q's operand order: the same bits role A of q computes), t / m / w
 //           for the pair (q, p); its mask is [p - o_i did not leave the image]: G += g_B ehat(q)
 // then de = dloss (G - ehat <ehat, G>) / n(p), G / eps where |e(p)| < eps.  The class-balance table of the workgroup's image is put
-// into LDS by the prologue: copied from the caller's wtab, or evaluated from the counts with the f64 formula of k_weight_table
-// (pea_fused_labels.h) -- the same bits pea_label_weights writes.
+// into LDS by the prologue: copied from the caller's wtab, or evaluated from the counts with class_balance() (pea_gather.h), which
+// k_weight_table (pea_fused_labels.h) calls too -- the same bits pea_label_weights writes.
 // Label reads with a step are uncoalesced (a wave's 64 labels of one row span 64 * sx * 4 bytes); the label images are 1.2 MB per
 // sample (544^2 int32) and L2-resident, every one of their cache lines is used by some scale, so they are not staged through LDS.
 // The body is a template of the storage type T (float / __half / __bf16: ld() / st_rounded() around the unchanged f32 arithmetic,
@@ -76,14 +76,6 @@ __device__ __forceinline__ bool target_of(int lown, int lnb, bool inside, bool p
   return inside ? eq : pad;
 }
 
-__device__ __forceinline__ void split_voxel(const MGeom& G, int p, int& z, int& y, int& x) {
-  const int yx = G.Y * G.X;
-  z = p / yx;
-  const int r = p - z * yx;
-  y = r / G.X;
-  x = r - y * G.X;
-}
-
 // ------------------------------------------------------------------------------------------------
 // counts of t_i != 0 per (entry, image, channel)
 // ------------------------------------------------------------------------------------------------
@@ -139,40 +131,26 @@ __device__ __forceinline__ void lab_body(const MLabEntry& E, int tile, unsigned 
   // the class-balance table of this image: {weight of target-1 voxels, weight of target-0 voxels} per channel
   if ((int)threadIdx.x < Gm.K) {
     const int i = threadIdx.x;
-    float wpos = 1.f, wneg = 1.f;
+    ClassWeights cw;
     if (E.wtab) {
-      wpos = E.wtab[2 * ((size_t)b * Gm.K + i)];
-      wneg = E.wtab[2 * ((size_t)b * Gm.K + i) + 1];
-    } else {  // k_weight_table (pea_fused_labels.h), term for term
-      const unsigned c = E.cnt[b * Gm.K + i];
-      if (c != 0 && c != (unsigned)Gm.S) {
-        double f = (double)c / (double)Gm.S;
-        f = fmin(fmax(f, 5e-2), 0.99);
-        if (f > 0.5) wneg = (float)(f / (1.0 - f));
-        else wpos = (float)((1.0 - f) / f);
-      }
+      cw.pos = E.wtab[2 * ((size_t)b * Gm.K + i)];
+      cw.neg = E.wtab[2 * ((size_t)b * Gm.K + i) + 1];
+    } else {
+      cw = class_balance(E.cnt[b * Gm.K + i], Gm.S);
     }
-    s_w[i][0] = wpos;
-    s_w[i][1] = wneg;
+    s_w[i][0] = cw.pos;
+    s_w[i][1] = cw.neg;
   }
 
   int x = 0, y = 0, z = 0, lown = 0;
-  float xc[D], G[D];
+  float xc[D], G[D] = {};
   float nrm = 0.f, inv_p = 0.f;
   if (live) {
     split_voxel(Gm, p, z, y, x);
     lown = lb[z * E.l.zs + y * E.l.ys + x * E.l.xs];
-    float ss = 0.f;
-#pragma unroll
-    for (int c = 0; c < D; ++c) {
-      xc[c] = ld(xb, c * S + p);
-      ss = fmaf(xc[c], xc[c], ss);
-    }
-    nrm = sqrtf(ss);
+    nrm = sqrtf(load_vec(xb, S, p, xc));
     inv_p = 1.0f / fmaxf(nrm, Gm.eps);  // inv_norm(ss, eps)
   }
-#pragma unroll
-  for (int c = 0; c < D; ++c) G[c] = 0.f;
   __syncthreads();  // s_w
 
   for (int i = 0; i < Gm.K; ++i) {
@@ -186,29 +164,22 @@ __device__ __forceinline__ void lab_body(const MLabEntry& E, int tile, unsigned 
         const int uz = z + sg * oz, uy = y + sg * oy, ux = x + sg * ox;
         // un-wrapped: a neighbour outside the image has no label, whatever the border does with the embedding
         const bool in = (unsigned)uz < (unsigned)Gm.Z && (unsigned)uy < (unsigned)Gm.Y && (unsigned)ux < (unsigned)Gm.X;
-        const int q = neighbour_of<BORDER>(Gm, z, y, x, sg * oz, sg * oy, sg * ox);  // -1: the pair is cropped away
+        const int q = neighbour<BORDER>(Gm, z, y, x, sg * oz, sg * oy, sg * ox);  // -1: the pair is cropped away
         const int lnb = in ? lb[uz * E.l.zs + uy * E.l.ys + ux * E.l.xs] : 0;
         const float t = target_of(lown, lnb, in, pad, fg) ? 1.f : 0.f;
         const float m = (msk && !in) ? 0.f : 1.f;
         const float w = t != 0.f ? wpos : wneg;
         float a = 0.f;
         if (q >= 0) {
-          float v[D], sq = 0.f, dot = 0.f;
-#pragma unroll
-          for (int c = 0; c < D; ++c) {
-            v[c] = ld(xb, c * S + q);
-            // (role B: the term lives at q, whose forward multiplies e(q)[c] * e(p)[c] -- the product commutes, the sum's order is c)
-            dot = fmaf(xc[c], v[c], dot);
-            sq = fmaf(v[c], v[c], sq);
-          }
-          const float inv_q = inv_norm(sq, Gm.eps);
-          a = role == 0 ? dot * inv_p * inv_q : dot * inv_q * inv_p;  // the first operand's 1 / norm first, as k_fwd_multi
-          const float r = a * m - t * m;
-          const float wr = w * r;
-          if (role == 0) contrib = wr * r;
-          const float g = gs * wr * m * inv_q;
-#pragma unroll
-          for (int c = 0; c < D; ++c) G[c] = fmaf(g, v[c], G[c]);
+          float v[D];
+          const float inv_q = inv_norm(load_vec(xb, S, q, v), Gm.eps);
+          // (role B: the term lives at q, whose forward multiplies e(q)[c] * e(p)[c] -- the product commutes, the sum's order is c)
+          const float dot = dot_vec(xc, v);
+          a = role == 0 ? dot * inv_p * inv_q : dot * inv_q * inv_p;  // the first operand's 1 / norm first, as cosine_streamed
+          float term;  // the term's share of the loss: counted where it lives, at role A's pixel
+          const float g = raw_loss_term(a, t, w, m, gs, term);
+          if (role == 0) contrib = term;
+          accumulate(G, g * inv_q, v);
         }
         if (role == 0 && ab) ab[(size_t)i * S + p] = act_affs(a, E.act);
       }
@@ -219,14 +190,7 @@ __device__ __forceinline__ void lab_body(const MLabEntry& E, int tile, unsigned 
 
   if (live) {
     const float dl = E.dloss ? E.dloss[0] : 1.f;
-    float proj = 0.f;
-#pragma unroll
-    for (int c = 0; c < D; ++c) proj = fmaf(xc[c] * inv_p, G[c], proj);
-    if (nrm < Gm.eps) proj = 0.f;  // clamp_min branch of F.normalize: d ehat / d e = I / eps
-    T* db = (T*)E.de + (size_t)b * D * S;
-    const float sc = dl * inv_p;
-#pragma unroll
-    for (int c = 0; c < D; ++c) st_rounded(db, c * S + p, (G[c] - xc[c] * inv_p * proj) * sc);  // 16-bit: rounded once, NaN kept
+    project_store<true>((T*)E.de + (size_t)b * D * S, S, p, xc, G, nrm, inv_p, Gm.eps, dl);
   }
   __syncthreads();
   if ((int)threadIdx.x < Gm.K) {
@@ -352,7 +316,7 @@ int pea_affinity_fwd_bwd_labels_multi(const PeaMultiLabels* entries, int n, unsi
     E.e = A.e; E.lab = A.labels; E.wtab = A.wtab; E.affs = A.affs; E.dloss = A.dloss; E.de = A.de;
     E.cnt = A.wtab ? nullptr : (unsigned*)scratch + cnt0[i];
     E.st = states + i;
-    for (int k = 0; k < d->K; ++k) E.gscale[k] = (float)(2.0 * (double)d->lambda[k] / normaliser(d, k));  // as make_params (pea_abi.hip)
+    for (int k = 0; k < d->K; ++k) E.gscale[k] = (float)(2.0 * (double)d->lambda[k] / normaliser(d, k));
     fill_finish(F.en[i], d, states + i, A.loss_out);
     if (!A.wtab) {  // (the launch order is kept: most tiles first)
       MCntEntry& Ce = C.en[C.n];

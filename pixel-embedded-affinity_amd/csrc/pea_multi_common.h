@@ -13,6 +13,7 @@
 
 #include "../../include/pea_multi.h"
 #include "pea_dispatch.h"
+#include "pea_gather.h"
 
 namespace pea {
 namespace multi {
@@ -42,20 +43,6 @@ struct MFinTable {
 };
 static_assert(sizeof(MFinTable) <= 4096 - 64, "the tables must fit the kernel-argument segment");
 
-// neighbour of (z, y, x) displaced by o: flat index, or -1 (CROP_ZERO, outside).  neighbour() of pea_common.h with the border known
-template <int BORDER>
-__device__ __forceinline__ int neighbour_of(const MGeom& G, int z, int y, int x, int oz, int oy, int ox) {
-  int zz = z + oz, yy = y + oy, xx = x + ox;
-  if constexpr (BORDER == PEA_BORDER_CIRCULAR) {  // the host guarantees |o| < dim
-    zz += (zz < 0) ? G.Z : 0; zz -= (zz >= G.Z) ? G.Z : 0;
-    yy += (yy < 0) ? G.Y : 0; yy -= (yy >= G.Y) ? G.Y : 0;
-    xx += (xx < 0) ? G.X : 0; xx -= (xx >= G.X) ? G.X : 0;
-  } else if ((unsigned)zz >= (unsigned)G.Z || (unsigned)yy >= (unsigned)G.Y || (unsigned)xx >= (unsigned)G.X) {
-    return -1;
-  }
-  return (zz * G.Y + yy) * G.X + xx;
-}
-
 // the launch's tile of this workgroup (XCD-aware, as logical_tile) and the entry it belongs to; false: past the last tile
 template <typename ENT>
 __device__ __forceinline__ bool find_entry(const MTable<ENT>& T, int& idx, int& tile) {
@@ -66,16 +53,6 @@ __device__ __forceinline__ bool find_entry(const MTable<ENT>& T, int& idx, int& 
     if (t >= T.en[i].g.tile0) idx = i;
   tile = t - T.en[idx].g.tile0;
   return true;
-}
-
-// st() of a value that exists as f32 BEFORE it is rounded to the storage type (the contract of include/pea.h: de16 = round(de32)).
-// Left alone the compiler folds the last multiply and the f16 conversion into one v_fma_mixlo_f16: a single rounding of the exact
-// product, one f16 ulp away from the rounded f32 result in a few of 100 000 values.  Only __half has such an instruction: the
-// f32 and the bf16 stores (a plain v_cvt_pk_bf16_f32 of the finished product) are left to the compiler.
-template <typename T>
-__device__ __forceinline__ void st_rounded(T* p, size_t i, float v) {
-  if constexpr (std::is_same<T, __half>::value) asm volatile("" : "+v"(v));
-  st(p, i, v);
 }
 
 // f(Int<v>{}) for the value a workgroup's entry has: SEL >= 0 when the whole table agrees on it, else a uniform branch over A, B(, C)
@@ -157,16 +134,7 @@ inline MGeom make_geom(const PeaDesc* d) {
   return g;
 }
 
-// N_i of include/pea.h
-inline double normaliser(const PeaDesc* d, int i) {
-  if (d->norm == PEA_NORM_BX) return (double)d->B * d->dims[2];
-  if (d->norm == PEA_NORM_FULL) return (double)d->B * d->dims[0] * d->dims[1] * d->dims[2];
-  double n = d->B;
-  for (int a = 0; a < 3; ++a) n *= (double)(d->dims[a] - abs(d->offsets[i][a]));
-  return n;
-}
-
-// the loss finish's entry i: the values make_params (pea_abi.hip) gives the single calls
+// the loss finish's entry i
 inline void fill_finish(MFinEntry& Fe, const PeaDesc* d, LossState* st, float* loss_out) {
   Fe.st = st; Fe.loss_out = loss_out; Fe.K = d->K;
   for (int k = 0; k < d->K; ++k) {

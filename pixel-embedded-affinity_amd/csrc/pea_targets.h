@@ -88,18 +88,11 @@ static __global__ __launch_bounds__(256) void k_gen_targets(const GParams G, con
 static __global__ __launch_bounds__(256) void k_gen_weights(const GParams G, const float* __restrict__ target,
                                                      const unsigned* __restrict__ counts, float* __restrict__ weight) {
   const int bi = blockIdx.y;  // b * K + i
-  const unsigned n = counts[bi];
-  float wpos = 1.f, wneg = 1.f;
-  if (n != 0 && n != (unsigned)G.S) {
-    double f = (double)n / (double)G.S;
-    f = fmin(fmax(f, 5e-2), 0.99);
-    if (f > 0.5) wneg = (float)(f / (1.0 - f));
-    else wpos = (float)((1.0 - f) / f);
-  }
+  const ClassWeights cw = class_balance(counts[bi], G.S);
   const int p = blockIdx.x * 256 + threadIdx.x;
   if (p < G.S) {
     const size_t o = (size_t)bi * G.S + p;
-    weight[o] = target[o] != 0.f ? wpos : wneg;
+    weight[o] = target[o] != 0.f ? cw.pos : cw.neg;
   }
 }
 
