@@ -1,18 +1,11 @@
 // pea_k_head16.hip -- entry points of the embedding head on 16-bit features (include/pea_head16.h): validation and the choice of
-// the storage type.  The kernels (pea_head16.h) live in pea_k_head16_f16.hip / pea_k_head16_bf16.hip.
+// the storage type.  The kernels (pea_head.h) live in pea_k_head16_f16.hip / pea_k_head16_bf16.hip.
 // One translation unit of libpea_hip.so (pea_host.h).
-#include "pea_head16.h"
+#include "pea_head.h"
 
 #include "../../include/pea_head16.h"
 
 using namespace pea;
-
-static bool head16_pair(int C, int D) {
-#define PEA_HEAD16_Q(c, d) if (C == c && D == d) return true;
-  PEA_HEAD16_CASES(PEA_HEAD16_Q)
-#undef PEA_HEAD16_Q
-  return false;
-}
 
 static bool dtype_known(int t) { return t == PEA_F32 || t == PEA_F16 || t == PEA_BF16; }
 
@@ -21,7 +14,7 @@ extern "C" {
 int pea_head_supported_t(int C, int D, int x_dtype, int e_dtype) {
   if (x_dtype != PEA_F16 && x_dtype != PEA_BF16) return 0;      // f32 features: pea_head_fwd / pea_head_bwd
   if (e_dtype != x_dtype && e_dtype != PEA_F32) return 0;       // mixed f16 / bf16
-  return head16_pair(C, D) ? 1 : 0;
+  return head_supported(C, D) ? 1 : 0;
 }
 
 int pea_head_fwd_t(int B, int C, int D, size_t S, const void* x, int x_dtype, const float* W, const float* bias, void* e, int e_dtype,

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""The embedding head on 16-bit features (include/pea_head16.h, csrc/pea_head16.h) against the f32 head and against torch's convolution
+"""The embedding head on 16-bit features (include/pea_head16.h, csrc/pea_head.h) against the f32 head and against torch's convolution
 under autocast, timed in ONE process at the shapes of the reference's heads:
 
   cvppp_B8     8 x 32 -> 16 x 544^2        (OutConv, CVPPP)
@@ -141,7 +141,7 @@ def main():
         del steps, keep
         torch.cuda.empty_cache()
     out = {"kernel_form": "two x-adjacent pixels per lane as one dword (S even, 4-byte aligned tensors), rows kept packed in registers, "
-                          "dW on v_mfma_f32_16x16x4_f32 after widening (csrc/pea_head16.h)",
+                          "dW on v_mfma_f32_16x16x4_f32 after widening (csrc/pea_head.h)",
            "torch": "F.conv2d / F.conv3d under torch.autocast on the 16-bit features with f32 parameters; backward = autograd.grad(x, weight, bias)",
            "batches": a.batches, "reps_per_batch": a.reps, "warmup": a.warmup, "us_per_call": rows, "device": torch.cuda.get_device_name(0)}
     if a.out and not a.only:

@@ -1,4 +1,4 @@
-"""GPU (-m gpu): the embedding head on 16-bit features -- pea_head_fwd_t / pea_head_bwd_t (include/pea_head16.h, csrc/pea_head16.h) and
+"""GPU (-m gpu): the embedding head on 16-bit features -- pea_head_fwd_t / pea_head_bwd_t (include/pea_head16.h, csrc/pea_head.h) and
 the Python layer on top of them (model/head.py, harness/head_loss.py).
 
 The C ABI runs on all twelve (C, D) pairs, both 16-bit types, the embedding in the same type and in f32, B = 2, inside a guard-banded
