@@ -116,6 +116,31 @@ extern "C" {
                                   pea_affinity_fwd_dual_ex (pea_cross_supported(desc, 5) == 0) and the three labels-in calls.  The L2 mode
                                   of loss_embedding_norm.py equals (1 + cos) / 2 for unit vectors only: at a pixel with |e| < eps
                                   F.normalize yields a non-unit vector and the two differ there; the library computes the cosine form */
+#define PEA_FLAG_LOSS_BCE 128u  /* the criterion of the PEA_FLAG_LOSS_ACT loss is the weighted BINARY CROSS-ENTROPY instead of the squared
+                                  residual: loss/loss.py:134-152 BCELoss / WeightedBCE (F.binary_cross_entropy(pred * mask, target * mask,
+                                  weight), the reference's `loss_func: BCELoss | WeightedBCELoss`, scripts_cvppp/main.py:182-189).  Valid only
+                                  together with PEA_FLAG_LOSS_ACT | PEA_FLAG_CLAMP01 (the argument must lie in [0, 1]), with or without
+                                  HALF_SHIFT; any other combination: PEA_E_DESC from pea_desc_validate and every entry point.  With u, v, s of
+                                  the LOSS_ACT comment, x = u m and y = t m, for every EXISTING pair:
+                                      l_i(p) = -w [ y max(log x, -100) + (1 - y) max(log1p(-x), -100) ],   L_i = sum l_i / N_i,
+                                      g_i(p) = lambda_i w (x - y) / max(x (1 - x), 1e-12) m s / N_i
+                                  -- the forward is torch's (logs clamped at -100), the gradient torch's own BCE backward (epsilon 1e-12, NOT
+                                  the derivative of the clamped logs) folded with the mask and the activation's slope; all in f32 (logf,
+                                  log1pf).  N_i is desc->norm's (torch's mean over [B,H,W] is PEA_NORM_FULL).  g_out is still d loss / d a(raw):
+                                  the backward and inference calls ignore the bit, as they ignore LOSS_ACT.
+                                    cropped pairs  a cropped-away pair has no term and g = 0;
+                                    mask zero      m = 0 gives l = 0 and g = 0 (by the formula: x = y = 0; no special case);
+                                    soft targets   any t in [0, 1] is served by the same formula;
+                                    f32 masks      with PEA_FLAG_MASK_F32 m must lie in [0, 1]; outside it the loss is unspecified (NaN or
+                                                   not), nothing faults;
+                                    non-finite e   a NaN u gives a NaN loss and g = 0 on that pair (u == v is false there: the
+                                                   LOSS_ACT | CLAMP01 rule above);
+                                    loss partials  through the integer accumulators unchanged: every term is at most 100 w;
+                                    loss finish    unchanged; the gradient's scale is lambda_i / N_i (no factor 2: that is the squared residual's).
+                                  Entry points without a LOSS_ACT form refuse the bit with it: pea_affinity_fwd_dual_ex and the labels-in
+                                  calls return PEA_E_UNSUPPORTED, pea_multi_supported and pea_infer_stitch_supported answer 0.  Kernels: the
+                                  f32 LDS-DMA cross forwards (self and detached second operand, D = 16 / 32 / 64, 2D) and the direct kernels
+                                  (everything else, 16-bit storage included) */
 
 /* error codes: 0 = ok, negative = PEA_E_*, positive = a hipError_t from the runtime */
 #define PEA_OK 0

@@ -13,7 +13,7 @@ from . import _lib
 from ._lib import PeaLibraryError, build
 from .affinity_op import (AffinityMap, AffinitySpec, FusedAffinityMSE, Graphed, LabelsAffinityMSE, MultiAffinityMSE, MultiLabelsAffinityMSE, affinity_infer, backward,
                           check_label_ranges, graphed, unflip)
-from .loss.loss import WeightedMSE
+from .loss.loss import BCELoss, MSELoss, WeightedBCE, WeightedMSE
 from .loss.loss_embedding_mse import (ema_embedding_loss, ema_embedding_loss_from_labels, embedding2affs, embedding_loss,
                                       embedding_loss_from_labels, embedding_loss_from_labels_multi, embedding_loss_multi)
 from .loss import loss_embedding, loss_embedding_exp, loss_embedding_norm
@@ -44,7 +44,7 @@ from .harness.loss_section import (ac3ac4_loss_section, ac3ac4_loss_section_comp
                                    finish_pred_2d_, finish_pred_3d_)
 
 __all__ = [
-    "PeaLibraryError", "build", "backward", "graphed", "Graphed", "check_label_ranges", "AffinityMap", "AffinitySpec", "FusedAffinityMSE", "affinity_infer", "WeightedMSE",
+    "PeaLibraryError", "build", "backward", "graphed", "Graphed", "check_label_ranges", "AffinityMap", "AffinitySpec", "FusedAffinityMSE", "affinity_infer", "WeightedMSE", "WeightedBCE", "BCELoss", "MSELoss",
     "embedding_loss", "ema_embedding_loss", "embedding2affs", "embedding_loss_norm1", "embedding_loss_norm5",
     "ema_embedding_loss_norm1", "ema_embedding_loss_norm5", "inf_embedding_loss_norm1", "inf_embedding_loss_norm5",
     "gen_offsets", "multi_offset", "fill_border_relu_", "relu_", "cvppp_loss_section", "ac3ac4_loss_section",

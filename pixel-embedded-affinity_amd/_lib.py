@@ -30,6 +30,7 @@ NORM_BX, NORM_CROPPED, NORM_FULL = 0, 1, 2
 FLAG_RELU_AFFS, FLAG_ONE_MINUS, FLAG_HALF_SHIFT, FLAG_CLAMP01, FLAG_ACCUMULATE_DE = 1, 2, 4, 8, 16  # activation of the affs output (include/pea.h)
 FLAG_MASK_F32 = 32  # the mask of the training forwards holds f32 values (include/pea.h PEA_FLAG_MASK_F32)
 FLAG_LOSS_ACT = 64  # the loss of the training forwards is taken on the activated map (include/pea.h PEA_FLAG_LOSS_ACT)
+FLAG_LOSS_BCE = 128  # with FLAG_LOSS_ACT | FLAG_CLAMP01: that loss is the weighted binary cross-entropy (include/pea.h PEA_FLAG_LOSS_BCE)
 RULES_U8, RULES_I32, RULES_I64, RULES_F32 = 0, 1, 2, 3  # element type of the rules table (include/pea_flip.h PEA_RULES_*)
 TGT_PADDING, TGT_BOTH_FOREGROUND, TGT_MASK_INSIDE, TGT_ACCUMULATE = 1, 2, 4, 8
 METRICS_COLS = 5  # mse, bce, tp, fp, fn (include/pea_metrics.h PEA_METRICS_COLS)

@@ -297,7 +297,9 @@ def unflip(t, rules):
 class FusedAffinityMSE(torch.autograd.Function):
     """loss, affs, per_offset_losses = f(e, e_other, target, weight, mask): the WeightedMSE criterion fused into the affinity
     forward.  One forward launch (saving g = d loss / d affs and, for the self loss, the 1 / norm plane of e) and one backward
-    launch.  (Round 1 also had an opt-in one-launch step on this tensor path, PEA_FUSED=1; it sampled target / weight / mask at
+    launch.  Despite its name it carries either criterion of the loss on the activated map: with FLAG_LOSS_ACT | FLAG_LOSS_BCE in
+    spec.act the forward's epilogue takes the weighted binary cross-entropy instead of the squared residual (include/pea.h); the
+    backward only ever sees g.  (Round 1 also had an opt-in one-launch step on this tensor path, PEA_FUSED=1; it sampled target / weight / mask at
     p and at p - o with one-dword loads, only ever tied the two launches and is gone -- the one-launch step that pays is the
     labels-in one, LabelsAffinityMSE below.)"""
 

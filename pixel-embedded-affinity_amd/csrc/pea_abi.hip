@@ -37,6 +37,8 @@ int validate(const PeaDesc* d) {
   if (d->flags & PEA_FLAG_LOSS_ACT) {  // the loss on the activated map: half shift and / or clamp, nothing else (include/pea.h)
     if (!(d->flags & (PEA_FLAG_HALF_SHIFT | PEA_FLAG_CLAMP01)) || (d->flags & (PEA_FLAG_RELU_AFFS | PEA_FLAG_ONE_MINUS))) return PEA_E_DESC;
   }
+  // binary cross-entropy: on the activated, clamped map only (its argument must lie in [0, 1])
+  if ((d->flags & PEA_FLAG_LOSS_BCE) && (~d->flags & (PEA_FLAG_LOSS_ACT | PEA_FLAG_CLAMP01))) return PEA_E_DESC;
   const long long S = (long long)d->dims[0] * d->dims[1] * d->dims[2];
   if (S > 0x7fffffffLL - kBlock) return PEA_E_UNSUPPORTED;
   if ((S + kBlock - 1) / kBlock * (long long)d->B > 0x7fffff00LL) return PEA_E_UNSUPPORTED;
@@ -184,6 +186,7 @@ int pea_affinity_fwd_ex(const PeaDesc* desc, const void* e, const void* e_other,
   A.st = (LossState*)workspace; A.loss_out = loss_out; A.inv_out = inv_norm_out;
   A.dtype = desc->dtype; A.train = true; A.mf32 = mask && (desc->flags & PEA_FLAG_MASK_F32);
   A.lact = (desc->flags & PEA_FLAG_LOSS_ACT) != 0;
+  A.bce = (desc->flags & PEA_FLAG_LOSS_BCE) != 0;
   rc = run_fwd(P, A, s);
   if (rc) return rc;
   if (e_other && e_other == e && inv_norm_out) {

@@ -108,6 +108,19 @@ __device__ __forceinline__ float act_u(float v, const ActK& k) { return clamp_ke
 // g of a term whose raw-cosine form is gs_sc * wr * m, gs_sc = gscale * ActK::sc (exact: sc is a power of two)
 __device__ __forceinline__ float act_g(float u, float v, float gs_sc, float wr, float m, const ActK& k) { return u == v ? gs_sc * wr * m : k.gz; }
 
+// PEA_FLAG_LOSS_BCE (the BCE instantiations of the LACT forwards: k_fwd_direct, k_fwd_xdma): the criterion on x = u m, y = t m is the
+// weighted binary cross-entropy of F.binary_cross_entropy -- both logs clamped at -100 (a select: NaN stays NaN), log1p for the second --
+// and the returned factor is torch's own BCE backward, w (x - y) / max(x (1 - x), 1e-12); the caller hands it to act_g as `wr` with
+// gs_sc = lambda / N * ActK::sc (no factor 2).  Stated once so that the direct and the cross kernel give the same bits of g and contrib
+// for the same a: explicit fmaf (no contraction left to the context), IEEE division, logf / log1pf (not the fast intrinsics).
+// m = 0: x = y = 0, contrib = -w (0 * -100 + 1 * log1p(-0)) = 0 and the factor is 0 / 1e-12 = 0.  x = 0, y = 1: contrib = 100 w exactly.
+__device__ __forceinline__ float bce_log(float l) { return l < -100.0f ? -100.0f : l; }
+__device__ __forceinline__ float bce_term(float x, float y, float w, float& contrib) {
+  const float lx = bce_log(logf(x)), l1 = bce_log(log1pf(-x));
+  contrib = -w * fmaf(y, lx, (1.0f - y) * l1);
+  return (x - y) / fmaxf(x * (1.0f - x), 1e-12f) * w;
+}
+
 __device__ __forceinline__ float inv_norm(float ss, float eps) { return 1.0f / fmaxf(sqrtf(ss), eps); }
 
 __device__ __forceinline__ float wave_sum(float v) {

@@ -14,8 +14,9 @@ namespace pea {
 // forward (direct form): affs, (TRAIN) per-workgroup loss partials and g = d loss / d affs
 //   D_T > 0: channels unrolled, own pixel kept in registers;  D_T == 0: generic D, own pixel re-read (L1)
 // ------------------------------------------------------------------------------------------------
-// MT: the mask, u8 or f32 (PEA_FLAG_MASK_F32);  LACT: the loss on the activated map (PEA_FLAG_LOSS_ACT, act_u)
-template <typename T, int D_T, bool TRAIN, typename MT = uint8_t, bool LACT = false>
+// MT: the mask, u8 or f32 (PEA_FLAG_MASK_F32);  LACT: the loss on the activated map (PEA_FLAG_LOSS_ACT, act_u);  BCE: with LACT, binary
+// cross-entropy instead of the squared residual (PEA_FLAG_LOSS_BCE, bce_term)
+template <typename T, int D_T, bool TRAIN, typename MT = uint8_t, bool LACT = false, bool BCE = false>
 __global__ __launch_bounds__(kBlock) void k_fwd_direct(const KParams P, const T* __restrict__ e,
                                                        const T* __restrict__ eo,
                                                        const float* __restrict__ target,
@@ -23,6 +24,7 @@ __global__ __launch_bounds__(kBlock) void k_fwd_direct(const KParams P, const T*
                                                        const MT* __restrict__ mask,
                                                        float* __restrict__ affs, float* __restrict__ gout,
                                                        LossState* __restrict__ st) {
+  static_assert(!BCE || LACT, "binary cross-entropy is taken on the activated map");
   extern __shared__ float s_acc[];  // [K][kBlock], TRAIN only
   const int tile = logical_tile(P);
   if (tile >= P.tiles) return;  // whole workgroup exits together (tile is uniform)
@@ -80,10 +82,15 @@ __global__ __launch_bounds__(kBlock) void k_fwd_direct(const KParams P, const T*
           if constexpr (LACT) {  // the loss on the activated value; its slope goes into g
             const ActK AK = act_consts(P.flags & kActMask);
             const float v = act_v(a, AK), u = act_u(v, AK);
-            const float r = u * m - t * m;
-            const float wr = w * r;
-            contrib = wr * r;
-            g = act_g(u, v, P.gscale[i] * AK.sc, wr, m, AK);
+            if constexpr (BCE) {
+              const float bt = bce_term(u * m, t * m, w, contrib);
+              g = act_g(u, v, P.lam[i] * P.inv_n[i] * AK.sc, bt, m, AK);
+            } else {
+              const float r = u * m - t * m;
+              const float wr = w * r;
+              contrib = wr * r;
+              g = act_g(u, v, P.gscale[i] * AK.sc, wr, m, AK);
+            }
           } else {
             g = raw_loss_term(a, t, w, m, P.gscale[i], contrib);
           }

@@ -50,4 +50,14 @@ inline auto with_mask_form(bool mf32, bool lact, F&& f) {
   return with_bool(lact, [&](auto la) { return mf32 ? f(Tag<float>{}, la) : f(Tag<uint8_t>{}, la); });
 }
 
+// f(Tag<MT>{}, LACT, BCE): with_mask_form and PEA_FLAG_LOSS_BCE; the criterion exists on the activated map only (pea_desc_validate), so
+// BCE without LACT is never instantiated
+template <typename F>
+inline auto with_loss_form(bool mf32, bool lact, bool bce, F&& f) {
+  return with_mask_form(mf32, lact, [&](auto mt, auto la) {
+    if constexpr (la.value) return bce ? f(mt, la, std::true_type{}) : f(mt, la, std::false_type{});
+    else return f(mt, la, std::false_type{});
+  });
+}
+
 }  // namespace pea

@@ -140,6 +140,8 @@ struct FwdArgs {
   bool train;
   bool mf32;            // m != NULL holds f32 (PEA_FLAG_MASK_F32): the families without an f32-mask form decline the call
   bool lact;            // training: the loss on the activated map (PEA_FLAG_LOSS_ACT); families without the form decline the call
+  bool bce;             // training, with lact: binary cross-entropy instead of the squared residual (PEA_FLAG_LOSS_BCE); the f32 cross
+                        // forwards and the direct kernels have the form, every other family declines the call
 };
 // Each returns true if it launched (the caller then launches the loss finish).
 bool xdma_fwd_self(const KParams& P, const FwdArgs& A, hipStream_t s);

@@ -59,7 +59,7 @@ bool box_supported(const KParams& P, int dtype) {
 
 bool box_fwd(const KParams& P, const FwdArgs& A, hipStream_t s) {
   if (A.dtype != PEA_F32 || P.D != 16 || A.eo != A.e || !env().box || env().force_direct) return false;
-  if (A.train && (A.mf32 || A.lact)) return false;  // no f32-mask / PEA_FLAG_LOSS_ACT form: those take the tiled kernels
+  if (A.train && (A.mf32 || A.lact || A.bce)) return false;  // no f32-mask / PEA_FLAG_LOSS_ACT / _BCE form: those take the tiled or direct kernels
   if (misaligned(A.e, 16) || misaligned(A.t, 16) || misaligned(A.w, 16) || misaligned(A.affs, 16) || misaligned(A.gout, 16) ||
       misaligned(A.m, 4) || misaligned(A.inv_out, 4))
     return false;

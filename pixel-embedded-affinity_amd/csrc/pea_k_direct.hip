@@ -118,17 +118,17 @@ void launch_loss_state_init(LossState* st, int n, hipStream_t s) {
 
 // ---- direct kernels ---------------------------------------------------------------------------------------------------------
 namespace {
-template <typename T, bool TRAIN, typename MT = uint8_t, bool LACT = false>
+template <typename T, bool TRAIN, typename MT = uint8_t, bool LACT = false, bool BCE = false>
 void fwd_direct(const KParams& P, const FwdArgs& A, hipStream_t s) {
   const T *ep = (const T*)A.e, *op = (const T*)A.eo;
   const MT* m = (const MT*)(const void*)A.m;
   const size_t lds = TRAIN ? (size_t)P.K * kBlock * sizeof(float) : 0;
   const dim3 g((unsigned)(P.tiles_per_xcd * kXcd)), blk(kBlock);
   switch (P.D) {
-    case 16: hipLaunchKernelGGL((k_fwd_direct<T, 16, TRAIN, MT, LACT>), g, blk, lds, s, P, ep, op, A.t, A.w, m, A.affs, A.gout, A.st); break;
-    case 32: hipLaunchKernelGGL((k_fwd_direct<T, 32, TRAIN, MT, LACT>), g, blk, lds, s, P, ep, op, A.t, A.w, m, A.affs, A.gout, A.st); break;
-    case 64: hipLaunchKernelGGL((k_fwd_direct<T, 64, TRAIN, MT, LACT>), g, blk, lds, s, P, ep, op, A.t, A.w, m, A.affs, A.gout, A.st); break;
-    default: hipLaunchKernelGGL((k_fwd_direct<T, 0, TRAIN, MT, LACT>), g, blk, lds, s, P, ep, op, A.t, A.w, m, A.affs, A.gout, A.st); break;
+    case 16: hipLaunchKernelGGL((k_fwd_direct<T, 16, TRAIN, MT, LACT, BCE>), g, blk, lds, s, P, ep, op, A.t, A.w, m, A.affs, A.gout, A.st); break;
+    case 32: hipLaunchKernelGGL((k_fwd_direct<T, 32, TRAIN, MT, LACT, BCE>), g, blk, lds, s, P, ep, op, A.t, A.w, m, A.affs, A.gout, A.st); break;
+    case 64: hipLaunchKernelGGL((k_fwd_direct<T, 64, TRAIN, MT, LACT, BCE>), g, blk, lds, s, P, ep, op, A.t, A.w, m, A.affs, A.gout, A.st); break;
+    default: hipLaunchKernelGGL((k_fwd_direct<T, 0, TRAIN, MT, LACT, BCE>), g, blk, lds, s, P, ep, op, A.t, A.w, m, A.affs, A.gout, A.st); break;
   }
 }
 
@@ -172,8 +172,11 @@ void direct_fwd(const KParams& P, const FwdArgs& A, hipStream_t s) {
   with_storage(A.dtype, [&](auto st) {
     using T = typename decltype(st)::type;
     if (!A.train) return fwd_direct<T, false>(P, A, s);
-    // an f32 mask (PEA_FLAG_MASK_F32) and the loss on the activated map (PEA_FLAG_LOSS_ACT: the catch-all of every descriptor): training only
-    with_mask_form(A.mf32, A.lact, [&](auto mt, auto lact) { fwd_direct<T, true, typename decltype(mt)::type, lact.value>(P, A, s); });
+    // an f32 mask (PEA_FLAG_MASK_F32), the loss on the activated map (PEA_FLAG_LOSS_ACT) and its binary cross-entropy form
+    // (PEA_FLAG_LOSS_BCE) -- the catch-all of every descriptor: training only
+    with_loss_form(A.mf32, A.lact, A.bce, [&](auto mt, auto lact, auto bce) {
+      fwd_direct<T, true, typename decltype(mt)::type, lact.value, bce.value>(P, A, s);
+    });
   });
 }
 

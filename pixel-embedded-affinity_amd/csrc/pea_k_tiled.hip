@@ -169,6 +169,7 @@ bool bwd_roles(const KParams& P, int roles, const void* x, const void* nbA, cons
 bool tiled_fwd(const KParams& P, const FwdArgs& A, hipStream_t s, bool* wrote_inv) {
   *wrote_inv = false;
   if (env().force_direct) return false;
+  if (A.train && A.bce) return false;  // no PEA_FLAG_LOSS_BCE form in the tiled / chunked forwards: the direct kernels take it
   const FwdT T_ = {A.e, A.eo, A.t, A.w, A.m, A.affs, A.gout, A.st, A.inv_out, A.train && A.mf32, A.train && A.lact};
   return with_storage(A.dtype, [&](auto st) {
     return with_bool(A.train, [&](auto train) { return fwd_any<typename decltype(st)::type, train.value>(P, T_, s, wrote_inv); });

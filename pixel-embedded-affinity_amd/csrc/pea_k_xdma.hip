@@ -16,7 +16,10 @@ bool fwd_self(const KParams& P, const FwdArgs& A, hipStream_t s) {
   if (TRAIN && ((P.tbs | P.wbs | P.mbs) & 3)) return false;
   XPlan X;
   bool z3 = false, wg3 = false;
-  if (env().fwd_wg3 && plan(P, kXdmaPSUF, 1, &X) && X.C.nfz == 0) {
+  // (binary cross-entropy with an f32 mask does not fit the 80 VGPRs of three workgroups per CU -- 5 to 8 registers spilled -- and is
+  //  not instantiated there: two workgroups per CU, 118 / 120 VGPRs)
+  const bool bce_mf = TRAIN && A.lact && A.bce && A.mf32;
+  if (env().fwd_wg3 && !bce_mf && plan(P, kXdmaPSUF, 1, &X) && X.C.nfz == 0) {
     wg3 = true;
   } else if (!plan(P, kXdmaPSU, 1, &X) || X.C.nfz > 0) {
     if (D_T != 16 || !plan(P, kXdmaPSU3F, 1, &X) || X.C.nfz == 0) return false;
@@ -34,10 +37,11 @@ bool fwd_self(const KParams& P, const FwdArgs& A, hipStream_t s) {
   // the f32-mask and LOSS_ACT forms are built for 2D training only (TRAIN, ZF = 0): every other call with them was declined above
   auto go = [&](auto psu, auto zf, auto wpe) {
     return with_bool(P.border != PEA_BORDER_CIRCULAR, [&](auto crop) {
-      return with_mask_form(mf, la, [&](auto mt, auto lact) {
+      return with_loss_form(mf, la, la && A.bce, [&](auto mt, auto lact, auto bce) {
         using MT = typename decltype(mt)::type;
-        if constexpr ((std::is_same<MT, uint8_t>::value && !lact.value) || (TRAIN && zf.value == 0))
-          return launch<k_fwd_xdma<D_T, kXdmaTH, kXdmaTW, psu.value, crop.value, TRAIN, zf.value, false, wpe.value, false, MT, lact.value>>(
+        constexpr bool kSpills = bce.value && wpe.value == 6 && std::is_same<MT, float>::value;  // (bce_mf above: never asked for)
+        if constexpr (((std::is_same<MT, uint8_t>::value && !lact.value) || (TRAIN && zf.value == 0)) && !kSpills)
+          return launch<k_fwd_xdma<D_T, kXdmaTH, kXdmaTW, psu.value, crop.value, TRAIN, zf.value, false, wpe.value, false, MT, lact.value, bce.value>>(
               grid, blk, X.lds, s, P, C, e, t, w, (const MT*)(const void*)A.m, A.affs, A.gout, A.st, A.inv_out, (const float*)nullptr,
               (float*)nullptr, LabArgs{});
         else return false;
@@ -143,9 +147,10 @@ static bool fwd_other_wide(const KParams& P, const FwdArgs& A, hipStream_t s) {
   const size_t lds = X.lds + (size_t)6 * 2048;  // + the own tiles: three buffers x two channels x 2 KB
   const dim3 grid((unsigned)(X.C.tiles_per_xcd * kXcd)), blk(kXdmaTH * kXdmaTW);
   return with_bool(P.border != PEA_BORDER_CIRCULAR, [&](auto crop) {
-    return with_mask_form(A.mf32, A.lact, [&](auto mt, auto lact) {  // lact: the loss on the activated map (PEA_FLAG_LOSS_ACT)
+    // lact: the loss on the activated map (PEA_FLAG_LOSS_ACT); bce: its binary cross-entropy form (PEA_FLAG_LOSS_BCE)
+    return with_loss_form(A.mf32, A.lact, A.bce, [&](auto mt, auto lact, auto bce) {
       using MT = typename decltype(mt)::type;
-      return launch<k_fwd_xdma<D_T, kXdmaTH, kXdmaTW, kXdmaPSUF, crop.value, true, 0, true, 4, false, MT, lact.value>>(
+      return launch<k_fwd_xdma<D_T, kXdmaTH, kXdmaTW, kXdmaPSUF, crop.value, true, 0, true, 4, false, MT, lact.value, bce.value>>(
           grid, blk, lds, s, P, X.C, e_other, A.t, A.w, (const MT*)(const void*)A.m, A.affs, A.gout, A.st, A.inv_out, e,
           A.inv_out + (size_t)P.B * P.S, LabArgs{});
     });
@@ -177,10 +182,10 @@ bool xdma_fwd_other(const KParams& P, const FwdArgs& A, hipStream_t s) {
   // the f32-mask and the loss on the activated map (PEA_FLAG_LOSS_ACT) are 2D forms (ZF = 0): z3 with them was declined above
   auto go = [&](auto psu, auto zf) {
     return with_bool(P.border != PEA_BORDER_CIRCULAR, [&](auto crop) {
-      return with_mask_form(A.mf32, A.lact, [&](auto mt, auto lact) {
+      return with_loss_form(A.mf32, A.lact, A.bce, [&](auto mt, auto lact, auto bce) {
         using MT = typename decltype(mt)::type;
         if constexpr ((std::is_same<MT, uint8_t>::value && !lact.value) || zf.value == 0)
-          return launch<k_fwd_xdma<16, kXdmaTH, kXdmaTW, psu.value, crop.value, true, zf.value, true, 4, false, MT, lact.value>>(
+          return launch<k_fwd_xdma<16, kXdmaTH, kXdmaTW, psu.value, crop.value, true, zf.value, true, 4, false, MT, lact.value, bce.value>>(
               grid, blk, X.lds, s, P, X.C, e_other, A.t, A.w, (const MT*)(const void*)A.m, A.affs, A.gout, A.st, A.inv_out, e,
               A.inv_out + (size_t)P.B * P.S, LabArgs{});
         else return false;

@@ -168,6 +168,7 @@ bool bwd_other_h(const KParams& P, const T* e, const T* eo, const float* inv2, c
 
 bool xdma_h_fwd_other(const KParams& P, const FwdArgs& A, hipStream_t s) {
   if (A.dtype != PEA_BF16 && !env().h16_hw) return false;
+  if (A.bce) return false;  // no PEA_FLAG_LOSS_BCE form in the 16-bit cross forwards: the direct kernels take it
   return with_bool(A.dtype == PEA_BF16, [&](auto bf) {
     using T = std::conditional_t<bf.value, __bf16, __half>;
     return with_width<16, 32, 64>(P.D, [&](auto d) { return fwd_other_h<T, d.value>(P, A, s); });
@@ -187,6 +188,7 @@ bool xdma_h_bwd_other(const KParams& P, int dtype, const void* e, const void* e_
 
 // entry points used by pea_k_xdma.hip's dispatchers
 bool xdma_h_fwd_self(const KParams& P, const FwdArgs& A, hipStream_t s) {
+  if (A.train && A.bce) return false;  // no PEA_FLAG_LOSS_BCE form in the 16-bit cross forwards: the direct kernels take it
   return with_bool(A.dtype == PEA_BF16, [&](auto bf) {
     using T = std::conditional_t<bf.value, __bf16, __half>;
     return with_width<16, 32, 64>(P.D, [&](auto d) {

@@ -76,7 +76,7 @@ bool plan(const KParams& P, int mode, ZPlan* out) {
 // forward / inference of the self loss on a 3D volume (f32, D = 16, CROP_ZERO, every z offset in {-1 .. -4}); true = launched
 bool zmarch_fwd(const KParams& P, const FwdArgs& A, hipStream_t s) {
   if (env().force_direct || !env().fwd_xdma || A.eo != A.e || A.dtype != PEA_F32) return false;
-  if (A.train && (A.mf32 || A.lact)) return false;  // (3D: no f32-mask form, no PEA_FLAG_LOSS_ACT form)
+  if (A.train && (A.mf32 || A.lact || A.bce)) return false;  // (3D: no f32-mask form, no PEA_FLAG_LOSS_ACT / _BCE form)
   const float* e = (const float*)A.e;
   if (misaligned(e, 16) || misaligned(A.t, 16) || misaligned(A.w, 16) || misaligned(A.affs, 16) || misaligned(A.gout, 16) ||
       misaligned(A.m, 4) || misaligned(A.inv_out, 4))

@@ -694,7 +694,7 @@ struct LabArgs {
   unsigned lflags;        // PEA_TGT_*
 };
 template <int D_T, int TH, int TW, int PSU, bool CROP, bool TRAIN, int ZF = 0, bool OTHER = false, int WPE = 4, bool LAB = false,
-          typename MT = uint8_t, bool LACT = false>
+          typename MT = uint8_t, bool LACT = false, bool BCE = false>
 __global__ __launch_bounds__(TH* TW, WPE) void k_fwd_xdma(const KParams P, const XParams C, const float* __restrict__ e,
                                                            const float* __restrict__ target, const float* __restrict__ weight,
                                                            const MT* __restrict__ mask, float* __restrict__ affs,
@@ -708,6 +708,7 @@ __global__ __launch_bounds__(TH* TW, WPE) void k_fwd_xdma(const KParams P, const
   static_assert(!OWNL || ZF == 0, "cross-loss instantiation at D > 16: in-plane");
   static_assert(!LAB || (TRAIN && ZF == 0 && !OTHER), "labels-in instantiation: 2D self loss");
   static_assert(!LACT || (TRAIN && ZF == 0 && !LAB), "loss on the activated map (PEA_FLAG_LOSS_ACT, act_u): 2D training forwards");
+  static_assert(!BCE || LACT, "binary cross-entropy (PEA_FLAG_LOSS_BCE, bce_term) is taken on the activated map");
   constexpr int NT = TH * TW, PS = PSU * 256, NP = D_T / 2, TP = NT, QP = TP / 4, NSL = QP / 64;
   constexpr int KMAX = ZF > 0 ? kXP + 2 : kXP;      // channels the epilogue handles (norm5: 8 in-plane + 4 z offsets)
   constexpr int ITEMS = (KMAX * QP + NT - 1) / NT;
@@ -1075,12 +1076,24 @@ __global__ __launch_bounds__(TH* TW, WPE) void k_fwd_xdma(const KParams P, const
     if (TRAIN) {
       float acc = 0.f;
       f4 g4;
-      const float gs = C.gs[sl];
+      const float gs = BCE ? P.lam[sl] * P.inv_n[sl] : C.gs[sl];  // BCE: lambda / N, without the squared residual's factor 2
       const int ax_ = C.oax[sl], od_ = C.od[sl];
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
         const float m = mq_get<MT>(m4[it], j);
         const float u = LACT ? act_u(v4[j], AK) : v4[j];
+        if constexpr (BCE) {  // the same epilogue with bce_term's (contrib, factor) in place of (wr * r, wr)
+          float l, bt = bce_term(u * m, t4[it][j] * m, w4[it][j], l);
+          if (CROP) {
+            const int q = (ax_ == 1 ? igx[it] + j : ax_ == 0 ? igy[it] : z) + od_;
+            const bool in = (unsigned)q < (unsigned)(ax_ == 1 ? P.X : ax_ == 0 ? P.Y : P.Z);
+            bt = in ? bt : 0.f;
+            l = in ? l : 0.f;
+          }
+          g4[j] = act_g(u, v4[j], gs * AK.sc, bt, m, AK);
+          acc += l;
+          continue;
+        }
         const float r = u * m - t4[it][j] * m;
         float wr = w4[it][j] * r;
         if (CROP) {  // a cropped-away neighbour carries no loss term (its a is already 0)

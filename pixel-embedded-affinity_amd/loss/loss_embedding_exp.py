@@ -1,7 +1,7 @@
 """Drop-in for the reference's scripts_cvppp/loss/loss_embedding_exp.py (the same file under scripts_bbbc039v1/loss/): same function
 names, argument order, defaults and return values.  The loss is taken on u = clamp(cos, 0, 1) with nn.CosineSimilarity's norm
 clamp (eps = 1e-6); `affs0_weight` scales the first two offsets; -> (loss, affs) with affs = u, un-masked.  The reference module
-has no EMA variant.  One fused forward launch and one backward launch with this package's WeightedMSE (loss/_activated.py)."""
+has no EMA variant.  One fused forward launch and one backward launch with this package's criteria -- WeightedMSE, MSELoss, BCELoss, WeightedBCE (loss/_activated.py)."""
 from ._activated import CLAMP, activated_affs, activated_loss
 
 _EPS = 1e-6

@@ -23,18 +23,25 @@ from .. import _lib
 from ..affinity_op import (AffinityMap, activation_flags, AffinitySpec, FusedAffinityMSE, LabelsAffinityMSE, LabelsStepUnsupported, LossList,
                            MultiAffinityMSE, MultiLabelsAffinityMSE, MultiLabelsUnsupported, MultiUnsupported, affinity_infer, label_sources,
                            materialise_labels)
+from ._activated import ones_weight
 
 
 def _eps(mode):
     return 1e-12 if mode == 'ours' else 1e-6
 
 
-def _spec(offsets, lam, mode, relu=False, act=0):
-    return AffinitySpec(2, offsets, lam, _lib.BORDER_CIRCULAR, _lib.NORM_BX, _eps(mode), relu, act)
+def _spec(offsets, lam, mode, relu=False, act=0, norm=_lib.NORM_BX):
+    return AffinitySpec(2, offsets, lam, _lib.BORDER_CIRCULAR, norm, _eps(mode), relu, act)
 
 
 def _fused(criterion):
     return getattr(criterion, 'pea_fused', False)
+
+
+def _plain_mse(criterion):
+    """this package's MSELoss (nn.MSELoss, the weight map ignored): the fused squared residual with a ones weight and torch's mean
+    over [B,H,W] (PEA_NORM_FULL).  Single losses only: the multi / labels paths key on pea_fused"""
+    return not _fused(criterion) and getattr(criterion, 'pea_criterion', None) == 'mse'
 
 
 def _foreign_criterion(embedding, ema_embedding, target, weightmap, mask, criterion, offsets, lam, mode):
@@ -54,6 +61,9 @@ def embedding_loss(embedding, target, weightmap, mask, criterion, offsets, affs0
     lam = [1.0] * len(offsets)  # the reference computes affs0_weight_factor but never applies it
     if _fused(criterion):
         loss, affs, parts = FusedAffinityMSE.apply(embedding, None, target, weightmap, mask, _spec(offsets, lam, mode))
+    elif _plain_mse(criterion):
+        loss, affs, parts = FusedAffinityMSE.apply(embedding, None, target, ones_weight(target), mask,
+                                                   _spec(offsets, lam, mode, norm=_lib.NORM_FULL))
     else:
         loss, affs, parts = _foreign_criterion(embedding, None, target, weightmap, mask, criterion, offsets, lam, mode)
     return loss, affs, LossList(parts)
@@ -99,6 +109,9 @@ def ema_embedding_loss(embedding, ema_embedding, target, weightmap, mask, criter
     lam = [float(affs0_weight) if i < 2 else 1.0 for i in range(len(offsets))]
     if _fused(criterion):
         loss, affs, _ = FusedAffinityMSE.apply(embedding, ema_embedding, target, weightmap, mask, _spec(offsets, lam, mode))
+    elif _plain_mse(criterion):
+        loss, affs, _ = FusedAffinityMSE.apply(embedding, ema_embedding, target, ones_weight(target), mask,
+                                               _spec(offsets, lam, mode, norm=_lib.NORM_FULL))
     else:
         loss, affs, _ = _foreign_criterion(embedding, ema_embedding, target, weightmap, mask, criterion, offsets, lam, mode)
     return loss, affs

@@ -16,6 +16,7 @@ from ..affinity_op import (AffinityMap, AffinitySpec, FusedAffinityMSE, LabelsAf
                            MultiLabelsAffinityMSE, MultiLabelsUnsupported, MultiUnsupported, affinity_infer, label_sources,
                            materialise_labels)
 from ..utils.affinity_ours import NORM5_SHIFTS, axis_offsets_3d
+from ._activated import ones_weight
 
 
 def _spec(shifts, affs0_weight, first):
@@ -39,6 +40,10 @@ def _run(embedding, ema_embedding, target, weightmap, criterion, shifts, affs0_w
     spec = _spec(shifts, affs0_weight, first)
     if getattr(criterion, 'pea_fused', False):
         loss, affs, _ = FusedAffinityMSE.apply(embedding, ema_embedding, target, weightmap, None, spec)
+        return loss, affs
+    if getattr(criterion, 'pea_criterion', None) == 'mse':
+        # this package's MSELoss: nn.MSELoss's mean over the cropped slice is WeightedMSE's normaliser there; the weight map is ignored
+        loss, affs, _ = FusedAffinityMSE.apply(embedding, ema_embedding, target, ones_weight(target), None, spec)
         return loss, affs
     return _foreign(embedding, ema_embedding, target, weightmap, criterion, shifts, spec)
 

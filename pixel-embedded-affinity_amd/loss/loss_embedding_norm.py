@@ -3,7 +3,7 @@ names, argument order, defaults and return values.  The embeddings go through F.
 u = clamp((dot + 1) / 2, 0, 1) (mode='cos') or u = clamp(1 - |ehat_s - ehat|^2 / 4, 0, 1) (any other mode).  For unit vectors the
 two are the same number, and both modes run the same kernels here; they differ only at a pixel with |e| < 1e-12, where
 F.normalize yields a non-unit vector (include/pea.h, PEA_FLAG_LOSS_ACT).  `affs0_weight` scales the first two offsets;
--> (loss, affs) with affs = u, un-masked.  One fused forward launch and one backward launch with this package's WeightedMSE
+-> (loss, affs) with affs = u, un-masked.  One fused forward launch and one backward launch with this package's criteria -- WeightedMSE, MSELoss, BCELoss, WeightedBCE
 (loss/_activated.py)."""
 from ._activated import HALF_CLAMP, activated_affs, activated_loss
 
