@@ -238,7 +238,11 @@ int pea_affinity_fwd(const PeaDesc *desc, const void *e, const void *e_other, co
  * argument, scripts_cvppp/main.py:188-189,284-293).  `dloss` is a DEVICE f32 scalar (autograd's grad_output)
  * or NULL (= 1), so no host sync is needed.  de_other: NULL when the second operand is detached
  * (convert_consistency_flip, scripts_cvppp/data/data_consistency.py:36), otherwise receives the gradient
- * w.r.t. e_other; de may be NULL when only de_other is wanted.  Gather form, no atomics, bit-reproducible. */
+ * w.r.t. e_other; de may be NULL when only de_other is wanted.  Gather form, no atomics, bit-reproducible.
+ * An upstream g need not be zero where the forward's is (tests/test_gpu_vjp.py holds every backward family, this call and the _ex /
+ * _ex2 / _dual_ex / _multi ones, to a float64 vjp with a dense g of order 1): under PEA_BORDER_CROP_ZERO the value of g_i(p) on a pair
+ * (p, p + o_i) that does not exist is not read, or if it is read it has no effect -- any FINITE value there gives bit-identical de /
+ * de_other.  A non-finite g, there or anywhere, is unspecified. */
 int pea_affinity_bwd(const PeaDesc *desc, const void *e, const void *e_other, const float *g, const float *dloss,
                      void *de, void *de_other, void *stream);
 
@@ -262,7 +266,9 @@ int pea_affinity_fwd_ex(const PeaDesc *desc, const void *e, const void *e_other,
 int pea_affinity_bwd_ex(const PeaDesc *desc, const void *e, const void *e_other, const float *g, const float *inv_norm,
                         const float *dloss, void *de, void *de_other, void *stream);
 /* pea_affinity_bwd_ex with the forward's affinity map as one more input: affs [B,K,Z,Y,X] f32 must be the RAW cosine map that
- * pea_affinity_fwd(_ex) wrote for the same descriptor with NO activation flag (PEA_FLAG_RELU_AFFS ...), unmodified.  The self-loss
+ * pea_affinity_fwd(_ex) wrote for the same descriptor with NO activation flag (PEA_FLAG_RELU_AFFS ...), unmodified -- or, for a vjp
+ * caller that never ran that forward, the map pea_affinity_infer writes for it (again no activation flag; with a second operand: the
+ * map of (e, e_other)): tests/test_gpu_vjp.py holds the backwards that read the map to float64 with it.  The self-loss
  * backward then knows <ehat, G> = sum_i g_i(p) a_i(p) + g_i(p - o_i) a_i(p - o_i) before it touches a channel and finishes two
  * channels per chunk (csrc/pea_xdma_pf.h): no second read of e at D > 16, three workgroups per CU for short stencils.  affs == NULL,
  * a second operand, z offsets, D = 16 (where the kernel that keeps G is the faster one) or an activation flag in desc->flags:
