@@ -13,7 +13,7 @@ from . import _lib
 from ._lib import PeaLibraryError, build
 from .affinity_op import (AffinityMap, AffinitySpec, FusedAffinityMSE, Graphed, LabelsAffinityMSE, MultiAffinityMSE, MultiLabelsAffinityMSE, affinity_infer, backward,
                           check_label_ranges, graphed, unflip)
-from .loss.loss import BCELoss, MSELoss, WeightedBCE, WeightedMSE
+from .loss.loss import BCE_loss_func, BCELoss, MSELoss, WeightedBCE, WeightedMSE
 from .loss.loss_embedding_mse import (ema_embedding_loss, ema_embedding_loss_from_labels, embedding2affs, embedding_loss,
                                       embedding_loss_from_labels, embedding_loss_from_labels_multi, embedding_loss_multi)
 from .loss import loss_embedding, loss_embedding_exp, loss_embedding_norm
@@ -32,6 +32,7 @@ from .utils.postproc import fill_border_relu_, relu_
 from .utils.targets import gen_affs_ours, gen_targets, seg_to_aff
 from .harness.stitch import VolumeStitcher
 from .harness.metrics import AffinityMetrics, affinity_metrics
+from .harness.fgmask import ForegroundMaskCE, foreground_mask, foreground_mask_loss
 from .harness.handoff import AffsCollector
 from .harness.head_loss import HeadAffinityMSE, head_embedding_loss
 from .harness.train_step import CvpppTrainStep, convert_consistency_flip, label_pyramid, make_optimizer
@@ -59,4 +60,5 @@ __all__ = [
     "MultiAffinityMSE", "embedding_loss_multi", "embedding_loss_norm1_multi", "unflip", "convert_consistency_flip",
     "MultiLabelsAffinityMSE", "embedding_loss_from_labels_multi", "embedding_loss_norm1_from_labels_multi",
     "affinity_metrics", "AffinityMetrics",
+    "BCE_loss_func", "foreground_mask_loss", "foreground_mask", "ForegroundMaskCE",
 ]

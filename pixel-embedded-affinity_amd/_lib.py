@@ -19,6 +19,7 @@ HEADER_FLIP = os.path.join(HERE, "..", "include", "pea_flip.h")
 HEADER_MULTI_LABELS = os.path.join(HERE, "..", "include", "pea_multi_labels.h")
 HEADER_HEAD16 = os.path.join(HERE, "..", "include", "pea_head16.h")
 HEADER_METRICS = os.path.join(HERE, "..", "include", "pea_metrics.h")
+HEADER_FGMASK = os.path.join(HERE, "..", "include", "pea_fgmask.h")
 
 PEA_ABI_VERSION = 2
 PEA_MAX_K = 32
@@ -35,6 +36,9 @@ RULES_U8, RULES_I32, RULES_I64, RULES_F32 = 0, 1, 2, 3  # element type of the ru
 TGT_PADDING, TGT_BOTH_FOREGROUND, TGT_MASK_INSIDE, TGT_ACCUMULATE = 1, 2, 4, 8
 METRICS_COLS = 5  # mse, bce, tp, fp, fn (include/pea_metrics.h PEA_METRICS_COLS)
 MET_RELU, MET_DIVIDE, MET_STORE, MET_MASK_F32 = 1, 2, 4, 8  # include/pea_metrics.h PEA_MET_*
+FG_LABELS_I32, FG_LABELS_U8 = 0, 1  # element type of the label image (include/pea_fgmask.h PEA_FG_LABELS_*)
+FG_SKIP_EMPTY_CLASS = 1  # include/pea_fgmask.h PEA_FG_SKIP_EMPTY_CLASS
+FG_STATS = 5  # loss, S0 / n0, S1 / n1, n0, n1 (include/pea_fgmask.h PEA_FG_STATS)
 
 EXPORTS = ("pea_version", "pea_strerror", "pea_desc_validate", "pea_workspace_bytes", "pea_workspace_init", "pea_reload_env",
            "pea_affinity_infer", "pea_affinity_fwd", "pea_affinity_bwd", "pea_affinity_fwd_ex", "pea_affinity_bwd_ex", "pea_affinity_bwd_ex2", "pea_inv_norm",
@@ -55,6 +59,8 @@ EXPORTS_MULTI_LABELS = ("pea_multi_labels_supported", "pea_multi_labels_scratch_
 EXPORTS_HEAD16 = ("pea_head_supported_t", "pea_head_fwd_t", "pea_head_bwd_t")
 # the entry points of include/pea_metrics.h (the validation pixel metrics: MSE, BCE and the F1 counts in one data launch)
 EXPORTS_METRICS = ("pea_metrics_validate", "pea_metrics_workspace_bytes", "pea_affs_metrics")
+# the entry points of include/pea_fgmask.h (the foreground-mask loss of the BBBC039V1 step and the validation mask)
+EXPORTS_FGMASK = ("pea_fgmask_validate", "pea_fgmask_workspace_bytes", "pea_fgmask_loss_fwd", "pea_fgmask_loss_bwd", "pea_fgmask_argmax")
 
 
 class PeaLibraryError(RuntimeError):
@@ -98,6 +104,13 @@ class PeaMetricsDesc(ctypes.Structure):
                 ("clip_lo", ctypes.c_float), ("clip_hi", ctypes.c_float)]
 
 
+class PeaFgDesc(ctypes.Structure):
+    """mirror of `struct PeaFgDesc` in include/pea_fgmask.h"""
+    _fields_ = [("B", ctypes.c_int32), ("Y", ctypes.c_int32), ("X", ctypes.c_int32), ("logits_dtype", ctypes.c_int32),
+                ("labels_type", ctypes.c_int32), ("flags", ctypes.c_uint32), ("origin", ctypes.c_int32 * 2),
+                ("out_dims", ctypes.c_int32 * 2)]
+
+
 HIPCC_FLAGS = ["-O3", "--offload-arch=gfx950", "-std=c++17", "-fPIC"]
 OBJ_DIR = os.path.join(CSRC, "build")
 
@@ -123,7 +136,7 @@ def build(force=False, verbose=False, jobs=None):
 
 def _build_locked(force, verbose, jobs):
     srcs = sources()
-    hdrs = [HEADER, HEADER_INFER, HEADER_MULTI, HEADER_FLIP, HEADER_MULTI_LABELS, HEADER_HEAD16, HEADER_METRICS] + [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".h")]
+    hdrs = [HEADER, HEADER_INFER, HEADER_MULTI, HEADER_FLIP, HEADER_MULTI_LABELS, HEADER_HEAD16, HEADER_METRICS, HEADER_FGMASK] + [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".h")]
     newest_hdr = max(os.path.getmtime(h) for h in hdrs)
     if not force and os.path.exists(SO_PATH) and os.path.getmtime(SO_PATH) >= max([newest_hdr] + [os.path.getmtime(x) for x in srcs]):
         return SO_PATH
@@ -187,7 +200,7 @@ def lib():
         L = ctypes.CDLL(SO_PATH)
     except OSError as ex:
         raise PeaLibraryError("cannot load %s: %s" % (SO_PATH, ex))
-    for name in EXPORTS + EXPORTS_INFER + EXPORTS_MULTI + EXPORTS_FLIP + EXPORTS_MULTI_LABELS + EXPORTS_HEAD16 + EXPORTS_METRICS:
+    for name in EXPORTS + EXPORTS_INFER + EXPORTS_MULTI + EXPORTS_FLIP + EXPORTS_MULTI_LABELS + EXPORTS_HEAD16 + EXPORTS_METRICS + EXPORTS_FGMASK:
         if not hasattr(L, name):
             raise PeaLibraryError("%s does not export %s" % (SO_PATH, name))
     vp, dp = ctypes.c_void_p, ctypes.POINTER(PeaDesc)
@@ -288,6 +301,17 @@ def lib():
     L.pea_metrics_workspace_bytes.argtypes = []
     L.pea_affs_metrics.restype = ctypes.c_int
     L.pea_affs_metrics.argtypes = [ctypes.POINTER(PeaMetricsDesc), vp, vp, vp, vp, vp, vp, ctypes.c_size_t, vp]
+    fp = ctypes.POINTER(PeaFgDesc)
+    L.pea_fgmask_validate.restype = ctypes.c_int
+    L.pea_fgmask_validate.argtypes = [fp]
+    L.pea_fgmask_workspace_bytes.restype = ctypes.c_size_t
+    L.pea_fgmask_workspace_bytes.argtypes = []
+    L.pea_fgmask_loss_fwd.restype = ctypes.c_int
+    L.pea_fgmask_loss_fwd.argtypes = [fp, vp, vp, vp, vp, vp, ctypes.c_size_t, vp]
+    L.pea_fgmask_loss_bwd.restype = ctypes.c_int
+    L.pea_fgmask_loss_bwd.argtypes = [fp, vp, vp, vp, vp, vp, vp]
+    L.pea_fgmask_argmax.restype = ctypes.c_int
+    L.pea_fgmask_argmax.argtypes = [fp, vp, vp, vp]
     if L.pea_version() != PEA_ABI_VERSION:
         raise PeaLibraryError("ABI mismatch: library %d, binding %d" % (L.pea_version(), PEA_ABI_VERSION))
     _lib = L

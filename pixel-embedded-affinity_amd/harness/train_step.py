@@ -22,6 +22,7 @@ import torch.nn.functional as F
 from ..loss.loss import WeightedMSE
 from ..affinity_op import UNFLIP_DTYPES, check_unflip_shapes, unflip
 from ..utils.affinity_ours import multi_offset
+from .fgmask import foreground_mask_loss
 from .loss_section import cvppp_loss_section, cvppp_loss_section_from_labels
 
 
@@ -90,10 +91,14 @@ def make_optimizer(model, base_lr=1e-4):
 
 class CvpppTrainStep(object):
     """step(inputs, ema_inputs, labels[, rules]) -> loss: forward x2, loss section, backward (DDP all-reduce inside), Adam step.
-    `model` is the (DDP-wrapped) ResidualUNet2D_deep; labels int32 [b,H,W] on the model's device."""
+    `model` is the (DDP-wrapped) ResidualUNet2D_deep; labels int32 [b,H,W] on the model's device.
+    mask_weight: None -- the mask logits of the binary_seg head are dropped (the CVPPP step) -- or a number (bbbc039v1.yaml: 1000.0):
+    the BBBC039V1 step, which adds mask_weight * BCE_loss_func(pred_mask, labels > 0) (scripts_bbbc039v1/main.py:289) as
+    foreground_mask_loss on the same int32 label image, without a host synchronisation; mask_skip_empty is its skip_empty (a crop
+    without foreground or without background: 0 for the absent class instead of the reference's NaN)."""
 
     def __init__(self, model, optimizer=None, shifts=(1, 3, 5, 9, 27), neighbor=4, deep_weight=1, self_emb=1.0, cross_emb=1.0,
-                 ct_weight=0.0, affs0_weight=1):
+                 ct_weight=0.0, affs0_weight=1, mask_weight=None, mask_skip_empty=False):
         self.model = model
         self.optimizer = optimizer if optimizer is not None else make_optimizer(model)
         self.offsets = multi_offset(list(shifts), neighbor)
@@ -101,12 +106,14 @@ class CvpppTrainStep(object):
         self.criterion = WeightedMSE()
         self.cfg = dict(deep_weight=deep_weight, self_emb=self_emb, cross_emb=cross_emb, affs0_weight=affs0_weight)
         self.ct_weight = ct_weight
+        self.mask_weight = None if mask_weight is None else float(mask_weight)
+        self.mask_skip_empty = bool(mask_skip_empty)
         self.pred = None
 
     def step(self, inputs, ema_inputs, labels, rules=None):
         self.model.train()
         self.optimizer.zero_grad(set_to_none=True)
-        emd4, emd3, emd2, emd1, embedding, _mask = self.model(inputs)
+        emd4, emd3, emd2, emd1, embedding, mask_logits = self.model(inputs)
         with torch.no_grad():
             ema_embedding = self.model(ema_inputs)[4]
         ema_embedding = convert_consistency_flip(ema_embedding, rules)
@@ -114,6 +121,8 @@ class CvpppTrainStep(object):
                                                             label_pyramid(labels), self.criterion, self.offsets, self.nb_half,
                                                             relu_pred=True, **self.cfg)
         loss = loss + self.ct_weight * F.mse_loss(embedding, ema_embedding)  # main.py:296 (weight 0.0 in the shipped yaml)
+        if self.mask_weight is not None:  # scripts_bbbc039v1/main.py:289
+            loss = loss + self.mask_weight * foreground_mask_loss(mask_logits, labels, self.mask_skip_empty)[0]
         loss.backward()
         self.optimizer.step()
         self.pred = pred

@@ -11,6 +11,8 @@ The other three say which criterion they are through `pea_criterion`; the single
 (loss/_activated.py; "mse" also in loss_embedding_mse.py and loss_embedding_mse_3d.py) then run fused as well, and everything else calls
 the module.  They do NOT carry `pea_fused`: the loss sections, head_embedding_loss and the multi / labels paths key on that attribute
 and fuse WeightedMSE only.
+
+BCE_loss_func (loss/loss.py:187-194 of scripts_bbbc039v1) is the foreground-mask loss on the binary_seg logits: a function, as there.
 """
 import torch
 import torch.nn as nn
@@ -78,3 +80,18 @@ class WeightedBCE(nn.Module):
 
     def forward(self, pred, target, weight=None):
         return F.binary_cross_entropy(pred, target, weight)
+
+
+def BCE_loss_func(output, target, weight_rate=[1, 1]):
+    """The foreground-mask loss of the BBBC039V1 step with the reference's name and signature (scripts_bbbc039v1/loss/loss.py:187-194;
+    called at scripts_bbbc039v1/main.py:289 and :385): nn.CrossEntropyLoss on the two-channel mask logits with the class weights
+    (count of foreground, count of background) -- there after two .item() round trips, here one forward and one backward launch with
+    no host synchronisation (include/pea_fgmask.h), one autograd node.
+
+    output  [B, 2, H, W] float32 / float16 / bfloat16 on the GPU
+    target  [B, H, W] or [B, 1, H, W]: bool or uint8 (read as it is) or int32, foreground <=> value > 0 -- for the reference's 0 / 1
+            targets the same classes; any other dtype raises ValueError
+    `weight_rate` is accepted and ignored, as in the reference.  A batch without foreground or without background gives NaN, as
+    there; pea.foreground_mask_loss(..., skip_empty=True) is the form that does not."""
+    from ..harness.fgmask import foreground_mask_loss
+    return foreground_mask_loss(output, target)[0]
