@@ -33,6 +33,8 @@ from .utils.targets import gen_affs_ours, gen_targets, seg_to_aff
 from .harness.stitch import VolumeStitcher
 from .harness.metrics import AffinityMetrics, affinity_metrics
 from .harness.fgmask import ForegroundMaskCE, foreground_mask, foreground_mask_loss
+from .harness.disc import DiscriminativeLoss, discriminative_loss_stats
+from .loss.loss_discriminative import discriminative_loss
 from .harness.handoff import AffsCollector
 from .harness.head_loss import HeadAffinityMSE, head_embedding_loss
 from .harness.train_step import CvpppTrainStep, convert_consistency_flip, label_pyramid, make_optimizer
@@ -61,4 +63,5 @@ __all__ = [
     "MultiLabelsAffinityMSE", "embedding_loss_from_labels_multi", "embedding_loss_norm1_from_labels_multi",
     "affinity_metrics", "AffinityMetrics",
     "BCE_loss_func", "foreground_mask_loss", "foreground_mask", "ForegroundMaskCE",
+    "discriminative_loss", "discriminative_loss_stats", "DiscriminativeLoss",
 ]

@@ -20,6 +20,7 @@ HEADER_MULTI_LABELS = os.path.join(HERE, "..", "include", "pea_multi_labels.h")
 HEADER_HEAD16 = os.path.join(HERE, "..", "include", "pea_head16.h")
 HEADER_METRICS = os.path.join(HERE, "..", "include", "pea_metrics.h")
 HEADER_FGMASK = os.path.join(HERE, "..", "include", "pea_fgmask.h")
+HEADER_DISC = os.path.join(HERE, "..", "include", "pea_disc.h")
 
 PEA_ABI_VERSION = 2
 PEA_MAX_K = 32
@@ -39,6 +40,9 @@ MET_RELU, MET_DIVIDE, MET_STORE, MET_MASK_F32 = 1, 2, 4, 8  # include/pea_metric
 FG_LABELS_I32, FG_LABELS_U8 = 0, 1  # element type of the label image (include/pea_fgmask.h PEA_FG_LABELS_*)
 FG_SKIP_EMPTY_CLASS = 1  # include/pea_fgmask.h PEA_FG_SKIP_EMPTY_CLASS
 FG_STATS = 5  # loss, S0 / n0, S1 / n1, n0, n1 (include/pea_fgmask.h PEA_FG_STATS)
+DISC_MAX_IDS, DISC_MAX_D = 4096, 64  # include/pea_disc.h PEA_DISC_MAX_IDS, PEA_DISC_MAX_D
+DISC_BACKGROUND, DISC_NEED_GRAD = 1, 2  # include/pea_disc.h PEA_DISC_*
+DISC_STATS = 5  # loss, var, dist, reg, n_bad; then var_b, dist_b, reg_b, C_b per image (include/pea_disc.h PEA_DISC_STATS)
 
 EXPORTS = ("pea_version", "pea_strerror", "pea_desc_validate", "pea_workspace_bytes", "pea_workspace_init", "pea_reload_env",
            "pea_affinity_infer", "pea_affinity_fwd", "pea_affinity_bwd", "pea_affinity_fwd_ex", "pea_affinity_bwd_ex", "pea_affinity_bwd_ex2", "pea_inv_norm",
@@ -61,6 +65,9 @@ EXPORTS_HEAD16 = ("pea_head_supported_t", "pea_head_fwd_t", "pea_head_bwd_t")
 EXPORTS_METRICS = ("pea_metrics_validate", "pea_metrics_workspace_bytes", "pea_affs_metrics")
 # the entry points of include/pea_fgmask.h (the foreground-mask loss of the BBBC039V1 step and the validation mask)
 EXPORTS_FGMASK = ("pea_fgmask_validate", "pea_fgmask_workspace_bytes", "pea_fgmask_loss_fwd", "pea_fgmask_loss_bwd", "pea_fgmask_argmax")
+# the entry points of include/pea_disc.h (the discriminative instance loss: segment means by label)
+EXPORTS_DISC = ("pea_disc_validate", "pea_disc_workspace_bytes", "pea_disc_workspace_init", "pea_disc_context_bytes", "pea_disc_loss_fwd",
+                "pea_disc_loss_bwd")
 
 
 class PeaLibraryError(RuntimeError):
@@ -111,6 +118,13 @@ class PeaFgDesc(ctypes.Structure):
                 ("out_dims", ctypes.c_int32 * 2)]
 
 
+class PeaDiscDesc(ctypes.Structure):
+    """mirror of `struct PeaDiscDesc` in include/pea_disc.h"""
+    _fields_ = [("B", ctypes.c_int32), ("D", ctypes.c_int32), ("S", ctypes.c_int64), ("num_ids", ctypes.c_int32), ("dtype", ctypes.c_int32),
+                ("flags", ctypes.c_uint32), ("delta_v", ctypes.c_float), ("delta_d", ctypes.c_float), ("alpha", ctypes.c_float),
+                ("beta", ctypes.c_float), ("gamma", ctypes.c_float)]
+
+
 HIPCC_FLAGS = ["-O3", "--offload-arch=gfx950", "-std=c++17", "-fPIC"]
 OBJ_DIR = os.path.join(CSRC, "build")
 
@@ -136,7 +150,7 @@ def build(force=False, verbose=False, jobs=None):
 
 def _build_locked(force, verbose, jobs):
     srcs = sources()
-    hdrs = [HEADER, HEADER_INFER, HEADER_MULTI, HEADER_FLIP, HEADER_MULTI_LABELS, HEADER_HEAD16, HEADER_METRICS, HEADER_FGMASK] + [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".h")]
+    hdrs = [HEADER, HEADER_INFER, HEADER_MULTI, HEADER_FLIP, HEADER_MULTI_LABELS, HEADER_HEAD16, HEADER_METRICS, HEADER_FGMASK, HEADER_DISC] + [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".h")]
     newest_hdr = max(os.path.getmtime(h) for h in hdrs)
     if not force and os.path.exists(SO_PATH) and os.path.getmtime(SO_PATH) >= max([newest_hdr] + [os.path.getmtime(x) for x in srcs]):
         return SO_PATH
@@ -200,7 +214,7 @@ def lib():
         L = ctypes.CDLL(SO_PATH)
     except OSError as ex:
         raise PeaLibraryError("cannot load %s: %s" % (SO_PATH, ex))
-    for name in EXPORTS + EXPORTS_INFER + EXPORTS_MULTI + EXPORTS_FLIP + EXPORTS_MULTI_LABELS + EXPORTS_HEAD16 + EXPORTS_METRICS + EXPORTS_FGMASK:
+    for name in EXPORTS + EXPORTS_INFER + EXPORTS_MULTI + EXPORTS_FLIP + EXPORTS_MULTI_LABELS + EXPORTS_HEAD16 + EXPORTS_METRICS + EXPORTS_FGMASK + EXPORTS_DISC:
         if not hasattr(L, name):
             raise PeaLibraryError("%s does not export %s" % (SO_PATH, name))
     vp, dp = ctypes.c_void_p, ctypes.POINTER(PeaDesc)
@@ -312,6 +326,19 @@ def lib():
     L.pea_fgmask_loss_bwd.argtypes = [fp, vp, vp, vp, vp, vp, vp]
     L.pea_fgmask_argmax.restype = ctypes.c_int
     L.pea_fgmask_argmax.argtypes = [fp, vp, vp, vp]
+    dd = ctypes.POINTER(PeaDiscDesc)
+    L.pea_disc_validate.restype = ctypes.c_int
+    L.pea_disc_validate.argtypes = [dd]
+    L.pea_disc_workspace_bytes.restype = ctypes.c_size_t
+    L.pea_disc_workspace_bytes.argtypes = [dd]
+    L.pea_disc_workspace_init.restype = ctypes.c_int
+    L.pea_disc_workspace_init.argtypes = [vp, ctypes.c_size_t, vp]
+    L.pea_disc_context_bytes.restype = ctypes.c_size_t
+    L.pea_disc_context_bytes.argtypes = [dd]
+    L.pea_disc_loss_fwd.restype = ctypes.c_int
+    L.pea_disc_loss_fwd.argtypes = [dd, vp, vp, vp, vp, vp, vp, ctypes.c_size_t, vp]
+    L.pea_disc_loss_bwd.restype = ctypes.c_int
+    L.pea_disc_loss_bwd.argtypes = [dd, vp, vp, vp, vp, vp, vp]
     if L.pea_version() != PEA_ABI_VERSION:
         raise PeaLibraryError("ABI mismatch: library %d, binding %d" % (L.pea_version(), PEA_ABI_VERSION))
     _lib = L

@@ -20,6 +20,7 @@
 // profiles/fgmask_ab.json): forward 10 us, finish 4 us, backward 6 us in a kernel trace; nothing was tuned.
 #include "../../include/pea_fgmask.h"
 #include "pea_dispatch.h"
+#include "pea_quad.h"
 
 #pragma clang fp contract(off)
 
@@ -27,7 +28,6 @@ using namespace pea;
 
 namespace {
 
-constexpr int kQuad = 4;                        // consecutive pixels per lane and step
 constexpr int kSteps = 4;                       // steps per lane
 constexpr int kRun = kBlock * kQuad * kSteps;   // pixels of one image per workgroup
 constexpr int kSums = 4;                        // S0, S1, n0, n1: indices of the one loss state
@@ -37,39 +37,7 @@ static_assert(kRun < (1 << 24), "a workgroup's count is an exact f32 integer");
 constexpr int kMaskRun = kBlock * kQuad;        // output pixels per workgroup of the argmax
 constexpr unsigned kKnownFlags = PEA_FG_SKIP_EMPTY_CLASS;
 
-typedef float quad_t __attribute__((ext_vector_type(4)));
-typedef int iquad_t __attribute__((ext_vector_type(4)));
-
-template <typename T>
-__device__ __forceinline__ float widen(unsigned short u) {
-  if constexpr (std::is_same<T, __half>::value) return __half2float(__ushort_as_half(u));
-  else return (float)__builtin_bit_cast(__bf16, u);
-}
-// round to nearest even, NaN kept (pea_common.h st())
-template <typename T>
-__device__ __forceinline__ unsigned short narrow(float v) {
-  if constexpr (std::is_same<T, __half>::value) return __half_as_ushort(__float2half(v));
-  else return __builtin_bit_cast(unsigned short, (__bf16)v);
-}
-
-// four consecutive logits from p, the first nv of them valid, widened to f32: one dwordx4 / dwordx2 where the quad is whole and aligned
-template <typename T>
-__device__ __forceinline__ void ld_quad(const T* __restrict__ p, int nv, float (&o)[kQuad]) {
-  if (nv == kQuad && ((uintptr_t)p & (kQuad * sizeof(T) - 1)) == 0) {
-    if constexpr (std::is_same<T, float>::value) {
-      const quad_t v = *(const quad_t*)p;
-      o[0] = v.x; o[1] = v.y; o[2] = v.z; o[3] = v.w;
-    } else {
-      const uint2 v = *(const uint2*)p;
-      o[0] = widen<T>((unsigned short)(v.x & 0xffffu)); o[1] = widen<T>((unsigned short)(v.x >> 16));
-      o[2] = widen<T>((unsigned short)(v.y & 0xffffu)); o[3] = widen<T>((unsigned short)(v.y >> 16));
-    }
-  } else {
-#pragma unroll
-    for (int e = 0; e < kQuad; ++e) o[e] = e < nv ? ld<T>(p, e) : 0.f;
-  }
-}
-// the same for the labels: y = [label > 0] (i32: one dwordx4, u8: one dword)
+// a quad of labels (pea_quad.h has the logits' ld_quad / st_quad): y = [label > 0] (i32: one dwordx4, u8: one dword)
 __device__ __forceinline__ void ld_fg(const int32_t* __restrict__ p, int nv, bool (&y)[kQuad]) {
   if (nv == kQuad && ((uintptr_t)p & 15) == 0) {
     const iquad_t v = *(const iquad_t*)p;
@@ -88,26 +56,6 @@ __device__ __forceinline__ void ld_fg(const uint8_t* __restrict__ p, int nv, boo
     for (int e = 0; e < kQuad; ++e) y[e] = e < nv && p[e] != 0;
   }
 }
-template <typename T>
-__device__ __forceinline__ void st_quad(T* __restrict__ p, int nv, const float (&v)[kQuad]) {
-  if (nv == kQuad && ((uintptr_t)p & (kQuad * sizeof(T) - 1)) == 0) {
-    if constexpr (std::is_same<T, float>::value) {
-      quad_t q;
-      q.x = v[0]; q.y = v[1]; q.z = v[2]; q.w = v[3];
-      *(quad_t*)p = q;
-    } else {
-      uint2 q;
-      q.x = (unsigned)narrow<T>(v[0]) | ((unsigned)narrow<T>(v[1]) << 16);
-      q.y = (unsigned)narrow<T>(v[2]) | ((unsigned)narrow<T>(v[3]) << 16);
-      *(uint2*)p = q;
-    }
-  } else {
-#pragma unroll
-    for (int e = 0; e < kQuad; ++e)
-      if (e < nv) st(p, e, v[e]);
-  }
-}
-
 // z = y ? l0 - l1 : l1 - l0: the logit of the WRONG class minus the logit of the right one
 __device__ __forceinline__ float wrong_minus_right(float l0, float l1, bool y) { return y ? l0 - l1 : l1 - l0; }
 

@@ -45,14 +45,15 @@ static_assert(sizeof(LossState) % 64 == 0, "states are laid out back to back in 
 typedef unsigned long long u64;
 #define PEA_ATOM_ADD(p, v) (void)__hip_atomic_fetch_add((p), (v), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)
 
-// one workgroup's partial of offset k: st->acc[tile % 16][k] += trunc(v * 2^64) (|v| < 2^60; exact from 2^-41 up, smaller than 2^-64 is 0)
-__device__ __forceinline__ void loss_accumulate(LossState* __restrict__ st, int tile, int k, float v) {
+// The f32 -> digits conversion on its own: a[0..2] += trunc(v * 2^64) as three digit words, *flags |= what cannot be summed.  `a` is
+// the row of ONE accumulator wherever it lies (a LossState, the per-id tables of pea_k_disc.hip).
+__device__ __forceinline__ void digits_accumulate(u64* __restrict__ a, unsigned* __restrict__ flags, float v) {
   const unsigned u = __builtin_bit_cast(unsigned, v);
   const int e = (int)((u >> 23) & 0xffu);
   if (e == 0) return;  // zero / denormal
   if (e >= 127 + 60) {  // overflow, infinity, NaN: remembered as a flag, the finish reports inf / NaN like a float sum would
     const unsigned f = (e == 0xff && (u & 0x7fffffu)) ? 4u : ((u >> 31) ? 2u : 1u);
-    (void)__hip_atomic_fetch_or(&st->flags[k], f, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    (void)__hip_atomic_fetch_or(flags, f, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     return;
   }
   const u64 m = (u64)((u & 0x7fffffu) | 0x800000u);
@@ -63,10 +64,14 @@ __device__ __forceinline__ void loss_accumulate(LossState* __restrict__ st, int 
   else return;
   if (u >> 31) X = (unsigned __int128)0 - X;
   const u64 lo = (u64)X & 0xffffffffull, mid = (u64)(X >> 32) & 0xffffffffull, hi = (u64)(X >> 64);
-  u64* a = st->acc[tile & (kLossSlots - 1)][k];
   if (lo) PEA_ATOM_ADD(a + 0, lo);
   if (mid) PEA_ATOM_ADD(a + 1, mid);
   if (hi) PEA_ATOM_ADD(a + 2, hi);
+}
+
+// one workgroup's partial of offset k: st->acc[tile % 16][k] += trunc(v * 2^64) (|v| < 2^60; exact from 2^-41 up, smaller than 2^-64 is 0)
+__device__ __forceinline__ void loss_accumulate(LossState* __restrict__ st, int tile, int k, float v) {
+  digits_accumulate(st->acc[tile & (kLossSlots - 1)][k], &st->flags[k], v);
 }
 
 // digit sums of one offset -> the value (double).  lo / mid: sums of 32-bit digits; hi: sum of the upper words (mod 2^64)

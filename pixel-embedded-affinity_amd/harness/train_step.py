@@ -22,6 +22,7 @@ import torch.nn.functional as F
 from ..loss.loss import WeightedMSE
 from ..affinity_op import UNFLIP_DTYPES, check_unflip_shapes, unflip
 from ..utils.affinity_ours import multi_offset
+from .disc import discriminative_loss_stats
 from .fgmask import foreground_mask_loss
 from .loss_section import cvppp_loss_section, cvppp_loss_section_from_labels
 
@@ -95,10 +96,14 @@ class CvpppTrainStep(object):
     mask_weight: None -- the mask logits of the binary_seg head are dropped (the CVPPP step) -- or a number (bbbc039v1.yaml: 1000.0):
     the BBBC039V1 step, which adds mask_weight * BCE_loss_func(pred_mask, labels > 0) (scripts_bbbc039v1/main.py:289) as
     foreground_mask_loss on the same int32 label image, without a host synchronisation; mask_skip_empty is its skip_empty (a crop
-    without foreground or without background: 0 for the absent class instead of the reference's NaN)."""
+    without foreground or without background: 0 for the absent class instead of the reference's NaN).
+    disc_weight: None -- the step as it is -- or a number: adds disc_weight * discriminative_loss(embedding, labels,
+    background=disc_background, num_ids=disc_num_ids) on the full-resolution embedding (include/pea_disc.h); give disc_num_ids (every
+    id < disc_num_ids) to keep the step free of host synchronisations."""
 
     def __init__(self, model, optimizer=None, shifts=(1, 3, 5, 9, 27), neighbor=4, deep_weight=1, self_emb=1.0, cross_emb=1.0,
-                 ct_weight=0.0, affs0_weight=1, mask_weight=None, mask_skip_empty=False):
+                 ct_weight=0.0, affs0_weight=1, disc_weight=None, disc_num_ids=None, disc_background=False, mask_weight=None,
+                 mask_skip_empty=False):
         self.model = model
         self.optimizer = optimizer if optimizer is not None else make_optimizer(model)
         self.offsets = multi_offset(list(shifts), neighbor)
@@ -108,6 +113,9 @@ class CvpppTrainStep(object):
         self.ct_weight = ct_weight
         self.mask_weight = None if mask_weight is None else float(mask_weight)
         self.mask_skip_empty = bool(mask_skip_empty)
+        self.disc_weight = None if disc_weight is None else float(disc_weight)
+        self.disc_num_ids = disc_num_ids
+        self.disc_background = bool(disc_background)
         self.pred = None
 
     def step(self, inputs, ema_inputs, labels, rules=None):
@@ -123,6 +131,8 @@ class CvpppTrainStep(object):
         loss = loss + self.ct_weight * F.mse_loss(embedding, ema_embedding)  # main.py:296 (weight 0.0 in the shipped yaml)
         if self.mask_weight is not None:  # scripts_bbbc039v1/main.py:289
             loss = loss + self.mask_weight * foreground_mask_loss(mask_logits, labels, self.mask_skip_empty)[0]
+        if self.disc_weight is not None:
+            loss = loss + self.disc_weight * discriminative_loss_stats(embedding, labels, self.disc_background, num_ids=self.disc_num_ids)[0]
         loss.backward()
         self.optimizer.step()
         self.pred = pred
