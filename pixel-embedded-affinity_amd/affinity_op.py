@@ -74,33 +74,50 @@ def _embedding_arg(t, name):
     return t if t.is_contiguous() else t.contiguous()
 
 
-def _batch_strided(t, name, dtype, shape):
-    """-> (tensor, batch stride in elements).  The [K, spatial...] block of every batch item must be
-    dense; the batch stride itself may be anything (channel slices of a packed tensor)."""
-    _require_gpu(t, name)
+def _batch_layout(t, name, dtype, shape):
+    """-> (tensor, batch stride in elements): the layout decision of _batch_strided, which needs no device (CPU tensors pass).
+    The library reads item b of a [B, K, spatial...] operand at data_ptr + b * (stride or K * S) elements as one dense [K, S] block
+    (include/pea.h: a *_bstride of 0 means "dense"), so what comes back is
+      * the tensor itself, with its own batch stride, where every item is such a block and the batch stride is positive: a channel
+        slice of a packed tensor, t[::2], overlapping read-only windows from as_strided (0 < stride < K * S) -- no copy;
+      * a dense copy with stride K * S for every other layout: a broadcast batch (stride(0) == 0 with B > 1 -- the descriptor has no
+        encoding for it, 0 is taken: it means dense), an expanded channel, a spatial crop, channels_last, a permuted view;
+      * stride 0 and a dense tensor for B == 1 (the stride is never used)."""
+    if not isinstance(t, torch.Tensor):
+        raise TypeError("%s must be a torch.Tensor" % name)
     if tuple(t.shape) != tuple(shape):
         raise ValueError("%s has shape %s, expected %s" % (name, tuple(t.shape), tuple(shape)))
     if t.dtype != dtype:
         t = t.to(dtype)
-    if t.shape[0] > 1 and not t[0].is_contiguous():
+    if t.shape[0] <= 1:
+        return (t if t.is_contiguous() else t.contiguous()), 0
+    if t.stride(0) <= 0 or not t[0].is_contiguous():
         t = t.contiguous()
-    elif t.shape[0] == 1 and not t.is_contiguous():
-        t = t.contiguous()
-    return t, (t.stride(0) if t.shape[0] > 1 else 0)
+    return t, t.stride(0)
 
 
-def mask_arg(m, shape):
+def _batch_strided(t, name, dtype, shape):
+    """-> (tensor, batch stride in elements) of a device tensor: _batch_layout behind the device check.  The [K, spatial...] block of
+    every batch item must be dense (it is copied otherwise); a positive batch stride is taken as it is (channel slices of a packed
+    tensor); a batch stride of 0 (a tensor expanded over the batch) is materialised."""
+    _require_gpu(t, name)
+    return _batch_layout(t, name, dtype, shape)
+
+
+def mask_arg(m, shape, gpu=True):
     """-> (mask, batch stride in elements, descriptor flag of its type).  A float32 mask goes to the kernels as it is
     (PEA_FLAG_MASK_F32: fractional values are honoured, as the reference's `affs * mask` after `mask.float()` does); other floating
-    dtypes are converted once with .float(); bool / uint8 masks take the u8 path (other integer dtypes are converted to uint8)."""
+    dtypes are converted once with .float(); bool / uint8 masks take the u8 path (other integer dtypes are converted to uint8).
+    The layout is _batch_layout's; gpu=False leaves the device check out (the layout decision alone, on any tensor)."""
     if m is None:
         return None, 0, 0
+    layout = _batch_strided if gpu else _batch_layout
     if m.dtype == torch.bool:
         m = m.view(torch.uint8)
     if m.is_floating_point():
-        m, ms = _batch_strided(m, "mask", torch.float32, shape)
+        m, ms = layout(m, "mask", torch.float32, shape)
         return m, ms, _lib.FLAG_MASK_F32
-    m, ms = _batch_strided(m, "mask", torch.uint8, shape)
+    m, ms = layout(m, "mask", torch.uint8, shape)
     return m, ms, 0
 
 

@@ -34,9 +34,11 @@ def _workspace(dev, nb):
     return w
 
 
-def _args(embedding, seg_gt, num_ids):
+def _args(embedding, seg_gt, num_ids, gpu=True):
     """-> (embedding [B, D, *spatial] contiguous, labels int32 [B, S] contiguous, num_ids): shapes and dtypes first, then the device, so
-    that what is wrong with a call can be said without a GPU"""
+    that what is wrong with a call can be said without a GPU.  Any layout torch can express is taken (a crop, a strided or expanded
+    label view, channels_last): what the kernels read is a dense copy of the same values.  gpu=False leaves the device checks out
+    (the normalisation alone, on any tensor)"""
     if not isinstance(embedding, torch.Tensor) or not isinstance(seg_gt, torch.Tensor):
         raise TypeError("embedding and seg_gt must be torch.Tensors")
     if embedding.dim() < 3:
@@ -56,8 +58,9 @@ def _args(embedding, seg_gt, num_ids):
         raise ValueError("embedding is empty: %s" % (tuple(embedding.shape),))
     if num_ids is not None and not 1 <= int(num_ids) <= _lib.DISC_MAX_IDS:
         raise ValueError("num_ids must be in 1 .. %d, got %r" % (_lib.DISC_MAX_IDS, num_ids))
-    _require_gpu(embedding, "embedding")
-    _require_gpu(seg_gt, "seg_gt")
+    if gpu:
+        _require_gpu(embedding, "embedding")
+        _require_gpu(seg_gt, "seg_gt")
     if seg_gt.device != embedding.device:
         raise RuntimeError("seg_gt is on %s, the embedding on %s" % (seg_gt.device, embedding.device))
     seg_gt = seg_gt.detach()

@@ -49,8 +49,9 @@ def _logits_arg(logits, gpu=True):
 _LABEL_CODE = {torch.bool: _lib.FG_LABELS_U8, torch.uint8: _lib.FG_LABELS_U8, torch.int32: _lib.FG_LABELS_I32}
 
 
-def _labels_arg(labels, logits, name):
-    """-> (tensor, PEA_FG_LABELS_*): bool and uint8 are read as they are (a view, no conversion), int32 likewise; nothing else is taken"""
+def _labels_arg(labels, logits, name, gpu=True):
+    """-> (tensor, PEA_FG_LABELS_*): bool and uint8 are read as they are (a view, no conversion), int32 likewise; nothing else is taken.
+    A label view that is not dense (a slice of a packed tensor, an expanded image) is copied.  gpu=False: as in _logits_arg"""
     if not isinstance(labels, torch.Tensor):
         raise TypeError("%s must be a torch.Tensor" % name)
     B, _, H, W = logits.shape
@@ -61,7 +62,8 @@ def _labels_arg(labels, logits, name):
     if labels.dtype not in _LABEL_CODE:
         raise ValueError("%s must be bool, uint8 or int32 (foreground <=> value > 0), got %s: pass torch.gt(%s, 0), or convert the "
                          "label image once with .to(torch.int32)" % (name, labels.dtype, name))
-    _require_gpu(labels, name)
+    if gpu:
+        _require_gpu(labels, name)
     if labels.device != logits.device:
         raise RuntimeError("%s is on %s, the logits on %s" % (name, labels.device, logits.device))
     labels = labels.detach()
