@@ -139,8 +139,10 @@ extern "C" {
                                     loss finish    unchanged; the gradient's scale is lambda_i / N_i (no factor 2: that is the squared residual's).
                                   Entry points without a LOSS_ACT form refuse the bit with it: pea_affinity_fwd_dual_ex and the labels-in
                                   calls return PEA_E_UNSUPPORTED, pea_multi_supported and pea_infer_stitch_supported answer 0.  Kernels: the
-                                  f32 LDS-DMA cross forwards (self and detached second operand, D = 16 / 32 / 64, 2D) and the direct kernels
-                                  (everything else, 16-bit storage included) */
+                                  f32 LDS-DMA cross forwards (self and detached second operand, D = 16 / 32 / 64, 2D; the self loss at D = 16 also on
+                                  3D volumes whose stencil steps along z, u8 mask or none) and the direct kernels (everything else,
+                                  16-bit storage included).  Under PEA_BORDER_CROP_ZERO `affs` holds act(0) on a pair that does not
+                                  exist; pea_affs_crop_zero (pea_crop.h) stores the 0 the reference's 3D modules hold there */
 
 /* error codes: 0 = ok, negative = PEA_E_*, positive = a hipError_t from the runtime */
 #define PEA_OK 0

@@ -16,19 +16,20 @@ from .affinity_op import (AffinityMap, AffinitySpec, FusedAffinityMSE, Graphed, 
 from .loss.loss import BCE_loss_func, BCELoss, MSELoss, WeightedBCE, WeightedMSE
 from .loss.loss_embedding_mse import (ema_embedding_loss, ema_embedding_loss_from_labels, embedding2affs, embedding_loss,
                                       embedding_loss_from_labels, embedding_loss_from_labels_multi, embedding_loss_multi)
-from .loss import loss_embedding, loss_embedding_exp, loss_embedding_norm
+from .loss import embedding2affs_3d, embedding2affs_3d_l2, loss_embedding, loss_embedding_exp, loss_embedding_norm
 from .loss.loss_embedding import (ema_embedding_loss as ema_embedding_loss_half_clamp, embedding2affs as embedding2affs_half_clamp,
                                   embedding_loss as embedding_loss_half_clamp)
 from .loss.loss_embedding_exp import embedding2affs as embedding2affs_clamp, embedding_loss as embedding_loss_clamp
 from .loss.loss_embedding_norm import (ema_embedding_loss as ema_embedding_loss_normalized, embedding2affs as embedding2affs_normalized,
                                        embedding_loss as embedding_loss_normalized)
-from .loss.loss_embedding_mse_3d import (ema_embedding_loss_norm1, ema_embedding_loss_norm5, ema_embedding_loss_norm5_from_labels,
+from .loss.loss_embedding_mse_3d import (ema_embedding_loss_norm1, ema_embedding_loss_norm2, ema_embedding_loss_norm5,
+                                         ema_embedding_loss_norm5_from_labels, embedding_loss_norm2,
                                          ema_embedding_loss_norm6, embedding_loss_norm6,
                                          embedding_loss_norm1, embedding_loss_norm1_from_labels, embedding_loss_norm1_from_labels_multi, embedding_loss_norm1_multi,
                                          embedding_loss_norm5,
                                          embedding_loss_norm5_from_labels, inf_embedding_loss_norm1, inf_embedding_loss_norm5)
 from .utils.affinity_ours import gen_offsets, multi_offset
-from .utils.postproc import fill_border_relu_, relu_
+from .utils.postproc import affs_crop_zero_, fill_border_relu_, relu_
 from .utils.targets import gen_affs_ours, gen_targets, seg_to_aff
 from .harness.stitch import VolumeStitcher
 from .harness.metrics import AffinityMetrics, affinity_metrics
@@ -64,4 +65,5 @@ __all__ = [
     "affinity_metrics", "AffinityMetrics",
     "BCE_loss_func", "foreground_mask_loss", "foreground_mask", "ForegroundMaskCE",
     "discriminative_loss", "discriminative_loss_stats", "DiscriminativeLoss",
+    "embedding2affs_3d", "embedding2affs_3d_l2", "embedding_loss_norm2", "ema_embedding_loss_norm2", "affs_crop_zero_",
 ]

@@ -21,6 +21,7 @@ HEADER_HEAD16 = os.path.join(HERE, "..", "include", "pea_head16.h")
 HEADER_METRICS = os.path.join(HERE, "..", "include", "pea_metrics.h")
 HEADER_FGMASK = os.path.join(HERE, "..", "include", "pea_fgmask.h")
 HEADER_DISC = os.path.join(HERE, "..", "include", "pea_disc.h")
+HEADER_CROP = os.path.join(HERE, "..", "include", "pea_crop.h")
 
 PEA_ABI_VERSION = 2
 PEA_MAX_K = 32
@@ -68,6 +69,8 @@ EXPORTS_FGMASK = ("pea_fgmask_validate", "pea_fgmask_workspace_bytes", "pea_fgma
 # the entry points of include/pea_disc.h (the discriminative instance loss: segment means by label)
 EXPORTS_DISC = ("pea_disc_validate", "pea_disc_workspace_bytes", "pea_disc_workspace_init", "pea_disc_context_bytes", "pea_disc_loss_fwd",
                 "pea_disc_loss_bwd")
+# the entry point of include/pea_crop.h (the reference's 3D border rule on an activated map: 0 where the pair does not exist)
+EXPORTS_CROP = ("pea_affs_crop_zero",)
 
 
 class PeaLibraryError(RuntimeError):
@@ -150,7 +153,7 @@ def build(force=False, verbose=False, jobs=None):
 
 def _build_locked(force, verbose, jobs):
     srcs = sources()
-    hdrs = [HEADER, HEADER_INFER, HEADER_MULTI, HEADER_FLIP, HEADER_MULTI_LABELS, HEADER_HEAD16, HEADER_METRICS, HEADER_FGMASK, HEADER_DISC] + [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".h")]
+    hdrs = [HEADER, HEADER_INFER, HEADER_MULTI, HEADER_FLIP, HEADER_MULTI_LABELS, HEADER_HEAD16, HEADER_METRICS, HEADER_FGMASK, HEADER_DISC, HEADER_CROP] + [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".h")]
     newest_hdr = max(os.path.getmtime(h) for h in hdrs)
     if not force and os.path.exists(SO_PATH) and os.path.getmtime(SO_PATH) >= max([newest_hdr] + [os.path.getmtime(x) for x in srcs]):
         return SO_PATH
@@ -214,7 +217,7 @@ def lib():
         L = ctypes.CDLL(SO_PATH)
     except OSError as ex:
         raise PeaLibraryError("cannot load %s: %s" % (SO_PATH, ex))
-    for name in EXPORTS + EXPORTS_INFER + EXPORTS_MULTI + EXPORTS_FLIP + EXPORTS_MULTI_LABELS + EXPORTS_HEAD16 + EXPORTS_METRICS + EXPORTS_FGMASK + EXPORTS_DISC:
+    for name in EXPORTS + EXPORTS_INFER + EXPORTS_MULTI + EXPORTS_FLIP + EXPORTS_MULTI_LABELS + EXPORTS_HEAD16 + EXPORTS_METRICS + EXPORTS_FGMASK + EXPORTS_DISC + EXPORTS_CROP:
         if not hasattr(L, name):
             raise PeaLibraryError("%s does not export %s" % (SO_PATH, name))
     vp, dp = ctypes.c_void_p, ctypes.POINTER(PeaDesc)
@@ -339,6 +342,8 @@ def lib():
     L.pea_disc_loss_fwd.argtypes = [dd, vp, vp, vp, vp, vp, vp, ctypes.c_size_t, vp]
     L.pea_disc_loss_bwd.restype = ctypes.c_int
     L.pea_disc_loss_bwd.argtypes = [dd, vp, vp, vp, vp, vp, vp]
+    L.pea_affs_crop_zero.restype = ctypes.c_int
+    L.pea_affs_crop_zero.argtypes = [dp, vp, vp]
     if L.pea_version() != PEA_ABI_VERSION:
         raise PeaLibraryError("ABI mismatch: library %d, binding %d" % (L.pea_version(), PEA_ABI_VERSION))
     _lib = L

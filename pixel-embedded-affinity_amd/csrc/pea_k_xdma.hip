@@ -30,17 +30,25 @@ bool fwd_self(const KParams& P, const FwdArgs& A, hipStream_t s) {
   // an f32 mask (2D training only): the quads' masks are dwordx4 loads -- a plane that is not 16-byte aligned takes the next family
   const bool mf = TRAIN && A.mf32;
   if (mf && (z3 || misaligned(A.m, 16))) return false;
-  const bool la = TRAIN && A.lact;  // the loss on the activated map (PEA_FLAG_LOSS_ACT): 2D training only, either mask type
-  if (la && z3) return false;
+  // the loss on the activated map (PEA_FLAG_LOSS_ACT): training only; 2D with either mask type; 3D (z3) its binary cross-entropy form with
+  // a u8 mask or none.
+  // (the squared-residual z3 form is not instantiated: at 2 x 16 x 18 x 160 x 160, norm5, it ran 64.8 us against the 79.0 us of k_fwd_tiled
+  //  that takes the call instead, but the eager step only went from 175.7 to 172.9 us with spreads of 4.9 + 9.0 us -- not the gain
+  //  beyond the spreads a new form is held to; the BCE form replaces k_fwd_direct, 113.7 against 102.7 us per launch but 201.2
+  //  against 210.0 us per step, spreads 0.9 + 0.8 -- the direct kernel also needs a k_inv_norm launch of 12.7 us: profiles/act3d_ab.json,
+  //  EXPERIMENTS.md)
+  const bool la = TRAIN && A.lact;
+  if (la && z3 && !A.bce) return false;
   const XParams& C = X.C;
   const dim3 grid((unsigned)(C.tiles_per_xcd * kXcd)), blk(kXdmaTH * kXdmaTW);
-  // the f32-mask and LOSS_ACT forms are built for 2D training only (TRAIN, ZF = 0): every other call with them was declined above
+  // the f32-mask forms are built for 2D training only (TRAIN, ZF = 0), the LOSS_ACT forms for 2D training and, BCE with the u8 mask,
+  // for z3: every other call with them was declined above
   auto go = [&](auto psu, auto zf, auto wpe) {
     return with_bool(P.border != PEA_BORDER_CIRCULAR, [&](auto crop) {
       return with_loss_form(mf, la, la && A.bce, [&](auto mt, auto lact, auto bce) {
         using MT = typename decltype(mt)::type;
         constexpr bool kSpills = bce.value && wpe.value == 6 && std::is_same<MT, float>::value;  // (bce_mf above: never asked for)
-        if constexpr (((std::is_same<MT, uint8_t>::value && !lact.value) || (TRAIN && zf.value == 0)) && !kSpills)
+        if constexpr (((std::is_same<MT, uint8_t>::value && (!lact.value || (TRAIN && bce.value))) || (TRAIN && zf.value == 0)) && !kSpills)
           return launch<k_fwd_xdma<D_T, kXdmaTH, kXdmaTW, psu.value, crop.value, TRAIN, zf.value, false, wpe.value, false, MT, lact.value, bce.value>>(
               grid, blk, X.lds, s, P, C, e, t, w, (const MT*)(const void*)A.m, A.affs, A.gout, A.st, A.inv_out, (const float*)nullptr,
               (float*)nullptr, LabArgs{});
@@ -177,7 +185,11 @@ bool xdma_fwd_other(const KParams& P, const FwdArgs& A, hipStream_t s) {
     z3 = true;
   }
   if (P.K > (z3 ? kXP + 2 : kXP)) return false;
-  if (z3 && (A.mf32 || A.lact)) return false;  // (the f32-mask and the PEA_FLAG_LOSS_ACT forms are 2D)
+  // the f32-mask forms are 2D.  So are the PEA_FLAG_LOSS_ACT forms of the second operand: the z3 squared-residual one was built and
+  // measured (ema_embedding_loss_norm2 at 2 x 16 x 18 x 160 x 160: 52.6 us per launch, 162.5 us per eager step against 152.5 us with
+  // PEA_FWD_XDMA=0, spreads 9.9 + 6.6 us -- no gain, profiles/act3d_ab.json, EXPERIMENTS.md) and is not instantiated; its BCE sibling
+  // was never measured
+  if (z3 && (A.mf32 || A.lact)) return false;
   const dim3 grid((unsigned)(X.C.tiles_per_xcd * kXcd)), blk(kXdmaTH * kXdmaTW);
   // the f32-mask and the loss on the activated map (PEA_FLAG_LOSS_ACT) are 2D forms (ZF = 0): z3 with them was declined above
   auto go = [&](auto psu, auto zf) {

@@ -707,7 +707,7 @@ __global__ __launch_bounds__(TH* TW, WPE) void k_fwd_xdma(const KParams P, const
   constexpr bool OWNL = OTHER && D_T > 16;
   static_assert(!OWNL || ZF == 0, "cross-loss instantiation at D > 16: in-plane");
   static_assert(!LAB || (TRAIN && ZF == 0 && !OTHER), "labels-in instantiation: 2D self loss");
-  static_assert(!LACT || (TRAIN && ZF == 0 && !LAB), "loss on the activated map (PEA_FLAG_LOSS_ACT, act_u): 2D training forwards");
+  static_assert(!LACT || (TRAIN && !LAB), "loss on the activated map (PEA_FLAG_LOSS_ACT, act_u): training forwards (2D, and the 3D ZF form)");
   static_assert(!BCE || LACT, "binary cross-entropy (PEA_FLAG_LOSS_BCE, bce_term) is taken on the activated map");
   constexpr int NT = TH * TW, PS = PSU * 256, NP = D_T / 2, TP = NT, QP = TP / 4, NSL = QP / 64;
   constexpr int KMAX = ZF > 0 ? kXP + 2 : kXP;      // channels the epilogue handles (norm5: 8 in-plane + 4 z offsets)

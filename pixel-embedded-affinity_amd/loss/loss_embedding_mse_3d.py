@@ -1,6 +1,7 @@
 """3D embedding -> affinity losses: drop-in for the reference's scripts_ac3ac4/loss/loss_embedding_mse.py
 (norm1, norm5 and their ema_/inf_ variants -- the ones the shipped ac3ac4.yaml selects, embedding_mode 5
-plus norm1 for the four deep-supervision heads, scripts_ac3ac4/main.py:219-230).
+plus norm1 for the four deep-supervision heads, scripts_ac3ac4/main.py:219-230 -- and norm2 / ema_norm2, :70-140, whose loss is
+taken on the activated map).
 
 Semantics kept from the reference (file:line there):
   * channel i compares p with p - shift along axis i % 3 of (z,y,x) on the CROPPED extent (:11-18,:143-151);
@@ -16,7 +17,8 @@ from ..affinity_op import (AffinityMap, AffinitySpec, FusedAffinityMSE, LabelsAf
                            MultiLabelsAffinityMSE, MultiLabelsUnsupported, MultiUnsupported, affinity_infer, label_sources,
                            materialise_labels)
 from ..utils.affinity_ours import NORM5_SHIFTS, axis_offsets_3d
-from ._activated import ones_weight
+from ._activated import HALF_CLAMP, ones_weight
+from ._activated3d import cropped_loss
 
 
 def _spec(shifts, affs0_weight, first):
@@ -84,6 +86,20 @@ def ema_embedding_loss_norm1(embedding, ema_embedding, target, weightmap, criter
 def inf_embedding_loss_norm1(embedding, shift=1):
     """-> affs [B,3,Z,Y,X] -- reference :54-67"""
     return affinity_infer(embedding, None, _spec([shift] * 3, 1, 1))
+
+
+def embedding_loss_norm2(embedding, target, weightmap, criterion, affs0_weight=1, shift=1, fill=True):
+    """-> (loss, affs [B,3,Z,Y,X]) -- reference :70-103: norm1 with the loss on u = clamp((cos + 1) / 2, 0, 1) (PEA_FLAG_LOSS_ACT: one
+    fused forward launch with WeightedMSE, MSELoss, BCELoss or WeightedBCE, loss/_activated3d.py); fill=True stores the next `shift`
+    slices in the first ones (:99-102), otherwise they hold 0"""
+    return cropped_loss(embedding, None, target, weightmap, criterion, [shift] * 3, affs0_weight, 1, HALF_CLAMP,
+                        fill_shift=shift if fill else 0)
+
+
+def ema_embedding_loss_norm2(embedding, ema_embedding, target, weightmap, criterion, affs0_weight=1, shift=1, fill=True):
+    """reference :106-140: the EMA embedding is the shifted-from operand"""
+    return cropped_loss(embedding, ema_embedding, target, weightmap, criterion, [shift] * 3, affs0_weight, 1, HALF_CLAMP,
+                        fill_shift=shift if fill else 0)
 
 
 def embedding_loss_norm5(embedding, target, weightmap, criterion, affs0_weight=1, shift=1, fill=True):
