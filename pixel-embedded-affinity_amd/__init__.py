@@ -36,6 +36,8 @@ from .harness.metrics import AffinityMetrics, affinity_metrics
 from .harness.fgmask import ForegroundMaskCE, foreground_mask, foreground_mask_loss
 from .harness.disc import DiscriminativeLoss, discriminative_loss_stats
 from .loss.loss_discriminative import discriminative_loss
+from .harness.dist import DistanceAffinities, distance_affinities
+from .utils import emb2affs, embeddings_ours
 from .harness.handoff import AffsCollector
 from .harness.head_loss import HeadAffinityMSE, head_embedding_loss
 from .harness.train_step import CvpppTrainStep, convert_consistency_flip, label_pyramid, make_optimizer
@@ -66,4 +68,5 @@ __all__ = [
     "BCE_loss_func", "foreground_mask_loss", "foreground_mask", "ForegroundMaskCE",
     "discriminative_loss", "discriminative_loss_stats", "DiscriminativeLoss",
     "embedding2affs_3d", "embedding2affs_3d_l2", "embedding_loss_norm2", "ema_embedding_loss_norm2", "affs_crop_zero_",
+    "distance_affinities", "DistanceAffinities", "emb2affs", "embeddings_ours",
 ]

@@ -22,6 +22,7 @@ HEADER_METRICS = os.path.join(HERE, "..", "include", "pea_metrics.h")
 HEADER_FGMASK = os.path.join(HERE, "..", "include", "pea_fgmask.h")
 HEADER_DISC = os.path.join(HERE, "..", "include", "pea_disc.h")
 HEADER_CROP = os.path.join(HERE, "..", "include", "pea_crop.h")
+HEADER_DIST = os.path.join(HERE, "..", "include", "pea_dist.h")
 
 PEA_ABI_VERSION = 2
 PEA_MAX_K = 32
@@ -43,6 +44,9 @@ FG_SKIP_EMPTY_CLASS = 1  # include/pea_fgmask.h PEA_FG_SKIP_EMPTY_CLASS
 FG_STATS = 5  # loss, S0 / n0, S1 / n1, n0, n1 (include/pea_fgmask.h PEA_FG_STATS)
 DISC_MAX_IDS, DISC_MAX_D = 4096, 64  # include/pea_disc.h PEA_DISC_MAX_IDS, PEA_DISC_MAX_D
 DISC_BACKGROUND, DISC_NEED_GRAD = 1, 2  # include/pea_disc.h PEA_DISC_*
+DIST_MAX_D = 64  # include/pea_dist.h PEA_DIST_MAX_D
+DIST_BORDER_ZERO_VECTOR = 3  # include/pea_dist.h: a value of PeaDistDesc.border beside BORDER_REPLICATE
+DIST_INVERT = 1  # include/pea_dist.h PEA_DIST_INVERT
 DISC_STATS = 5  # loss, var, dist, reg, n_bad; then var_b, dist_b, reg_b, C_b per image (include/pea_disc.h PEA_DISC_STATS)
 
 EXPORTS = ("pea_version", "pea_strerror", "pea_desc_validate", "pea_workspace_bytes", "pea_workspace_init", "pea_reload_env",
@@ -71,6 +75,8 @@ EXPORTS_DISC = ("pea_disc_validate", "pea_disc_workspace_bytes", "pea_disc_works
                 "pea_disc_loss_bwd")
 # the entry point of include/pea_crop.h (the reference's 3D border rule on an activated map: 0 where the pair does not exist)
 EXPORTS_CROP = ("pea_affs_crop_zero",)
+# the entry points of include/pea_dist.h (distance-form affinities of the raw embedding: forward and vjp)
+EXPORTS_DIST = ("pea_dist_validate", "pea_dist_affinity", "pea_dist_affinity_vjp")
 
 
 class PeaLibraryError(RuntimeError):
@@ -128,6 +134,13 @@ class PeaDiscDesc(ctypes.Structure):
                 ("beta", ctypes.c_float), ("gamma", ctypes.c_float)]
 
 
+class PeaDistDesc(ctypes.Structure):
+    """mirror of `struct PeaDistDesc` in include/pea_dist.h"""
+    _fields_ = [("B", ctypes.c_int32), ("D", ctypes.c_int32), ("dims", ctypes.c_int32 * 3), ("K", ctypes.c_int32),
+                ("offsets", (ctypes.c_int32 * 3) * PEA_MAX_K), ("dtype", ctypes.c_int32), ("border", ctypes.c_int32),
+                ("flags", ctypes.c_uint32), ("delta_v", ctypes.c_float), ("delta_d", ctypes.c_float)]
+
+
 HIPCC_FLAGS = ["-O3", "--offload-arch=gfx950", "-std=c++17", "-fPIC"]
 OBJ_DIR = os.path.join(CSRC, "build")
 
@@ -153,7 +166,7 @@ def build(force=False, verbose=False, jobs=None):
 
 def _build_locked(force, verbose, jobs):
     srcs = sources()
-    hdrs = [HEADER, HEADER_INFER, HEADER_MULTI, HEADER_FLIP, HEADER_MULTI_LABELS, HEADER_HEAD16, HEADER_METRICS, HEADER_FGMASK, HEADER_DISC, HEADER_CROP] + [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".h")]
+    hdrs = [HEADER, HEADER_INFER, HEADER_MULTI, HEADER_FLIP, HEADER_MULTI_LABELS, HEADER_HEAD16, HEADER_METRICS, HEADER_FGMASK, HEADER_DISC, HEADER_CROP, HEADER_DIST] + [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".h")]
     newest_hdr = max(os.path.getmtime(h) for h in hdrs)
     if not force and os.path.exists(SO_PATH) and os.path.getmtime(SO_PATH) >= max([newest_hdr] + [os.path.getmtime(x) for x in srcs]):
         return SO_PATH
@@ -217,7 +230,7 @@ def lib():
         L = ctypes.CDLL(SO_PATH)
     except OSError as ex:
         raise PeaLibraryError("cannot load %s: %s" % (SO_PATH, ex))
-    for name in EXPORTS + EXPORTS_INFER + EXPORTS_MULTI + EXPORTS_FLIP + EXPORTS_MULTI_LABELS + EXPORTS_HEAD16 + EXPORTS_METRICS + EXPORTS_FGMASK + EXPORTS_DISC + EXPORTS_CROP:
+    for name in EXPORTS + EXPORTS_INFER + EXPORTS_MULTI + EXPORTS_FLIP + EXPORTS_MULTI_LABELS + EXPORTS_HEAD16 + EXPORTS_METRICS + EXPORTS_FGMASK + EXPORTS_DISC + EXPORTS_CROP + EXPORTS_DIST:
         if not hasattr(L, name):
             raise PeaLibraryError("%s does not export %s" % (SO_PATH, name))
     vp, dp = ctypes.c_void_p, ctypes.POINTER(PeaDesc)
@@ -344,6 +357,13 @@ def lib():
     L.pea_disc_loss_bwd.argtypes = [dd, vp, vp, vp, vp, vp, vp]
     L.pea_affs_crop_zero.restype = ctypes.c_int
     L.pea_affs_crop_zero.argtypes = [dp, vp, vp]
+    ds = ctypes.POINTER(PeaDistDesc)
+    L.pea_dist_validate.restype = ctypes.c_int
+    L.pea_dist_validate.argtypes = [ds]
+    L.pea_dist_affinity.restype = ctypes.c_int
+    L.pea_dist_affinity.argtypes = [ds, vp, vp, vp]
+    L.pea_dist_affinity_vjp.restype = ctypes.c_int
+    L.pea_dist_affinity_vjp.argtypes = [ds, vp, vp, vp, vp, vp]
     if L.pea_version() != PEA_ABI_VERSION:
         raise PeaLibraryError("ABI mismatch: library %d, binding %d" % (L.pea_version(), PEA_ABI_VERSION))
     _lib = L

@@ -14,6 +14,7 @@
 //   pea_k_direct.hip   global-memory kernels (pea_direct.h): the general fallback; loss finish; caller epilogues, stitcher
 //   pea_k_head.hip     the embedding head (pea_head.h) and target generation (pea_targets.h)
 //   pea_k_crop.hip     the 3D border rule on an activated map (include/pea_crop.h): 0 where the pair does not exist, one launch
+//   pea_k_dist.hip     distance-form affinities of the raw embedding (include/pea_dist.h): forward and vjp, gather form
 // Each kernel file exports a few plain functions (declared here) that pick the instantiation and launch it; a function returns
 // false when its family has no kernel for the descriptor and the caller tries the next one.  No device code crosses a file.
 // pea_dispatch.h holds what the launchers share to get from run-time facts (storage dtype, D, border, mask type, ..) to template

@@ -116,6 +116,27 @@ class VolumeStitcher(object):
                     pred = fill_border_relu_(affinity_infer(eb, None, spec), shift=shift, relu=relu)
                     self.add_vol(pred[0], pos[b])
 
+    def add_distance_embedding(self, embedding, pos, offsets, delta_v, delta_d, border, invert=False):
+        """A window of a model trained with the discriminative loss: the distance-form affinities of the raw embedding
+        (harness/dist.py distance_affinities, include/pea_dist.h) followed by add_vol -- two launches per window.
+        embedding [B, D, oz, oy, ox] on the GPU, f32 / f16 / bf16; pos = one (z0, y0, x0) or B of them; len(offsets) channels.  Batch
+        items are added in order, as add_embedding does."""
+        from .dist import distance_affinities
+        if not isinstance(embedding, torch.Tensor) or embedding.dim() != 5 or tuple(embedding.shape[2:]) != self.out_size:
+            raise ValueError("embedding must be [B, D] + %s, got %s" % (self.out_size, tuple(getattr(embedding, "shape", ()))))
+        if len(offsets) != self.C:
+            raise ValueError("%d offsets, the stitcher has %d channels" % (len(offsets), self.C))
+        B = embedding.shape[0]
+        pos = np.asarray(pos, dtype=np.int64)
+        pos = np.broadcast_to(pos, (B, 3)) if pos.ndim == 1 else pos
+        if pos.shape != (B, 3):
+            raise ValueError("pos must be (z0, y0, x0) or one per batch item, got shape %s" % (pos.shape,))
+        affs = distance_affinities(embedding.detach(), offsets, delta_v=delta_v, delta_d=delta_d, border=border, invert=invert)
+        if affs.device != self.weight_vol.device:
+            raise ValueError("embedding is on %s, the stitcher on %s" % (affs.device, self.weight_vol.device))
+        for b in range(B):
+            self.add_vol(affs[b], pos[b])
+
     def get_results(self, valid_padding):
         """provider_valid.py:337-349: out / weight_map, cropped by valid_padding (a view of the device tensor)"""
         Z, Y, X = self.shape
