@@ -212,18 +212,11 @@ __global__ __launch_bounds__(kBoxTH* kBoxTW, 4) void k_fwd_box(const KParams P, 
       bs128<true>(mkbuf(affs + ((size_t)b * P.K + k) * S), o, vo, 0u);
     }
     if (TRAIN) {
-      float acc = 0.f;
-      f4 g4;
-      const float gs = C.gs[k];
+      float acc;
+      bool exists[4];  // a cropped-away neighbour carries no loss term
 #pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        const float m = (float)((m4 >> (8 * j)) & 0xffu);
-        const float r = a4[j] * m - t4[j] * m;
-        float wr = w4[j] * r;
-        if (CROP) wr = rowok && (unsigned)(gx + j + ox) < (unsigned)P.X ? wr : 0.f;  // a cropped-away neighbour carries no loss term
-        g4[j] = gs * wr * m;
-        acc = fmaf(wr, r, acc);
-      }
+      for (int j = 0; j < 4; ++j) exists[j] = !CROP || (rowok && (unsigned)(gx + j + ox) < (unsigned)P.X);
+      const f4 g4 = loss_quad<uint8_t>(a4, t4, w4, m4, exists, C.gs[k], acc);
       if (has_g) bs128<false>(mkbuf(gout + ((size_t)b * P.K + k) * S), g4, vo, 0u);
       const float red = wave_sum63(acc);
       if (lane == 63) s_part[k * NSL + (qd >> 6)] = red;
@@ -231,12 +224,7 @@ __global__ __launch_bounds__(kBoxTH* kBoxTW, 4) void k_fwd_box(const KParams P, 
   }
   if (TRAIN) {
     lds_barrier();
-    if (wave == 0 && (int)threadIdx.x < P.K) {
-      float v = 0.f;
-#pragma unroll
-      for (int s = 0; s < NSL; ++s) v += s_part[threadIdx.x * NSL + s];
-      loss_accumulate(st, tile, threadIdx.x, v);
-    }
+    if (wave == 0 && (int)threadIdx.x < P.K) part_accumulate<NSL>(st, tile, threadIdx.x, s_part, NSL, 1);
   }
 }
 

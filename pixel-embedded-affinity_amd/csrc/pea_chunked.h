@@ -224,12 +224,7 @@ __global__ __launch_bounds__(TH* TW, (DC > 16 ? 2 : 4)) void k_fwd_tiled_chunked
 
   if (TRAIN) {
     lds_barrier();
-    if (threadIdx.x < P.K) {
-      float v = 0.f;
-#pragma unroll
-      for (int w = 0; w < NW; ++w) v += s_part[w * P.K + threadIdx.x];
-      loss_accumulate(st, tile, threadIdx.x, v);
-    }
+    if (threadIdx.x < P.K) part_accumulate<NW>(st, tile, threadIdx.x, s_part, 1, P.K);
   }
 }
 

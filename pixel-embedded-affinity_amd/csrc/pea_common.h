@@ -87,10 +87,9 @@ __device__ __forceinline__ float act_affs(float a, unsigned af) {
 //   v = a * sc + of,  u = v < lo ? lo : v > hi ? hi : v   (sc, of) = (1/2, 1/2) for the half shift, (lo, hi) = (0, 1) for the clamp, else infinite
 // -- the same bits act_affs stores ((a + 1) / 2 and a / 2 + 1/2 round alike: halving is exact) -- and the slope du / da is sc where the
 // clamp left v alone (u == v: torch.clamp's backward is INCLUSIVE at both edges), 0 where it did not.  The forward folds the slope
-// into g (act_g), so the backward kernels do not know about activations.  The epilogues keep v, not u, across their stores (u is two
-// instructions away from v; keeping both spilled in the 64-VGPR forwards).  A NaN v (a non-finite embedding) stays NaN in u, so the loss
-// is NaN; u == v is then false and g is `gz`: 0 with the clamp (what torch.clamp's backward gives at a NaN input), NaN without it (the
-// half shift alone has no branch: g = 2 w m r s / N is NaN like r).
+// into g (act_g), so the backward kernels do not know about activations.  `gz` is g where u != v because v is NaN: 0 with the clamp,
+// NaN without it (the half shift alone has no branch: g = 2 w m r s / N is NaN like r).  How the epilogues use these -- the order of
+// operations, what they keep across their stores, the NaN policy -- is stated with the loss term in pea_epilogue.h.
 struct ActK {
   float sc, of, lo, hi, gz;
 };
@@ -110,9 +109,9 @@ __device__ __forceinline__ float act_g(float u, float v, float gs_sc, float wr, 
 
 // PEA_FLAG_LOSS_BCE (the BCE instantiations of the LACT forwards: k_fwd_direct, k_fwd_xdma): the criterion on x = u m, y = t m is the
 // weighted binary cross-entropy of F.binary_cross_entropy -- both logs clamped at -100 (a select: NaN stays NaN), log1p for the second --
-// and the returned factor is torch's own BCE backward, w (x - y) / max(x (1 - x), 1e-12); the caller hands it to act_g as `wr` with
-// gs_sc = lambda / N * ActK::sc (no factor 2).  Stated once so that the direct and the cross kernel give the same bits of g and contrib
-// for the same a: explicit fmaf (no contraction left to the context), IEEE division, logf / log1pf (not the fast intrinsics).
+// and the returned factor is torch's own BCE backward, w (x - y) / max(x (1 - x), 1e-12); loss_term (pea_epilogue.h) hands it to act_g
+// as `wr` with gs_sc = lambda / N * ActK::sc (no factor 2).  Explicit fmaf (no contraction left to the context), IEEE division, logf /
+// log1pf (not the fast intrinsics): the direct and the cross kernel give the same bits of g and contrib for the same a.
 // m = 0: x = y = 0, contrib = -w (0 * -100 + 1 * log1p(-0)) = 0 and the factor is 0 / 1e-12 = 0.  x = 0, y = 1: contrib = 100 w exactly.
 __device__ __forceinline__ float bce_log(float l) { return l < -100.0f ? -100.0f : l; }
 __device__ __forceinline__ float bce_term(float x, float y, float w, float& contrib) {

@@ -81,18 +81,9 @@ __global__ __launch_bounds__(kBlock) void k_fwd_direct(const KParams P, const T*
           const float t = target[(size_t)b * P.tbs + in], w = weight[(size_t)b * P.wbs + in];
           if constexpr (LACT) {  // the loss on the activated value; its slope goes into g
             const ActK AK = act_consts(P.flags & kActMask);
-            const float v = act_v(a, AK), u = act_u(v, AK);
-            if constexpr (BCE) {
-              const float bt = bce_term(u * m, t * m, w, contrib);
-              g = act_g(u, v, P.lam[i] * P.inv_n[i] * AK.sc, bt, m, AK);
-            } else {
-              const float r = u * m - t * m;
-              const float wr = w * r;
-              contrib = wr * r;
-              g = act_g(u, v, P.gscale[i] * AK.sc, wr, m, AK);
-            }
+            g = loss_term<true, BCE>(act_v(a, AK), t, w, m, true, BCE ? P.lam[i] * P.inv_n[i] : P.gscale[i], AK, contrib);
           } else {
-            g = raw_loss_term(a, t, w, m, P.gscale[i], contrib);
+            g = loss_term(a, t, w, m, true, P.gscale[i], contrib);
           }
         }
         if (gout) gout[kb + in] = g;

@@ -8,13 +8,14 @@
 // The contracts between these families are contracts on BITS (the batched launches carry the single calls' affs and g, and their
 // de in f32 and bf16 -- an f16 de lies within one f16 ulp: the two store policies of project_store --; role B of the labels-in form
 // reproduces what role A of the neighbour computes), so the order of the fused multiply-adds exists here: the bodies compose these
-// blocks (k_bwd_direct restates gather_pair, see there).  What differs between the families on purpose stays in the kernels: the
-// loss-partial reductions, the tile walk, the REPLICATE pre-image loop, the runtime-D paths and the loss on the activated map.
+// blocks (k_bwd_direct restates gather_pair, see there).  The loss term of a pair is loss_term of pea_epilogue.h, shared with the
+// LDS-staged families.  What differs between the families on purpose stays in the kernels: which lanes hold a loss partial and how
+// they meet, the tile walk, the REPLICATE pre-image loop and the runtime-D paths.
 //
 // Every block is a __forceinline__ template of the storage type T (float / __half / __bf16 through ld() / st()), the width D and a
 // geometry GEO: anything with S, Z, Y, X, K, eps, off[i][3] (and border for the runtime neighbour) -- KParams and multi::MGeom.
 #pragma once
-#include "pea_loss.h"
+#include "pea_epilogue.h"
 
 namespace pea {
 
@@ -83,14 +84,6 @@ __device__ __forceinline__ float cosine_streamed(const float (&own)[D], float in
     sq = fmaf(v, v, sq);
   }
   return dot * inv_own * inv_norm(sq, eps);
-}
-
-// the loss term of the raw cosine a (target t, weight w, mask m): its share of the loss into `contrib`, returns g = d loss / d a
-__device__ __forceinline__ float raw_loss_term(float a, float t, float w, float m, float gscale, float& contrib) {
-  const float r = a * m - t * m;
-  const float wr = w * r;
-  contrib = wr * r;
-  return gscale * wr * m;
 }
 
 // G += coef * v

@@ -39,7 +39,7 @@
 #include <type_traits>
 
 #include "pea_host.h"
-#include "pea_tiled.h"  // wave_sum63
+#include "pea_epilogue.h"  // wave_sum63
 
 namespace pea {
 

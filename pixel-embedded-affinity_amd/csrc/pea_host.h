@@ -19,6 +19,8 @@
 // false when its family has no kernel for the descriptor and the caller tries the next one.  No device code crosses a file.
 // pea_dispatch.h holds what the launchers share to get from run-time facts (storage dtype, D, border, mask type, ..) to template
 // arguments: launch<KERNEL>() and the with_bool / with_storage / with_width / with_mask_form callers of generic lambdas.
+// pea_epilogue.h holds what every training forward ends with: the loss term of a pair (scalar and quad form), wave_sum63 and the
+// workgroup's tail into the loss state; pea_gather.h and the LDS-staged families include it.
 #pragma once
 #include <stdint.h>
 #include <stdlib.h>
@@ -59,6 +61,11 @@ void env_reload();          // pea_reload_env(): tests that change a switch call
 unsigned env_generation();  // = env().gen; a new one with every env_reload(): memoised plans that baked a switch in (PEA_ZBLK_*, ..) are dropped
 
 inline bool misaligned(const void* p, size_t a) { return ((uintptr_t)p & (a - 1)) != 0; }
+// a * b, UINT64_MAX where it does not fit
+inline uint64_t mul_sat(uint64_t a, uint64_t b) {
+  uint64_t r;
+  return __builtin_mul_overflow(a, b, &r) ? UINT64_MAX : r;
+}
 // bytes per element of the embedding's storage dtype (validate() admits PEA_F32, PEA_F16 and PEA_BF16 only)
 inline size_t dtype_bytes(int dtype) { return dtype == PEA_F32 ? 4 : 2; }
 // N_i of include/pea.h: what the loss of offset i is divided by (1 / N_i in the loss finish, 2 lambda_i / N_i in g)

@@ -63,7 +63,6 @@ __device__ __forceinline__ float wrong_minus_right(float l0, float l1, bool y) {
 template <typename T, typename LT>
 __global__ __launch_bounds__(kBlock) void k_fg_fwd(const size_t S, const unsigned chunks, const T* __restrict__ logits,
                                                    const LT* __restrict__ labels, LossState* __restrict__ st) {
-  __shared__ float s_part[kSums][kBlock / 64];
   const unsigned chunk = blockIdx.x % chunks;
   const size_t b = blockIdx.x / chunks;
   const T* __restrict__ p0 = logits + b * 2 * S;
@@ -97,24 +96,7 @@ __global__ __launch_bounds__(kBlock) void k_fg_fwd(const size_t S, const unsigne
   }
 
   float q[kSums] = {s0, s1, c0, c1};
-#pragma unroll
-  for (int k = 0; k < kSums; ++k) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) q[k] += __shfl_xor(q[k], o, 64);
-  }
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  if (lane == 0) {
-#pragma unroll
-    for (int k = 0; k < kSums; ++k) s_part[k][wave] = q[k];
-  }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-#pragma unroll
-    for (int k = 0; k < kSums; ++k) {
-      const float v = ((s_part[k][0] + s_part[k][1]) + s_part[k][2]) + s_part[k][3];
-      loss_accumulate(st, (int)blockIdx.x, k, v);
-    }
-  }
+  block_sums(q, [&](int k, float v) { loss_accumulate(st, (int)blockIdx.x, k, v); });
 }
 
 // The finish, one wave: lane = 16 * k + slot reads index k of the state (as k_loss_finish), writes loss and stats and puts the state
@@ -124,19 +106,8 @@ __global__ __launch_bounds__(64) void k_fg_finish(LossState* __restrict__ st, fl
   __shared__ double s_v[kSums];
   const int lane = threadIdx.x, s = lane & (kLossSlots - 1), k = lane >> 4;
   const bool good = st->magic == kLossMagic;
-  u64* a = st->acc[s][k];
-  u64 v0 = a[0], v1 = a[1], v2 = a[2];
-  a[0] = 0; a[1] = 0; a[2] = 0;
-  unsigned fl = 0;
-  if (s == 0) { fl = st->flags[k]; st->flags[k] = 0; }
-#pragma unroll
-  for (int o = 1; o < kLossSlots; o <<= 1) {
-    v0 += __shfl_xor(v0, o, 64);
-    v1 += __shfl_xor(v1, o, 64);
-    v2 += __shfl_xor(v2, o, 64);
-    fl |= __shfl_xor(fl, o, 64);
-  }
-  if (s == 0) s_v[k] = loss_value(v0, v1, v2, fl);
+  const double v = loss_row_collect(st, k, s, true);
+  if (s == 0) s_v[k] = v;
   __syncthreads();
   if (lane == 0) {
     const double qnan = __builtin_nan("");
@@ -239,11 +210,6 @@ __global__ __launch_bounds__(kBlock) void k_fg_argmax(const CropParams P, const 
     for (int e = 0; e < kQuad; ++e)
       if (e < nv) op[e] = (uint8_t)m[e];
   }
-}
-
-inline uint64_t mul_sat(uint64_t a, uint64_t b) {
-  uint64_t r;
-  return __builtin_mul_overflow(a, b, &r) ? UINT64_MAX : r;
 }
 
 // workgroups of a loss launch (one per kRun pixels of an image); 0: more than 2^31 - 1

@@ -27,6 +27,7 @@
 // with STORE), two logf per element: bandwidth-bound.
 #include "../../include/pea_metrics.h"
 #include "pea_dispatch.h"
+#include "pea_quad.h"
 
 #pragma clang fp contract(off)
 
@@ -34,15 +35,12 @@ using namespace pea;
 
 namespace {
 
-constexpr int kQuad = 4;                        // consecutive elements per lane and step
 constexpr int kSteps = 4;                       // steps per lane
 constexpr int kRun = kBlock * kQuad * kSteps;   // elements of one plane per workgroup
 constexpr int kStates = 5;                      // mse, bce, tp, fp, fn
 static_assert(kStates == PEA_METRICS_COLS, "one state per column");
 static_assert(kRun < (1 << 24), "a workgroup's count is an exact f32 integer");
 constexpr unsigned kKnownFlags = PEA_MET_RELU | PEA_MET_DIVIDE | PEA_MET_STORE | PEA_MET_MASK_F32;
-
-typedef float quad_t __attribute__((ext_vector_type(4)));
 
 struct MetParams {
   int C, CP, CW;        // channels evaluated, channels of pred, channels walked (STORE: CP, else C)
@@ -55,49 +53,10 @@ struct MetParams {
   float lo, hi;
 };
 
-// four consecutive floats from p, the first nv of them valid: one dwordx4 where the quad is whole and 16-byte aligned
-__device__ __forceinline__ void ld_quad(const float* __restrict__ p, int nv, float (&o)[kQuad]) {
-  if (nv == kQuad && ((uintptr_t)p & 15) == 0) {
-    const quad_t v = *(const quad_t*)p;
-    o[0] = v.x; o[1] = v.y; o[2] = v.z; o[3] = v.w;
-  } else {
-#pragma unroll
-    for (int e = 0; e < kQuad; ++e) o[e] = e < nv ? p[e] : 0.f;
-  }
-}
-// the same for a u8 mask (one dword)
-__device__ __forceinline__ void ld_quad(const uint8_t* __restrict__ p, int nv, float (&o)[kQuad]) {
-  if (nv == kQuad && ((uintptr_t)p & 3) == 0) {
-    const uint32_t v = *(const uint32_t*)p;
-    o[0] = (float)(v & 0xffu); o[1] = (float)((v >> 8) & 0xffu); o[2] = (float)((v >> 16) & 0xffu); o[3] = (float)(v >> 24);
-  } else {
-#pragma unroll
-    for (int e = 0; e < kQuad; ++e) o[e] = e < nv ? (float)p[e] : 0.f;
-  }
-}
-__device__ __forceinline__ void st_quad(float* __restrict__ p, int nv, const float (&v)[kQuad]) {
-  if (nv == kQuad && ((uintptr_t)p & 15) == 0) {
-    quad_t q;
-    q.x = v[0]; q.y = v[1]; q.z = v[2]; q.w = v[3];
-    *(quad_t*)p = q;
-  } else {
-#pragma unroll
-    for (int e = 0; e < kQuad; ++e)
-      if (e < nv) p[e] = v[e];
-  }
-}
-
-// log with nn.BCELoss's floor; a select, so a NaN stays NaN (fmaxf would answer -100)
-__device__ __forceinline__ float log_floor(float u) {
-  const float l = logf(u);
-  return l < -100.0f ? -100.0f : l;
-}
-
 template <typename MT, bool DIVIDE, bool STORE>
 __global__ __launch_bounds__(kBlock) void k_metrics(const MetParams P, float* __restrict__ pred, const float* __restrict__ wmap,
                                                     const float* __restrict__ target, const MT* __restrict__ mask,
                                                     LossState* __restrict__ st) {
-  __shared__ float s_part[kStates][kBlock / 64];
   // blockIdx -> (b, c, chunk): uniform over the workgroup
   const unsigned chunk = blockIdx.x % P.chunks, bc = blockIdx.x / P.chunks;
   const unsigned c = bc % (unsigned)P.CW;
@@ -174,7 +133,7 @@ __global__ __launch_bounds__(kBlock) void k_metrics(const MetParams P, float* __
         const float sq = d * d;
         s_mse += sq;
         const float omu = 1.0f - u, omt = 1.0f - tq;
-        const float p1 = tq * log_floor(u), p2 = omt * log_floor(omu);
+        const float p1 = tq * bce_log(logf(u)), p2 = omt * bce_log(logf(omu));  // nn.BCELoss's floor, a select: NaN stays NaN
         const float term = -(p1 + p2);
         s_bce += term;
         const bool gb = tq < 1.0f, pb = u <= 0.5f;
@@ -188,24 +147,7 @@ __global__ __launch_bounds__(kBlock) void k_metrics(const MetParams P, float* __
   if (!eval) return;  // (uniform: the whole workgroup leaves before the barrier)
 
   float q[kStates] = {s_mse, s_bce, s_tp, s_fp, s_fn};
-#pragma unroll
-  for (int k = 0; k < kStates; ++k) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) q[k] += __shfl_xor(q[k], o, 64);
-  }
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  if (lane == 0) {
-#pragma unroll
-    for (int k = 0; k < kStates; ++k) s_part[k][wave] = q[k];
-  }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-#pragma unroll
-    for (int k = 0; k < kStates; ++k) {
-      const float v = ((s_part[k][0] + s_part[k][1]) + s_part[k][2]) + s_part[k][3];
-      loss_accumulate(st + k, (int)blockIdx.x, (int)c, v);
-    }
-  }
+  block_sums(q, [&](int k, float v) { loss_accumulate(st + k, (int)blockIdx.x, (int)c, v); });
 }
 
 // The finish: wave q reads state q, four channels per pass (lane = 16 * j + slot, as k_loss_finish), writes the table and puts the
@@ -221,22 +163,8 @@ __global__ __launch_bounds__(64 * kStates) void k_metrics_finish(LossState* __re
   for (int k0 = 0; k0 < C; k0 += 4) {
     const int k = k0 + j;
     const bool on = k < C;
-    u64 v0 = 0, v1 = 0, v2 = 0;
-    unsigned fl = 0;
-    if (on) {
-      u64* a = S->acc[s][k];
-      v0 = a[0]; v1 = a[1]; v2 = a[2];
-      a[0] = 0; a[1] = 0; a[2] = 0;
-      if (s == 0) { fl = S->flags[k]; S->flags[k] = 0; }
-    }
-#pragma unroll
-    for (int o = 1; o < kLossSlots; o <<= 1) {
-      v0 += __shfl_xor(v0, o, 64);
-      v1 += __shfl_xor(v1, o, 64);
-      v2 += __shfl_xor(v2, o, 64);
-      fl |= __shfl_xor(fl, o, 64);
-    }
-    if (on && s == 0) s_v[q][k] = loss_value(v0, v1, v2, fl);
+    const double v = loss_row_collect(S, k, s, on);
+    if (on && s == 0) s_v[q][k] = v;
   }
   __syncthreads();
   const bool bad = s_bad != 0;
@@ -252,11 +180,6 @@ __global__ __launch_bounds__(64 * kStates) void k_metrics_finish(LossState* __re
     for (int k = 0; k < C; ++k) tot += s_v[col][k];
     out[col] = bad ? qnan : (col < 2 ? tot / ((double)C * n) : tot);
   }
-}
-
-inline uint64_t mul_sat(uint64_t a, uint64_t b) {
-  uint64_t r;
-  return __builtin_mul_overflow(a, b, &r) ? UINT64_MAX : r;
 }
 
 }  // namespace

@@ -94,7 +94,7 @@ __device__ __forceinline__ void fwd_body(const MFwdEntry& E, int tile, float (*s
         float m = 1.f;
         if constexpr (MT == kMaskU8) m = (float)((const uint8_t*)E.m)[(size_t)b * E.mbs + in];
         if constexpr (MT == kMaskF32) m = ((const float*)E.m)[(size_t)b * E.mbs + in];
-        g = raw_loss_term(a, E.t[(size_t)b * E.tbs + in], E.w[(size_t)b * E.wbs + in], m, E.gscale[i], contrib);
+        g = loss_term(a, E.t[(size_t)b * E.tbs + in], E.w[(size_t)b * E.wbs + in], m, true, E.gscale[i], contrib);
       }
       E.gout[kb + in] = g;
     }

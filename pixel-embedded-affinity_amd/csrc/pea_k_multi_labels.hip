@@ -177,7 +177,7 @@ __device__ __forceinline__ void lab_body(const MLabEntry& E, int tile, unsigned 
           const float dot = dot_vec(xc, v);
           a = role == 0 ? dot * inv_p * inv_q : dot * inv_q * inv_p;  // the first operand's 1 / norm first, as cosine_streamed
           float term;  // the term's share of the loss: counted where it lives, at role A's pixel
-          const float g = raw_loss_term(a, t, w, m, gs, term);
+          const float g = loss_term(a, t, w, m, true, gs, term);
           if (role == 0) contrib = term;
           accumulate(G, g * inv_q, v);
         }

@@ -112,11 +112,6 @@ __global__ __launch_bounds__(kBlock) void k_unflip(const T* __restrict__ src, T*
   }
 }
 
-// a * b, UINT64_MAX where it does not fit
-inline uint64_t mul_sat(uint64_t a, uint64_t b) {
-  uint64_t r;
-  return __builtin_mul_overflow(a, b, &r) ? UINT64_MAX : r;
-}
 inline uint64_t add_sat(uint64_t a, uint64_t b) {
   uint64_t r;
   return __builtin_add_overflow(a, b, &r) ? UINT64_MAX : r;

@@ -96,16 +96,10 @@ __device__ __forceinline__ double loss_value(u64 lo_s, u64 mid_s, u64 hi_s, unsi
   return d;
 }
 
-// The finish: one workgroup of ceil(K / 4) waves, four offsets per wave (lane = 16 * j + s: offset 4 * wave + j, slot s), so every
-// accumulator word is requested in ONE round of loads (the one-wave form walked the offsets four at a time: three dependent round
-// trips at K = 10, 10 us per launch in the loss section's trace); the weighted total is summed in offset order by one lane.
-// Plain loads and plain zero stores: a kernel boundary lies between the adds and these reads.
-static __global__ __launch_bounds__(512) void k_loss_finish(const KParams P, LossState* __restrict__ st, float* __restrict__ loss_out) {
-  __shared__ double s_l[PEA_MAX_K];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, s = lane & (kLossSlots - 1), j = lane >> 4;
-  const bool good = st->magic == kLossMagic;
-  const int k = 4 * wave + j;
-  const bool on = k < P.K;
+// The row collector of every finish.  Lane 16 * j + s of a wave reads slot s of row k of the state (on: the lane has a row), zeroes
+// it, slot 0 takes and clears the row's flag word, and the 16 adjacent lanes of a row meet in a butterfly: each of them returns the
+// row's value.  All 64 lanes call it.  Plain loads and plain zero stores: a kernel boundary lies between the adds and these reads.
+__device__ __forceinline__ double loss_row_collect(LossState* __restrict__ st, int k, int s, bool on) {
   u64 v0 = 0, v1 = 0, v2 = 0;
   unsigned fl = 0;
   if (on) {
@@ -115,13 +109,29 @@ static __global__ __launch_bounds__(512) void k_loss_finish(const KParams P, Los
     if (s == 0) { fl = st->flags[k]; st->flags[k] = 0; }
   }
 #pragma unroll
-  for (int o = 1; o < kLossSlots; o <<= 1) {  // the 16 slots of an offset sit in 16 adjacent lanes
+  for (int o = 1; o < kLossSlots; o <<= 1) {
     v0 += __shfl_xor(v0, o, 64);
     v1 += __shfl_xor(v1, o, 64);
     v2 += __shfl_xor(v2, o, 64);
     fl |= __shfl_xor(fl, o, 64);
   }
-  double Li = on ? loss_value(v0, v1, v2, fl) * (double)P.inv_n[k] : 0.0;
+  return loss_value(v0, v1, v2, fl);
+}
+
+// The finish of a loss: one workgroup of ceil(K / 4) waves, four offsets per wave (lane = 16 * j + s: offset 4 * wave + j, slot s), so
+// every accumulator word is requested in ONE round of loads (the one-wave form walked the offsets four at a time: three dependent round
+// trips at K = 10, 10 us per launch in the loss section's trace); the weighted total is summed in offset order by one lane.
+// The body of k_loss_finish and of k_loss_finish_multi (pea_multi_common.h: a workgroup per entry); MAXK sizes the LDS row.
+template <int MAXK>
+__device__ __forceinline__ void loss_finish(LossState* __restrict__ st, float* __restrict__ loss_out, int K, const float* inv_n,
+                                            const float* lam) {
+  __shared__ double s_l[MAXK];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, s = lane & (kLossSlots - 1), j = lane >> 4;
+  const bool good = st->magic == kLossMagic;
+  const int k = 4 * wave + j;
+  const bool on = k < K;
+  const double v = loss_row_collect(st, k, s, on);
+  double Li = on ? v * (double)inv_n[on ? k : 0] : 0.0;
   if (!good) Li = __builtin_nan("");  // the state block was never initialised (pea_workspace_init): say so
   if (on && s == 0) {
     loss_out[1 + k] = (float)Li;
@@ -130,9 +140,12 @@ static __global__ __launch_bounds__(512) void k_loss_finish(const KParams P, Los
   __syncthreads();
   if (threadIdx.x == 0) {
     double tot = 0.0;
-    for (int i = 0; i < P.K; ++i) tot += (double)P.lam[i] * s_l[i];
+    for (int i = 0; i < K; ++i) tot += (double)lam[i] * s_l[i];
     loss_out[0] = (float)tot;
   }
+}
+static __global__ __launch_bounds__(512) void k_loss_finish(const KParams P, LossState* __restrict__ st, float* __restrict__ loss_out) {
+  loss_finish<PEA_MAX_K>(st, loss_out, P.K, P.inv_n, P.lam);
 }
 
 // pea_workspace_init: zero `n` states and mark them initialised

@@ -64,43 +64,10 @@ __device__ __forceinline__ void with_value(int v, F&& f) {
   else f(Int<C>{});
 }
 
-// k_loss_finish (pea_loss.h) with one workgroup per entry: lane = 16 * j + s holds slot s of offset 4 * wave + j; reads the
-// accumulators, writes loss_out, puts the state back to zero.  A kernel boundary lies between the adds and these plain loads.
+// k_loss_finish (pea_loss.h) with one workgroup per entry
 static __global__ __launch_bounds__(64 * ((kMaxK + 3) / 4)) void k_loss_finish_multi(const MFinTable T) {
-  __shared__ double s_l[kMaxK];
   const MFinEntry& E = T.en[blockIdx.x];
-  LossState* __restrict__ st = E.st;
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, s = lane & (kLossSlots - 1), j = lane >> 4;
-  const bool good = st->magic == kLossMagic;
-  const int k = 4 * wave + j;
-  const bool on = k < E.K;
-  u64 v0 = 0, v1 = 0, v2 = 0;
-  unsigned fl = 0;
-  if (on) {
-    u64* a = st->acc[s][k];
-    v0 = a[0]; v1 = a[1]; v2 = a[2];
-    a[0] = 0; a[1] = 0; a[2] = 0;
-    if (s == 0) { fl = st->flags[k]; st->flags[k] = 0; }
-  }
-#pragma unroll
-  for (int o = 1; o < kLossSlots; o <<= 1) {
-    v0 += __shfl_xor(v0, o, 64);
-    v1 += __shfl_xor(v1, o, 64);
-    v2 += __shfl_xor(v2, o, 64);
-    fl |= __shfl_xor(fl, o, 64);
-  }
-  double Li = on ? loss_value(v0, v1, v2, fl) * (double)E.inv_n[on ? k : 0] : 0.0;
-  if (!good) Li = __builtin_nan("");  // the state block was never initialised (pea_workspace_init): say so
-  if (on && s == 0) {
-    E.loss_out[1 + k] = (float)Li;
-    s_l[k] = Li;
-  }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    double tot = 0.0;
-    for (int i = 0; i < E.K; ++i) tot += (double)E.lam[i] * s_l[i];
-    E.loss_out[0] = (float)tot;
-  }
+  loss_finish<kMaxK>(E.st, E.loss_out, E.K, E.inv_n, E.lam);
 }
 
 inline void launch_loss_finish_multi(const MFinTable& F, int n, hipStream_t s) {

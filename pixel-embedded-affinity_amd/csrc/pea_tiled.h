@@ -31,7 +31,6 @@
 
 namespace pea {
 
-typedef float f4 __attribute__((ext_vector_type(4)));
 typedef __amdgpu_buffer_rsrc_t rsrc_t;
 
 struct OffEnt {  // per-offset constants, one s_load_dwordx4
@@ -87,11 +86,9 @@ __device__ __forceinline__ float bl8(rsrc_t r, unsigned vo, unsigned so) {
 }
 // The mask of the 2D training forwards: MT = uint8_t, or float (PEA_FLAG_MASK_F32: include/pea.h), a template parameter of each.
 // Per lane: m_load (vo / so address the pixel in an f32 plane, vo8 / so8 in the u8 plane).  Per quad of four x-adjacent pixels
-// (the dwordx4 epilogues): mq_t<MT> holds the four masks -- one dword of four bytes, or one dwordx4 requested at the same point.
+// (the dwordx4 epilogues): mq_t<MT> (pea_epilogue.h, with mq_get) holds the four masks, requested at the same point.
 template <typename MT>
 constexpr bool kMaskF32 = std::is_same<MT, float>::value;
-template <typename MT>
-using mq_t = typename std::conditional<kMaskF32<MT>, f4, unsigned>::type;
 template <typename MT>
 __device__ __forceinline__ mq_t<MT> mq_ones() {
   if constexpr (kMaskF32<MT>) return f4{1.f, 1.f, 1.f, 1.f};
@@ -102,11 +99,6 @@ __device__ __forceinline__ mq_t<MT> mq_load(rsrc_t r, unsigned vo, unsigned so, 
   static_assert(kMaskF32<MT> || std::is_same<MT, uint8_t>::value, "the mask is u8 or f32");
   if constexpr (kMaskF32<MT>) return __builtin_bit_cast(f4, __builtin_amdgcn_raw_buffer_load_b128(r, vo, so, kAuxNT));
   else return __builtin_amdgcn_raw_buffer_load_b32(r, vo8, so8, kAuxNT);
-}
-template <typename MT>
-__device__ __forceinline__ float mq_get(const mq_t<MT>& q, int j) {
-  if constexpr (kMaskF32<MT>) return q[j];
-  else return (float)((q >> (8 * j)) & 0xffu);
 }
 template <typename MT>
 __device__ __forceinline__ float m_load(rsrc_t r, unsigned vo, unsigned so, unsigned vo8, unsigned so8) {
@@ -137,20 +129,6 @@ __device__ __forceinline__ void bs_emb(rsrc_t r, float v, unsigned vo, unsigned 
   else if constexpr (std::is_same<T, __half>::value)
     __builtin_amdgcn_raw_buffer_store_b16(__builtin_bit_cast(unsigned short, __float2half(v)), r, vo, so, NTL ? kAuxNT : 0);
   else __builtin_amdgcn_raw_buffer_store_b16(__builtin_bit_cast(unsigned short, (__bf16)v), r, vo, so, NTL ? kAuxNT : 0);
-}
-
-// sum over the 64 lanes, result valid in lane 63: 6 DPP adds (no LDS traffic)
-__device__ __forceinline__ float wave_sum63(float v) {
-#define PEA_DPP_ADD(ctrl, rmask) \
-  v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), ctrl, rmask, 0xf, false))
-  PEA_DPP_ADD(0x111, 0xf);  // row_shr:1
-  PEA_DPP_ADD(0x112, 0xf);  // row_shr:2
-  PEA_DPP_ADD(0x114, 0xf);  // row_shr:4
-  PEA_DPP_ADD(0x118, 0xf);  // row_shr:8   -> lane 15 of each row = row total
-  PEA_DPP_ADD(0x142, 0xa);  // row_bcast:15 into rows 1,3
-  PEA_DPP_ADD(0x143, 0xc);  // row_bcast:31 into rows 2,3 -> lane 63 = wave total
-#undef PEA_DPP_ADD
-  return v;
 }
 
 // ---- LDS geometry: [slot q][region pixel] of float4, PLQ = compile-time plane stride in pixels ----------
@@ -365,10 +343,10 @@ __device__ __forceinline__ void fwd_finish(const FwdU U, int K, float* s_part, c
   }
   if (U.has_a) bs32<true>(hi ? U.aB1 : U.aB, LACT ? u : act_affs(a, U.af), pb, so);
   if (TRAIN) {
-    const float r = u * m - t * m;
-    const float wr = valid ? w * r : 0.f;
-    if (U.has_g) bs32(hi ? U.gB1 : U.gB, LACT ? act_g(u, v, e.gscale * AK.sc, wr, m, AK) : e.gscale * wr * m, pb, so);
-    const float red = wave_sum63(wr * r);
+    float contrib;
+    const float g = loss_term<LACT>(v, t, w, m, valid, e.gscale, AK, contrib);
+    if (U.has_g) bs32(hi ? U.gB1 : U.gB, g, pb, so);
+    const float red = wave_sum63(contrib);
     if ((threadIdx.x & 63) == 63) s_part[(threadIdx.x >> 6) * K + e.i] = red;
   }
 }
@@ -525,12 +503,7 @@ __global__ __launch_bounds__(TH* TW, (D_T > 16 ? 2 : 4)) void k_fwd_tiled(const 
 
   if (TRAIN) {
     lds_barrier();
-    if (threadIdx.x < P.K) {
-      float v = 0.f;
-#pragma unroll
-      for (int w = 0; w < NW; ++w) v += s_part[w * P.K + threadIdx.x];
-      loss_accumulate(st, tile, threadIdx.x, v);
-    }
+    if (threadIdx.x < P.K) part_accumulate<NW>(st, tile, threadIdx.x, s_part, 1, P.K);
   }
 }
 
@@ -743,6 +716,9 @@ __global__ __launch_bounds__(TH* TW, (D_T > 16 ? 2 : 4)) void k_fwd_tiled_v(cons
       bs128<true>(aB, o, ivo[it], so);
     }
     if (TRAIN) {
+      // loss_quad (pea_epilogue.h) written out: this kernel decides `rep` at run time, the compiler clones the quad for the two answers,
+      // and behind the call the clones contracted r differently from these lines (v_pk_fma_f32 where they give v_mul + v_sub): other
+      // bits of g and the loss for any mask that is not 0 / 1.  The lines stay until the residual's rounding is stated explicitly.
       float acc = 0.f;
       f4 g4;
 #pragma unroll
@@ -766,12 +742,7 @@ __global__ __launch_bounds__(TH* TW, (D_T > 16 ? 2 : 4)) void k_fwd_tiled_v(cons
   }
   if (TRAIN) {
     lds_barrier();
-    if (threadIdx.x < P.K) {
-      float v = 0.f;
-#pragma unroll
-      for (int s = 0; s < NSL; ++s) v += s_part[threadIdx.x * NSL + s];
-      loss_accumulate(st, tile, threadIdx.x, v);
-    }
+    if (threadIdx.x < P.K) part_accumulate<NSL>(st, tile, threadIdx.x, s_part, NSL, 1);
   }
 }
 

@@ -1050,11 +1050,8 @@ __global__ __launch_bounds__(TH* TW, WPE) void k_fwd_xdma(const KParams P, const
         const float w = t != 0.f ? w1 : w0;
         const bool exists = lv && (!CROP || inside);
         const float a = exists ? a4[j] : 0.f;
-        const float rr = a * m - t * m;
-        const float wr = exists ? w * rr : 0.f;
         o4[j] = act_affs(a, af);
-        g4[j] = gs * wr * m;
-        acc = fmaf(wr, rr, acc);
+        g4[j] = loss_term_acc(a, t, w, m, exists, gs, acc);
       }
       if (has_a) bs128<true>(aB, o4, ivo[it], so);
       if (has_g) bs128<false>(gB, g4, ivo[it], so);
@@ -1074,35 +1071,16 @@ __global__ __launch_bounds__(TH* TW, WPE) void k_fwd_xdma(const KParams P, const
       bs128<true>(aB, o, ivo[it], so);
     }
     if (TRAIN) {
-      float acc = 0.f;
-      f4 g4;
+      float acc;
       const float gs = BCE ? P.lam[sl] * P.inv_n[sl] : C.gs[sl];  // BCE: lambda / N, without the squared residual's factor 2
       const int ax_ = C.oax[sl], od_ = C.od[sl];
+      bool exists[4];  // a cropped-away neighbour carries no loss term (its a is already 0)
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
-        const float m = mq_get<MT>(m4[it], j);
-        const float u = LACT ? act_u(v4[j], AK) : v4[j];
-        if constexpr (BCE) {  // the same epilogue with bce_term's (contrib, factor) in place of (wr * r, wr)
-          float l, bt = bce_term(u * m, t4[it][j] * m, w4[it][j], l);
-          if (CROP) {
-            const int q = (ax_ == 1 ? igx[it] + j : ax_ == 0 ? igy[it] : z) + od_;
-            const bool in = (unsigned)q < (unsigned)(ax_ == 1 ? P.X : ax_ == 0 ? P.Y : P.Z);
-            bt = in ? bt : 0.f;
-            l = in ? l : 0.f;
-          }
-          g4[j] = act_g(u, v4[j], gs * AK.sc, bt, m, AK);
-          acc += l;
-          continue;
-        }
-        const float r = u * m - t4[it][j] * m;
-        float wr = w4[it][j] * r;
-        if (CROP) {  // a cropped-away neighbour carries no loss term (its a is already 0)
-          const int q = (ax_ == 1 ? igx[it] + j : ax_ == 0 ? igy[it] : z) + od_;
-          wr = (unsigned)q < (unsigned)(ax_ == 1 ? P.X : ax_ == 0 ? P.Y : P.Z) ? wr : 0.f;
-        }
-        g4[j] = LACT ? act_g(u, v4[j], gs * AK.sc, wr, m, AK) : gs * wr * m;
-        acc = fmaf(wr, r, acc);
+        const int q = (ax_ == 1 ? igx[it] + j : ax_ == 0 ? igy[it] : z) + od_;
+        exists[j] = !CROP || (unsigned)q < (unsigned)(ax_ == 1 ? P.X : ax_ == 0 ? P.Y : P.Z);
       }
+      const f4 g4 = loss_quad<MT, LACT, BCE>(v4, t4[it], w4[it], m4[it], exists, gs, AK, acc);
       if (has_g) bs128<false>(gB, g4, ivo[it], so);
       const float red = wave_sum63(acc);
       if ((threadIdx.x & 63) == 63) s_part[sl * NSL + (iqd[it] >> 6)] = red;
@@ -1111,12 +1089,7 @@ __global__ __launch_bounds__(TH* TW, WPE) void k_fwd_xdma(const KParams P, const
   if (TRAIN) {
     lds_barrier();
     if (wave == 0) {  // the one wave that touches the loss state
-      if ((int)threadIdx.x < P.K) {
-        float v = 0.f;
-#pragma unroll
-        for (int s = 0; s < NSL; ++s) v += s_part[threadIdx.x * NSL + s];
-        loss_accumulate(st, tile, threadIdx.x, v);
-      }
+      if ((int)threadIdx.x < P.K) part_accumulate<NSL>(st, tile, threadIdx.x, s_part, NSL, 1);
     }
   }
 }

@@ -360,27 +360,16 @@ __global__ __launch_bounds__(TH* TW, NB == 3 ? 2 : 4) void k_fwd_xdma_dual(const
       if (af) { o.x = act_affs(o.x, af); o.y = act_affs(o.y, af); o.z = act_affs(o.z, af); o.w = act_affs(o.w, af); }
       bs128<true>(aB, o, ivo[it], so);
     }
-    float acc = 0.f, acc2 = 0.f;
-    f4 g4, h4;
-    const float gs = C.gs[sl], gs2 = DA.gs2[sl];
+    float acc, acc2;
     const int ax_ = C.oax[sl], od_ = C.od[sl];
+    bool exists[4];  // a cropped-away neighbour carries no loss term (its a is already 0)
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
-      const float m = mq_get<MT>(m4[it], j);
-      const float r = a4[j] * m - t4[it][j] * m;
-      const float r2 = c4[j] * m - t4[it][j] * m;
-      float wr = w4[it][j] * r, wr2 = w4[it][j] * r2;
-      if (CROP) {  // a cropped-away neighbour carries no loss term (its a is already 0)
-        const int q = (ax_ == 1 ? igx[it] + j : igy[it]) + od_;
-        const bool in = (unsigned)q < (unsigned)(ax_ == 1 ? P.X : P.Y);
-        wr = in ? wr : 0.f;
-        wr2 = in ? wr2 : 0.f;
-      }
-      g4[j] = gs * wr * m;
-      h4[j] = gs2 * wr2 * m;
-      acc = fmaf(wr, r, acc);
-      acc2 = fmaf(wr2, r2, acc2);
+      const int q = (ax_ == 1 ? igx[it] + j : igy[it]) + od_;
+      exists[j] = !CROP || (unsigned)q < (unsigned)(ax_ == 1 ? P.X : P.Y);
     }
+    const f4 g4 = loss_quad<MT>(a4, t4[it], w4[it], m4[it], exists, C.gs[sl], acc);
+    const f4 h4 = loss_quad<MT>(c4, t4[it], w4[it], m4[it], exists, DA.gs2[sl], acc2);
     bs128<false>(gB, g4, ivo[it], so);
     bs128<false>(g2B, h4, ivo[it], so);
     const float red = wave_sum63(acc), red2 = wave_sum63(acc2);
@@ -391,13 +380,7 @@ __global__ __launch_bounds__(TH* TW, NB == 3 ? 2 : 4) void k_fwd_xdma_dual(const
   }
   lds_barrier();
   if (wave < 2) {  // the two waves that touch the loss states: wave 0 the self loss', wave 1 the cross loss'
-    if (lane < P.K) {
-      const float* sp = wave == 0 ? s_part : s_part2;
-      float v = 0.f;
-#pragma unroll
-      for (int s = 0; s < NSL; ++s) v += sp[lane * NSL + s];
-      loss_accumulate(wave == 0 ? st : DA.st2, tile, lane, v);
-    }
+    if (lane < P.K) part_accumulate<NSL>(wave == 0 ? st : DA.st2, tile, lane, wave == 0 ? s_part : s_part2, NSL, 1);
   }
 }
 

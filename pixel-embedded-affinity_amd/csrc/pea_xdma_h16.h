@@ -618,23 +618,15 @@ __global__ __launch_bounds__(TH* TW, WPE) void k_fwd_xdma_h(const KParams P, con
       bs128<true>(aB, o, ivo[it], so);
     }
     if (TRAIN) {
-      float acc = 0.f;
-      f4 g4;
-      const float gs = C.gs[sl];
+      float acc;
       const int ax_ = C.oax[sl], od_ = C.od[sl];
+      bool exists[4];
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
-        const float m = mq_get<MT>(m4[it], j);
-        const float u = LACT ? act_u(v4[j], AK) : v4[j];
-        const float r = u * m - t4[it][j] * m;
-        float wr = w4[it][j] * r;
-        if (CROP) {
-          const int q = (ax_ == 1 ? igx[it] + j : igy[it]) + od_;
-          wr = (unsigned)q < (unsigned)(ax_ == 1 ? P.X : P.Y) ? wr : 0.f;
-        }
-        g4[j] = LACT ? act_g(u, v4[j], gs * AK.sc, wr, m, AK) : gs * wr * m;
-        acc = fmaf(wr, r, acc);
+        const int q = (ax_ == 1 ? igx[it] + j : igy[it]) + od_;
+        exists[j] = !CROP || (unsigned)q < (unsigned)(ax_ == 1 ? P.X : P.Y);
       }
+      const f4 g4 = loss_quad<MT, LACT>(v4, t4[it], w4[it], m4[it], exists, C.gs[sl], AK, acc);
       if (has_g) bs128<false>(gB, g4, ivo[it], so);
       const float red = wave_sum63(acc);
       if ((tid_ & 63) == 63) s_part[sl * NSL + (iqd[it] >> 6)] = red;
@@ -642,12 +634,7 @@ __global__ __launch_bounds__(TH* TW, WPE) void k_fwd_xdma_h(const KParams P, con
   }
   if (TRAIN) {
     lds_barrier();
-    if (wave == 0 && (int)threadIdx.x < P.K) {
-      float v = 0.f;
-#pragma unroll
-      for (int s = 0; s < NSL; ++s) v += s_part[threadIdx.x * NSL + s];
-      loss_accumulate(st, tile, threadIdx.x, v);
-    }
+    if (wave == 0 && (int)threadIdx.x < P.K) part_accumulate<NSL>(st, tile, threadIdx.x, s_part, NSL, 1);
   }
 }
 

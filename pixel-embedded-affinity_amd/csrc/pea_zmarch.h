@@ -559,9 +559,8 @@ __global__ __launch_bounds__(TH* TW, 2) void k_fwd_zm(const KParams P, const XPa
           if (ps < 7) PEA_ZM_WAIT(24 + NLD);                                                                                   \
           else PEA_ZM_WAIT(24);                                                                                                \
           PEA_ZMF_CHUNK(ps, ezn + (unsigned)(2 * ps) * ecs, vn0, vn1)                                                          \
-          if (TRAIN && ps == 0 && !first && lane_k) { /* the PREVIOUS plane's loss partials: behind this barrier they are all */ \
-            _Pragma("unroll") for (int s = 0; s < NSL; ++s) lacc += s_part[threadIdx.x * NSL + s]; /* written (no barrier of */ \
-          }                                                                                        /* their own)            */ \
+          /* the PREVIOUS plane's loss partials: behind this barrier they are all written (no barrier of their own) */         \
+          if (TRAIN && ps == 0 && !first && lane_k) lacc = part_sum<NSL>(s_part, threadIdx.x, NSL, 1, lacc);                   \
         }                                                                                                                      \
         const float osum = oss.x + oss.y;                                                                                      \
         const float inv_own = rnorm(osum, inv_eps);                                                                            \
@@ -591,19 +590,14 @@ __global__ __launch_bounds__(TH* TW, 2) void k_fwd_zm(const KParams P, const XPa
           f4 o4 = a4;                                                                                                          \
           if (af) { o4.x = act_affs(o4.x, af); o4.y = act_affs(o4.y, af); o4.z = act_affs(o4.z, af); o4.w = act_affs(o4.w, af); } \
           bs128<true>(aB, o4, (has_a && ion[it]) ? ivo[it] : kOOB, so);                                                        \
-          float acc = 0.f;                                                                                                     \
-          f4 g4;                                                                                                               \
-          const float gs = C.gs[sl];                                                                                           \
+          float acc;                                                                                                           \
           const int ax_ = C.oax[sl], od_ = C.od[sl];                                                                           \
+          bool exists[4];                                                                                                      \
           _Pragma("unroll") for (int j = 0; j < 4; ++j) {                                                                      \
-            const float m = (float)((m4[it] >> (8 * j)) & 0xffu);                                                              \
-            const float r = a4[j] * m - t4[it][j] * m;                                                                         \
-            float wr = w4[it][j] * r;                                                                                          \
             const int q = (ax_ == 1 ? igx[it] + j : ax_ == 0 ? igy[it] : z) + od_;                                             \
-            wr = (unsigned)q < (unsigned)(ax_ == 1 ? P.X : ax_ == 0 ? P.Y : P.Z) ? wr : 0.f;                                   \
-            g4[j] = gs * wr * m;                                                                                               \
-            acc = fmaf(wr, r, acc);                                                                                            \
+            exists[j] = (unsigned)q < (unsigned)(ax_ == 1 ? P.X : ax_ == 0 ? P.Y : P.Z);                                       \
           }                                                                                                                    \
+          const f4 g4 = loss_quad<uint8_t>(a4, t4[it], w4[it], m4[it], exists, C.gs[sl], acc);                                 \
           bs128<false>(gB, g4, (TRAIN && has_g && ion[it]) ? ivo[it] : kOOB, so);                                              \
           if (TRAIN && ion[it]) {                                                                                              \
             const float red = wave_sum63(acc);                                                                                 \
@@ -623,11 +617,7 @@ __global__ __launch_bounds__(TH* TW, 2) void k_fwd_zm(const KParams P, const XPa
 #undef PEA_ZMF_CHUNK
   if (TRAIN) {
     lds_barrier();  // the last plane's partials
-    if (lane_k) {
-#pragma unroll
-      for (int s = 0; s < NSL; ++s) lacc += s_part[threadIdx.x * NSL + s];
-      loss_accumulate(st, tile, threadIdx.x, lacc);
-    }
+    if (lane_k) part_accumulate<NSL>(st, tile, threadIdx.x, s_part, NSL, 1, lacc);
   }
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the last plane's look-ahead DMA (out-of-range: zeros) has drained
 }
