@@ -72,12 +72,12 @@ __device__ __forceinline__ unsigned box_item(const KParams& P, int q, int nq_pla
   return ok ? (unsigned)(((j * P.Z + gz) * P.Y + gy) * P.X + gx) * 4u : kOOB;  // j * S + voxel < 2^29 (host-checked)
 }
 
-#define PEA_BWAIT(n) asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)\n\ts_barrier" ::"n"(n) : "memory")
 // wait until only the youngest chunk's DMA (3 wave instructions in wave 0, 2 in the others) may be in flight, then the barrier
-#define PEA_BWAIT1()                   \
-  {                                    \
-    if (wave == 0) PEA_BWAIT(3);       \
-    else PEA_BWAIT(2);                 \
+// (pea_stage.h)
+#define PEA_BWAIT1()                          \
+  {                                           \
+    if (wave == 0) loads_barrier<3>();        \
+    else loads_barrier<2>();                  \
   }
 #define PEA_BDMA(buf, so)                                                                                                      \
   {                                                                                                                            \
@@ -156,7 +156,7 @@ __global__ __launch_bounds__(kBoxTH* kBoxTW, 4) void k_fwd_box(const KParams P, 
     asm volatile("" : "+v"(oss));
     if (ps + 1 < NP) {
       if (ps + 2 < NP) PEA_BWAIT1()
-      else PEA_BWAIT(0);
+      else loads_barrier<0>();
       if (ps + 3 < NP) PEA_BDMA(ps % 3, (unsigned)(2 * ps + 6) * ecs)
     }
   }
@@ -298,7 +298,7 @@ __global__ __launch_bounds__(kBoxTH* kBoxTW, 6) void k_bwd_box(const KParams P, 
   }
 #pragma unroll
   for (int s = 0; s < kBoxND / 2; ++s) asm volatile("" : "+v"(c2[s]));
-  asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");  // the 1 / norm region is dead: the third buffer may be filled
+  lds_barrier();  // the 1 / norm region is dead: the third buffer may be filled
   PEA_BDMA(2, 4u * ecs)
 
   f2 G[NP], eh[NP];
@@ -323,7 +323,7 @@ __global__ __launch_bounds__(kBoxTH* kBoxTW, 6) void k_bwd_box(const KParams P, 
     G[ps] = acc;
     if (ps + 1 < NP) {
       if (ps + 2 < NP) PEA_BWAIT1()
-      else PEA_BWAIT(0);
+      else loads_barrier<0>();
       if (ps + 3 < NP) PEA_BDMA(ps % 3, (unsigned)(2 * ps + 6) * ecs)
     }
   }
@@ -342,7 +342,6 @@ __global__ __launch_bounds__(kBoxTH* kBoxTW, 6) void k_bwd_box(const KParams P, 
 
 #undef PEA_BDMA
 #undef PEA_BWAIT1
-#undef PEA_BWAIT
 
 // host: the plan.  false = an offset leaves the unit box, or the volume does not meet the kernels' addressing limits
 inline bool plan_box(const KParams& P, BParams* out) {

@@ -40,7 +40,6 @@ __host__ __device__ constexpr int boxm_lds(int s) {
   return ((J + box_dz(s) + 3) % 3) * kBmUnit + (box_dy(s) * kBoxRW + box_dx(s)) * 4 + kBmBias;
 }
 
-#define PEA_BM_WAIT(n) asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)\n\ts_barrier" ::"n"(n) : "memory")
 
 // plane zp of pair c into its slot (zp mod 3 == slot_); a plane outside the volume arrives as zeros
 #define PEA_BM_UNIT(c_, zp_, slot_)                                                                                            \
@@ -119,7 +118,7 @@ __host__ __device__ constexpr int boxm_lds(int s) {
         asm volatile("" : "+v"(acc), "+v"(eh[c]));                                                                             \
         G[c] = acc;                                                                                                            \
         if (c == 3) { /* B1: pairs 0 - 3 are done with plane z - 1, the coefficients with 1 / norm plane z - 1 */             \
-          PEA_BM_WAIT(2 * kBoxND); /* what was requested at the previous B2 has landed (the g loads behind it may fly) */     \
+          loads_barrier<2 * kBoxND>(); /* what was requested at the previous B2 has landed (the g loads behind it may fly) */ \
           PEA_BM_UNIT(0, z + 2, (J + 2) % 3)                                                                                   \
           PEA_BM_UNIT(1, z + 2, (J + 2) % 3)                                                                                   \
           PEA_BM_UNIT(2, z + 2, (J + 2) % 3)                                                                                   \
@@ -134,8 +133,8 @@ __host__ __device__ constexpr int boxm_lds(int s) {
       const unsigned pe = live ? (unsigned)((z * P.Y + py) * P.X + px) * 4u : kOOB;                                            \
       /* B2: pairs 4 - 7 are done with plane z - 1; what was requested at B1 has landed: no load is younger than it (the      */ \
       /* gradient stores follow the barrier: a store may retire before an older load, so none may sit between a request and the */ \
-      /* wait that counts on it -- pea_zmarch.h zm_bwd_wait)                                                                    */ \
-      PEA_BM_WAIT(0);                                                                                                          \
+      /* wait that counts on it -- pea_stage.h)                                                                                */ \
+      loads_barrier<0>();                                                                                                      \
       PEA_BM_UNIT(4, z + 2, (J + 2) % 3)                                                                                       \
       PEA_BM_UNIT(5, z + 2, (J + 2) % 3)                                                                                       \
       PEA_BM_UNIT(6, z + 2, (J + 2) % 3)                                                                                       \
@@ -202,19 +201,18 @@ __global__ __launch_bounds__(kBoxTH* kBoxTW, 2) void k_bwd_boxm(const KParams P,
   PEA_BM_INV(zb, 0)
   PEA_BM_INV(zb + 1, 1)
   PEA_BM_GLOAD(zb)
-  PEA_BM_WAIT(0);
+  loads_barrier<0>();
   for (int zq = zb; zq < ze; zq += 3) {
     PEA_BM_STEP(0, zq)
     PEA_BM_STEP(1, zq + 1)
     PEA_BM_STEP(2, zq + 2)
   }
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the look-ahead beyond the segment has drained
+  loads_landed<0>();  // the look-ahead beyond the segment has drained
 }
 
 #undef PEA_BM_STEP
 #undef PEA_BM_GLOAD
 #undef PEA_BM_INV
 #undef PEA_BM_UNIT
-#undef PEA_BM_WAIT
 
 }  // namespace pea

@@ -19,6 +19,8 @@
 // false when its family has no kernel for the descriptor and the caller tries the next one.  No device code crosses a file.
 // pea_dispatch.h holds what the launchers share to get from run-time facts (storage dtype, D, border, mask type, ..) to template
 // arguments: launch<KERNEL>() and the with_bool / with_storage / with_width / with_mask_form callers of generic lambdas.
+// pea_stage.h holds what the LDS-staged families (pea_xdma*.h, pea_zmarch.h, pea_box*.h) rest on: the staging geometry of the cross,
+// the LDS slot of a neighbour, the LDS-DMA issue of a plane and the load-counted hand-off (s_waitcnt vmcnt(N); s_barrier).
 // pea_epilogue.h holds what every training forward ends with: the loss term of a pair (scalar and quad form), wave_sum63 and the
 // workgroup's tail into the loss state; pea_gather.h and the LDS-staged families include it.
 #pragma once

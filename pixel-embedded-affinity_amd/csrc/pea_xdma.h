@@ -1,6 +1,7 @@
 // pea_xdma.h -- backward for AXIS-ALIGNED in-plane stencils (every offset moves along y or along x only: the CVPPP /
 // BBBC039V1 multi_offset(neighbor=4) tables, the in-plane AC3/AC4 tables), the whole stencil served from LDS, staged by
-// LDS-DMA.  Included by pea_k_xdma.hip (and, for the staging geometry and the tile walk, by pea_box.h / pea_zmarch.h).
+// LDS-DMA.  Included by pea_k_xdma.hip (and, for the tile walk, by pea_box.h / pea_zmarch.h).  The staging geometry, the DMA issue and
+// the load-counted hand-off are pea_stage.h's.
 //
 // Why a second backward next to k_bwd_tiled (pea_tiled.h): that kernel stages a (TH+2h) x (TW+2h) BOX of 64-byte
 // pixels through registers; at h = 9 one 32x32 tile fills the CU's 160 KB (one workgroup per CU: staging, gather and
@@ -23,7 +24,7 @@
 // (c & 31) resp. (c & (SW-1)): bank (c mod 32) -- the same bank it would have inside the tile, i.e. a wave whose lanes
 // split between VF and a strip still reads 32 distinct banks.
 #pragma once
-#include "pea_tiled.h"
+#include "pea_stage.h"
 
 namespace pea {
 
@@ -51,7 +52,6 @@ constexpr int kXP = 10;  // (offset, role) pairs per axis held in registers (CVP
 constexpr int kXZ = 8;   // (offset, role) pairs along z (AC3/AC4 norm5: shifts 1, 2, 3, 4)
 constexpr int kXK = 16;  // channels (offsets) the forward's epilogue handles
 typedef float f2 __attribute__((ext_vector_type(2)));
-typedef __attribute__((address_space(3))) void* lds_ptr_t;
 
 // acc += c * v for both channels of a pair, the coefficient c taken from the LOW (HI = false) or HIGH half of a register pair
 // that holds TWO pairs' coefficients.  hipcc materialises (f2){c, c} in two registers per coefficient (20 pairs: 40 VGPRs of
@@ -211,84 +211,29 @@ struct DualArgs {
 // second phase of k_bwd_xdma<.., DUAL>: role-A pairs of the second operand into G (D = 16: NP = 8 chunk pairs), 2D, no z.
 // Round 5: the phase no longer starts from an empty pipeline.  While the first phase gathers its last two chunks the kernel has
 // already requested this phase's 1 / norm plane (into plane 4, free behind chunk NP - 3), its g values (cx / cy: role A, the own
-// pixel) and its first chunk (into buffer 0, free behind chunk NP - 2) -- dual_geom / the hand-offs of k_bwd_xdma; here the
+// pixel) and its first chunk (into buffer 0, free behind chunk NP - 2) -- cross_stage on C2 / the hand-offs of k_bwd_xdma; here the
 // coefficients are formed at once, chunks 1 and 2 follow, and the ring runs as before.
-struct DualGeom {
-  unsigned vo[2];
-  bool act[2];
-  int npc;
-};
-template <int TH, int TW, bool CROP>
-__device__ __forceinline__ DualGeom dual_geom(const KParams& P, const XParams& C, const int y0, const int x0) {
-  constexpr int NT = TH * TW;
-  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
-  DualGeom g;
-#pragma unroll
-  for (int s = 0; s < 2; ++s) {
-    const int q = (s * (NT / 64) + wave) * 64 + lane;
-    int gy, gx;
-    if (q < C.QV) {
-      gy = y0 - C.hy0 + (q >> 3);
-      gx = x0 + 4 * (q & 7);
-    } else {
-      const int k = q - C.QV;
-      const int sh = C.SW == 64 ? 4 : 3;
-      const int cc = 4 * (k & ((1 << sh) - 1));
-      gy = y0 + (k >> sh);
-      gx = cc < C.split ? x0 + TW + cc : x0 - C.SW + cc;
-    }
-    g.act[s] = q < C.QA;
-    bool oky, okx;
-    gy = wrap1<CROP>(gy, P.Y, oky);
-    gx = wrap1<CROP>(gx, P.X, okx);
-    g.vo[s] = (g.act[s] && oky && okx) ? (unsigned)(gy * P.X + gx) * 4u : kOOB;
-  }
-  g.npc = 2 * ((__builtin_amdgcn_ballot_w64(g.act[0]) != 0) + (__builtin_amdgcn_ballot_w64(g.act[1]) != 0));
-  return g;
-}
-#define PEA_X2DMA(rsrc, plane_byte, so)                                                                                             \
-  {                                                                                                                                 \
-    if (DG.act[0]) __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (lds_ptr_t)(lds + (plane_byte) + wbase2), 16, DG.vo[0], so, 0, 0); \
-    if (DG.act[1]) __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (lds_ptr_t)(lds + (plane_byte) + w12), 16, DG.vo[1], so, 0, 0);    \
-  }
 template <int TH, int TW, int PSU, bool CROP, int XP>
-__device__ __forceinline__ void bwd_phase_role_a(const KParams& P, const XParams& C, char* lds, const rsrc_t xB, const DualGeom& DG,
+__device__ __forceinline__ void bwd_phase_role_a(const KParams& P, const XParams& C, char* lds, const rsrc_t xB, const CrossStage<>& DG,
                                                  float (&cx)[XP], float (&cy)[XP], const float dlx, const unsigned ezo,
                                                  const unsigned ecs, f2 (&G)[8]) {
-  constexpr int NT = TH * TW, PS = PSU * 256, NP = 8;
-  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int ly = threadIdx.x >> 5, lx = threadIdx.x & 31;
-  const int wbase2 = wave * 1024, w12 = wbase2 + (NT / 64) * 1024;
-  const int npc = DG.npc;
-#define PEA_X2WAIT1()                                                                            \
-  {                                                                                              \
-    if (npc == 4) asm volatile("s_waitcnt vmcnt(4) lgkmcnt(0)\n\ts_barrier" ::: "memory");       \
-    else if (npc == 2) asm volatile("s_waitcnt vmcnt(2) lgkmcnt(0)\n\ts_barrier" ::: "memory");  \
-    else asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory");                \
-  }
+  constexpr int PS = PSU * 256, NP = 8;
   int ax[XP], ay[XP];
-  const int vown = ((C.hy0 + ly) * TW + lx) * 4;
-  const int hrow = (C.QV * 4 + ly * C.SW) * 4;
-#pragma unroll
-  for (int k = 0; k < XP; ++k) {
-    const int d = C.xd[k], c = lx + d;
-    ax[k] = (unsigned)c < (unsigned)TW ? vown + d * 4 : hrow + (c & C.xm[k]) * 4;
-    ay[k] = vown + C.yd[k] * TW * 4;
-  }
+  cross_slots<TW>(C, threadIdx.x >> 5, threadIdx.x & 31, ax, ay);
   // every wave is done with the first phase's last chunk; this phase's 1 / norm plane, g values and first chunk -- requested one and
   // two chunks ago -- have landed
-  asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory");
+  loads_barrier<0>();
 #pragma unroll
   for (int k = 0; k < XP; ++k) {
     cx[k] *= fabsf(*(const float*)(lds + 4 * PS + ax[k])) * dlx;
     cy[k] *= fabsf(*(const float*)(lds + 4 * PS + ay[k])) * dlx;
     asm volatile("" : "+v"(cx[k]), "+v"(cy[k]));
   }
-  PEA_X2DMA(xB, 2 * PS, ezo + 2u * ecs)  // chunk 1 into buffer 1 (the first phase's last chunk is done)
-  PEA_X2DMA(xB, 3 * PS, ezo + 3u * ecs)
-  asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");  // the inv plane is dead: buffer 2 may be filled
-  PEA_X2DMA(xB, 4 * PS, ezo + 4u * ecs)
-  PEA_X2DMA(xB, 5 * PS, ezo + 5u * ecs)
+  cross_dma(DG, xB, lds, 2 * PS, ezo + 2u * ecs);  // chunk 1 into buffer 1 (the first phase's last chunk is done)
+  cross_dma(DG, xB, lds, 3 * PS, ezo + 3u * ecs);
+  lds_barrier();  // the inv plane is dead: buffer 2 may be filled
+  cross_dma(DG, xB, lds, 4 * PS, ezo + 4u * ecs);
+  cross_dma(DG, xB, lds, 5 * PS, ezo + 5u * ecs);
 #pragma unroll
   for (int ps = 0; ps < NP; ++ps) {
     const int bo = (ps % 3) * 2 * PS;
@@ -312,15 +257,14 @@ __device__ __forceinline__ void bwd_phase_role_a(const KParams& P, const XParams
     asm volatile("" : "+v"(acc));
     G[ps] = acc;
     if (ps + 1 < NP) {
-      if (ps + 2 < NP) PEA_X2WAIT1()
-      else asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory");
+      if (ps + 2 < NP) loads_barrier_among<4, 2>(DG.npc);
+      else loads_barrier<0>();
       if (ps + 3 < NP) {
-        PEA_X2DMA(xB, bo, ezo + (unsigned)(2 * ps + 6) * ecs)
-        PEA_X2DMA(xB, bo + PS, ezo + (unsigned)(2 * ps + 7) * ecs)
+        cross_dma(DG, xB, lds, bo, ezo + (unsigned)(2 * ps + 6) * ecs);
+        cross_dma(DG, xB, lds, bo + PS, ezo + (unsigned)(2 * ps + 7) * ecs);
       }
     }
   }
-#undef PEA_X2WAIT1
 }
 
 // OTHER: the cross loss with a detached second operand (ema_embedding_loss, scripts_cvppp/loss/loss_embedding_mse.py:79-95 with
@@ -360,88 +304,37 @@ __global__ __launch_bounds__(TH* TW, 4) void k_bwd_xdma(const KParams P, const X
   const unsigned po4 = (unsigned)(py * P.X + px) * 4u;
   const unsigned pe = live ? po4 : kOOB;
 
-  // ---- the (up to) two quads this lane moves per plane: blocks of 64 quads go round the waves (block s * NW + wave)
-  unsigned vo[2];
-  bool act[2];
-#pragma unroll
-  for (int s = 0; s < 2; ++s) {
-    const int q = (s * (NT / 64) + wave) * 64 + lane;
-    int gy, gx;
-    if (q < C.QV) {
-      gy = y0 - C.hy0 + (q >> 3);
-      gx = x0 + 4 * (q & 7);
-    } else {
-      const int k = q - C.QV;
-      const int sh = C.SW == 64 ? 4 : 3;  // quads per strip row: 16 / 8
-      const int cc = 4 * (k & ((1 << sh) - 1));
-      gy = y0 + (k >> sh);
-      gx = cc < C.split ? x0 + TW + cc : x0 - C.SW + cc;
-    }
-    act[s] = q < C.QA;
-    bool oky, okx;
-    gy = wrap1<CROP>(gy, P.Y, oky);
-    gx = wrap1<CROP>(gx, P.X, okx);
-    vo[s] = (act[s] && oky && okx) ? (unsigned)(gy * P.X + gx) * 4u : kOOB;
-  }
-  const int wbase = wave * 1024;  // this wave's first block inside a plane; its second one is NW KiB further
+  // ---- the (up to) two quads this lane moves per plane (SDMA, the 3D instantiation: both, unconditionally -- pea_stage.h)
+  constexpr bool SDMA = ZP > 0;
+  const CrossStage<SDMA> ST = cross_stage<TH, TW, CROP, SDMA>(P, C, y0, x0, wave, lane);
   // DUAL: the second phase's staging geometry, buffers and g registers (requested from the first phase's last hand-offs)
-  DualGeom DG = {};
+  CrossStage<> DG = {};
   float cx2[DUAL ? XP : 1], cy2[DUAL ? XP : 1];
   rsrc_t x2B = xB, i2B = xB, g2B = xB;
   if constexpr (DUAL) {
-    DG = dual_geom<TH, TW, CROP>(P, Q.C2, y0, x0);
+    DG = cross_stage<TH, TW, CROP>(P, Q.C2, y0, x0, wave, lane);
     x2B = mkbuf(Q.ema + (size_t)b * D_T * S);
     i2B = mkbuf(Q.inv_other + (size_t)b * S);
     g2B = mkbuf(Q.g_cross + (size_t)b * P.K * S);
   }
-  // SDMA (the 3D instantiation): every wave issues BOTH slots for every plane, unconditionally -- a wave without a second block
-  // repeats its first one (same bytes to the same place), the tail lanes of the last block write zeros into the plane's
-  // padding.  The count of DMA instructions per chunk is then a compile-time 4, which is what lets the compiler wait for the
-  // z gathers with vmcnt(4) instead of vmcnt(0): with a DMA inside an `if` it has to assume that none was issued.
-  constexpr bool SDMA = ZP > 0;
-  const bool two = __builtin_amdgcn_readfirstlane(((NT / 64) + wave) * 64 < C.QA);
-  const unsigned vo1 = SDMA ? (two ? vo[1] : vo[0]) : vo[1];
-  const int w1 = SDMA ? (two ? wbase + (NT / 64) * 1024 : wbase) : wbase + (NT / 64) * 1024;
-  // DMA instructions this wave issues per chunk (a slot without a live lane is skipped): what `vmcnt` has to count
-  const int npc = SDMA ? 4 : 2 * ((__builtin_amdgcn_ballot_w64(act[0]) != 0) + (__builtin_amdgcn_ballot_w64(act[1]) != 0));
-  // wait until only the youngest chunk's DMA may still be in flight, then the workgroup barrier
-#define PEA_XWAIT1()                                                                             \
-  {                                                                                              \
-    if (npc == 4) asm volatile("s_waitcnt vmcnt(4) lgkmcnt(0)\n\ts_barrier" ::: "memory");       \
-    else if (npc == 2) asm volatile("s_waitcnt vmcnt(2) lgkmcnt(0)\n\ts_barrier" ::: "memory");  \
-    else asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory");                \
-  }
-  // in the chunk loop of the 3D instantiation the z gathers of the NEXT chunk (2 * ZP loads, issued one iteration earlier) sit
-  // between the DMA that has to have landed and the youngest DMA: they may stay in flight too
-#define PEA_XWAITZ() asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)\n\ts_barrier" ::"n"(2 * ZP + 4) : "memory");
-#define PEA_XDMA(rsrc, plane_byte, so)                                                                              \
-  {                                                                                                                 \
-    if (SDMA) {                                                                                                     \
-      __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (lds_ptr_t)(lds + (plane_byte) + wbase), 16, vo[0], so, 0, 0); \
-      __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (lds_ptr_t)(lds + (plane_byte) + w1), 16, vo1, so, 0, 0);      \
-    } else {                                                                                                        \
-      if (act[0]) __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (lds_ptr_t)(lds + (plane_byte) + wbase), 16, vo[0], so, 0, 0);        \
-      if (act[1]) __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (lds_ptr_t)(lds + (plane_byte) + w1), 16, vo1, so, 0, 0); \
-    }                                                                                                               \
-  }
+  // the hand-off of the chunk loop: only the youngest chunk's DMA (ST.npc instructions) may still be in flight.  In the 3D
+  // instantiation the z gathers of the NEXT chunk (2 * ZP loads, issued one iteration earlier) sit between the DMA that has to have
+  // landed and the youngest DMA: they may stay in flight too
+  const auto chunk_landed = [&]() {
+    if constexpr (ZP > 0) loads_barrier<2 * ZP + 4>();
+    else loads_barrier_among<4, 2>(ST.npc);
+  };
   PEA_STAMP(0)
-  PEA_XDMA(iB, 4 * PS, ezo)
-  PEA_XDMA(xB, 0, ezo)
-  PEA_XDMA(xB, PS, ezo + ecs)
+  cross_dma(ST, iB, lds, 4 * PS, ezo);
+  cross_dma(ST, xB, lds, 0, ezo);
+  cross_dma(ST, xB, lds, PS, ezo + ecs);
 
   // ---- g of every pair (role A at p, role B at p - o) and the LDS slot of every neighbour
   // dead lanes: an offset that stays out of range when a small displacement is added
   const unsigned pg = live ? po4 : 0xC0000000u;
   float cx[XP], cy[XP];
   int ax[XP], ay[XP];
-  const int vown = ((C.hy0 + ly) * TW + lx) * 4;
-  const int hrow = (C.QV * 4 + ly * C.SW) * 4;
-#pragma unroll
-  for (int k = 0; k < XP; ++k) {
-    const int d = C.xd[k], c = lx + d;
-    ax[k] = (unsigned)c < (unsigned)TW ? vown + d * 4 : hrow + (c & C.xm[k]) * 4;
-    ay[k] = vown + C.yd[k] * TW * 4;
-  }
+  const int vown = cross_slots<TW>(C, ly, lx, ax, ay);
   // one dword per lane and pair (the lane's own pixel)
 #define PEA_XG_DWORDS()                                                                                                              \
   {                                                                                                                                  \
@@ -496,11 +389,11 @@ __global__ __launch_bounds__(TH* TW, 4) void k_bwd_xdma(const KParams P, const X
     }
     invo_g = bl32(oiB, pe, ezo);
   }
-  PEA_XDMA(xB, 2 * PS, ezo + 2u * ecs)
-  PEA_XDMA(xB, 3 * PS, ezo + 3u * ecs)
+  cross_dma(ST, xB, lds, 2 * PS, ezo + 2u * ecs);
+  cross_dma(ST, xB, lds, 3 * PS, ezo + 3u * ecs);
   // inv, chunk 0 and g have landed (the 4 DMA instructions of chunk 1 may still fly); every wave's share of them too
   PEA_STAMP(1)
-  PEA_XWAIT1()
+  loads_barrier_among<4, 2>(ST.npc);
   PEA_STAMP(2)
 
   // coefficient of a pair = g * 1 / |e(q)|
@@ -514,7 +407,7 @@ __global__ __launch_bounds__(TH* TW, 4) void k_bwd_xdma(const KParams P, const X
     // below the last barrier and keeps every LDS value of every chunk in registers (256 VGPRs + spills)
     asm volatile("" : "+v"(cx[k]), "+v"(cy[k]));
   }
-  asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");  // the inv plane is dead: buffer 2 may be filled
+  lds_barrier();  // the inv plane is dead: buffer 2 may be filled
   // the z neighbours' two channels of a chunk are requested TWO chunks ahead (two register sets), before the DMA of the chunk
   // three ahead: a gather from another plane is an L2 miss more often than not here (section 5.7 item 9), and one chunk's LDS
   // pairs do not cover that latency.  vmcnt retires in order, so the waits count the younger DMA / gathers exactly.
@@ -530,8 +423,8 @@ __global__ __launch_bounds__(TH* TW, 4) void k_bwd_xdma(const KParams P, const X
   PEA_XZLOAD(0)
   if (NP > 1) PEA_XZLOAD(1)
   if (NP > 2) {
-    PEA_XDMA(xB, 4 * PS, ezo + 4u * ecs)
-    PEA_XDMA(xB, 5 * PS, ezo + 5u * ecs)
+    cross_dma(ST, xB, lds, 4 * PS, ezo + 4u * ecs);
+    cross_dma(ST, xB, lds, 5 * PS, ezo + 5u * ecs);
   }
   // D_T <= 16: the lane keeps its own normalised pixel (eh) for the projection at the end; wider embeddings have no
   // registers for it (G alone is D_T of them): <ehat, G> is accumulated chunk by chunk and the own pixel is read again
@@ -585,22 +478,19 @@ __global__ __launch_bounds__(TH* TW, 4) void k_bwd_xdma(const KParams P, const X
     PEA_STAMP(3 + 3 * ps)
     if (ps + 1 < NP) {
       // chunk ps + 1 has landed (chunk ps + 2, issued after it, may still fly); everyone is done with buffer ps % 3
-      if (ps + 2 < NP) {
-        if (ZP > 0) PEA_XWAITZ()
-        else PEA_XWAIT1()
-      } else asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory");
+      if (ps + 2 < NP) chunk_landed();
+      else loads_barrier<0>();
       PEA_STAMP(4 + 3 * ps)
       if (ps + 2 < NP) PEA_XZLOAD(ps + 2)
 #ifndef PEA_ABL_NODMA
       if (ps + 3 < NP) {
-        PEA_XDMA(xB, bo, ezo + (unsigned)(2 * ps + 6) * ecs)
-        PEA_XDMA(xB, bo + PS, ezo + (unsigned)(2 * ps + 7) * ecs)
+        cross_dma(ST, xB, lds, bo, ezo + (unsigned)(2 * ps + 6) * ecs);
+        cross_dma(ST, xB, lds, bo + PS, ezo + (unsigned)(2 * ps + 7) * ecs);
       }
 #endif
       if constexpr (DUAL) {  // the second phase's first requests ride in the ring slots the first phase no longer needs (see bwd_phase_role_a)
-        const int wbase2 = wbase, w12 = wbase + (NT / 64) * 1024;
         if (ps == NP - 3) {  // buffer 2 is free: the second operand's 1 / norm plane into plane 4, and the cross loss' g values
-          PEA_X2DMA(i2B, 4 * PS, ezo)
+          cross_dma(DG, i2B, lds, 4 * PS, ezo);
           const unsigned pg2 = live ? po4 : kOOB;  // role A: g at the own pixel
 #pragma unroll
           for (int k = 0; k < XP; ++k) {
@@ -609,16 +499,13 @@ __global__ __launch_bounds__(TH* TW, 4) void k_bwd_xdma(const KParams P, const X
           }
         }
         if (ps == NP - 2) {  // buffer 0 is free: the second phase's chunk 0
-          PEA_X2DMA(x2B, 0, ezo)
-          PEA_X2DMA(x2B, PS, ezo + ecs)
+          cross_dma(DG, x2B, lds, 0, ezo);
+          cross_dma(DG, x2B, lds, PS, ezo + ecs);
         }
       }
       PEA_STAMP(5 + 3 * ps)
     }
   }
-#undef PEA_XDMA
-#undef PEA_XWAIT1
-#undef PEA_XWAITZ
 #undef PEA_XZLOAD
 
   if constexpr (DUAL) {
@@ -781,7 +668,11 @@ __global__ __launch_bounds__(TH* TW, WPE) void k_fwd_xdma(const KParams P, const
   const bool live = py < P.Y && px < P.X;
   const unsigned pe = live ? (unsigned)(py * P.X + px) * 4u : kOOB;
 
-  // ---- the (up to) two quads this lane moves per plane
+  // ---- the (up to) two quads this lane moves per plane.  THIS KERNEL KEEPS ITS OWN LINES for what pea_stage.h states (cross_stage,
+  // cross_slots, cross_dma, loads_barrier*): behind cross_stage alone, and behind loads_barrier_among alone, the three 80-VGPR
+  // instantiations with the cross-entropy (WPE = 6, LACT, BCE: 79 / 80 registers) spilled one to four registers; with only the slots,
+  // the single DMA instruction and the literal hand-off taken from the header the 3D instantiation (ZF) ran 4 % slower
+  // (profiles/README.md, "Stage refactor").  A change to the header's rules has to be made here as well.
   unsigned vo[2];
   bool act[2];
 #pragma unroll

@@ -69,85 +69,41 @@ __global__ __launch_bounds__(TH* TW, NB == 3 ? 2 : 4) void k_fwd_xdma_dual(const
   const unsigned pe = live ? (unsigned)(py * P.X + px) * 4u : kOOB;
 
   // ---- the (up to) two quads this lane moves per plane (k_fwd_xdma's geometry)
-  unsigned vo[2];
-  bool act[2];
-#pragma unroll
-  for (int s = 0; s < 2; ++s) {
-    const int q = (s * (NT / 64) + wave) * 64 + lane;
-    int gy, gx;
-    if (q < C.QV) {
-      gy = y0 - C.hy0 + (q >> 3);
-      gx = x0 + 4 * (q & 7);
-    } else {
-      const int k = q - C.QV;
-      const int sh = C.SW == 64 ? 4 : 3;
-      const int cc = 4 * (k & ((1 << sh) - 1));
-      gy = y0 + (k >> sh);
-      gx = cc < C.split ? x0 + TW + cc : x0 - C.SW + cc;
-    }
-    act[s] = q < C.QA;
-    bool oky, okx;
-    gy = wrap1<CROP>(gy, P.Y, oky);
-    gx = wrap1<CROP>(gx, P.X, okx);
-    vo[s] = (act[s] && oky && okx) ? (unsigned)(gy * P.X + gx) * 4u : kOOB;
-  }
-  const int wbase = wave * 1024, w1 = wbase + (NT / 64) * 1024;
-  const bool act0 = __builtin_amdgcn_ballot_w64(act[0]) != 0, act1 = __builtin_amdgcn_ballot_w64(act[1]) != 0;  // wave-uniform
-  const int npt = 4 * ((int)act0 + (int)act1);  // DMA instructions of this wave per chunk: 0, 4 or 8
-#define PEA_DDMA1(rs_, byte_, v_, so_) __builtin_amdgcn_raw_ptr_buffer_load_lds(rs_, (lds_ptr_t)(lds + (byte_)), 16, v_, so_, 0, 0);
+  const CrossStage<> ST = cross_stage<TH, TW, CROP>(P, C, y0, x0, wave, lane);
+  const int npt = 2 * ST.npc;  // DMA instructions of this wave per chunk (four planes): 0, 4 or 8
 // chunk ch (channels 2 ch, 2 ch + 1 of both operands) into ring buffer buf
-#define PEA_DDMA(buf, ch)                                       \
-  {                                                             \
-    const unsigned so_ = ezo + (unsigned)(2 * (ch)) * ecs;      \
-    const int pb_ = (buf) * BUF;                                \
-    if (act[0]) { /* per LANE: a lane beyond the region writes nothing (its 16 bytes would land in the next plane) */ \
-      PEA_DDMA1(xB, pb_ + wbase, vo[0], so_)                    \
-      PEA_DDMA1(xB, pb_ + PS + wbase, vo[0], so_ + ecs)         \
-      PEA_DDMA1(yB, pb_ + 2 * PS + wbase, vo[0], so_)           \
-      PEA_DDMA1(yB, pb_ + 3 * PS + wbase, vo[0], so_ + ecs)     \
-    }                                                           \
-    if (act[1]) {                                               \
-      PEA_DDMA1(xB, pb_ + w1, vo[1], so_)                       \
-      PEA_DDMA1(xB, pb_ + PS + w1, vo[1], so_ + ecs)            \
-      PEA_DDMA1(yB, pb_ + 2 * PS + w1, vo[1], so_)              \
-      PEA_DDMA1(yB, pb_ + 3 * PS + w1, vo[1], so_ + ecs)        \
-    }                                                           \
+// (the two blocks of a wave one after the other, each through its four planes: the order the requests leave in)
+#define PEA_DDMA(buf, ch)                                                                                            \
+  {                                                                                                                  \
+    const unsigned so_ = ezo + (unsigned)(2 * (ch)) * ecs;                                                           \
+    const int pb_ = (buf) * BUF;                                                                                     \
+    _Pragma("unroll") for (int s_ = 0; s_ < 2; ++s_) {                                                               \
+      if (ST.act[s_]) { /* per LANE: a lane beyond the region writes nothing (pea_stage.h) */                       \
+        char* const d_ = lds + pb_ + (s_ ? ST.w1 : ST.wbase);                                                        \
+        cross_dma1(xB, d_, ST.vo[s_], so_);                                                                          \
+        cross_dma1(xB, d_ + PS, ST.vo[s_], so_ + ecs);                                                               \
+        cross_dma1(yB, d_ + 2 * PS, ST.vo[s_], so_);                                                                 \
+        cross_dma1(yB, d_ + 3 * PS, ST.vo[s_], so_ + ecs);                                                           \
+      }                                                                                                              \
+    }                                                                                                                \
   }
 // the oldest chunk in flight has landed (n younger ones may still fly), and every wave is done with the buffer behind the barrier
-#define PEA_DWAIT(n)                                                                                  \
-  {                                                                                                   \
-    const int fly_ = (n) * npt;                                                                       \
-    if (fly_ == 16) asm volatile("s_waitcnt vmcnt(16) lgkmcnt(0)\n\ts_barrier" ::: "memory");         \
-    else if (fly_ == 8) asm volatile("s_waitcnt vmcnt(8) lgkmcnt(0)\n\ts_barrier" ::: "memory");      \
-    else if (fly_ == 4) asm volatile("s_waitcnt vmcnt(4) lgkmcnt(0)\n\ts_barrier" ::: "memory");      \
-    else asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory");                     \
-  }
+#define PEA_DWAIT(n) loads_barrier_among<16, 8, 4>((n) * npt);
 // half a chunk: the e pair (op_ = 0, planes 0 and 1 of the buffer) or the ema pair (op_ = 1, planes 2 and 3)
-#define PEA_DDMAH(buf, ch, op_)                                                          \
-  {                                                                                      \
-    const unsigned so_ = ezo + (unsigned)(2 * (ch)) * ecs;                               \
-    const int pb_ = (buf) * BUF + (op_) * 2 * PS;                                        \
-    if (act[0]) {                                                                        \
-      PEA_DDMA1((op_) ? yB : xB, pb_ + wbase, vo[0], so_)                                \
-      PEA_DDMA1((op_) ? yB : xB, pb_ + PS + wbase, vo[0], so_ + ecs)                     \
-    }                                                                                    \
-    if (act[1]) {                                                                        \
-      PEA_DDMA1((op_) ? yB : xB, pb_ + w1, vo[1], so_)                                   \
-      PEA_DDMA1((op_) ? yB : xB, pb_ + PS + w1, vo[1], so_ + ecs)                        \
-    }                                                                                    \
+#define PEA_DDMAH(buf, ch, op_)                                                                                      \
+  {                                                                                                                  \
+    const unsigned so_ = ezo + (unsigned)(2 * (ch)) * ecs;                                                           \
+    const int pb_ = (buf) * BUF + (op_) * 2 * PS;                                                                    \
+    _Pragma("unroll") for (int s_ = 0; s_ < 2; ++s_) {                                                               \
+      if (ST.act[s_]) {                                                                                              \
+        char* const d_ = lds + pb_ + (s_ ? ST.w1 : ST.wbase);                                                        \
+        cross_dma1((op_) ? yB : xB, d_, ST.vo[s_], so_);                                                             \
+        cross_dma1((op_) ? yB : xB, d_ + PS, ST.vo[s_], so_ + ecs);                                                  \
+      }                                                                                                              \
+    }                                                                                                                \
   }
 // at most `loads_` (a wave-uniform multiple of 2 up to 16) younger DMA instructions may still fly; then the barrier
-#define PEA_DWAITL(loads_)                                                                            \
-  {                                                                                                   \
-    const int fl_ = (loads_);                                                                         \
-    if (fl_ >= 16) asm volatile("s_waitcnt vmcnt(16) lgkmcnt(0)\n\ts_barrier" ::: "memory");          \
-    else if (fl_ >= 12) asm volatile("s_waitcnt vmcnt(12) lgkmcnt(0)\n\ts_barrier" ::: "memory");     \
-    else if (fl_ >= 8) asm volatile("s_waitcnt vmcnt(8) lgkmcnt(0)\n\ts_barrier" ::: "memory");       \
-    else if (fl_ >= 6) asm volatile("s_waitcnt vmcnt(6) lgkmcnt(0)\n\ts_barrier" ::: "memory");       \
-    else if (fl_ >= 4) asm volatile("s_waitcnt vmcnt(4) lgkmcnt(0)\n\ts_barrier" ::: "memory");       \
-    else if (fl_ >= 2) asm volatile("s_waitcnt vmcnt(2) lgkmcnt(0)\n\ts_barrier" ::: "memory");       \
-    else asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory");                     \
-  }
+#define PEA_DWAITL(loads_) loads_barrier_among<16, 12, 8, 6, 4, 2>(loads_);
   const int nh = npt / 2;  // DMA instructions of this wave per HALF chunk
   if (NB == 4) {  // (half by half: a wait counts whole halves)
     PEA_DDMAH(0, 0, 0) PEA_DDMAH(0, 0, 1) PEA_DDMAH(1, 1, 0) PEA_DDMAH(1, 1, 1)
@@ -158,14 +114,7 @@ __global__ __launch_bounds__(TH* TW, NB == 3 ? 2 : 4) void k_fwd_xdma_dual(const
 
   // ---- LDS slot of every offset's neighbour
   int an[kXP];
-  const int vown = ((C.hy0 + ly) * TW + lx) * 4;
-  const int hrow = (C.QV * 4 + ly * C.SW) * 4;
-#pragma unroll
-  for (int k = 0; k < kXP; ++k) {
-    const int d = C.fd[k], c = lx + d;
-    const int a_x = (unsigned)c < (unsigned)TW ? vown + d * 4 : hrow + (c & C.fm[k]) * 4;
-    an[k] = C.fax[k] ? a_x : vown + d * TW * 4;  // unused offsets: d = 0, the own slot
-  }
+  const int vown = cross_slots<TW>(C, ly, lx, an);
   if (NB == 4) PEA_DWAITL(3 * nh)  // the first e pair has landed
   else PEA_DWAIT(NBUF - 1)
 
@@ -289,7 +238,6 @@ __global__ __launch_bounds__(TH* TW, NB == 3 ? 2 : 4) void k_fwd_xdma_dual(const
 #undef PEA_DDMAH
 #undef PEA_DWAITL
 #undef PEA_DDMA
-#undef PEA_DDMA1
 #undef PEA_DWAIT
 
   // ---- normalise; both 1 / norm planes for the backward

@@ -44,62 +44,37 @@ __device__ __forceinline__ float dot2(h16x2_t<__bf16> a, h16x2_t<__bf16> b, floa
   return __builtin_amdgcn_fdot2_f32_bf16(a, b, acc, false);
 }
 
-// geometry of this lane's DMA items: up to two QUADS (4 pixels: the f32 1 / norm plane, and the conversion) and one OCT
-// (8 pixels: the f16 channel planes).  Same region order as pea_xdma.h (VF rows of TW pixels, then strip rows of SW pixels).
-// (Plain locals, not a struct: with the operands of the LDS-DMA builtin taken from members of a local struct, ROCm 7.2's host pass
-//  silently emits no stub for the kernel -- an undefined symbol at load time.  Found by bisection.)
-template <int TH, int TW, bool CROP>
-__device__ __forceinline__ void x_items(const KParams& P, const XParams& C, int y0, int x0, int wave, int lane, unsigned (&vo)[2],
-                                        bool (&act)[2], int (&qq)[2], unsigned& vo8, bool& act8) {
-  constexpr int NT = TH * TW;
-#pragma unroll
-  for (int s = 0; s < 2; ++s) {
-    const int q = (s * (NT / 64) + wave) * 64 + lane;
-    qq[s] = q;
-    int gy, gx;
-    if (q < C.QV) {
-      gy = y0 - C.hy0 + q / (TW / 4);
-      gx = x0 + 4 * (q % (TW / 4));
-    } else {
-      const int k = q - C.QV;
-      const int sh = C.SW == 64 ? 4 : 3;
-      const int cc = 4 * (k & ((1 << sh) - 1));
-      gy = y0 + (k >> sh);
-      gx = cc < C.split ? x0 + TW + cc : x0 - C.SW + cc;
-    }
-    act[s] = q < C.QA;
-    bool oky, okx;
-    gy = wrap1<CROP>(gy, P.Y, oky);
-    gx = wrap1<CROP>(gx, P.X, okx);
-    vo[s] = (act[s] && oky && okx) ? (unsigned)(gy * P.X + gx) * 4u : kOOB;
+// This lane's DMA items (pea_stage.h): up to two QUADS per f32 plane (4 pixels: the 1 / norm plane, and the conversion) and one OCT
+// per 16-bit channel plane (8 pixels).  Same region order as pea_xdma.h (VF rows of TW pixels, then strip rows of SW pixels).
+
+// The hand-off of k_bwd_xdma_h's chunk loop, as a switch the optimiser folds where the count is a constant: this one site keeps the
+// form it had before pea_stage.h.  As loads_barrier_among<4, 2> (a compare ladder instead of a jump table) the role-A instantiation at
+// D = 64 ran out of scalar registers: 12 of them spilled into a vector register and 20 bytes of scratch (profiles/README.md, "Stage
+// refactor").  Loads only, and a literal count: pea_stage.h.
+__device__ __forceinline__ void h16_loads_barrier(int n) {
+#define PEA_PFW(k) case k: loads_barrier<k>(); break;
+  switch (n) {
+    PEA_PFW(0) PEA_PFW(1) PEA_PFW(2) PEA_PFW(3) PEA_PFW(4) PEA_PFW(5) PEA_PFW(6) PEA_PFW(7) PEA_PFW(8) PEA_PFW(9) PEA_PFW(10)
+    PEA_PFW(11) PEA_PFW(12) PEA_PFW(13) PEA_PFW(14) PEA_PFW(15) PEA_PFW(16) PEA_PFW(17) PEA_PFW(18) PEA_PFW(19) PEA_PFW(20)
+    PEA_PFW(21) PEA_PFW(22) PEA_PFW(23) PEA_PFW(24) PEA_PFW(25) PEA_PFW(26) PEA_PFW(27) PEA_PFW(28) PEA_PFW(29) PEA_PFW(30)
+    PEA_PFW(31) PEA_PFW(32)
+    default: loads_barrier<0>(); break;
   }
-  const int o = wave * 64 + lane;
-  int gy, gx;
-  if (o < (C.QV >> 1)) {
-    gy = y0 - C.hy0 + o / (TW / 8);
-    gx = x0 + 8 * (o % (TW / 8));
-  } else {
-    const int k = o - (C.QV >> 1);
-    const int sh = C.SW == 64 ? 3 : 2;
-    const int cc = 8 * (k & ((1 << sh) - 1));
-    gy = y0 + (k >> sh);
-    gx = cc < C.split ? x0 + TW + cc : x0 - C.SW + cc;
-  }
-  act8 = o < (C.QA >> 1);
-  bool oky, okx;
-  gy = wrap1<CROP>(gy, P.Y, oky);
-  gx = wrap1<CROP>(gx, P.X, okx);
-  vo8 = (act8 && oky && okx) ? (unsigned)(gy * P.X + gx) * 2u : kOOB;
+#undef PEA_PFW
 }
 
-// wait until only the youngest chunk's DMA (npc wave instructions of this wave: 2 or 0) may be in flight, then the barrier
-#define PEA_HWAIT1(npc)                                                                          \
-  {                                                                                              \
-    if ((npc) == 4) asm volatile("s_waitcnt vmcnt(4) lgkmcnt(0)\n\ts_barrier" ::: "memory");     \
-    else if ((npc) == 2) asm volatile("s_waitcnt vmcnt(2) lgkmcnt(0)\n\ts_barrier" ::: "memory"); \
-    else asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory");                \
+// one chunk of the 16-bit ring: channels ch, ch + 1 into ring buffer rbuf (half-size planes at R), and -- ownw, the role-A
+// instantiations -- the own tile's two channels (1 KB each, at OW) by the wave that moves it
+template <int PH>
+__device__ __forceinline__ void h16_chunk_dma(const CrossStage8& S8, const rsrc_t xB, char* R, const bool ownw, const rsrc_t oB, char* OW,
+                                              const unsigned ownvo, const int rbuf, const unsigned so, const unsigned hcs) {
+  cross_dma(S8, xB, R, (rbuf * 2) * PH, so);
+  cross_dma(S8, xB, R, (rbuf * 2 + 1) * PH, so + hcs);
+  if (ownw) {
+    cross_dma1(oB, OW + (rbuf * 2) * 1024, ownvo, so);
+    cross_dma1(oB, OW + (rbuf * 2 + 1) * 1024, ownvo, so + hcs);
   }
-#define PEA_HWAIT0() asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory");
+}
 
 // f16 chunk `rbuf` of the ring -> the f32 working buffer, the two channels of a pixel SIDE BY SIDE (8 bytes per region pixel).
 // The layout is free here (this step writes it, not the DMA), and it is what makes the gather cheap: one ds_read_b64 per
@@ -192,11 +167,8 @@ __global__ __launch_bounds__(TH* TW, WPE) void k_bwd_xdma_h(const KParams P, con
   const unsigned po = (unsigned)(py * P.X + px);
   const unsigned ph = live ? po * 2u : kOOB;
 
-  unsigned vo[2], vo8;
-  bool act[2], act8;
-  int qq[2];
-  x_items<TH, TW, CROP>(P, C, y0, x0, wave, lane, vo, act, qq, vo8, act8);
-  const int wbase = wave * 1024;
+  const CrossStage<> ST = cross_stage<TH, TW, CROP>(P, C, y0, x0, wave, lane);
+  const CrossStage8 S8 = cross_stage8<TH, TW, CROP>(P, C, y0, x0, wave, lane);
   const bool ownw = OTHER && wave == 0;  // uniform: the wave that moves the own tile (64 octs = 16 rows of 32 pixels)
   const rsrc_t oB = mkbuf(OTHER ? own + (size_t)b * D_T * S : nullptr);
   unsigned ownvo = kOOB;
@@ -204,21 +176,9 @@ __global__ __launch_bounds__(TH* TW, WPE) void k_bwd_xdma_h(const KParams P, con
     const int oy = y0 + (lane >> 2), ox = x0 + 8 * (lane & 3);
     ownvo = (oy < P.Y && ox < P.X) ? (unsigned)(oy * P.X + ox) * 2u : kOOB;
   }
-  const int npc = 2 * (__builtin_amdgcn_ballot_w64(act8) != 0) + (ownw ? 2 : 0);
-#define PEA_HDMA16(rbuf, ch)                                                                                                  \
-  {                                                                                                                         \
-    if (act8) {                                                                                                             \
-      __builtin_amdgcn_raw_ptr_buffer_load_lds(xB, (lds_ptr_t)(R + ((rbuf) * 2) * PH + wbase), 16, vo8, hzo + (unsigned)(ch) * hcs, 0, 0);        \
-      __builtin_amdgcn_raw_ptr_buffer_load_lds(xB, (lds_ptr_t)(R + ((rbuf) * 2 + 1) * PH + wbase), 16, vo8, hzo + (unsigned)((ch) + 1) * hcs, 0, 0); \
-    }                                                                                                                       \
-    if (ownw) {                                                                                                             \
-      __builtin_amdgcn_raw_ptr_buffer_load_lds(oB, (lds_ptr_t)(lds + OWNR + ((rbuf) * 2) * 1024), 16, ownvo, hzo + (unsigned)(ch) * hcs, 0, 0);        \
-      __builtin_amdgcn_raw_ptr_buffer_load_lds(oB, (lds_ptr_t)(lds + OWNR + ((rbuf) * 2 + 1) * 1024), 16, ownvo, hzo + (unsigned)((ch) + 1) * hcs, 0, 0); \
-    }                                                                                                                       \
-  }
-  // the 1 / norm plane (f32) -> the second working plane
-  if (act[0]) __builtin_amdgcn_raw_ptr_buffer_load_lds(iB, (lds_ptr_t)(W + PS + wbase), 16, vo[0], fzo, 0, 0);
-  if (act[1]) __builtin_amdgcn_raw_ptr_buffer_load_lds(iB, (lds_ptr_t)(W + PS + wbase + (NT / 64) * 1024), 16, vo[1], fzo, 0, 0);
+  const int npc = S8.npc + (ownw ? 2 : 0);
+#define PEA_HDMA16(rbuf, ch) h16_chunk_dma<PH>(S8, xB, R, ownw, oB, lds + OWNR, ownvo, rbuf, hzo + (unsigned)(ch) * hcs, hcs);
+  cross_dma(ST, iB, W, PS, fzo);  // the 1 / norm plane (f32) -> the second working plane
   PEA_HDMA16(0, 0)
 
   // ---- g of every pair (role A at p, role B at p - o) and the LDS slot of every neighbour (pea_xdma.h k_bwd_xdma)
@@ -227,9 +187,6 @@ __global__ __launch_bounds__(TH* TW, WPE) void k_bwd_xdma_h(const KParams P, con
   const unsigned pg = live ? po * 4u : 0xC0000000u;
   static_assert(XP % 2 == 0, "coefficients are kept two to a register pair");
   f2 cx2[XP / 2], cy2[XP / 2];  // pair k in half (k & 1) of element k / 2
-  int ax[XP], ay[XP];
-  const int vown = ((C.hy0 + ly) * TW + lx) * 4;   // byte offset of the own pixel in a PLANE (the 1 / norm plane); x 2 in W
-  const int hrow = (C.QV * 4 + ly * C.SW) * 4;
 #pragma unroll
   for (int k = 0; k < XP; ++k) {
     const int go = C.xgo[k];
@@ -240,8 +197,6 @@ __global__ __launch_bounds__(TH* TW, WPE) void k_bwd_xdma_h(const KParams P, con
     const float gk = bl32(gB, k < C.npx ? o : kOOB, fzo + (unsigned)C.xgi[k] * fcs);
     cx2[k / 2][k & 1] = gk;
     if (PF) proj = fmaf(gk, bl32(aB, k < C.npx ? o : kOOB, fzo + (unsigned)C.xgi[k] * fcs), proj);
-    const int d = C.xd[k], c = lx + d;
-    ax[k] = (unsigned)c < (unsigned)TW ? vown + d * 4 : hrow + (c & C.xm[k]) * 4;
   }
 #pragma unroll
   for (int k = 0; k < XP; ++k) {
@@ -253,14 +208,15 @@ __global__ __launch_bounds__(TH* TW, WPE) void k_bwd_xdma_h(const KParams P, con
     const float gk = bl32(gB, k < C.npy ? o : kOOB, fzo + (unsigned)C.ygi[k] * fcs);
     cy2[k / 2][k & 1] = gk;
     if (PF) proj = fmaf(gk, bl32(aB, k < C.npy ? o : kOOB, fzo + (unsigned)C.ygi[k] * fcs), proj);
-    ay[k] = vown + C.yd[k] * TW * 4;
   }
+  int ax[XP], ay[XP];  // byte offsets in a PLANE (the 1 / norm plane); x 2 in W
+  const int vown = cross_slots<TW>(C, ly, lx, ax, ay);
   float invo_g = 0.f;
   if (OTHER) invo_g = bl32(mkbuf(own_inv + (size_t)b * S), live ? po * 4u : kOOB, fzo);
   if (NP > 1) PEA_HDMA16(1, 2)
   // the 1 / norm plane, chunk 0 and g have landed (chunk 1 may still fly)
-  if (NP > 1) PEA_HWAIT1(npc)
-  else PEA_HWAIT0()
+  if (NP > 1) loads_barrier_among<4, 2>(npc);
+  else loads_barrier<0>();
   const float invo = OTHER ? invo_g : *(const float*)(W + PS + vown);
   const float inv_own = fabsf(invo);
 #pragma unroll
@@ -337,7 +293,7 @@ __global__ __launch_bounds__(TH* TW, WPE) void k_bwd_xdma_h(const KParams P, con
     }
     float sx = 0.f, sy = 0.f;
     if (PF) {  // this chunk's two channels are final; stored BEHIND the hand-off below: a store issued just before a counted wait is
-               // still in flight when the wait is reached, and stores cannot be counted on (pea_xdma_pf.h) -- behind it, it has a
+               // still in flight when the wait is reached, and stores cannot be counted on (pea_stage.h) -- behind it, it has a
                // whole chunk's time to retire before the next one
       sx = pf_finish(acc.x, o.x, proj, inv_own, dl);
       sy = pf_finish(acc.y, o.y, proj, inv_own, dl);
@@ -351,13 +307,11 @@ __global__ __launch_bounds__(TH* TW, WPE) void k_bwd_xdma_h(const KParams P, con
       G[ps] = acc;
     }
     if (ps + 1 < NP) {
-      // everyone is done with the working buffer and with ring buffer ps % 3; chunk ps + 1 has landed (chunk ps + 2 and, PF, the
-      // stores of the last chunks are not counted on, pea_xdma_pf.h)
-      // (loads only: a store may retire before an older load, pea_xdma_pf.h)
-      // (and a wave that issues no DMA -- npc == 0 -- waits for nothing: vmcnt(0) would make it drain its stores at every chunk)
+      // everyone is done with the working buffer and with ring buffer ps % 3; chunk ps + 1 has landed (chunk ps + 2 may still fly;
+      // PF: the stores of the last chunks are not counted, and a wave without DMA waits for nothing -- pea_stage.h)
       const int nd = ps + 2 < NP ? 1 : 0;
       if (PF && npc == 0) lds_barrier();
-      else pf_wait(nd * npc);
+      else h16_loads_barrier(nd * npc);
 #ifndef PEA_ABL_H_NODMA
       if (ps + 3 < NP) PEA_HDMA16(ps % 3, 2 * ps + 6)
 #endif
@@ -440,11 +394,7 @@ __global__ __launch_bounds__(TH* TW, WPE) void k_fwd_xdma_h(const KParams P, con
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
   const int ly = threadIdx.x >> 5, lx = threadIdx.x & 31;
 
-  unsigned vo[2], vo8;
-  bool act[2], act8;
-  int qq[2];
-  x_items<TH, TW, CROP>(P, C, y0, x0, wave, lane, vo, act, qq, vo8, act8);
-  const int wbase = wave * 1024;
+  const CrossStage8 S8 = cross_stage8<TH, TW, CROP>(P, C, y0, x0, wave, lane);
   constexpr int OWNR = (WP + 3) * PS;  // OTHER: three buffers x two channels x 1 KB of own tile behind the ring
   const bool ownw = OTHER && wave == 0;  // uniform: the wave that moves the own tile
   const rsrc_t oB = mkbuf(OTHER ? own + (size_t)b * D_T * S : nullptr);
@@ -453,35 +403,15 @@ __global__ __launch_bounds__(TH* TW, WPE) void k_fwd_xdma_h(const KParams P, con
     const int oy = y0 + (lane >> 2), ox = x0 + 8 * (lane & 3);
     ownvo = (oy < P.Y && ox < P.X) ? (unsigned)(oy * P.X + ox) * 2u : kOOB;
   }
-  const int npc = 2 * (__builtin_amdgcn_ballot_w64(act8) != 0) + (ownw ? 2 : 0);
-// (ONE statement: the call sites are `if (..) PEA_HDMA16(..)` -- as two statements the own tile's DMA escaped the condition, was requested
-//  for chunks that do not exist and read past the end of the tensor: harmless bytes, and a memory fault once the tensor ended near a
-//  mapping's end.  Found at 400 x 400; tests/test_gpu_fullsize2.py runs the full size.)
-#define PEA_HDMA16(rbuf, ch)                                                                                                  \
-  {                                                                                                                         \
-    if (act8) {                                                                                                             \
-      __builtin_amdgcn_raw_ptr_buffer_load_lds(xB, (lds_ptr_t)(R + ((rbuf) * 2) * PH + wbase), 16, vo8, hzo + (unsigned)(ch) * hcs, 0, 0);        \
-      __builtin_amdgcn_raw_ptr_buffer_load_lds(xB, (lds_ptr_t)(R + ((rbuf) * 2 + 1) * PH + wbase), 16, vo8, hzo + (unsigned)((ch) + 1) * hcs, 0, 0); \
-    }                                                                                                                       \
-    if (ownw) {                                                                                                             \
-      __builtin_amdgcn_raw_ptr_buffer_load_lds(oB, (lds_ptr_t)(lds + OWNR + ((rbuf) * 2) * 1024), 16, ownvo, hzo + (unsigned)(ch) * hcs, 0, 0);        \
-      __builtin_amdgcn_raw_ptr_buffer_load_lds(oB, (lds_ptr_t)(lds + OWNR + ((rbuf) * 2 + 1) * 1024), 16, ownvo, hzo + (unsigned)((ch) + 1) * hcs, 0, 0); \
-    }                                                                                                                       \
-  }
+  const int npc = S8.npc + (ownw ? 2 : 0);
+#define PEA_HDMA16(rbuf, ch) h16_chunk_dma<PH>(S8, xB, R, ownw, oB, lds + OWNR, ownvo, rbuf, hzo + (unsigned)(ch) * hcs, hcs);
   PEA_HDMA16(0, 0)
   if (NP > 1) PEA_HDMA16(1, 2)
 
   int an[NXP];
-  const int vown = ((C.hy0 + ly) * TW + lx) * 4;
-  const int hrow = (C.QV * 4 + ly * C.SW) * 4;
-#pragma unroll
-  for (int k = 0; k < NXP; ++k) {
-    const int d = C.fd[k], c = lx + d;
-    const int a_x = (unsigned)c < (unsigned)TW ? vown + d * 4 : hrow + (c & C.fm[k]) * 4;
-    an[k] = C.fax[k] ? a_x : vown + d * TW * 4;
-  }
-  if (NP > 1) PEA_HWAIT1(npc)
-  else PEA_HWAIT0()
+  const int vown = cross_slots<TW>(C, ly, lx, an);
+  if (NP > 1) loads_barrier_among<4, 2>(npc);
+  else loads_barrier<0>();
   if (NP > 2) PEA_HDMA16(2, 4)
 
   // HW: scalar accumulators (the two channels of a chunk are summed by v_dot2); else packed over the two channels
@@ -530,8 +460,8 @@ __global__ __launch_bounds__(TH* TW, WPE) void k_fwd_xdma_h(const KParams P, con
     asm volatile("" : "+v"(oss));
     if (OTHER) asm volatile("" : "+v"(css));
     if (ps + 1 < NP) {
-      if (ps + 2 < NP) PEA_HWAIT1(npc)
-      else PEA_HWAIT0()
+      if (ps + 2 < NP) loads_barrier_among<4, 2>(npc);
+      else loads_barrier<0>();
       if (ps + 3 < NP) PEA_HDMA16(ps % 3, 2 * ps + 6)
     }
   }
@@ -637,8 +567,5 @@ __global__ __launch_bounds__(TH* TW, WPE) void k_fwd_xdma_h(const KParams P, con
     if (wave == 0 && (int)threadIdx.x < P.K) part_accumulate<NSL>(st, tile, threadIdx.x, s_part, NSL, 1);
   }
 }
-
-#undef PEA_HWAIT1
-#undef PEA_HWAIT0
 
 }  // namespace pea

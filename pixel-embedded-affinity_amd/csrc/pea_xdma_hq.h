@@ -100,18 +100,9 @@ __device__ __forceinline__ void hq_transpose(const u2_t (&r)[4], u4_t& lo, u4_t&
 #endif
 // the chunk whose registers are about to be written has landed: only the `younger` chunks requested after it (4 * NQ loads each) may
 // still fly.  Loads retire in order, so "at most that many outstanding" means the older chunk is complete whatever the stores did
-// (they share the counter and may retire early or late: pea_zmarch.h zm_bwd_wait -- a late store only makes this wait longer,
-// never unsound)
-__device__ __forceinline__ void hq_wait(int n) {
-#define PEA_HQW(k) case k: asm volatile("s_waitcnt vmcnt(" #k ")" ::: "memory"); break;
-  switch (n) {
-    PEA_HQW(0) PEA_HQW(4) PEA_HQW(8) PEA_HQW(12) PEA_HQW(16) PEA_HQW(20) PEA_HQW(24) PEA_HQW(28) PEA_HQW(32) PEA_HQW(36) PEA_HQW(40)
-    PEA_HQW(48) PEA_HQW(56)
-    default: asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); break;
-  }
-#undef PEA_HQW
-}
-#define PEA_HQ_LANDED(younger) hq_wait(4 * NQ * (younger));
+// (they share the counter and may retire early or late: pea_stage.h -- a late store only makes this wait longer, never unsound)
+// (a ladder over the counts the instantiations reach, pea_stage.h: the count is a constant once the chunk loop is unrolled)
+#define PEA_HQ_LANDED(younger) loads_landed_among<56, 48, 40, 36, 32, 28, 24, 20, 16, 12, 8, 4>(4 * NQ * (younger));
 
 // ------------------------------------------------------------------------------------------------------------------
 // backward, self loss (both roles), f16 e / de, the projection first (pea_xdma_pf.h: `affs` = the forward's raw cosine map)
@@ -264,7 +255,7 @@ __global__ __launch_bounds__(TH* TW + 64 * NPW, WPE) void k_bwd_xdma_hqs(const K
     ay[k] = pown + C.yd[k] * TW;
   }
   // #0: the 1 / norm plane, g and the raw map have landed (the only time a consumer waits for memory)
-  asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory");
+  loads_barrier<0>();
   const float invo = *(const float*)(W + WB + pown * 4);
   const float inv_own = fabsf(invo);
 #pragma unroll

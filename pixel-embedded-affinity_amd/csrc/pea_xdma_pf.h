@@ -23,24 +23,9 @@
 
 namespace pea {
 
-// s_waitcnt vmcnt(n) lgkmcnt(0); s_barrier for an n that is a constant only after the chunk loop is unrolled (the immediate of
-// s_waitcnt has to be a literal: a switch the optimiser folds).  LOADS retire in order: n = the DMA instructions of the chunks
-// after the one that has to have landed.  (Rounds 3 counted the gradient stores issued since as well; a store may retire before
-// an older load, so that count was unsound -- round 4, pea_zmarch.h zm_bwd_wait.)
-__device__ __forceinline__ void pf_wait(int n) {
-#define PEA_PFW(k) case k: asm volatile("s_waitcnt vmcnt(" #k ") lgkmcnt(0)\n\ts_barrier" ::: "memory"); break;
-  switch (n) {
-    PEA_PFW(0) PEA_PFW(1) PEA_PFW(2) PEA_PFW(3) PEA_PFW(4) PEA_PFW(5) PEA_PFW(6) PEA_PFW(7) PEA_PFW(8) PEA_PFW(9) PEA_PFW(10)
-    PEA_PFW(11) PEA_PFW(12) PEA_PFW(13) PEA_PFW(14) PEA_PFW(15) PEA_PFW(16) PEA_PFW(17) PEA_PFW(18) PEA_PFW(19) PEA_PFW(20)
-    PEA_PFW(21) PEA_PFW(22) PEA_PFW(23) PEA_PFW(24) PEA_PFW(25) PEA_PFW(26) PEA_PFW(27) PEA_PFW(28) PEA_PFW(29) PEA_PFW(30)
-    PEA_PFW(31) PEA_PFW(32)
-    default: asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory"); break;
-  }
-#undef PEA_PFW
-}
-
 // RB: buffers of the ring (3: two chunks in flight beside the one being gathered; more where the planes are small -- a store has
-// to be acknowledged RB - 1 chunk periods after it was issued, or the next hand-off waits for it)
+// to be acknowledged RB - 1 chunk periods after it was issued, or the next hand-off waits for it).  The hand-offs (pea_stage.h) leave
+// the DMA of up to RB - 2 chunks in flight: a ladder over the counts this wave can have issued for them.
 template <int D_T, int TH, int TW, int PSU, bool CROP, int WPE, int RB = 3>
 __global__ __launch_bounds__(TH* TW, WPE) void k_bwd_xdma_pf(const KParams P, const XParams C, const float* __restrict__ xt,
                                                               const float* __restrict__ invp, const float* __restrict__ gin,
@@ -65,47 +50,19 @@ __global__ __launch_bounds__(TH* TW, WPE) void k_bwd_xdma_pf(const KParams P, co
   const unsigned po4 = (unsigned)(py * P.X + px) * 4u;
   const unsigned pe = live ? po4 : kOOB;
 
-  // ---- the (up to) two quads this lane moves per plane (pea_xdma.h)
-  unsigned vo[2];
-  bool act[2];
-#pragma unroll
-  for (int s = 0; s < 2; ++s) {
-    const int q = (s * (NT / 64) + wave) * 64 + lane;
-    int gy, gx;
-    if (q < C.QV) {
-      gy = y0 - C.hy0 + (q >> 3);
-      gx = x0 + 4 * (q & 7);
-    } else {
-      const int k = q - C.QV;
-      const int sh = C.SW == 64 ? 4 : 3;
-      const int cc = 4 * (k & ((1 << sh) - 1));
-      gy = y0 + (k >> sh);
-      gx = cc < C.split ? x0 + TW + cc : x0 - C.SW + cc;
-    }
-    act[s] = q < C.QA;
-    bool oky, okx;
-    gy = wrap1<CROP>(gy, P.Y, oky);
-    gx = wrap1<CROP>(gx, P.X, okx);
-    vo[s] = (act[s] && oky && okx) ? (unsigned)(gy * P.X + gx) * 4u : kOOB;
-  }
-  const int wbase = wave * 1024, w1 = wbase + (NT / 64) * 1024;
-  const int npc = 2 * ((__builtin_amdgcn_ballot_w64(act[0]) != 0) + (__builtin_amdgcn_ballot_w64(act[1]) != 0));
-#define PEA_PFDMA(rsrc, plane_byte, so)                                                                                          \
-  {                                                                                                                              \
-    if (act[0]) __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (lds_ptr_t)(lds + (plane_byte) + wbase), 16, vo[0], so, 0, 0);    \
-    if (act[1]) __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (lds_ptr_t)(lds + (plane_byte) + w1), 16, vo[1], so, 0, 0);       \
-  }
-  PEA_PFDMA(iB, IP * PS, ezo)
-  PEA_PFDMA(xB, 0, ezo)
-  PEA_PFDMA(xB, PS, ezo + ecs)
+  // ---- the (up to) two quads this lane moves per plane
+  const CrossStage<> ST = cross_stage<TH, TW, CROP>(P, C, y0, x0, wave, lane);
+  const int npc = ST.npc;
+  cross_dma(ST, iB, lds, IP * PS, ezo);
+  cross_dma(ST, xB, lds, 0, ezo);
+  cross_dma(ST, xB, lds, PS, ezo + ecs);
 
   // ---- g and the affinity of every pair (role A at p, role B at p - o): the coefficients, and the projection
   const unsigned pg = live ? po4 : 0xC0000000u;
   float cx[XP], cy[XP];
   int ax[XP], ay[XP];
   float proj = 0.f;
-  const int vown = ((C.hy0 + ly) * TW + lx) * 4;
-  const int hrow = (C.QV * 4 + ly * C.SW) * 4;
+  const int vown = cross_slots<TW>(C, ly, lx, ax, ay);
 #pragma unroll
   for (int k = 0; k < XP; ++k) {
     const int go = C.xgo[k];
@@ -116,8 +73,6 @@ __global__ __launch_bounds__(TH* TW, WPE) void k_bwd_xdma_pf(const KParams P, co
     const unsigned so = ezo + (unsigned)C.xgi[k] * ecs;
     cx[k] = bl32(gB, k < C.npx ? o : kOOB, so);
     proj = fmaf(cx[k], bl32(aB, k < C.npx ? o : kOOB, so), proj);
-    const int d = C.xd[k], c = lx + d;
-    ax[k] = (unsigned)c < (unsigned)TW ? vown + d * 4 : hrow + (c & C.xm[k]) * 4;
   }
 #pragma unroll
   for (int k = 0; k < XP; ++k) {
@@ -129,15 +84,14 @@ __global__ __launch_bounds__(TH* TW, WPE) void k_bwd_xdma_pf(const KParams P, co
     const unsigned so = ezo + (unsigned)C.ygi[k] * ecs;
     cy[k] = bl32(gB, k < C.npy ? o : kOOB, so);
     proj = fmaf(cy[k], bl32(aB, k < C.npy ? o : kOOB, so), proj);
-    ay[k] = vown + C.yd[k] * TW * 4;
   }
 #pragma unroll
   for (int c = 1; c <= RB - 2; ++c) {  // chunks 1 .. RB - 2 into their buffers (the last buffer holds the 1 / norm plane for now)
-    PEA_PFDMA(xB, 2 * c * PS, ezo + (unsigned)(2 * c) * ecs)
-    PEA_PFDMA(xB, (2 * c + 1) * PS, ezo + (unsigned)(2 * c + 1) * ecs)
+    cross_dma(ST, xB, lds, 2 * c * PS, ezo + (unsigned)(2 * c) * ecs);
+    cross_dma(ST, xB, lds, (2 * c + 1) * PS, ezo + (unsigned)(2 * c + 1) * ecs);
   }
   // inv, chunk 0, g and affs have landed (the DMA instructions of chunks 1 .. RB - 2 may still fly)
-  pf_wait((RB - 2) * npc);
+  loads_barrier_upto<4 * (RB - 2), 2>((RB - 2) * npc);
 
   const float invo = *(const float*)(lds + IP * PS + vown);
   const float inv_own = fabsf(invo);
@@ -149,9 +103,9 @@ __global__ __launch_bounds__(TH* TW, WPE) void k_bwd_xdma_pf(const KParams P, co
   }
   if (invo < 0.f) proj = 0.f;  // clamp branch of F.normalize: d ehat / d e = I / eps
   asm volatile("" : "+v"(proj));
-  asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");  // the inv plane is dead: the last buffer may be filled
-  PEA_PFDMA(xB, IP * PS, ezo + (unsigned)(2 * (RB - 1)) * ecs)
-  PEA_PFDMA(xB, (IP + 1) * PS, ezo + (unsigned)(2 * (RB - 1) + 1) * ecs)
+  lds_barrier();  // the inv plane is dead: the last buffer may be filled
+  cross_dma(ST, xB, lds, IP * PS, ezo + (unsigned)(2 * (RB - 1)) * ecs);
+  cross_dma(ST, xB, lds, (IP + 1) * PS, ezo + (unsigned)(2 * (RB - 1) + 1) * ecs);
   const float sc = dl * inv_own;
 
 #pragma unroll
@@ -183,23 +137,17 @@ __global__ __launch_bounds__(TH* TW, WPE) void k_bwd_xdma_pf(const KParams P, co
     asm volatile("" : "+v"(vx), "+v"(vy));  // (stored behind the hand-off: there the stores have a chunk's time to retire)
     if (ps + 1 < NP) {
       // chunk ps + 1 has landed; younger than it: the DMA of chunks ps + 2 .. ps + RB - 1 (those that exist) and the stores of the
-      // last min(ps + 1, RB - 1) chunks; everyone is done with buffer ps % RB
-      // (the stores in between are NOT counted: they sit on the same counter but may retire before an older load -- counted in,
-      //  they let the wait pass with part of the awaited chunk in flight; pea_zmarch.h zm_bwd_wait has the case that showed it)
-      // A wave that issues no DMA (npc == 0: the region has fewer blocks than the workgroup has waves) has nothing to wait for --
-      // vmcnt(0) would make it drain its own stores at every chunk and hold everybody's barrier.
+      // last min(ps + 1, RB - 1) chunks, which are not counted (pea_stage.h); everyone is done with buffer ps % RB
       const int nd = (ps + RB - 1 < NP ? ps + RB - 1 : NP - 1) - (ps + 1);
-      if (npc == 0) lds_barrier();
-      else pf_wait(nd * npc);
+      loads_barrier_upto<4 * (RB - 2), 2>(nd * npc, npc == 0);
       if (ps + RB < NP) {
-        PEA_PFDMA(xB, bo, ezo + (unsigned)(2 * (ps + RB)) * ecs)
-        PEA_PFDMA(xB, bo + PS, ezo + (unsigned)(2 * (ps + RB) + 1) * ecs)
+        cross_dma(ST, xB, lds, bo, ezo + (unsigned)(2 * (ps + RB)) * ecs);
+        cross_dma(ST, xB, lds, bo + PS, ezo + (unsigned)(2 * (ps + RB) + 1) * ecs);
       }
     }
     __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, vx), dB, pe, ezo + (unsigned)(2 * ps) * ecs, kAuxNT);
     __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, vy), dB, pe, ezo + (unsigned)(2 * ps + 1) * ecs, kAuxNT);
   }
-#undef PEA_PFDMA
 }
 
 // ------------------------------------------------------------------------------------------------------------------
@@ -236,82 +184,49 @@ __global__ __launch_bounds__(TH* TW, WPE) void k_bwd_xdma_pfo(const KParams P, c
   const bool live = py < P.Y && px < P.X;
   const unsigned pe = live ? (unsigned)(py * P.X + px) * 4u : kOOB;
 
-  unsigned vo[2];
-  bool act[2];
-#pragma unroll
-  for (int s = 0; s < 2; ++s) {
-    const int q = (s * (NT / 64) + wave) * 64 + lane;
-    int gy, gx;
-    if (q < C.QV) {
-      gy = y0 - C.hy0 + (q >> 3);
-      gx = x0 + 4 * (q & 7);
-    } else {
-      const int k = q - C.QV;
-      const int sh = C.SW == 64 ? 4 : 3;
-      const int cc = 4 * (k & ((1 << sh) - 1));
-      gy = y0 + (k >> sh);
-      gx = cc < C.split ? x0 + TW + cc : x0 - C.SW + cc;
-    }
-    act[s] = q < C.QA;
-    bool oky, okx;
-    gy = wrap1<CROP>(gy, P.Y, oky);
-    gx = wrap1<CROP>(gx, P.X, okx);
-    vo[s] = (act[s] && oky && okx) ? (unsigned)(gy * P.X + gx) * 4u : kOOB;
-  }
-  const int wbase = wave * 1024, w1 = wbase + (NT / 64) * 1024;
+  const CrossStage<> ST = cross_stage<TH, TW, CROP>(P, C, y0, x0, wave, lane);
   const bool ownw = wave < NT / 256;  // uniform: the waves that move the own tile (quads 0 .. 127)
   unsigned ownvo = kOOB;
   {
     const int q = (int)threadIdx.x, qy = y0 + (q >> 3), qx = x0 + 4 * (q & 7);
     ownvo = (q < NT / 4 && qy < P.Y && qx < P.X) ? (unsigned)(qy * P.X + qx) * 4u : kOOB;
   }
-  const int npc = 2 * ((__builtin_amdgcn_ballot_w64(act[0]) != 0) + (__builtin_amdgcn_ballot_w64(act[1]) != 0)) + (ownw ? 2 : 0);
-#define PEA_PFDMA(rsrc, plane_byte, so)                                                                                          \
-  {                                                                                                                              \
-    if (act[0]) __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (lds_ptr_t)(lds + (plane_byte) + wbase), 16, vo[0], so, 0, 0);    \
-    if (act[1]) __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (lds_ptr_t)(lds + (plane_byte) + w1), 16, vo[1], so, 0, 0);       \
-  }
+  const int npc = ST.npc + (ownw ? 2 : 0);
 // chunk c: the second operand's cross into ring buffer c % RB, the own tile into its 4 KB slot
 #define PEA_PFCHUNK(c)                                                                                                            \
   {                                                                                                                              \
-    PEA_PFDMA(xB, (2 * ((c) % RB)) * PS, ezo + (unsigned)(2 * (c)) * ecs)                                                        \
-    PEA_PFDMA(xB, (2 * ((c) % RB) + 1) * PS, ezo + (unsigned)(2 * (c) + 1) * ecs)                                                \
+    cross_dma(ST, xB, lds, (2 * ((c) % RB)) * PS, ezo + (unsigned)(2 * (c)) * ecs);                                              \
+    cross_dma(ST, xB, lds, (2 * ((c) % RB) + 1) * PS, ezo + (unsigned)(2 * (c) + 1) * ecs);                                      \
     if (ownw) {                                                                                                                  \
-      __builtin_amdgcn_raw_ptr_buffer_load_lds(oB, (lds_ptr_t)(lds + OWNB + (2 * ((c) % RB)) * 2048 + wave * 1024), 16, ownvo,    \
-                                               ezo + (unsigned)(2 * (c)) * ecs, 0, 0);                                            \
-      __builtin_amdgcn_raw_ptr_buffer_load_lds(oB, (lds_ptr_t)(lds + OWNB + (2 * ((c) % RB) + 1) * 2048 + wave * 1024), 16, ownvo, \
-                                               ezo + (unsigned)(2 * (c) + 1) * ecs, 0, 0);                                        \
+      cross_dma1(oB, lds + OWNB + (2 * ((c) % RB)) * 2048 + wave * 1024, ownvo, ezo + (unsigned)(2 * (c)) * ecs);                \
+      cross_dma1(oB, lds + OWNB + (2 * ((c) % RB) + 1) * 2048 + wave * 1024, ownvo, ezo + (unsigned)(2 * (c) + 1) * ecs);        \
     }                                                                                                                            \
   }
   // the second operand's 1 / norm plane sits in the LAST buffer's first plane until the coefficients are done; chunk 0 .. RB - 2
-  PEA_PFDMA(iB, IP * PS, ezo)
+  cross_dma(ST, iB, lds, IP * PS, ezo);
   PEA_PFCHUNK(0)
 
   // ---- g and the raw affinity at the own pixel: the coefficients, and the projection
   float cx[XP], cy[XP];
   int ax[XP], ay[XP];
   float proj = 0.f;
-  const int vown = ((C.hy0 + ly) * TW + lx) * 4;
-  const int hrow = (C.QV * 4 + ly * C.SW) * 4;
+  cross_slots<TW>(C, ly, lx, ax, ay);
 #pragma unroll
   for (int k = 0; k < XP; ++k) {
     const unsigned so = ezo + (unsigned)C.xgi[k] * ecs;
     cx[k] = bl32(gB, k < C.npx ? pe : kOOB, so);
     proj = fmaf(cx[k], bl32(aB, k < C.npx ? pe : kOOB, so), proj);
-    const int d = C.xd[k], c = lx + d;
-    ax[k] = (unsigned)c < (unsigned)TW ? vown + d * 4 : hrow + (c & C.xm[k]) * 4;
   }
 #pragma unroll
   for (int k = 0; k < XP; ++k) {
     const unsigned so = ezo + (unsigned)C.ygi[k] * ecs;
     cy[k] = bl32(gB, k < C.npy ? pe : kOOB, so);
     proj = fmaf(cy[k], bl32(aB, k < C.npy ? pe : kOOB, so), proj);
-    ay[k] = vown + C.yd[k] * TW * 4;
   }
   const float invo = bl32(oiB, pe, ezo);
 #pragma unroll
   for (int c = 1; c <= RB - 2; ++c) PEA_PFCHUNK(c)
-  pf_wait((RB - 2) * npc);  // inv, chunk 0, g, affs and the own 1 / norm have landed (chunks 1 .. RB - 2 may still fly)
+  loads_barrier_upto<6 * (RB - 2), 2>((RB - 2) * npc);  // inv, chunk 0, g, affs and the own 1 / norm have landed (chunks 1 .. RB - 2 may still fly)
 
   const float inv_own = fabsf(invo);
 #pragma unroll
@@ -322,7 +237,7 @@ __global__ __launch_bounds__(TH* TW, WPE) void k_bwd_xdma_pfo(const KParams P, c
   }
   if (invo < 0.f) proj = 0.f;  // clamp branch of F.normalize
   asm volatile("" : "+v"(proj));
-  asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");  // the inv plane is dead: the last buffer may be filled
+  lds_barrier();  // the inv plane is dead: the last buffer may be filled
   PEA_PFCHUNK(RB - 1)
   const float sc = dl * inv_own;
   const float pq = proj * inv_own;
@@ -354,14 +269,12 @@ __global__ __launch_bounds__(TH* TW, WPE) void k_bwd_xdma_pfo(const KParams P, c
     asm volatile("" : "+v"(vx), "+v"(vy));
     if (ps + 1 < NP) {
       const int nd = (ps + RB - 1 < NP ? ps + RB - 1 : NP - 1) - (ps + 1);  // chunks requested behind the one that has to have landed
-      if (npc == 0) lds_barrier();
-      else pf_wait(nd * npc);
+      loads_barrier_upto<6 * (RB - 2), 2>(nd * npc, npc == 0);
       if (ps + RB < NP) PEA_PFCHUNK(ps + RB)
     }
     __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, vx), dB, pe, ezo + (unsigned)(2 * ps) * ecs, kAuxNT);
     __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, vy), dB, pe, ezo + (unsigned)(2 * ps + 1) * ecs, kAuxNT);
   }
-#undef PEA_PFDMA
 #undef PEA_PFCHUNK
 }
 

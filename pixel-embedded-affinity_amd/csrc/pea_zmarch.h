@@ -50,13 +50,6 @@ struct ZMParams {
   int zseg, nseg;  // planes per segment, segments per tile column
 };
 
-#define PEA_ZM_DMA(rsrc, plane_byte, so)                                                                          \
-  {                                                                                                               \
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (lds_ptr_t)(lds + (plane_byte) + wbase), 16, vo0, so, 0, 0);   \
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (lds_ptr_t)(lds + (plane_byte) + w1), 16, vo1, so, 0, 0);      \
-  }
-#define PEA_ZM_WAIT(n) asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)\n\ts_barrier" ::"n"(n) : "memory")
-
 // ------------------------------------------------------------------------------------------------------------------
 // backward
 // ------------------------------------------------------------------------------------------------------------------
@@ -74,8 +67,8 @@ struct ZmSlot { static constexpr int v = ((JO - D_) % kZS + kZS) % kZS; };
 // requested together with the next plane's I.  Buffers beyond the 64 KB a ds_read immediate reaches get their addresses formed
 // per chunk.
 // Every staged plane issues the SAME sequence of LOAD instructions per wave (planes beyond the volume, and the plane after the
-// last, are requested at out-of-range offsets), so the hand-offs are literal s_waitcnt vmcnt(N), N = the loads that may still fly
-// behind the item waited for (zm_bwd_wait; the two gradient stores per chunk are NOT counted, see there):
+// last, are requested at out-of-range offsets), so the hand-offs are literal loads_barrier<N>() (pea_stage.h), N = the loads that may
+// still fly behind the item waited for (zm_bwd_wait; the two gradient stores per chunk are NOT counted):
 //     item i: W_i: item i + 1 has landed; barrier; request item i + NB (of the next plane from i + NB >= 9 on; item 0 = I,
 //     2 instructions, + G, 24); [2 stores of plane z - 4, i >= 1]
 // NB = 3: vmcnt(4) everywhere, vmcnt(26) behind the request of I + G.   NB = 4: 8 and 30.
@@ -84,12 +77,8 @@ constexpr int kZmG = 24;  // prefetched values per lane: 8 + 8 in-plane pairs, 4
 
 constexpr int zm_bwd_sz(int m) { return ((m % 9) + 9) % 9 == 0 ? 2 + kZmG : 4; }   // LOAD instructions of the request of item m
 // vmcnt of W_i: the LOADS issued after the request of item i + 1 (made after item i + 1 - NB) and before W_i.  Stores are NOT
-// counted although they sit on the same counter: loads retire in order among themselves, but a store may retire before an older
-// load (LLVM's waitcnt pass treats a gfx9 vmcnt with loads and stores pending as out of order for the same reason).  Counting the
-// stores in -- "only these may still fly" -- let a wait pass with part of the awaited chunk in flight whenever stores had retired
-// early: with a ring of three the gradient differed between identical launches at 17 k of 403 M values (runs of eight pixels;
-// profiles/r4_zm_race.txt), with a ring of four it never showed -- and was just as unsound.  With loads only, outstanding stores
-// make a wait a little longer, never shorter.
+// counted (pea_stage.h): here, with a ring of three, counting them made the gradient differ between identical launches at 17 k of
+// 403 M values (runs of eight pixels; profiles/r4_zm_race.txt); with a ring of four it never showed -- and was just as unsound.
 constexpr int zm_bwd_wait(int NB, int i) {
   int n = 0;
   for (int j = i + 2 - NB; j <= i - 1; ++j) n += zm_bwd_sz(j + NB);
@@ -169,7 +158,7 @@ __device__ __forceinline__ void zm_bwd_full(const KParams& P, const XParams& C, 
   if (first) {  // the pipeline's head: items 0 .. NB - 1
 #pragma unroll
     for (int m = 0; m < NB - 1; ++m) PEA_ZMB_ITEM(JO, m, ezo, vh0, vh1, here)
-    PEA_ZM_WAIT(zm_bwd_wait(NB, 8));
+    loads_barrier<zm_bwd_wait(NB, 8)>();
     PEA_ZMB_ITEM(JO, NB - 1, ezo, vh0, vh1, here)
   }
   // ---- I-proc: coefficient of a pair = g * 1 / |e(q)|, two pairs to a register pair (pk_fma_c selects the half)
@@ -197,7 +186,7 @@ __device__ __forceinline__ void zm_bwd_full(const KParams& P, const XParams& C, 
 #pragma unroll
   for (int k = 0; k < XP / 2; ++k) asm volatile("" : "+v"(ccx[k]), "+v"(ccy[k]));
   const f2 gz01 = {gz[0], gz[1]}, gz23 = {gz[2], gz[3]};
-  PEA_ZM_WAIT(zm_bwd_wait(NB, 0));  // W_I: C0 has landed; the 1 / norm plane is dead: its buffer may be filled
+  loads_barrier<zm_bwd_wait(NB, 0)>();  // W_I: C0 has landed; the 1 / norm plane is dead: its buffer may be filled
   const unsigned vn0 = there ? vo0 : kOOB, vn1 = there ? vo1 : kOOB;
   PEA_ZMB_ITEM(JO, NB, ezo, vh0, vh1, here)
   // <ehat, G> of the pending planes: role B of plane z - d through offset d is g_d(z) a_d(z)
@@ -257,8 +246,9 @@ __device__ __forceinline__ void zm_bwd_full(const KParams& P, const XParams& C, 
     __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, vx), dB, pf, fzo + (unsigned)(2 * ps) * ecs, PEA_ZMV_STORE_AUX);
     __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, vy), dB, pf, fzo + (unsigned)(2 * ps + 1) * ecs, PEA_ZMV_STORE_AUX);
 #endif
-    // the next item has landed; everyone is done with this buffer; refill it with the item NB behind
-    PEA_ZM_WAIT(zm_bwd_wait(NB, ps + 1));
+    // the next item has landed; everyone is done with this buffer; refill it with the item NB behind.  (W_1 .. W_8 take two values:
+    // W_7's while the request of I + G is among the loads behind, W_8's otherwise -- a constant once the loop is unrolled.)
+    loads_barrier_among<zm_bwd_wait(NB, 7), zm_bwd_wait(NB, 8)>(zm_bwd_wait(NB, ps + 1));
     if (ps + 1 + NB < 9) PEA_ZMB_ITEM(JO, ps + 1 + NB, ezo, vh0, vh1, here)
     else PEA_ZMB_ITEM(JN, ps + 1 + NB - 9, ezn, vn0, vn1, there)
 #if PEA_ZMV_STORE_LATE
@@ -300,41 +290,13 @@ __global__ __launch_bounds__(TH* TW, 2) void k_bwd_zm(const KParams P, const XPa
   const int py = y0 + ly, px = x0 + lx;
   const bool live = py < P.Y && px < P.X;
   const unsigned pe = live ? (unsigned)(py * P.X + px) * 4u : kOOB;
-  // the two quads this lane moves per plane (pea_xdma.h; unconditional DMA: a wave without a second block repeats its first)
-  unsigned vo[2];
-#pragma unroll
-  for (int s = 0; s < 2; ++s) {
-    const int q = (s * (NT / 64) + wave) * 64 + lane;
-    int gy, gx;
-    if (q < C.QV) {
-      gy = y0 - C.hy0 + (q >> 3);
-      gx = x0 + 4 * (q & 7);
-    } else {
-      const int k = q - C.QV;
-      const int sh = C.SW == 64 ? 4 : 3;
-      const int cc = 4 * (k & ((1 << sh) - 1));
-      gy = y0 + (k >> sh);
-      gx = cc < C.split ? x0 + TW + cc : x0 - C.SW + cc;
-    }
-    bool oky, okx;
-    gy = wrap1<true>(gy, P.Y, oky);
-    gx = wrap1<true>(gx, P.X, okx);
-    vo[s] = (q < C.QA && oky && okx) ? (unsigned)(gy * P.X + gx) * 4u : kOOB;
-  }
-  const int wbase = wave * 1024;
-  const bool two = __builtin_amdgcn_readfirstlane(((NT / 64) + wave) * 64 < C.QA);
-  const unsigned vo0 = vo[0], vo1 = two ? vo[1] : vo[0];
-  const int w1 = two ? wbase + (NT / 64) * 1024 : wbase;
-  // LDS slot of every in-plane neighbour
+  // the two quads this lane moves per plane (unconditional DMA: a wave without a second block repeats its first) and the LDS slot
+  // of every in-plane neighbour; handed to the steps as plain values
+  const CrossStage<true> ST = cross_stage<TH, TW, true, true>(P, C, y0, x0, wave, lane);
+  const unsigned vo0 = ST.vo[0], vo1 = ST.vo[1];
+  const int wbase = ST.wbase, w1 = ST.w1;
   int ax[8], ay[8];
-  const int vown = ((C.hy0 + ly) * TW + lx) * 4;
-  const int hrow = (C.QV * 4 + ly * C.SW) * 4;
-#pragma unroll
-  for (int k = 0; k < 8; ++k) {
-    const int d = C.xd[k], c = lx + d;
-    ax[k] = (unsigned)c < (unsigned)TW ? vown + d * 4 : hrow + (c & C.xm[k]) * 4;
-    ay[k] = vown + C.yd[k] * TW * 4;
-  }
+  const int vown = cross_slots<TW>(C, ly, lx, ax, ay);
   const int gwave = wave * (kZmG * 256), glane = gwave + lane * 4;  // the wave's block of prefetched g / a values: [value][lane]
   f2 Eh[8][kZS], Pd[8][kZS];
   float prj[kZS], ivs[kZS];
@@ -362,7 +324,7 @@ __global__ __launch_bounds__(TH* TW, 2) void k_bwd_zm(const KParams P, const XPa
     PEA_ZM_FULL(3, z + 3)
   }
 #undef PEA_ZM_FULL
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the last plane's look-ahead DMA (out-of-range: zeros) has drained
+  loads_landed<0>();  // the last plane's look-ahead DMA (out-of-range: zeros) has drained
 }
 
 // ------------------------------------------------------------------------------------------------------------------
@@ -376,8 +338,8 @@ __global__ __launch_bounds__(TH* TW, 2) void k_bwd_zm(const KParams P, const XPa
 // array behind the ring.  The upper four buffers lie beyond the 64 KB a ds_read immediate reaches: their addresses are formed per
 // chunk (one add per read; hoisted out of the march they would cost eleven registers beside the window).
 // Every staged plane issues the SAME sequence of LOAD instructions per wave (absent operands and the plane after the last are
-// requested at an out-of-range offset), so every hand-off is a literal s_waitcnt vmcnt(N), N = the loads that may still fly behind
-// the chunk waited for (stores sit on the same counter but may retire before older loads: they are NOT counted, zm_bwd_wait):
+// requested at an out-of-range offset), so every hand-off is a literal loads_barrier<N>() (pea_stage.h), N = the loads that may still
+// fly behind the chunk waited for (the stores are NOT counted):
 //     T  : 3 * ITEMS loads (target, weight, mask quads of the plane's items)
 //     c  : gather chunk c; wait W_c for chunk c + 1; barrier; 4 DMA instructions: chunk c of the NEXT plane into the same buffer
 //     E  : 1 + 2 * ITEMS stores (the 1 / norm plane, affs and g quads)
@@ -438,39 +400,11 @@ __global__ __launch_bounds__(TH* TW, 2) void k_fwd_zm(const KParams P, const XPa
   const int py = y0 + ly, px = x0 + lx;
   const bool live = py < P.Y && px < P.X;
   const unsigned pe = live ? (unsigned)(py * P.X + px) * 4u : kOOB;
-  unsigned vo[2];
-#pragma unroll
-  for (int s = 0; s < 2; ++s) {
-    const int q = (s * (NT / 64) + wave) * 64 + lane;
-    int gy, gx;
-    if (q < C.QV) {
-      gy = y0 - C.hy0 + (q >> 3);
-      gx = x0 + 4 * (q & 7);
-    } else {
-      const int k = q - C.QV;
-      const int sh = C.SW == 64 ? 4 : 3;
-      const int cc = 4 * (k & ((1 << sh) - 1));
-      gy = y0 + (k >> sh);
-      gx = cc < C.split ? x0 + TW + cc : x0 - C.SW + cc;
-    }
-    bool oky, okx;
-    gy = wrap1<true>(gy, P.Y, oky);
-    gx = wrap1<true>(gx, P.X, okx);
-    vo[s] = (q < C.QA && oky && okx) ? (unsigned)(gy * P.X + gx) * 4u : kOOB;
-  }
-  const int wbase = wave * 1024;
-  const bool two = __builtin_amdgcn_readfirstlane(((NT / 64) + wave) * 64 < C.QA);
-  const unsigned vo0 = vo[0], vo1 = two ? vo[1] : vo[0];
-  const int w1 = two ? wbase + (NT / 64) * 1024 : wbase;
+  const CrossStage<true> ST = cross_stage<TH, TW, true, true>(P, C, y0, x0, wave, lane);
+  const unsigned vo0 = ST.vo[0], vo1 = ST.vo[1];
+  const int wbase = ST.wbase, w1 = ST.w1;
   int an[NXP];
-  const int vown = ((C.hy0 + ly) * TW + lx) * 4;
-  const int hrow = (C.QV * 4 + ly * C.SW) * 4;
-#pragma unroll
-  for (int k = 0; k < NXP; ++k) {
-    const int d = C.fd[k], c = lx + d;
-    const int a_x = (unsigned)c < (unsigned)TW ? vown + d * 4 : hrow + (c & C.fm[k]) * 4;
-    an[k] = C.fax[k] ? a_x : vown + d * TW * 4;  // unused offsets: d = 0, the own slot
-  }
+  const int vown = cross_slots<TW>(C, ly, lx, an);
   // the window: raw own pixel of the last four planes (slot = step mod 4) and their 1 / norm
   f2 W[NP][kZS];
   float iw[kZS];
@@ -529,7 +463,7 @@ __global__ __launch_bounds__(TH* TW, 2) void k_fwd_zm(const KParams P, const XPa
                                                                    (ezo >> 2) + (unsigned)isl[it] * (unsigned)P.S, kAuxNT);    \
           m4[it] = has_m ? mm : 0x01010101u;                                                                                   \
         }                                                                                                                      \
-        if (first) PEA_ZM_WAIT(28 + NLD); /* chunk 0 has landed (chunks 1 - 7 and T may fly) */                                \
+        if (first) loads_barrier<28 + NLD>(); /* chunk 0 has landed (chunks 1 - 7 and T may fly) */                            \
         f2 dot[NXP], ssq[NXP], dz[kZS], oss = {0.f, 0.f};                                                                      \
         _Pragma("unroll") for (int k = 0; k < NXP; ++k) { dot[k] = (f2){0.f, 0.f}; ssq[k] = (f2){0.f, 0.f}; }                  \
         _Pragma("unroll") for (int k = 0; k < kZS; ++k) dz[k] = (f2){0.f, 0.f};                                                \
@@ -556,8 +490,8 @@ __global__ __launch_bounds__(TH* TW, 2) void k_fwd_zm(const KParams P, const XPa
           _Pragma("unroll") for (int j = 0; j < kZS; ++j) asm volatile("" : "+v"(dz[j]));                                      \
           asm volatile("" : "+v"(oss), "+v"(W[ps][JO]));                                                                       \
           /* the next chunk has landed (W_c); everyone is done with this buffer; refill it with the next plane's chunk */   \
-          if (ps < 7) PEA_ZM_WAIT(24 + NLD);                                                                                   \
-          else PEA_ZM_WAIT(24);                                                                                                \
+          if (ps < 7) loads_barrier<24 + NLD>();                                                                               \
+          else loads_barrier<24>();                                                                                            \
           PEA_ZMF_CHUNK(ps, ezn + (unsigned)(2 * ps) * ecs, vn0, vn1)                                                          \
           /* the PREVIOUS plane's loss partials: behind this barrier they are all written (no barrier of their own) */         \
           if (TRAIN && ps == 0 && !first && lane_k) lacc = part_sum<NSL>(s_part, threadIdx.x, NSL, 1, lacc);                   \
@@ -619,11 +553,8 @@ __global__ __launch_bounds__(TH* TW, 2) void k_fwd_zm(const KParams P, const XPa
     lds_barrier();  // the last plane's partials
     if (lane_k) part_accumulate<NSL>(st, tile, threadIdx.x, s_part, NSL, 1, lacc);
   }
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the last plane's look-ahead DMA (out-of-range: zeros) has drained
+  loads_landed<0>();  // the last plane's look-ahead DMA (out-of-range: zeros) has drained
 }
-
-#undef PEA_ZM_DMA
-#undef PEA_ZM_WAIT
 
 // host: which channel holds the offset (-s, 0, 0); false: a z offset the march does not cover (positive, longer than kZS, twice)
 inline bool plan_zmarch(const KParams& P, ZMParams* M) {
