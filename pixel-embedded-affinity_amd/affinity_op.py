@@ -12,6 +12,7 @@ Reference behaviour mirrored (file:line in the reference tree):
 import collections
 import collections.abc
 import ctypes
+import operator
 import os
 import threading
 
@@ -140,27 +141,47 @@ def make_desc(spec, e, tstride=0, wstride=0, mstride=0, mflag=0):
     return d
 
 
-_CROSS_OK = {}
 _CROSS_LOCK = threading.Lock()
+
+
+class _IdMemo(object):
+    """answers remembered by the IDENTITY of the objects they are about (memoised descriptors: comparing their bytes would cost what
+    the memo saves).  The key is the objects' ids plus `extra`; an id can be reused once its object is gone, so the entry pins the
+    objects, and a hit counts only if every pinned object `is` the one asked about.  More than `cap` entries clear the memo;
+    insertion and clearing happen under the one lock (nn.DataParallel replicas ask from one thread per device)."""
+
+    def __init__(self, cap):
+        self.cap, self._d = cap, {}
+
+    def get(self, objs, extra, compute):
+        """compute() for the tuple `objs` and the hashable `extra`, remembered"""
+        key = (*map(id, objs), extra)
+        hit = self._d.get(key)
+        if hit is None or not all(map(operator.is_, hit[1], objs)):
+            r = compute()
+            with _CROSS_LOCK:
+                if len(self._d) > self.cap:
+                    self._d.clear()
+                self._d[key] = hit = (r, objs)
+        return hit[0]
+
+    def clear(self):
+        with _CROSS_LOCK:
+            self._d.clear()
+
+    def __len__(self):
+        return len(self._d)
+
+
+_CROSS_OK = _IdMemo(2048)
+_lib._RELOAD_HOOKS.append(_CROSS_OK.clear)  # pea_cross_supported depends on the PEA_* switches
 
 
 def cross_supported(d, mode):
     """pea_cross_supported(desc, mode), remembered per memoised descriptor AND current device (the host-side plan behind it costs a few
     microseconds; the march kernels' answer depends on the device's CU count, and nn.DataParallel replicas call this from one thread
     per device: round-4 advice)"""
-    key = (id(d), mode, torch.cuda.current_device())
-    hit = _CROSS_OK.get(key)
-    if hit is None or hit[1] is not d:  # (the entry keeps its descriptor alive: an id cannot be reused while it is a key)
-        r = bool(_lib.lib().pea_cross_supported(ctypes.byref(d), mode))
-        with _CROSS_LOCK:
-            if len(_CROSS_OK) > 2048:
-                _CROSS_OK.clear()
-            _CROSS_OK[key] = (r, d)
-        return r
-    return hit[0]
-
-
-_lib._RELOAD_HOOKS.append(_CROSS_OK.clear)  # pea_cross_supported depends on the PEA_* switches
+    return _CROSS_OK.get((d,), (mode, torch.cuda.current_device()), lambda: bool(_lib.lib().pea_cross_supported(ctypes.byref(d), mode)))
 
 
 def _build_desc(spec, e, tstride, wstride, mstride, mflag=0):
@@ -244,13 +265,62 @@ def _affs_shape(e, K):
     return (e.shape[0], K) + tuple(e.shape[2:])
 
 
+def _pair_args(e, e_other):
+    """-> (e_c, o_c): the embedding and the second operand (the EMA embedding, or None) as the kernels take them: contiguous, the
+    second in the first's dtype and shape"""
+    e_c = _embedding_arg(e, "embedding")
+    if e_other is None:
+        return e_c, None
+    o_c = _embedding_arg(e_other, "ema_embedding").to(e_c.dtype)
+    if o_c.shape != e_c.shape:
+        raise ValueError("ema_embedding shape %s != embedding shape %s" % (tuple(o_c.shape), tuple(e_c.shape)))
+    return e_c, o_c
+
+
+def _loss_operands(spec, e_c, target, weight, mask, dev=None):
+    """-> (desc, target, weight, mask, kshape) of a tensor-form loss on e_c: the three [B, K, spatial...] operands in the layout the
+    kernels read (_batch_strided, mask_arg) and the descriptor that carries their batch strides and the mask's type.
+    dev: the device every operand must live on (the autograd nodes ask; the section nodes never did)"""
+    kshape = _affs_shape(e_c, spec.K)
+    t, ts = _batch_strided(target, "target", torch.float32, kshape)
+    w, ws = _batch_strided(weight, "weightmap", torch.float32, kshape)
+    m, ms, mflag = mask_arg(mask, kshape)
+    if dev is not None:
+        for x in (e_c, t, w, m):
+            if x is not None and x.device != dev:
+                raise RuntimeError("all operands must live on %s" % dev)
+    return make_desc(spec, e_c, ts, ws, ms, mflag), t, w, m, kshape
+
+
+def _backward_operands(spec, d, e_c, role):
+    """-> (inv, raw_ok): what a training forward on descriptor d writes for its backward besides g.  role: 1 -- a self loss; 2 -- a
+    cross loss whose second operand is detached; 0 -- anything else: nothing.
+    inv: the 1 / norm plane of e, 4 bytes per pixel, which the cross backward (axis-aligned stencil) stages next to e -- for role 2
+    two planes (e, e_other) --, allocated where those kernels cover the shape (pea_cross_supported modes 1 / 2), else None.
+    raw_ok: the backward also reads the forward's RAW cosine map (modes 3 / 4: the projection-first kernels at D > 16, the z-march
+    backward of 3D volumes; never on an activated map).  Only then is the map written for a loss whose map nobody asked for, and
+    only then is it saved like an input -- autograd's version counter then catches an in-place edit of the returned map between
+    forward and backward; saved everywhere it would turn a harmless affs.relu_() before backward() into a RuntimeError."""
+    if not role or not cross_supported(d, role):
+        return None, False
+    shape = (e_c.shape[0],) + tuple(e_c.shape[2:])
+    inv = torch.empty(shape if role == 1 else (2,) + shape, dtype=torch.float32, device=e_c.device)
+    return inv, spec.act == 0 and cross_supported(d, 3 if role == 1 else 4)
+
+
+def _check_trainable(spec, D):
+    if D not in SPECIALISED_TRAIN_D and spec.border == _lib.BORDER_REPLICATE:
+        raise NotImplementedError("the replicate-border backward needs D in %s (got %d)" % (SPECIALISED_TRAIN_D, D))
+
+
+def _loss_rows(specs, dev):
+    """[n, 1 + kmax] f32: row j takes loss j and its K_j per-offset parts"""
+    return torch.empty((len(specs), 1 + max(sp.K for sp in specs)), dtype=torch.float32, device=dev)
+
+
 def affinity_infer(e, e_other, spec):
     """affs [B,K,...] f32 = pea_affinity_infer (no autograd)."""
-    e = _embedding_arg(e, "embedding")
-    if e_other is not None:
-        e_other = _embedding_arg(e_other, "ema_embedding").to(e.dtype)
-        if e_other.shape != e.shape:
-            raise ValueError("ema_embedding shape %s != embedding shape %s" % (tuple(e_other.shape), tuple(e.shape)))
+    e, e_other = _pair_args(e, e_other)
     with _on_device(e.device):
         d = make_desc(spec, e)
         affs = torch.empty(_affs_shape(e, spec.K), dtype=torch.float32, device=e.device)
@@ -323,51 +393,26 @@ class FusedAffinityMSE(torch.autograd.Function):
     @staticmethod
     def forward(ctx, e, e_other, target, weight, mask, spec):
         ctx.set_materialize_grads(False)  # no 95 MB zero tensors for the gradients of the non-differentiable outputs
-        e_c = _embedding_arg(e, "embedding")
-        o_c = None
-        if e_other is not None:
-            o_c = _embedding_arg(e_other, "ema_embedding").to(e_c.dtype)
-            if o_c.shape != e_c.shape:
-                raise ValueError("ema_embedding shape %s != embedding shape %s" % (tuple(o_c.shape), tuple(e_c.shape)))
-        kshape = _affs_shape(e_c, spec.K)
-        target, ts = _batch_strided(target, "target", torch.float32, kshape)
-        weight, ws = _batch_strided(weight, "weightmap", torch.float32, kshape)
-        mask, ms, mflag = mask_arg(mask, kshape)
-        for t in (o_c, target, weight, mask):
-            if t is not None and t.device != e_c.device:
-                raise RuntimeError("all operands must live on %s" % e_c.device)
+        e_c, o_c = _pair_args(e, e_other)
+        if o_c is not None and o_c.device != e_c.device:
+            raise RuntimeError("all operands must live on %s" % e_c.device)
         want_e = e.requires_grad
         want_o = e_other is not None and e_other.requires_grad
         with _on_device(e_c.device):
-            d = make_desc(spec, e_c, ts, ws, ms, mflag)
+            d, target, weight, mask, kshape = _loss_operands(spec, e_c, target, weight, mask, e_c.device)
             L = _lib.lib()
             affs = torch.empty(kshape, dtype=torch.float32, device=e_c.device)
             loss_vec = torch.empty(1 + spec.K, dtype=torch.float32, device=e_c.device)
             work, wsb = workspace(e_c.device, d)
             # g = d loss / d affs is all the backward needs besides the embeddings; skip it when nothing trains
             g = torch.empty(kshape, dtype=torch.float32, device=e_c.device) if (want_e or want_o) else None
-            # 1 / norm of e, 4 bytes per pixel: what the cross backward (self loss, axis-aligned stencil) stages next to e;
-            # with a detached second operand two planes (e, e_other) where the role-A cross kernels cover the shape
-            inv = None
-            if want_e and o_c is None and cross_supported(d, 1):
-                inv = torch.empty((e_c.shape[0],) + tuple(e_c.shape[2:]), dtype=torch.float32, device=e_c.device)
-            elif want_e and o_c is not None and not want_o and cross_supported(d, 2):
-                inv = torch.empty((2, e_c.shape[0]) + tuple(e_c.shape[2:]), dtype=torch.float32, device=e_c.device)
+            inv, raw_ok = _backward_operands(spec, d, e_c, 0 if not want_e or want_o else 1 if o_c is None else 2)
             _lib.check(L.pea_affinity_fwd_ex(ctypes.byref(d), _ptr(e_c), _ptr(o_c), _ptr(target), _ptr(weight), _ptr(mask),
                                              _ptr(affs), _ptr(g), _ptr(inv), _ptr(loss_vec), _ptr(work), wsb, _stream()),
                        "pea_affinity_fwd_ex")
         ctx.spec, ctx.desc = spec, d
         ctx.has_other = o_c is not None
-        # the raw cosine map is an input of the projection-first backward (pea_affinity_bwd_ex2): saved like an input, so autograd's
-        # version counter catches an in-place edit of the returned map (affs.relu_()) between forward and backward
-        # -- and only where the backward reads it (pea_cross_supported mode 3: the projection-first kernels at D > 16, the z-march
-        # backward of 3D volumes): elsewhere saving it would turn a harmless affs.relu_() before backward() into a RuntimeError
-        # (mode 4: the same for the cross loss with a detached second operand -- D = 32 / 64)
-        raw = None
-        if inv is not None and spec.act == 0:
-            if (o_c is None and cross_supported(d, 3)) or (o_c is not None and cross_supported(d, 4)):
-                raw = affs
-        ctx.save_for_backward(e_c, o_c, g, inv, raw)
+        ctx.save_for_backward(e_c, o_c, g, inv, affs if raw_ok else None)
         loss, per_offset = loss_vec[0], loss_vec[1:]  # views of a buffer that is not itself returned
         ctx.mark_non_differentiable(affs, per_offset)
         return loss, affs, per_offset
@@ -379,8 +424,7 @@ class FusedAffinityMSE(torch.autograd.Function):
         want_o = ctx.has_other and ctx.needs_input_grad[1]
         if not (want_e or want_o) or dloss is None:
             return None, None, None, None, None, None
-        if e_c.shape[1] not in SPECIALISED_TRAIN_D and ctx.spec.border == _lib.BORDER_REPLICATE:
-            raise NotImplementedError("the replicate-border backward needs D in %s (got %d)" % (SPECIALISED_TRAIN_D, e_c.shape[1]))
+        _check_trainable(ctx.spec, e_c.shape[1])
         with _on_device(e_c.device):
             L = _lib.lib()
             dl = dloss.to(device=e_c.device, dtype=torch.float32).contiguous()
@@ -399,22 +443,16 @@ class MultiUnsupported(NotImplementedError):
     results"""
 
 
-_MULTI_OK = {}
+_MULTI_OK = _IdMemo(256)
 
 
 def multi_supported(descs):
     """pea_multi_supported for a list of memoised descriptors, remembered by their identities (host-only, but it validates each
     descriptor again: more host time than the launch it decides about)"""
-    key = tuple(id(d) for d in descs)
-    hit = _MULTI_OK.get(key)
-    if hit is None or any(a is not b for a, b in zip(hit[1], descs)):  # (the entry keeps its descriptors alive: no id is reused)
+    def ask():
         arr = (ctypes.POINTER(PeaDesc) * len(descs))(*[ctypes.pointer(d) for d in descs])
-        r = bool(_lib.lib().pea_multi_supported(arr, len(descs)))
-        with _CROSS_LOCK:
-            if len(_MULTI_OK) > 256:
-                _MULTI_OK.clear()
-            _MULTI_OK[key] = hit = (r, list(descs))
-    return hit[0]
+        return bool(_lib.lib().pea_multi_supported(arr, len(descs)))
+    return _MULTI_OK.get(tuple(descs), (), ask)
 
 
 # The tensor-form batched launches on 16-bit storage pay while the table is launch-sized.  Measured on an MI355X with bf16 embeddings
@@ -456,67 +494,61 @@ def multi_backward(descs, e_cs, gs, dlosses):
     return des
 
 
+def multi_forward(specs, tensors, need_affs, rows, embs):
+    """n self losses as ONE forward launch and one loss finish (pea_affinity_fwd_multi): loss j and its per-offset parts into
+    rows[j] (rows=None: a block of its own) -> (descs, e_cs, gs, affs, rows), with g_j = d loss_j / d affs_j for multi_backward.
+    specs: n AffinitySpecs; tensors: n (target, weight, mask) triples as FusedAffinityMSE takes them; need_affs=False: the maps are
+    not written (empty tensors come back).  Embeddings: float32, float16 or bfloat16, all n of ONE dtype; maps, loss rows and g stay
+    float32.  Raises MultiUnsupported, before anything is launched, where the table is outside the fused set."""
+    n = len(embs)
+    if not (len(specs) == len(tensors) == n):
+        raise ValueError("one spec and one (target, weight, mask) triple per embedding")
+    e_cs = [_embedding_arg(e, "embedding") for e in embs]
+    dev = e_cs[0].device
+    ops = [_loss_operands(spec, e_c, t, w, m, dev) for spec, e_c, (t, w, m) in zip(specs, e_cs, tensors)]
+    descs = [a[0] for a in ops]
+    if not 1 <= n <= _lib.PEA_MULTI_MAX_N or not multi_supported(descs):
+        raise MultiUnsupported("the table is outside the fused set of include/pea_multi.h")
+    if not multi16_pays(descs):
+        raise MultiUnsupported("a 16-bit table of more than %d tiles: the single calls are faster (multi16_pays)" % MULTI16_MAX_TILES)
+    with _on_device(dev):
+        if rows is None:
+            rows = _loss_rows(specs, dev).unbind(0)
+        gs = [torch.empty(a[4], dtype=torch.float32, device=dev) for a in ops]  # (g_out is required by the C call)
+        affs = [torch.empty(a[4] if need_affs else (0,), dtype=torch.float32, device=dev) for a in ops]
+        work, wsb = workspace(dev, descs[0], n)
+        table = (_lib.PeaMultiFwd * n)()
+        for j in range(n):
+            a, (d, t, w, m, _) = table[j], ops[j]
+            a.desc, a.e, a.target, a.weight = ctypes.pointer(d), e_cs[j].data_ptr(), t.data_ptr(), w.data_ptr()
+            a.mask = None if m is None else m.data_ptr()
+            a.affs = affs[j].data_ptr() if need_affs else None
+            a.g_out, a.loss_out = gs[j].data_ptr(), rows[j].data_ptr()
+        rc = _lib.lib().pea_affinity_fwd_multi(table, n, _ptr(work), wsb, _stream())
+    if rc == _lib.E_UNSUPPORTED:  # (nothing was launched)
+        raise MultiUnsupported("pea_affinity_fwd_multi: the table is outside the fused set")
+    _lib.check(rc, "pea_affinity_fwd_multi")
+    return descs, e_cs, gs, affs, rows
+
+
 class MultiAffinityMSE(torch.autograd.Function):
     """n self losses with the fused WeightedMSE as ONE node -- the four deep-supervision scales of a training step
     (scripts_cvppp/main.py:284-287, scripts_ac3ac4/main.py:227-230): one forward launch over every tile of every scale, one loss
-    finish, one backward launch (include/pea_multi.h) instead of three launches per scale.
+    finish (multi_forward), one backward launch (multi_backward, with autograd's grad_outputs as the per-loss dloss) instead of
+    three launches per scale (include/pea_multi.h).
 
-        loss_0 .. loss_{n-1}, affs_0 .. affs_{n-1}, per_offset_0 .. per_offset_{n-1} = f(specs, tensors, need_affs, pre, *embeddings)
+        loss_0 .. loss_{n-1}, affs_0 .. affs_{n-1}, per_offset_0 .. per_offset_{n-1} = f(specs, tensors, need_affs, *embeddings)
 
-    specs: n AffinitySpecs; tensors: n (target, weight, mask) triples as FusedAffinityMSE takes them; need_affs=False: the maps are
-    not written (empty tensors come back).  pre: None -- the backward launch is made by backward(), with autograd's grad_outputs as
-    the per-loss dloss -- or (rows, dlosses) for a caller that OWNS the weighting and the backward (the section nodes, which call
-    forward() directly inside their own forward): n loss rows [1 + K] to write into and the n per-loss weights as device scalars;
-    the backward launch is then enqueued right behind the forward and its gradients are left in ctx.grads.
-    Embeddings: float32, float16 or bfloat16, all n of ONE dtype; maps, loss rows and g stay float32, gradients take the embedding's dtype.
-    Raises MultiUnsupported, before anything is launched, where the table is outside the fused set."""
+    The arguments are multi_forward's; gradients take the embedding's dtype.  A caller that owns the weighting and the backward (the
+    section nodes) calls multi_forward and multi_backward itself."""
 
     @staticmethod
-    def forward(ctx, specs, tensors, need_affs, pre, *embs):
+    def forward(ctx, specs, tensors, need_affs, *embs):
         ctx.set_materialize_grads(False)
         n = len(embs)
-        if not (len(specs) == len(tensors) == n):
-            raise ValueError("one spec and one (target, weight, mask) triple per embedding")
-        e_cs = [_embedding_arg(e, "embedding") for e in embs]
-        dev = e_cs[0].device
-        descs, twm = [], []
-        for spec, e_c, (t, w, m) in zip(specs, e_cs, tensors):
-            kshape = _affs_shape(e_c, spec.K)
-            t, ts = _batch_strided(t, "target", torch.float32, kshape)
-            w, ws = _batch_strided(w, "weightmap", torch.float32, kshape)
-            m, ms, mflag = mask_arg(m, kshape)
-            for x in (e_c, t, w, m):
-                if x is not None and x.device != dev:
-                    raise RuntimeError("all operands must live on %s" % dev)
-            descs.append(make_desc(spec, e_c, ts, ws, ms, mflag))
-            twm.append((t, w, m, kshape))
-        if not 1 <= n <= _lib.PEA_MULTI_MAX_N or not multi_supported(descs):
-            raise MultiUnsupported("the table is outside the fused set of include/pea_multi.h")
-        if not multi16_pays(descs):
-            raise MultiUnsupported("a 16-bit table of more than %d tiles: the single calls are faster (multi16_pays)" % MULTI16_MAX_TILES)
-        with _on_device(dev):
-            if pre is None:
-                rows = torch.empty((n, 1 + max(sp.K for sp in specs)), dtype=torch.float32, device=dev).unbind(0)
-            else:
-                rows = pre[0]
-            train = pre is not None or any(e.requires_grad for e in embs)
-            gs = [torch.empty(a[3], dtype=torch.float32, device=dev) for a in twm]  # (g_out is required by the C call)
-            affs = [torch.empty(a[3] if need_affs else (0,), dtype=torch.float32, device=dev) for a in twm]
-            work, wsb = workspace(dev, descs[0], n)
-            table = (_lib.PeaMultiFwd * n)()
-            for j in range(n):
-                a, (t, w, m, _) = table[j], twm[j]
-                a.desc, a.e, a.target, a.weight = ctypes.pointer(descs[j]), e_cs[j].data_ptr(), t.data_ptr(), w.data_ptr()
-                a.mask = None if m is None else m.data_ptr()
-                a.affs = affs[j].data_ptr() if need_affs else None
-                a.g_out, a.loss_out = gs[j].data_ptr(), rows[j].data_ptr()
-            rc = _lib.lib().pea_affinity_fwd_multi(table, n, _ptr(work), wsb, _stream())
-            if rc == _lib.E_UNSUPPORTED:  # (nothing was launched)
-                raise MultiUnsupported("pea_affinity_fwd_multi: the table is outside the fused set")
-            _lib.check(rc, "pea_affinity_fwd_multi")
-            ctx.grads = multi_backward(descs, e_cs, gs, pre[1]) if pre is not None else None
+        descs, e_cs, gs, affs, rows = multi_forward(specs, tensors, need_affs, None, embs)
         ctx.descs, ctx.n = descs, n
-        if pre is None and train:
+        if any(e.requires_grad for e in embs):
             ctx.save_for_backward(*(e_cs + gs))
         losses = [rows[j][0] for j in range(n)]
         parts = [rows[j][1:1 + specs[j].K] for j in range(n)]
@@ -526,13 +558,10 @@ class MultiAffinityMSE(torch.autograd.Function):
     @staticmethod
     def backward(ctx, *grads):
         n = ctx.n
-        none = (None, None, None, None) + (None,) * n
-        if ctx.grads is not None:
-            raise RuntimeError("MultiAffinityMSE with pre=(rows, dlosses) belongs to a caller that owns the backward")
         # one launch over the losses that take part in this backward (a sub-table of a fused table is fused)
-        live = [j for j in range(n) if grads[j] is not None and ctx.needs_input_grad[4 + j]]
+        live = [j for j in range(n) if grads[j] is not None and ctx.needs_input_grad[3 + j]]
         if not live:
-            return none
+            return (None, None, None) + (None,) * n
         saved = ctx.saved_tensors
         e_cs, gs = saved[:n], saved[n:]
         dev = e_cs[0].device
@@ -542,7 +571,7 @@ class MultiAffinityMSE(torch.autograd.Function):
         out = [None] * n
         for j, de in zip(live, des):
             out[j] = de
-        return (None, None, None, None) + tuple(out)
+        return (None, None, None) + tuple(out)
 
 
 _ONES = {}
@@ -614,9 +643,8 @@ class AffinityMap(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, e, e_other, spec):
-        affs = affinity_infer(e, e_other, spec)
-        e_c = _embedding_arg(e, "embedding")
-        o_c = None if e_other is None else _embedding_arg(e_other, "ema_embedding").to(e_c.dtype)
+        e_c, o_c = _pair_args(e, e_other)
+        affs = affinity_infer(e_c, o_c, spec)
         ctx.spec = spec
         ctx.has_other = o_c is not None
         ctx.save_for_backward(e_c, o_c)
@@ -631,8 +659,7 @@ class AffinityMap(torch.autograd.Function):
             return None, None, None
         if ctx.spec.act:
             raise NotImplementedError("an activation of the affs output is inference-only: apply it to the map yourself")
-        if e_c.shape[1] not in SPECIALISED_TRAIN_D and ctx.spec.border == _lib.BORDER_REPLICATE:
-            raise NotImplementedError("the replicate-border backward needs D in %s (got %d)" % (SPECIALISED_TRAIN_D, e_c.shape[1]))
+        _check_trainable(ctx.spec, e_c.shape[1])
         with _on_device(e_c.device):
             d = make_desc(ctx.spec, e_c)
             da = d_affs.to(torch.float32).contiguous()
@@ -823,7 +850,32 @@ def materialise_labels(lab, e, ndim, step):
     return (v.squeeze(1) if ndim == 2 else v).contiguous()
 
 
-_MULTI_LABELS_OK = {}
+def label_weight_table(d, lab, flags, B, K):
+    """-> (wtab, counts, cb): the class-balance table [B, K, 2] of the int32 label image `lab` under descriptor d and the target
+    flags (pea_label_weights: weight_binary_ratio per image and channel, one count launch), with the counts buffer it used"""
+    counts, cb = label_counts(d, lab.device)
+    wtab = torch.empty(B * K * 2, dtype=torch.float32, device=lab.device)
+    _lib.check(_lib.lib().pea_label_weights(ctypes.byref(d), _ptr(lab), flags, _ptr(wtab), _ptr(counts), cb, _stream()),
+               "pea_label_weights")
+    return wtab, counts, cb
+
+
+def label_counts(d, dev):
+    """-> (counts, cb): the scratch of the label count reductions (pea_label_weights, pea_gen_targets) and its size in bytes"""
+    cb = _lib.lib().pea_targets_workspace_bytes(ctypes.byref(d))
+    return torch.empty(max(cb, 4) // 4, dtype=torch.int32, device=dev), cb
+
+
+def check_weight_table(wtab, j, B, K, dev):
+    """a caller's weight table for loss j must be what label_weight_table makes for this batch and stencil -> wtab"""
+    if wtab.numel() != B * K * 2 or wtab.dtype != torch.float32 or wtab.device != dev:
+        raise ValueError("weight table %d does not fit this batch / stencil" % j)
+    if not wtab.is_contiguous():
+        raise ValueError("weight table %d must be contiguous" % j)
+    return wtab
+
+
+_MULTI_LABELS_OK = _IdMemo(256)
 
 
 def multi_labels_call(specs, e_cs, sources, flags, tables, need_affs, rows, dlosses):
@@ -851,14 +903,8 @@ def multi_labels_call(specs, e_cs, sources, flags, tables, need_affs, rows, dlos
         a.desc, a.e, a.labels = ctypes.pointer(descs[j]), e_cs[j].data_ptr(), lab.data_ptr()
         a.label_dims[:] = [1] * (4 - lab.dim()) + list(lab.shape[1:])
         a.label_step[:] = step
-    key = tuple(id(d) for d in descs) + tuple(tuple(a.label_dims) + tuple(a.label_step) for a in table) + (flags,)
-    hit = _MULTI_LABELS_OK.get(key)
-    if hit is None or any(x is not y for x, y in zip(hit[1], descs)):  # (the entry keeps its descriptors alive: no id is reused)
-        with _CROSS_LOCK:
-            if len(_MULTI_LABELS_OK) > 256:
-                _MULTI_LABELS_OK.clear()
-            _MULTI_LABELS_OK[key] = hit = (bool(L.pea_multi_labels_supported(table, n, flags)), list(descs))
-    if not hit[0]:
+    geometry = tuple(tuple(a.label_dims) + tuple(a.label_step) for a in table) + (flags,)
+    if not _MULTI_LABELS_OK.get(tuple(descs), geometry, lambda: bool(L.pea_multi_labels_supported(table, n, flags))):
         raise MultiLabelsUnsupported("the table is outside the fused set of include/pea_multi_labels.h")
     with _on_device(dev):
         affs = [torch.empty(_affs_shape(e_c, sp.K) if need_affs else (0,), dtype=torch.float32, device=dev) for e_c, sp in zip(e_cs, specs)]
@@ -866,12 +912,7 @@ def multi_labels_call(specs, e_cs, sources, flags, tables, need_affs, rows, dlos
         for j in range(n):
             a = table[j]
             if tables is not None and tables[j] is not None:
-                wtab = tables[j]
-                if wtab.numel() != e_cs[j].shape[0] * specs[j].K * 2 or wtab.dtype != torch.float32 or wtab.device != dev:
-                    raise ValueError("weight table %d does not fit this batch / stencil" % j)
-                if not wtab.is_contiguous():
-                    raise ValueError("weight table %d must be contiguous" % j)
-                a.wtab = wtab.data_ptr()
+                a.wtab = check_weight_table(tables[j], j, e_cs[j].shape[0], specs[j].K, dev).data_ptr()
             a.affs = affs[j].data_ptr() if need_affs else None
             a.loss_out, a.de = rows[j].data_ptr(), des[j].data_ptr()
             a.dloss = None if dlosses is None or dlosses[j] is None else dlosses[j].data_ptr()
@@ -889,16 +930,16 @@ class MultiLabelsAffinityMSE(torch.autograd.Function):
     """n self losses straight from label images as ONE node and ONE library call (include/pea_multi_labels.h): a count launch for the
     class-balance tables, one fused forward + backward launch over every tile of every scale, one loss finish.
 
-        loss_0 .., affs_0 .., per_offset_0 .. = f(specs, sources, flags, need_affs, tables, pre, *embeddings)
+        loss_0 .., affs_0 .., per_offset_0 .. = f(specs, sources, flags, need_affs, tables, *embeddings)
 
     specs: n AffinitySpecs; sources: label_sources(...) -- per loss (label tensor, (sz, sy, sx)), a tensor of its own or one all
     losses sample with a step; flags: _lib.TGT_*; tables: None or per loss None / a [B, K, 2] table of pea_label_weights.
-    pre: None -- the gradients are computed for grad_output = 1 and backward() hands them out scaled by autograd's grad_outputs -- or
-    (rows, dlosses) for a caller that owns the weighting and the backward (the section node): loss rows to write into and per-loss
-    weights as device scalars; the gradients are then left in ctx.grads.  Raises MultiLabelsUnsupported before anything is launched."""
+    The gradients are computed for grad_output = 1 and backward() hands them out scaled by autograd's grad_outputs; a caller that
+    owns the weighting and the backward (the section node) calls multi_labels_call itself.  Raises MultiLabelsUnsupported before
+    anything is launched."""
 
     @staticmethod
-    def forward(ctx, specs, sources, flags, need_affs, tables, pre, *embs):
+    def forward(ctx, specs, sources, flags, need_affs, tables, *embs):
         ctx.set_materialize_grads(False)
         n = len(embs)
         if not (len(specs) == len(sources) == n):
@@ -906,17 +947,12 @@ class MultiLabelsAffinityMSE(torch.autograd.Function):
         e_cs = [_embedding_arg(e, "embedding") for e in embs]
         dev = e_cs[0].device
         with _on_device(dev):
-            if pre is None:
-                rows = torch.empty((n, 1 + max(sp.K for sp in specs)), dtype=torch.float32, device=dev).unbind(0)
-                affs, des = multi_labels_call(specs, e_cs, sources, flags, tables, need_affs, rows, None)
-                ctx.des, ctx.grads = des, None
-                ctx.args = (specs, [st for _, st in sources], flags)
-                ctx.n_tab = 0 if tables is None else n
-                tabs = [] if tables is None else [t if t is not None else torch.empty(0, device=dev) for t in tables]
-                ctx.save_for_backward(*(e_cs + [lab for lab, _ in sources] + tabs))
-            else:
-                rows = pre[0]
-                affs, ctx.grads = multi_labels_call(specs, e_cs, sources, flags, tables, need_affs, rows, pre[1])
+            rows = _loss_rows(specs, dev).unbind(0)
+            affs, ctx.des = multi_labels_call(specs, e_cs, sources, flags, tables, need_affs, rows, None)
+            ctx.args = (specs, [st for _, st in sources], flags)
+            ctx.n_tab = 0 if tables is None else n
+            tabs = [] if tables is None else [t if t is not None else torch.empty(0, device=dev) for t in tables]
+            ctx.save_for_backward(*(e_cs + [lab for lab, _ in sources] + tabs))
         ctx.n = n
         losses = [rows[j][0] for j in range(n)]
         parts = [rows[j][1:1 + specs[j].K] for j in range(n)]
@@ -926,19 +962,16 @@ class MultiLabelsAffinityMSE(torch.autograd.Function):
     @staticmethod
     def backward(ctx, *grads):
         n = ctx.n
-        none = (None,) * 6 + (None,) * n
-        if ctx.grads is not None:
-            raise RuntimeError("MultiLabelsAffinityMSE with pre=(rows, dlosses) belongs to a caller that owns the backward")
-        live = [j for j in range(n) if grads[j] is not None and ctx.needs_input_grad[6 + j]]
+        live = [j for j in range(n) if grads[j] is not None and ctx.needs_input_grad[5 + j]]
         if not live:
-            return none
+            return (None,) * (5 + n)
         if ctx.des is None:  # a second backward over a retained graph: the call once more on the saved inputs
             saved = ctx.saved_tensors
             specs, steps, flags = ctx.args
             e_cs, labs = list(saved[:n]), saved[n:2 * n]
             tables = [t if t.numel() else None for t in saved[2 * n:]] if ctx.n_tab else None
             with _on_device(e_cs[0].device):
-                rows = torch.empty((n, 1 + max(sp.K for sp in specs)), dtype=torch.float32, device=e_cs[0].device).unbind(0)
+                rows = _loss_rows(specs, e_cs[0].device).unbind(0)
                 _, ctx.des = multi_labels_call(specs, e_cs, list(zip(labs, steps)), flags, tables, False, rows, None)
         des, ctx.des = ctx.des, None
         out = [None] * n
@@ -951,7 +984,7 @@ class MultiLabelsAffinityMSE(torch.autograd.Function):
                 _lib.check(_lib.lib().pea_scale_inplace(_ptr(de), _DTYPE_CODE[de.dtype], de.numel(), _ptr(dl), _stream()),
                            "pea_scale_inplace")
                 out[j] = de
-        return (None,) * 6 + tuple(out)
+        return (None,) * 5 + tuple(out)
 
 
 class LabelsAffinityMSE(torch.autograd.Function):
@@ -963,12 +996,7 @@ class LabelsAffinityMSE(torch.autograd.Function):
     @staticmethod
     def forward(ctx, e, e_other, labels, spec, flags, need_affs=True):
         ctx.set_materialize_grads(False)
-        e_c = _embedding_arg(e, "embedding")
-        o_c = None
-        if e_other is not None:
-            o_c = _embedding_arg(e_other, "ema_embedding").to(e_c.dtype)
-            if o_c.shape != e_c.shape:
-                raise ValueError("ema_embedding shape %s != embedding shape %s" % (tuple(o_c.shape), tuple(e_c.shape)))
+        e_c, o_c = _pair_args(e, e_other)
         _require_gpu(labels, "labels")
         if labels.dtype.is_floating_point or tuple(labels.shape) != (e_c.shape[0],) + tuple(e_c.shape[2:]):
             raise ValueError("labels must be an integer tensor of shape %s" % ((e_c.shape[0],) + tuple(e_c.shape[2:]),))
@@ -982,10 +1010,7 @@ class LabelsAffinityMSE(torch.autograd.Function):
             L = _lib.lib()
             affs = torch.empty(kshape if need_affs else (0,), dtype=torch.float32, device=e_c.device)
             loss_vec = torch.empty(1 + spec.K, dtype=torch.float32, device=e_c.device)
-            wtab = torch.empty(e_c.shape[0] * spec.K * 2, dtype=torch.float32, device=e_c.device)
-            cb = L.pea_targets_workspace_bytes(ctypes.byref(d))
-            counts = torch.empty(max(cb, 4) // 4, dtype=torch.int32, device=e_c.device)
-            _lib.check(L.pea_label_weights(ctypes.byref(d), _ptr(lab), flags, _ptr(wtab), _ptr(counts), cb, _stream()), "pea_label_weights")
+            wtab, _, _ = label_weight_table(d, lab, flags, e_c.shape[0], spec.K)
             work, wsb = workspace(e_c.device, d)
             de_unit = torch.empty_like(e_c)
             # large self losses on the cross kernels: two launches (labels-in forward + cross backward) through a scratch buffer

@@ -77,7 +77,7 @@ class _TensorSection(torch.autograd.Function):
     """cvppp_loss_section's six losses as ONE autograd node on the tensor path: per loss one forward launch (saving g)
     and one backward launch whose dloss is the loss' weight; the EMA cross gradient is added to the self gradient with one
     add.  Same reasons as _LabelsSection: nothing per loss is left to autograd."""
-    batched = False  # _TensorSectionBatched: the four deep-supervision scales through op.MultiAffinityMSE
+    batched = False  # _TensorSectionBatched: the four deep-supervision scales through op.multi_forward / op.multi_backward
 
     @staticmethod
     def forward(ctx, *args):
@@ -90,38 +90,25 @@ class _TensorSection(torch.autograd.Function):
         dev = embs[0].device
         L = _lib.lib()
         ncall = len(specs)
-        kmax = max(sp.K for sp in specs)
         with op._on_device(dev):
             wdev = _weights_on(dev, weights)
-            rows = torch.empty((ncall, 1 + kmax), dtype=torch.float32, device=dev)
+            rows = op._loss_rows(specs, dev)
             grads, pred = [], None
 
-            def forward_one(j, e_c, o_c, want_affs, planes=0):
-                """forward launch of loss j -> (desc, g, affs, inv); planes: 1 / norm planes wanted for the cross backward
-                (1: self loss, 2: cross loss with the detached second operand), allocated where those kernels cover the shape"""
+            def forward_one(j, e_c, o_c, want_affs, role):
+                """forward launch of loss j -> (desc, g, affs, inv, raw); role: op._backward_operands' (1: self loss, 2: cross loss
+                with the detached second operand, 0: no 1 / norm planes)"""
                 spec = specs[j]
                 # a map nobody sees (the cross loss'): without the activation it can serve the backward -- unless the loss itself is
                 # taken on the activated map (FLAG_LOSS_ACT): then the bits are part of the loss and stay
                 if not want_affs and spec.act and not spec.act & _lib.FLAG_LOSS_ACT:
                     spec = copy.copy(spec)
                     spec.act = 0
-                kshape = op._affs_shape(e_c, spec.K)
-                t, w, m = tensors[0] if j == ncall - 1 else tensors[j]
-                t, ts = op._batch_strided(t, "target", torch.float32, kshape)
-                w, ws = op._batch_strided(w, "weightmap", torch.float32, kshape)
                 # (the reference packs the deep-supervision masks as float thirds of `downN`: taken as they are, no copy)
-                m, ms, mflag = op.mask_arg(m, kshape)
-                d = op.make_desc(spec, e_c, ts, ws, ms, mflag)
+                d, t, w, m, kshape = op._loss_operands(spec, e_c, *(tensors[0] if j == ncall - 1 else tensors[j]))
                 work, wsb = op.workspace(dev, d)
                 g = torch.empty(kshape, dtype=torch.float32, device=dev)
-                inv = None
-                if planes and op.cross_supported(d, planes):
-                    inv = torch.empty(((planes,) if planes == 2 else ()) + (e_c.shape[0],) + tuple(e_c.shape[2:]), dtype=torch.float32,
-                                      device=dev)
-                # the RAW cosine map is an input of the projection-first backward (D > 16, f16) and of the z-march backward (3D):
-                # written also for a loss whose map nobody asked for, where one of those kernels takes the shape (mode 3) -- round-4
-                # advice: without it the section's 3D backwards ran on the tile-per-plane kernels, not on the march
-                raw_ok = inv is not None and spec.act == 0 and op.cross_supported(d, 3 if planes == 1 else 4)
+                inv, raw_ok = op._backward_operands(spec, d, e_c, role)
                 affs = torch.empty(kshape, dtype=torch.float32, device=dev) if (want_affs or raw_ok) else None
                 _lib.check(L.pea_affinity_fwd_ex(ctypes.byref(d), op._ptr(e_c), op._ptr(o_c), op._ptr(t), op._ptr(w), op._ptr(m),
                                                  op._ptr(affs), op._ptr(g), op._ptr(inv), op._ptr(rows[j]), op._ptr(work), wsb,
@@ -138,15 +125,10 @@ class _TensorSection(torch.autograd.Function):
                     specx.act = 0
                 if spec0.K != specx.K or o_c.data_ptr() == e_c.data_ptr():
                     return None
-                kshape = op._affs_shape(e_c, spec0.K)
-                t, w, m = tensors[0]
-                t, ts = op._batch_strided(t, "target", torch.float32, kshape)
-                w, ws = op._batch_strided(w, "weightmap", torch.float32, kshape)
-                m, ms, mflag = op.mask_arg(m, kshape)
-                d0 = op.make_desc(spec0, e_c, ts, ws, ms, mflag)
+                d0, t, w, m, kshape = op._loss_operands(spec0, e_c, *tensors[0])
                 if not op.cross_supported(d0, 5):
                     return None
-                dx = op.make_desc(specx, e_c, ts, ws, ms, mflag)
+                dx = op.make_desc(specx, e_c, d0.target_bstride, d0.weight_bstride, d0.mask_bstride, d0.flags & _lib.FLAG_MASK_F32)
                 work, wsb = op.workspace(dev, d0, 2)
                 half = wsb // 2
                 g0 = torch.empty(kshape, dtype=torch.float32, device=dev)
@@ -178,8 +160,7 @@ class _TensorSection(torch.autograd.Function):
             jx = ncall - 1
             small = None
             fork = _side_stream(dev)  # (the fork point: the small scales wait for nothing this section launches)
-            e0 = op._embedding_arg(embs[0], "embedding")
-            ema_c = op._embedding_arg(ema_embedding, "ema_embedding").to(e0.dtype)
+            e0, ema_c = op._pair_args(embs[0], ema_embedding)
             pair = forward_pair(e0, ema_c)
             if pair is not None:  # one forward launch for the two losses (pea_affinity_fwd_dual_ex: e, target, weight, mask read once)
                 d0, dxx, g0, gx, pred, invx = pair  # invx: the two planes (own, second operand's) as the cross forward writes them
@@ -234,29 +215,25 @@ class _TensorSectionBatched(_TensorSection):
 
 
 def _small_scales_batched(specs, tensors, embs, rows, dlosses):
-    """the deep-supervision self losses of a section as op.MultiAffinityMSE: loss rows into `rows`, gradients weighted by the device
-    scalars `dlosses` -> the gradients, or None where the table is outside the fused set (nothing launched: the caller's loop runs)"""
-    stub = _Rerun()
+    """the deep-supervision self losses of a section as op.multi_forward + op.multi_backward: loss rows into `rows`, gradients weighted
+    by the device scalars `dlosses` -> the gradients, or None where the table is outside the fused set (nothing launched: the caller's loop runs)"""
     try:
-        op.MultiAffinityMSE.forward(stub, specs, tensors, False, (rows, dlosses), *embs)
+        descs, e_cs, gs, _, _ = op.multi_forward(specs, tensors, False, rows, embs)
+        return op.multi_backward(descs, e_cs, gs, dlosses)
     except op.MultiUnsupported:
         return None
-    return stub.grads
 
 
-_ACC_DESC = {}
+_ACC_DESC = op._IdMemo(256)
 
 
 def _accumulating(d):
     """the memoised descriptor d with PEA_FLAG_ACCUMULATE_DE set (pea_affinity_bwd_ex2 then adds to de)"""
-    hit = _ACC_DESC.get(id(d))
-    if hit is None or hit[0] is not d:
-        if len(_ACC_DESC) > 256:
-            _ACC_DESC.clear()
+    def copy_with_flag():
         da = type(d).from_buffer_copy(d)
         da.flags |= _lib.FLAG_ACCUMULATE_DE
-        hit = _ACC_DESC[id(d)] = (d, da)  # (d is kept: its id cannot be reused while the entry lives)
-    return hit[1]
+        return da
+    return _ACC_DESC.get((d,), (), copy_with_flag)
 
 
 def _section_total(L, rows, wdev, ncall):
@@ -428,7 +405,7 @@ def cvppp_loss_section(embedding, emds, ema_embedding, target, weightmap, affs_m
     [B,K,H,W] are dropped; nothing else reads pred in the training loop.
 
     batched=True: the four deep-supervision scales run as ONE forward, one loss finish and one backward launch (include/pea_multi.h,
-    op.MultiAffinityMSE) instead of three launches per scale -- on the same side stream; where the library does not fuse the table
+    op.multi_forward) instead of three launches per scale -- on the same side stream; where the library does not fuse the table
     (pea_multi_supported == 0) the per-scale launches run as before.  Same results to rounding (profiles/multi_scale_ab.json).
     16-bit embeddings (what the heads emit under autocast) are fused like float32 ones as long as the four scales share one dtype
     AND the table is launch-sized (op.MULTI16_MAX_TILES tiles of 256 pixels): measured with bf16 (profiles/multi16_ab.json) the one
@@ -655,27 +632,18 @@ class _LabelsSection(torch.autograd.Function):
         tables = label_cfg.tables  # precomputed by *_label_weight_tables (off the critical path), or None
         steps = label_cfg.steps
         ncall = len(specs)
-        kmax = max(sp.K for sp in specs)
         with op._on_device(dev):
             wdev = _weights_on(dev, weights)
-            rows = torch.empty((ncall, 1 + kmax), dtype=torch.float32, device=dev)
+            rows = op._loss_rows(specs, dev)
 
             def prep(j):
                 e_c = op._embedding_arg(embs[j], "embedding")
                 lab = labels_list[j] if steps is None else op.materialise_labels(labels_list[j], e_c, specs[j].ndim, steps[j])
                 lab = op._labels_int32(lab)
                 d = op.make_desc(specs[j], e_c)
-                cb = L.pea_targets_workspace_bytes(ctypes.byref(d))
-                counts = torch.empty(max(cb, 4) // 4, dtype=torch.int32, device=dev)
                 if tables is not None:
-                    wtab = tables[j]
-                    if wtab.numel() != e_c.shape[0] * specs[j].K * 2 or wtab.dtype != torch.float32 or wtab.device != dev:
-                        raise ValueError("weight table %d does not fit this batch / stencil" % j)
-                    return e_c, lab, d, wtab, counts, cb
-                wtab = torch.empty(e_c.shape[0] * specs[j].K * 2, dtype=torch.float32, device=dev)
-                _lib.check(L.pea_label_weights(ctypes.byref(d), op._ptr(lab), lflags, op._ptr(wtab), op._ptr(counts), cb, op._stream()),
-                           "pea_label_weights")
-                return e_c, lab, d, wtab, counts, cb
+                    return (e_c, lab, d, op.check_weight_table(tables[j], j, e_c.shape[0], specs[j].K, dev)) + op.label_counts(d, dev)
+                return (e_c, lab, d) + op.label_weight_table(d, lab, lflags, e_c.shape[0], specs[j].K)
 
             def one(j, e_c, o_c, lab, d, wtab, counts, cb, affs, de, accumulate):
                 """loss j as one labels-in launch (or, where no labels kernel applies -- the coarsest scales are smaller
@@ -708,7 +676,7 @@ class _LabelsSection(torch.autograd.Function):
             small = []
             fork = _side_stream(dev)  # (the fork point)
             e0, lab0, d0, wtab0, counts0, cb0 = prep(0)
-            ema_c = op._embedding_arg(ema_embedding, "ema_embedding").to(e0.dtype)
+            ema_c = op._pair_args(e0, ema_embedding)[1]
             dx_ = op.make_desc(specs[jx], e0)
             pred = torch.empty(op._affs_shape(e0, specs[0].K), dtype=torch.float32, device=dev)
             de0 = torch.empty_like(e0)
@@ -798,7 +766,6 @@ def cvppp_label_weight_tables(labels, label_downs=None, offsets=None, nb_half=No
         raise TypeError("cvppp_label_weight_tables() needs offsets and nb_half")
     specs, _ = _section_specs(offsets, nb_half, 1, dis_mode, 1, 1.0, 1.0)
     flags = _lib.TGT_PADDING | _lib.TGT_MASK_INSIDE
-    L = _lib.lib()
     if label_downs is None:  # the reference's fx = 1/2 .. 1/16 nearest resize: a plain stride where the size divides
         if labels.shape[-2] % 16 or labels.shape[-1] % 16:
             raise ValueError("label image %s is no multiple of 16: pass the four nearest-downsampled label_downs" % (tuple(labels.shape[1:]),))
@@ -810,12 +777,7 @@ def cvppp_label_weight_tables(labels, label_downs=None, offsets=None, nb_half=No
         like = torch.empty((lab.shape[0], 16) + tuple(lab.shape[1:]), device="meta")  # geometry only
         d = op.make_desc(specs[j], like)
         with op._on_device(lab.device):
-            cb = L.pea_targets_workspace_bytes(ctypes.byref(d))
-            counts = torch.empty(max(cb, 4) // 4, dtype=torch.int32, device=lab.device)
-            wtab = torch.empty(lab.shape[0] * specs[j].K * 2, dtype=torch.float32, device=lab.device)
-            _lib.check(L.pea_label_weights(ctypes.byref(d), op._ptr(lab), flags, op._ptr(wtab), op._ptr(counts), cb, op._stream()),
-                       "pea_label_weights")
-        tables.append(wtab)
+            tables.append(op.label_weight_table(d, lab, flags, lab.shape[0], specs[j].K)[0])
     return tables
 
 

@@ -85,7 +85,7 @@ def embedding_loss_multi(embeddings, targets, weightmaps, masks, criterion, offs
     if _fused(criterion):
         specs = [_spec(offs, [1.0] * len(offs), mode) for offs in offsets_list]
         try:
-            out = MultiAffinityMSE.apply(specs, list(zip(targets, weightmaps, masks)), bool(need_affs), None, *embeddings)
+            out = MultiAffinityMSE.apply(specs, list(zip(targets, weightmaps, masks)), bool(need_affs), *embeddings)
             return [(out[j], out[n + j] if need_affs else None, LossList(out[2 * n + j])) for j in range(n)]
         except MultiUnsupported:
             pass
@@ -171,7 +171,7 @@ def embedding_loss_from_labels_multi(embeddings, labels, criterion, offsets_list
     if _fused(criterion):
         specs = [_spec(offs, [1.0] * len(offs), mode) for offs in offsets_list]
         try:
-            out = MultiLabelsAffinityMSE.apply(specs, sources, _FLAGS_2D, bool(need_affs), weight_tables, None, *embeddings)
+            out = MultiLabelsAffinityMSE.apply(specs, sources, _FLAGS_2D, bool(need_affs), weight_tables, *embeddings)
             return [(out[j], out[n + j], LossList(out[2 * n + j])) for j in range(n)]
         except MultiLabelsUnsupported:
             pass

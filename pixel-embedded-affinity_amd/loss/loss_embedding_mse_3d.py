@@ -69,7 +69,7 @@ def embedding_loss_norm1_multi(embeddings, targets, weightmaps, criterion, affs0
     if getattr(criterion, 'pea_fused', False):
         specs = [_spec([s] * 3, affs0_weight, 1) for s in shifts]
         try:
-            out = MultiAffinityMSE.apply(specs, [(t, w, None) for t, w in zip(targets, weightmaps)], bool(need_affs), None, *embeddings)
+            out = MultiAffinityMSE.apply(specs, [(t, w, None) for t, w in zip(targets, weightmaps)], bool(need_affs), *embeddings)
             return [(out[j], out[n + j] if need_affs else None) for j in range(n)]
         except MultiUnsupported:
             pass
@@ -188,7 +188,7 @@ def embedding_loss_norm1_from_labels_multi(embeddings, labels, criterion, label_
         raise NotImplementedError("the labels-in step fuses WeightedMSE; for another criterion use gen_targets + the tensor API")
     specs = [_spec([s] * 3, affs0_weight, 1) for s in shifts]
     try:
-        out = MultiLabelsAffinityMSE.apply(specs, sources, _FLAGS_3D, bool(need_affs), weight_tables, None, *embeddings)
+        out = MultiLabelsAffinityMSE.apply(specs, sources, _FLAGS_3D, bool(need_affs), weight_tables, *embeddings)
         return [(out[j], out[n + j]) for j in range(n)]
     except MultiLabelsUnsupported:
         pass
