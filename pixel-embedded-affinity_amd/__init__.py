@@ -38,6 +38,10 @@ from .harness.disc import DiscriminativeLoss, discriminative_loss_stats
 from .loss.loss_discriminative import discriminative_loss
 from .harness.dist import DistanceAffinities, distance_affinities
 from .utils import emb2affs, embeddings_ours
+from .harness.segscore import SegmentationScores, segmentation_scores
+from .utils import evaluate, seg_scores
+from .utils.evaluate import AbsDiffFGLabels, BestDice, Dice, DiffFGLabels, FGBGDice, SymmetricBestDice
+from .utils.seg_scores import adapted_rand_error, variation_of_information
 from .harness.handoff import AffsCollector
 from .harness.head_loss import HeadAffinityMSE, head_embedding_loss
 from .harness.train_step import CvpppTrainStep, convert_consistency_flip, label_pyramid, make_optimizer
@@ -70,3 +74,10 @@ __all__ = [
     "embedding2affs_3d", "embedding2affs_3d_l2", "embedding_loss_norm2", "ema_embedding_loss_norm2", "affs_crop_zero_",
     "distance_affinities", "DistanceAffinities", "emb2affs", "embeddings_ours",
 ]
+# The segmentation scores (include/pea_segscore.h) are public attributes of the package like everything above.  They are listed here
+# and not in __all__, whose exact contents tests/test_dist_host.py pins: `from pixel_embedded_affinity_amd import *` does not bring
+# them in, `pea.segmentation_scores` and `from pixel_embedded_affinity_amd import SymmetricBestDice` do.
+SEGSCORE_EXPORTS = (
+    "segmentation_scores", "SegmentationScores", "evaluate", "seg_scores", "DiffFGLabels", "BestDice", "FGBGDice", "Dice",
+    "AbsDiffFGLabels", "SymmetricBestDice", "adapted_rand_error", "variation_of_information",
+)

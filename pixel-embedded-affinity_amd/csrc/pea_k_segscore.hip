@@ -1,0 +1,573 @@
+// pea_k_segscore.hip -- the segmentation scores of the validation loops from one contingency table per image (include/pea_segscore.h):
+// SymmetricBestDice / AbsDiffFGLabels / FGBGDice of utils/evaluate.py and skimage's adapted_rand_error / variation_of_information, which
+// the reference computes with a Python double loop over label pairs and one scipy sparse table per score.  The header states the
+// semantics and the arithmetic; this comment says how the launches are laid out.
+//
+//   k_seg_pairs      streaming over the pixels: the joint histogram n_ij into a per-image open-addressing table keyed by (pred, gt)
+//   k_seg_marginals  over the pair slots: a_i, a'_i and b_j into two tables of the same kind keyed by id; min / max label, N',
+//                    sum n_ij^2, sum n_ij log2 n_ij, the number of pairs
+//   k_seg_dice       over the slots of all three tables: per pair 2 n_ij / (a_i + b_j), its maximum per row and per column (an integer
+//                    max on the f64 bits); per row / column the squares, the n log2 n terms, the foreground counts, the id counts
+//   k_seg_best       over the row / column slots: the sums of the best Dice values; every slot goes back to zero
+//   k_seg_finish     a lane per image: the columns; the per-image words go back to zero
+//
+// The pass over pixels is the segmented reduction of pea_k_disc.hip with a 64-bit key: a WAVE owns 256 consecutive pixels of one image,
+// a lane one quad of four, and the wave PEELS its pairs -- it takes the key of the first lane that still has an open pixel, every lane
+// closes its pixels of that key, the count is a butterfly of popcounts -- so neighbouring pixels, which mostly share their pair, cost
+// one table update per (wave, distinct pair), not one per pixel.  The r-th peeled pair is kept by lane r, and the lanes then claim
+// their slots side by side (one round of probes for the wave's pairs instead of a dependent chain per pair); a wave with more than 64
+// pairs flushes and goes on.  There is no workgroup-side LDS table in front of the global one: at the shapes of the drivers a wave
+// meets two to six pairs, so the four waves of a workgroup would save a handful of atomics per kilobyte of labels read.
+//
+// The tables.  Slot = hash(key) mod capacity, linear probing; the stored key is key + 1, so a zero word is an empty slot and the
+// prepared workspace is all zero.  A slot is claimed with ONE compare-and-swap of the key word (empty -> key); whoever finds the key
+// there, by that swap or by the load before it, adds to the slot's count words with integer atomics.  No lane ever waits for another
+// lane: a probe that meets a foreign key moves on, and EVERY probe sequence ends after `capacity` slots, so a full table drops the
+// pair (counted in n_overflow) and the kernel ends.  Lookups in later launches are plain loads behind the kernel boundary.
+// Slot placement depends on arrival order; nothing that is summed in floating point runs over slots (header: Arithmetic).
+#include "../../include/pea_segscore.h"
+#include "pea_host.h"
+#include "pea_quad.h"
+
+#pragma clang fp contract(off)
+
+using namespace pea;
+
+namespace {
+
+constexpr int kWaveRun = 64 * kQuad;            // pixels of one image per wave: one quad per lane
+constexpr int kRun = kWaveRun * (kBlock / 64);  // .. per workgroup of the pass over pixels
+constexpr unsigned kSegMagic = 0x50454153u;     // "PEAS"
+constexpr int kHdrWords = 8;                    // u64 words: [0] magic
+constexpr int kImgWords = 32;                   // per image, below
+constexpr int kPairWords = 2;                   // per pair slot: key + 1, n_ij
+constexpr int kMargWords = 4;                   // per row slot: id + 1, a_i, a'_i, best Dice bits; per column slot: id + 1, b_j, best Dice bits, -
+constexpr u64 kMaxCapacity = 1ull << 31;
+constexpr double kFx = 4294967296.0;            // 2^32: the fixed-point sums carry 32 fractional bits
+
+// the per-image words.  The four extrema are kept as (label + 1) and (2^31 - label) under an integer max, so that zero means "none yet"
+enum {
+  I_BAD = 0, I_OVF, I_MAXP, I_MINP, I_MAXG, I_MING, I_N2, I_NP, I_PAIRS, I_NPRED, I_NGT, I_A2, I_B2, I_FGP, I_FGG, I_FGB,
+  I_NLN = 16,  // fixed point, two words each (fraction digits, whole part): sum n_ij log2 n_ij
+  I_ALA = 18,  // sum a'_i log2 a'_i
+  I_BLB = 20,  // sum b_j log2 b_j
+  I_BDR = 22,  // sum of the rows' best Dice
+  I_BDC = 24,  // sum of the columns' best Dice
+};
+static_assert(I_BDC + 2 <= kImgWords, "the per-image words");
+
+struct Tables {
+  u64* hdr;
+  u64* img;    // [B][kImgWords]
+  u64* pairs;  // [B][cap][kPairWords]
+  u64* rows;   // [B][cap][kMargWords]
+  u64* cols;   // [B][cap][kMargWords]
+  u64 cap;
+  int B;
+};
+
+inline size_t tables_layout(const PeaSegDesc* d, void* base, Tables* t) {
+  const size_t B = (size_t)d->B, cap = (size_t)d->capacity;
+  if (t) {
+    t->hdr = (u64*)base;
+    t->img = t->hdr + kHdrWords;
+    t->pairs = t->img + kImgWords * B;
+    t->rows = t->pairs + B * cap * kPairWords;
+    t->cols = t->rows + B * cap * kMargWords;
+    t->cap = cap;
+    t->B = d->B;
+  }
+  return 8 * (kHdrWords + kImgWords * B + B * cap * (kPairWords + 2 * kMargWords));
+}
+
+#define PEA_LD_AGENT(p) __hip_atomic_load((p), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)
+#define PEA_ATOM_MAX(p, v) (void)__hip_atomic_fetch_max((p), (v), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)
+
+__device__ __forceinline__ u64 mix64(u64 x) {
+  x ^= x >> 33; x *= 0xff51afd7ed558ccdull;
+  x ^= x >> 33; x *= 0xc4ceb9fe1a85ec53ull;
+  x ^= x >> 33;
+  return x;
+}
+
+// the slot of `key1` (a stored key: never 0) in a table of `cap` slots of W words, claiming an empty one; -1 after cap probes
+template <int W>
+__device__ __forceinline__ long long slot_claim(u64* __restrict__ tab, u64 cap, u64 key1) {
+  u64 s = mix64(key1) & (cap - 1);
+  for (u64 i = 0; i < cap; ++i) {
+    u64* kp = tab + s * W;
+    u64 cur = PEA_LD_AGENT(kp);
+    if (cur == 0) {
+      u64 expect = 0;
+      if (__hip_atomic_compare_exchange_strong(kp, &expect, key1, __ATOMIC_RELAXED, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) return (long long)s;
+      cur = expect;  // another lane took the slot: for the same key, or this probe moves on
+    }
+    if (cur == key1) return (long long)s;
+    s = (s + 1) & (cap - 1);
+  }
+  return -1;
+}
+// the slot of `key1` in a table that an EARLIER launch filled; -1: not there
+template <int W>
+__device__ __forceinline__ long long slot_find(const u64* __restrict__ tab, u64 cap, u64 key1) {
+  u64 s = mix64(key1) & (cap - 1);
+  for (u64 i = 0; i < cap; ++i) {
+    const u64 cur = tab[s * W];
+    if (cur == key1) return (long long)s;
+    if (cur == 0) return -1;
+    s = (s + 1) & (cap - 1);
+  }
+  return -1;
+}
+
+__device__ __forceinline__ u64 wsum(u64 v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  return v;
+}
+__device__ __forceinline__ u64 wmax(u64 v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    const u64 w = __shfl_xor(v, o, 64);
+    v = w > v ? w : v;
+  }
+  return v;
+}
+// a lane's wave total into a per-image word (all 64 lanes call)
+__device__ __forceinline__ void wave_add(u64* p, u64 v, int lane) {
+  v = wsum(v);
+  if (lane == 0 && v) PEA_ATOM_ADD(p, v);
+}
+__device__ __forceinline__ void wave_max(u64* p, u64 v, int lane) {
+  v = wmax(v);
+  if (lane == 0 && v) PEA_ATOM_MAX(p, v);
+}
+// v >= 0, finite, below 2^63 -> fixed point with 32 fractional bits, truncated: lo = the fraction's digits, hi = the whole part
+__device__ __forceinline__ void fx_split(double v, u64& lo, u64& hi) {
+  hi = (u64)v;
+  lo = (u64)((v - (double)hi) * kFx);
+}
+__device__ __forceinline__ void wave_add_fx(u64* p, double v, int lane) {
+  u64 lo, hi;
+  fx_split(v, lo, hi);
+  wave_add(p, lo, lane);
+  wave_add(p + 1, hi, lane);
+}
+__device__ __forceinline__ double nlog2n(u64 n) { return n > 1 ? (double)n * log2((double)n) : 0.0; }
+// the two words of a fixed-point sum -> its value; and the difference p - q of two sums, taken on the integers
+__device__ __forceinline__ double fx_value(const u64* p) {
+  const u64 hi = p[1] + (p[0] >> 32), lo = p[0] & 0xffffffffull;
+  return (double)hi + (double)lo / kFx;
+}
+__device__ __forceinline__ double fx_diff(const u64* p, const u64* q) {
+  const long long hp = (long long)(p[1] + (p[0] >> 32)), hq = (long long)(q[1] + (q[0] >> 32));
+  const long long lp = (long long)(p[0] & 0xffffffffull), lq = (long long)(q[0] & 0xffffffffull);
+  return (double)(hp - hq) + (double)(lp - lq) / kFx;
+}
+__device__ __forceinline__ long long label_min(u64 w) { return w ? (long long)0x80000000ll - (long long)w : 0; }
+__device__ __forceinline__ long long label_max(u64 w) { return w ? (long long)w - 1 : 0; }
+
+__device__ __forceinline__ int quad_nv(size_t i0, size_t S) { return i0 >= S ? 0 : (S - i0 >= (size_t)kQuad ? kQuad : (int)(S - i0)); }
+
+__device__ __forceinline__ void ld_labels(const int32_t* __restrict__ p, int nv, int (&l)[kQuad]) {
+  if (nv == kQuad && ((uintptr_t)p & 15) == 0) {
+    const iquad_t v = *(const iquad_t*)p;
+    l[0] = v.x; l[1] = v.y; l[2] = v.z; l[3] = v.w;
+  } else {
+#pragma unroll
+    for (int i = 0; i < kQuad; ++i) l[i] = i < nv ? p[i] : -1;
+  }
+}
+
+// ---- 1: the joint histogram -------------------------------------------------------------------------------------------------------------
+// pred / gt: image 0 of the launch; img / pairs: the words and the table of image 0 of the launch (pea_seg_table launches one image)
+__global__ __launch_bounds__(kBlock) void k_seg_pairs(const size_t S, const unsigned chunks, const u64 cap, const int32_t* __restrict__ pred,
+                                                      const int32_t* __restrict__ gt, u64* __restrict__ img, u64* __restrict__ pairs) {
+  const unsigned chunk = blockIdx.x % chunks;
+  const size_t b = blockIdx.x / chunks;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const size_t w0 = (size_t)chunk * kRun + (size_t)wave * kWaveRun;
+  if (w0 >= S) return;  // the whole wave; nothing below meets another wave
+  const size_t i0 = w0 + (size_t)lane * kQuad;
+  const int nv = quad_nv(i0, S);
+  int lp[kQuad], lg[kQuad];
+  ld_labels(pred + b * S + (nv ? i0 : 0), nv, lp);
+  ld_labels(gt + b * S + (nv ? i0 : 0), nv, lg);
+  u64 key[kQuad];
+  unsigned open = 0;
+  u64 bad = 0;
+#pragma unroll
+  for (int i = 0; i < kQuad; ++i) {
+    key[i] = 0;
+    if (i < nv) {
+      bad += (u64)(lp[i] < 0) + (u64)(lg[i] < 0);
+      if (lp[i] >= 0 && lg[i] >= 0) {
+        key[i] = (((u64)(unsigned)lp[i] << 32) | (u64)(unsigned)lg[i]) + 1;
+        open |= 1u << i;
+      }
+    }
+  }
+  u64* __restrict__ tab = pairs + b * cap * kPairWords;
+  u64 mykey = 0, mycnt = 0, dropped = 0;
+  const auto flush = [&]() {  // every lane that holds a peeled pair claims its slot and adds its count
+    if (mykey) {
+      const long long s = slot_claim<kPairWords>(tab, cap, mykey);
+      if (s >= 0) PEA_ATOM_ADD(tab + s * kPairWords + 1, mycnt);
+      else dropped += mycnt;
+    }
+    mykey = 0;
+  };
+  int r = 0;
+  for (;;) {
+    const unsigned long long any = __ballot(open != 0);
+    if (!any) break;
+    u64 cand = 0;
+#pragma unroll
+    for (int i = kQuad - 1; i >= 0; --i)
+      if ((open >> i) & 1u) cand = key[i];
+    const u64 cur = __shfl(cand, __ffsll(any) - 1, 64);
+    unsigned mm = 0;
+#pragma unroll
+    for (int i = 0; i < kQuad; ++i)
+      if (((open >> i) & 1u) && key[i] == cur) mm |= 1u << i;
+    open &= ~mm;
+    const u64 cnt = wsum((u64)__popc(mm));
+    if (lane == r) { mykey = cur; mycnt = cnt; }
+    if (++r == 64) { flush(); r = 0; }
+  }
+  flush();
+  u64* w = img + b * kImgWords;
+  wave_add(w + I_BAD, bad, lane);
+  wave_add(w + I_OVF, dropped, lane);
+}
+
+// the wave's 64 consecutive slots lie in one image (capacity is a multiple of 64): -> false past the last image
+__device__ __forceinline__ bool slot_of_lane(const Tables& T, size_t* b, size_t* s) {
+  const size_t gs = (size_t)blockIdx.x * kBlock + threadIdx.x;
+  *b = gs / T.cap;
+  *s = gs - *b * T.cap;
+  return *b < (size_t)T.B;
+}
+
+// ---- 2: marginals, extrema and the sums over pairs -----------------------------------------------------------------------------------------
+__global__ __launch_bounds__(kBlock) void k_seg_marginals(const Tables T) {
+  size_t b, s;
+  if (!slot_of_lane(T, &b, &s)) return;
+  const int lane = threadIdx.x & 63;
+  const u64* ps = T.pairs + (b * T.cap + s) * kPairWords;
+  const u64 key = ps[0], n = ps[1];
+  u64 one = 0, n2 = 0, np = 0, lo = 0, hi = 0, mxp = 0, mnp = 0, mxg = 0, mng = 0, ovf = 0;
+  if (key) {
+    const u64 p = (key - 1) >> 32, g = (key - 1) & 0xffffffffull;
+    one = 1;
+    mxp = p + 1; mnp = 0x80000000ull - p;
+    mxg = g + 1; mng = 0x80000000ull - g;
+    u64* rows = T.rows + b * T.cap * kMargWords;
+    u64* cols = T.cols + b * T.cap * kMargWords;
+    const long long rs = slot_claim<kMargWords>(rows, T.cap, p + 1);
+    const long long cs = slot_claim<kMargWords>(cols, T.cap, g + 1);
+    if (rs >= 0) {
+      PEA_ATOM_ADD(rows + rs * kMargWords + 1, n);
+      if (g != 0) PEA_ATOM_ADD(rows + rs * kMargWords + 2, n);
+    }
+    if (cs >= 0) PEA_ATOM_ADD(cols + cs * kMargWords + 1, n);
+    if (rs < 0 || cs < 0) ovf = n;  // (cannot happen: there are no more ids than pairs)
+    if (g != 0) {
+      n2 = n * n;
+      np = n;
+      fx_split(nlog2n(n), lo, hi);
+    }
+  }
+  u64* w = T.img + b * kImgWords;
+  wave_add(w + I_PAIRS, one, lane);
+  wave_add(w + I_N2, n2, lane);
+  wave_add(w + I_NP, np, lane);
+  wave_add(w + I_NLN, lo, lane);
+  wave_add(w + I_NLN + 1, hi, lane);
+  wave_add(w + I_OVF, ovf, lane);
+  wave_max(w + I_MAXP, mxp, lane);
+  wave_max(w + I_MINP, mnp, lane);
+  wave_max(w + I_MAXG, mxg, lane);
+  wave_max(w + I_MING, mng, lane);
+}
+
+// ---- 3: the Dice of every pair, the sums over rows and columns ----------------------------------------------------------------------------
+__global__ __launch_bounds__(kBlock) void k_seg_dice(const Tables T) {
+  size_t b, s;
+  if (!slot_of_lane(T, &b, &s)) return;
+  const int lane = threadIdx.x & 63;
+  u64* w = T.img + b * kImgWords;
+  const u64 minP = (u64)label_min(w[I_MINP]), minG = (u64)label_min(w[I_MING]);
+  u64* rows = T.rows + b * T.cap * kMargWords;
+  u64* cols = T.cols + b * T.cap * kMargWords;
+  u64 fgb = 0;
+  {
+    const u64* ps = T.pairs + (b * T.cap + s) * kPairWords;
+    const u64 key = ps[0], n = ps[1];
+    if (key) {
+      const u64 p = (key - 1) >> 32, g = (key - 1) & 0xffffffffull;
+      if (p > minP && g > minG) {
+        fgb = n;
+        const long long rs = slot_find<kMargWords>(rows, T.cap, p + 1);
+        const long long cs = slot_find<kMargWords>(cols, T.cap, g + 1);
+        if (rs >= 0 && cs >= 0) {
+          const u64 a = rows[rs * kMargWords + 1], bj = cols[cs * kMargWords + 1];
+          const double dice = 2.0 * (double)n / (double)(a + bj);
+          const u64 bits = __builtin_bit_cast(u64, dice);  // positive: the bit patterns order like the values
+          PEA_ATOM_MAX(rows + rs * kMargWords + 3, bits);
+          PEA_ATOM_MAX(cols + cs * kMargWords + 2, bits);
+        }
+      }
+    }
+  }
+  u64 npred = 0, a2 = 0, fgp = 0, alo = 0, ahi = 0;
+  {
+    const u64* rw = rows + s * kMargWords;
+    const u64 key = rw[0];
+    if (key) {
+      const u64 a = rw[1], ap = rw[2];
+      npred = 1;
+      a2 = ap * ap;
+      fx_split(nlog2n(ap), alo, ahi);
+      if (key - 1 != minP) fgp = a;
+    }
+  }
+  u64 ngt = 0, b2 = 0, fgg = 0, blo = 0, bhi = 0;
+  {
+    const u64* cw = cols + s * kMargWords;
+    const u64 key = cw[0];
+    if (key) {
+      const u64 bj = cw[1];
+      ngt = 1;
+      if (key - 1 != 0) {
+        b2 = bj * bj;
+        fx_split(nlog2n(bj), blo, bhi);
+      }
+      if (key - 1 != minG) fgg = bj;
+    }
+  }
+  wave_add(w + I_FGB, fgb, lane);
+  wave_add(w + I_NPRED, npred, lane);
+  wave_add(w + I_A2, a2, lane);
+  wave_add(w + I_FGP, fgp, lane);
+  wave_add(w + I_ALA, alo, lane);
+  wave_add(w + I_ALA + 1, ahi, lane);
+  wave_add(w + I_NGT, ngt, lane);
+  wave_add(w + I_B2, b2, lane);
+  wave_add(w + I_FGG, fgg, lane);
+  wave_add(w + I_BLB, blo, lane);
+  wave_add(w + I_BLB + 1, bhi, lane);
+}
+
+// ---- 4: the sums of the best Dice values; the slots go back to zero -------------------------------------------------------------------------
+__global__ __launch_bounds__(kBlock) void k_seg_best(const Tables T) {
+  size_t b, s;
+  if (!slot_of_lane(T, &b, &s)) return;
+  const int lane = threadIdx.x & 63;
+  u64* w = T.img + b * kImgWords;
+  const u64 minP = (u64)label_min(w[I_MINP]), minG = (u64)label_min(w[I_MING]);
+  u64* ps = T.pairs + (b * T.cap + s) * kPairWords;
+  u64* rw = T.rows + (b * T.cap + s) * kMargWords;
+  u64* cw = T.cols + (b * T.cap + s) * kMargWords;
+  double dr = 0.0, dc = 0.0;
+  if (rw[0] && rw[0] - 1 > minP) dr = __builtin_bit_cast(double, rw[3]);
+  if (cw[0] && cw[0] - 1 > minG) dc = __builtin_bit_cast(double, cw[2]);
+  if (ps[0]) { ps[0] = 0; ps[1] = 0; }
+  if (rw[0]) { rw[0] = 0; rw[1] = 0; rw[2] = 0; rw[3] = 0; }
+  if (cw[0]) { cw[0] = 0; cw[1] = 0; cw[2] = 0; }
+  wave_add_fx(w + I_BDR, dr, lane);
+  wave_add_fx(w + I_BDC, dc, lane);
+}
+
+// ---- 5: the columns -------------------------------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(64) void k_seg_finish(const Tables T, double* __restrict__ out) {
+  const int b = blockIdx.x * 64 + threadIdx.x;
+  if (b >= T.B) return;
+  const bool good = *(const unsigned*)T.hdr == kSegMagic;
+  u64* w = T.img + (size_t)b * kImgWords;
+  u64 v[kImgWords];
+  for (int i = 0; i < kImgWords; ++i) {
+    v[i] = w[i];
+    w[i] = 0;
+  }
+  double* o = out + (size_t)b * PEA_SEG_COLS;
+  const double qnan = __builtin_nan("");
+  if (!good) {
+    for (int i = 0; i < PEA_SEG_COLS; ++i) o[i] = qnan;
+    return;
+  }
+  o[PEA_SEG_N_OVERFLOW] = (double)v[I_OVF];
+  o[PEA_SEG_N_BAD] = (double)v[I_BAD];
+  if (v[I_OVF] || v[I_BAD]) {
+    for (int i = 2; i < PEA_SEG_COLS; ++i) o[i] = qnan;
+    return;
+  }
+  const long long spanP = label_max(v[I_MAXP]) - label_min(v[I_MINP]), spanG = label_max(v[I_MAXG]) - label_min(v[I_MING]);
+  const double bd = spanP > 0 ? fx_value(v + I_BDR) / (double)spanP : 0.0;
+  const double bdr = spanG > 0 ? fx_value(v + I_BDC) / (double)spanG : 0.0;
+  o[PEA_SEG_BEST_DICE] = bd;
+  o[PEA_SEG_BEST_DICE_REV] = bdr;
+  o[PEA_SEG_SBD] = bd < bdr ? bd : bdr;
+  o[PEA_SEG_DIFF_FG] = (double)(spanP - spanG);
+  const u64 fgden = v[I_FGP] + v[I_FGG];
+  o[PEA_SEG_FGBG_DICE] = fgden ? 2.0 * (double)v[I_FGB] / (double)fgden : 0.0;
+  const u64 np = v[I_NP];
+  double split = 0.0, merge = 0.0;
+  if (np) {  // a conditional entropy is never negative: a difference that truncation made negative is 0
+    const double ds = fx_diff(v + I_BLB, v + I_NLN), dm = fx_diff(v + I_ALA, v + I_NLN);
+    split = (ds > 0.0 ? ds : 0.0) / (double)np;
+    merge = (dm > 0.0 ? dm : 0.0) / (double)np;
+  }
+  o[PEA_SEG_VOI_SPLIT] = split;
+  o[PEA_SEG_VOI_MERGE] = merge;
+  const double P2 = (double)(v[I_N2] - np), A2 = (double)(v[I_A2] - np), B2 = (double)(v[I_B2] - np);
+  o[PEA_SEG_ARE] = 1.0 - P2 / (0.5 * A2 + 0.5 * B2);
+  o[PEA_SEG_ARE_PRECISION] = P2 / A2;
+  o[PEA_SEG_ARE_RECALL] = P2 / B2;
+  o[PEA_SEG_SUM_NIJ2] = (double)v[I_N2];
+  o[PEA_SEG_SUM_AI2] = (double)v[I_A2];
+  o[PEA_SEG_SUM_BJ2] = (double)v[I_B2];
+  o[PEA_SEG_N_PRIME] = (double)np;
+  o[PEA_SEG_N_PRED_IDS] = (double)v[I_NPRED];
+  o[PEA_SEG_N_GT_IDS] = (double)v[I_NGT];
+  o[PEA_SEG_N_PAIRS] = (double)v[I_PAIRS];
+}
+
+// ---- pea_seg_table: the triples of one image (its table is image 0 of the workspace) -------------------------------------------------------
+__global__ __launch_bounds__(kBlock) void k_seg_compact(const u64 cap, u64* __restrict__ img, u64* __restrict__ pairs, int32_t* __restrict__ pred_ids,
+                                                        int32_t* __restrict__ gt_ids, int64_t* __restrict__ counts, const u64 max_triples) {
+  const size_t s = (size_t)blockIdx.x * kBlock + threadIdx.x;
+  if (s >= cap) return;
+  u64* ps = pairs + s * kPairWords;
+  const u64 key = ps[0], n = ps[1];
+  if (!key) return;
+  ps[0] = 0;
+  ps[1] = 0;
+  const u64 at = __hip_atomic_fetch_add(img + I_PAIRS, 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  if (at < max_triples) {
+    pred_ids[at] = (int32_t)((key - 1) >> 32);
+    gt_ids[at] = (int32_t)((key - 1) & 0xffffffffull);
+    counts[at] = (int64_t)n;
+  }
+}
+__global__ __launch_bounds__(64) void k_seg_table_finish(const u64* __restrict__ hdr, u64* __restrict__ img, int64_t* __restrict__ n_out) {
+  if (threadIdx.x != 0) return;
+  const bool good = *(const unsigned*)hdr == kSegMagic;
+  n_out[0] = good ? (int64_t)img[I_PAIRS] : -1;
+  n_out[1] = good ? (int64_t)img[I_OVF] : -1;
+  n_out[2] = good ? (int64_t)img[I_BAD] : -1;
+  img[I_PAIRS] = 0;
+  img[I_OVF] = 0;
+  img[I_BAD] = 0;
+}
+
+// pea_seg_workspace_init: all zero but for the magic word
+__global__ __launch_bounds__(kBlock) void k_seg_init(u64* __restrict__ w, size_t words) {
+  for (size_t i = (size_t)blockIdx.x * kBlock + threadIdx.x; i < words; i += (size_t)gridDim.x * kBlock) w[i] = i == 0 ? (u64)kSegMagic : 0ull;
+}
+
+inline void launch_init(void* ws, size_t bytes, hipStream_t s) {
+  const size_t words = bytes / 8;
+  const size_t g = (words + kBlock - 1) / kBlock;
+  hipLaunchKernelGGL(k_seg_init, dim3((unsigned)(g < 1024 ? g : 1024)), dim3(kBlock), 0, s, (u64*)ws, words);
+}
+
+// workgroups of the pass over `images` images' pixels and of a pass over their slots; false: a grid exceeds 2^31 - 1
+inline bool seg_grids(const PeaSegDesc* d, uint64_t images, unsigned* chunks, unsigned* pixel_groups, unsigned* slot_groups) {
+  const uint64_t c = ((uint64_t)d->S + kRun - 1) / kRun;
+  const uint64_t g = c * images, sg = images * ((uint64_t)d->capacity / kBlock + ((uint64_t)d->capacity % kBlock ? 1 : 0));
+  if (g > 0x7fffffffULL || sg > 0x7fffffffULL) return false;
+  *chunks = (unsigned)c;
+  *pixel_groups = (unsigned)g;
+  *slot_groups = (unsigned)((images * (uint64_t)d->capacity + kBlock - 1) / kBlock);
+  return true;
+}
+
+}  // namespace
+
+extern "C" int pea_seg_validate(const PeaSegDesc* d) {
+  if (!d) return PEA_E_NULL;
+  if (d->B < 1 || d->S < 1) return PEA_E_DESC;
+  if (d->capacity < PEA_SEG_MIN_CAPACITY || (uint64_t)d->capacity > kMaxCapacity || (d->capacity & (d->capacity - 1))) return PEA_E_DESC;
+  if (d->flags) return PEA_E_DESC;
+  if (d->S > 0x7fffffffLL) return PEA_E_UNSUPPORTED;
+  return PEA_OK;
+}
+
+extern "C" size_t pea_seg_workspace_bytes(const PeaSegDesc* d) { return pea_seg_validate(d) ? 0 : tables_layout(d, nullptr, nullptr); }
+
+extern "C" int pea_seg_workspace_init(void* workspace, size_t bytes, void* stream) {
+  if (!workspace) return PEA_E_NULL;
+  if (misaligned(workspace, 8)) return PEA_E_ALIGN;
+  if (bytes < 8 * kHdrWords || bytes % 8) return PEA_E_WORKSPACE;
+  launch_init(workspace, bytes, (hipStream_t)stream);
+  return hip_rc();
+}
+
+extern "C" int pea_seg_scores(const PeaSegDesc* d, const int32_t* pred, const int32_t* gt, double* out, void* workspace, size_t workspace_bytes,
+                              void* stream) {
+  const int vrc = pea_seg_validate(d);
+  if (vrc) return vrc;
+  if (!pred || !gt || !out) return PEA_E_NULL;
+  if (misaligned(pred, 4) || misaligned(gt, 4) || misaligned(out, 8) || misaligned(workspace, 8)) return PEA_E_ALIGN;
+  const size_t need = pea_seg_workspace_bytes(d);
+  if (!workspace || workspace_bytes < need) return PEA_E_WORKSPACE;
+  unsigned chunks, pgroups, sgroups;
+  if (!seg_grids(d, (uint64_t)d->B, &chunks, &pgroups, &sgroups)) return PEA_E_UNSUPPORTED;
+
+  hipStream_t s = (hipStream_t)stream;
+  Tables T;
+  tables_layout(d, workspace, &T);
+  int rc = [&]() {
+    hipLaunchKernelGGL(k_seg_pairs, dim3(pgroups), dim3(kBlock), 0, s, (size_t)d->S, chunks, T.cap, pred, gt, T.img, T.pairs);
+    int r = hip_rc();
+    if (r) return r;
+    hipLaunchKernelGGL(k_seg_marginals, dim3(sgroups), dim3(kBlock), 0, s, T);
+    if ((r = hip_rc())) return r;
+    hipLaunchKernelGGL(k_seg_dice, dim3(sgroups), dim3(kBlock), 0, s, T);
+    if ((r = hip_rc())) return r;
+    hipLaunchKernelGGL(k_seg_best, dim3(sgroups), dim3(kBlock), 0, s, T);
+    if ((r = hip_rc())) return r;
+    hipLaunchKernelGGL(k_seg_finish, dim3((unsigned)((d->B + 63) / 64)), dim3(64), 0, s, T, out);
+    return hip_rc();
+  }();
+  if (rc) {  // counts may be queued without what zeroes them: prepare the block again (the contract of pea_seg_workspace_init)
+    launch_init(workspace, need, s);
+    (void)hipGetLastError();
+  }
+  return rc;
+}
+
+extern "C" int pea_seg_table(const PeaSegDesc* d, const int32_t* pred, const int32_t* gt, int32_t b, int32_t* pred_ids, int32_t* gt_ids,
+                             int64_t* counts, int64_t* n_out, int64_t max_triples, void* workspace, size_t workspace_bytes, void* stream) {
+  const int vrc = pea_seg_validate(d);
+  if (vrc) return vrc;
+  if (b < 0 || b >= d->B || max_triples < 1) return PEA_E_DESC;
+  if (!pred || !gt || !pred_ids || !gt_ids || !counts || !n_out) return PEA_E_NULL;
+  if (misaligned(pred, 4) || misaligned(gt, 4) || misaligned(pred_ids, 4) || misaligned(gt_ids, 4) || misaligned(counts, 8) ||
+      misaligned(n_out, 8) || misaligned(workspace, 8))
+    return PEA_E_ALIGN;
+  const size_t need = pea_seg_workspace_bytes(d);
+  if (!workspace || workspace_bytes < need) return PEA_E_WORKSPACE;
+  unsigned chunks, pgroups, sgroups;
+  if (!seg_grids(d, 1, &chunks, &pgroups, &sgroups)) return PEA_E_UNSUPPORTED;
+
+  hipStream_t s = (hipStream_t)stream;
+  Tables T;
+  tables_layout(d, workspace, &T);
+  const size_t off = (size_t)b * (size_t)d->S;
+  int rc = [&]() {
+    hipLaunchKernelGGL(k_seg_pairs, dim3(pgroups), dim3(kBlock), 0, s, (size_t)d->S, chunks, T.cap, pred + off, gt + off, T.img, T.pairs);
+    int r = hip_rc();
+    if (r) return r;
+    hipLaunchKernelGGL(k_seg_compact, dim3(sgroups), dim3(kBlock), 0, s, T.cap, T.img, T.pairs, pred_ids, gt_ids, counts, (u64)max_triples);
+    if ((r = hip_rc())) return r;
+    hipLaunchKernelGGL(k_seg_table_finish, dim3(1), dim3(64), 0, s, (const u64*)T.hdr, T.img, n_out);
+    return hip_rc();
+  }();
+  if (rc) {
+    launch_init(workspace, need, s);
+    (void)hipGetLastError();
+  }
+  return rc;
+}
