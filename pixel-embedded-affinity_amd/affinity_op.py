@@ -222,26 +222,37 @@ def _stream():
 
 
 _WS = {}
+_RETIRED = []
 _STATE_BYTES = [0]
+
+
+def stream_workspace(family, dev, nb, init, name):
+    """the workspace block of `family` (any hashable: a name, or a name and a count) for the CURRENT stream of `dev`, at least nb
+    bytes: one block per (family, device, stream), allocated and prepared once with init(ptr, bytes, stream) -- `name` is what an
+    error calls it -- on that stream, then reused by every call: each call leaves its block ready for the next one, and calls on one
+    stream cannot overlap.  A call that needs more gets a larger block; the smaller one is retired, not freed, because a captured
+    graph may still replay on it."""
+    idx = dev.index if dev.index is not None else torch.cuda.current_device()
+    raw = _RAW_STREAM(idx) if _RAW_STREAM is not None else torch.cuda.current_stream(dev).cuda_stream
+    key = (family, idx, raw)
+    w = _WS.get(key)
+    if w is None or w.numel() * 4 < nb:
+        if w is not None:
+            _RETIRED.append(w)
+        w = torch.empty(nb // 4, dtype=torch.float32, device=dev)
+        _lib.check(init(ctypes.c_void_p(w.data_ptr()), nb, ctypes.c_void_p(raw)), name)
+        _WS[key] = w
+    return w
 
 
 def workspace(dev, desc, nstates=1):
     """(tensor, bytes): the loss-state block(s) of the training forward for the CURRENT stream of `dev` (include/pea.h,
-    pea_workspace_bytes): allocated and initialised once per (device, stream), then reused by every call -- each call leaves it
-    ready for the next one, and calls on one stream cannot overlap.  ~16 KB per state."""
+    pea_workspace_bytes), ~16 KB per state: the stream_workspace of ("loss", nstates)."""
     L = _lib.lib()
     if not _STATE_BYTES[0]:
         _STATE_BYTES[0] = int(L.pea_workspace_bytes(ctypes.byref(desc)))
-    idx = dev.index if dev.index is not None else torch.cuda.current_device()
-    raw = _RAW_STREAM(idx) if _RAW_STREAM is not None else torch.cuda.current_stream(dev).cuda_stream
-    key = (idx, raw, nstates)
-    w = _WS.get(key)
     nb = _STATE_BYTES[0] * nstates
-    if w is None:
-        w = torch.empty(nb // 4, dtype=torch.float32, device=dev)
-        _lib.check(L.pea_workspace_init(ctypes.c_void_p(w.data_ptr()), nb, ctypes.c_void_p(raw)), "pea_workspace_init")
-        _WS[key] = w
-    return w, nb
+    return stream_workspace(("loss", nstates), dev, nb, L.pea_workspace_init, "pea_workspace_init"), nb
 
 
 class _on_device(object):

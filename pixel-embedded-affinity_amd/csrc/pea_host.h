@@ -15,6 +15,9 @@
 //   pea_k_head.hip     the embedding head (pea_head.h) and target generation (pea_targets.h)
 //   pea_k_crop.hip     the 3D border rule on an activated map (include/pea_crop.h): 0 where the pair does not exist, one launch
 //   pea_k_dist.hip     distance-form affinities of the raw embedding (include/pea_dist.h): forward and vjp, gather form
+//   pea_k_metrics.hip  the validation pixel metrics (include/pea_metrics.h), pea_k_fgmask.hip the foreground-mask loss and mask
+//                      (include/pea_fgmask.h), pea_k_disc.hip the discriminative loss (include/pea_disc.h), pea_k_segscore.hip the
+//                      segmentation scores (include/pea_segscore.h): the streaming reductions over a flat pixel range
 // Each kernel file exports a few plain functions (declared here) that pick the instantiation and launch it; a function returns
 // false when its family has no kernel for the descriptor and the caller tries the next one.  No device code crosses a file.
 // pea_dispatch.h holds what the launchers share to get from run-time facts (storage dtype, D, border, mask type, ..) to template
@@ -23,6 +26,8 @@
 // the LDS slot of a neighbour, the LDS-DMA issue of a plane and the load-counted hand-off (s_waitcnt vmcnt(N); s_barrier).
 // pea_epilogue.h holds what every training forward ends with: the loss term of a pair (scalar and quad form), wave_sum63 and the
 // workgroup's tail into the loss state; pea_gather.h and the LDS-staged families include it.
+// pea_stream.h (on pea_quad.h: a lane's quad loads and stores) holds what the four streaming reductions are made of: the lane-run and
+// wave-run walks, the tail quad, wave_sum / wave_max / block_sums, the peel, the cropped cursor, the table workspace, stream_grid.
 #pragma once
 #include <stdint.h>
 #include <stdlib.h>

@@ -31,7 +31,7 @@
 // per-cluster launches by their chain of dependent steps in one workgroup.
 #include "../../include/pea_disc.h"
 #include "pea_dispatch.h"
-#include "pea_quad.h"
+#include "pea_stream.h"
 
 #pragma clang fp contract(off)
 
@@ -40,14 +40,11 @@ using namespace pea;
 namespace {
 
 constexpr int kCh = 4;                                // channels in flight per lane: independent loads and butterflies
-constexpr int kWaveRun = 64 * kQuad;                  // pixels of one image per wave: one quad per lane
-constexpr int kRun = kWaveRun * (kBlock / 64);        // .. per workgroup of the two reducing passes
-constexpr int kBwdRun = kBlock * kQuad;               // pixels of one image per workgroup of the backward
 constexpr int kClBlock = 1024;                        // lanes of the two per-cluster launches
 constexpr int kClWaves = kClBlock / 64;
 constexpr unsigned kDiscMagic = 0x50454144u;          // "PEAD"
 constexpr unsigned kKnownFlags = PEA_DISC_BACKGROUND | PEA_DISC_NEED_GRAD;
-constexpr int kHdrWords = 8;                          // u64 words: [0] magic, [1] n_bad
+constexpr int kHdrWords = kTableHdrWords;             // u64 words: [0] magic, [1] n_bad
 constexpr int kImgWords = 4;                          // per image: three digit words of sum w_c h_p^2, flags
 constexpr int kRowHead = 2;                           // per (image, id): [0] count, [1] flags, then three digit words per channel
 static_assert(PEA_DISC_MAX_IDS % kClBlock == 0 && PEA_DISC_MAX_D == 64, "the compaction's chunks; one lane per channel");
@@ -75,7 +72,6 @@ struct DiscK {
   float dv, dd2, alpha, beta, gamma;  // dd2 = 2 delta_d
 };
 
-inline size_t al8(size_t x) { return (x + 7) & ~(size_t)7; }
 inline size_t tables_layout(const PeaDiscDesc* d, void* base, Tables* t) {
   const size_t R = kRowHead + 3 * (size_t)d->D;
   if (t) {
@@ -103,34 +99,21 @@ inline size_t ctx_layout(const PeaDiscDesc* d, void* base, Ctx* c) {
   return o;
 }
 
+// wave_sum(float) of pea_stream.h written out for k_disc_pull, which came out 0.8 % slower behind the template (profiles/README.md)
 __device__ __forceinline__ float bfly(float v) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
   return v;
 }
-template <int N>
-__device__ __forceinline__ void bfly(float (&v)[N]) {  // N butterflies side by side, each in the order of bfly(float)
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1)
-#pragma unroll
-    for (int u = 0; u < N; ++u) v[u] += __shfl_xor(v[u], o, 64);
-}
-__device__ __forceinline__ int bfly(int v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
 
-// ---- a wave's pixels and the peel ---------------------------------------------------------------------------------------------------
+// ---- a wave's pixels (the peel of their ids: pea_stream.h) ------------------------------------------------------------------------------
 struct WaveRun {
   size_t i0;        // the lane's first pixel
   int nv;           // its valid pixels (0 .. 4)
-  int lab[kQuad];   // their labels
+  int lab[kQuad];   // their labels (-1 past the end)
   unsigned act;     // bit i: pixel i is valid and counted
   int bad;          // the lane's out-of-range labels
 };
-
-__device__ __forceinline__ int quad_nv(size_t i0, size_t S) { return i0 >= S ? 0 : (S - i0 >= (size_t)kQuad ? kQuad : (int)(S - i0)); }
 
 __device__ __forceinline__ void wave_labels(WaveRun& W, const int32_t* __restrict__ lp, size_t w0, size_t S, int N, int bg, int lane) {
   W.i0 = w0 + (size_t)lane * kQuad;
@@ -156,23 +139,6 @@ __device__ __forceinline__ void wave_labels(WaveRun& W, const int32_t* __restric
   }
 }
 
-// the next id among the pixels still `open` (false: none left) and the lane's pixels of it (mm), which are closed
-__device__ __forceinline__ bool peel(const WaveRun& W, unsigned& open, int& cur, unsigned& mm) {
-  const unsigned long long any = __ballot(open != 0);
-  if (!any) return false;
-  int cand = 0;
-#pragma unroll
-  for (int i = kQuad - 1; i >= 0; --i)
-    if ((open >> i) & 1u) cand = W.lab[i];
-  cur = __builtin_amdgcn_readfirstlane(__shfl(cand, __ffsll(any) - 1, 64));
-  mm = 0;
-#pragma unroll
-  for (int i = 0; i < kQuad; ++i)
-    if (((open >> i) & 1u) && W.lab[i] == cur) mm |= 1u << i;
-  open &= ~mm;
-  return true;
-}
-
 // kCh channel planes of the lane's quad, d0 first; past the last channel the last one again (loaded, never used)
 template <typename T>
 __device__ __forceinline__ void ld_group(const WaveRun& W, const T* __restrict__ eb, int d0, int D, size_t S, float (&v)[kCh][kQuad]) {
@@ -190,7 +156,7 @@ __device__ __forceinline__ void reduce_group(const WaveRun& W, const float (&t)[
                                              int lane, F&& first) {
   unsigned open = W.act, mm;
   int cur;
-  while (peel(W, open, cur, mm)) {
+  while (peel(W.lab, open, cur, mm)) {
     u64* row = rows + (bN + (size_t)cur) * R;
     first(row, mm);
     float s[kCh];
@@ -201,7 +167,7 @@ __device__ __forceinline__ void reduce_group(const WaveRun& W, const float (&t)[
       for (int i = 0; i < kQuad; ++i)
         if ((mm >> i) & 1u) s[u] += t[u][i];
     }
-    bfly(s);
+    wave_sums(s);
     float mine = 0.f;
 #pragma unroll
     for (int u = 0; u < kCh; ++u)
@@ -214,11 +180,11 @@ __device__ __forceinline__ void reduce_group(const WaveRun& W, const float (&t)[
 template <typename T>
 __global__ __launch_bounds__(kBlock) void k_disc_sums(const size_t S, const unsigned chunks, const DiscK K, const T* __restrict__ e,
                                                       const int32_t* __restrict__ labels, const Tables Tb) {
-  const unsigned chunk = blockIdx.x % chunks;
-  const size_t b = blockIdx.x / chunks;
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const size_t w0 = (size_t)chunk * kRun + (size_t)wave * kWaveRun;
-  if (w0 >= S) return;  // the whole wave; nothing below meets another wave
+  const BlockAt at = block_at(chunks);
+  const size_t b = at.plane;
+  const int lane = threadIdx.x & 63;
+  size_t w0;
+  if (!wave_start(at.chunk, S, &w0)) return;
   WaveRun W;
   wave_labels(W, labels + b * S, w0, S, K.N, K.bg, lane);
   const T* __restrict__ eb = e + b * K.D * S;
@@ -228,12 +194,12 @@ __global__ __launch_bounds__(kBlock) void k_disc_sums(const size_t S, const unsi
     ld_group(W, eb, d0, K.D, S, v);
     reduce_group(W, v, d0, K.D, Tb.rows, b * K.N, Tb.R, lane, [&](u64* row, unsigned mm) {
       if (d0 == 0) {  // the pixel count, once
-        const int cnt = bfly((int)__popc(mm));
+        const int cnt = wave_sum((int)__popc(mm));
         if (lane == 0) PEA_ATOM_ADD(row, (u64)cnt);
       }
     });
   }
-  const int bad = bfly(W.bad);
+  const int bad = wave_sum(W.bad);
   if (lane == 0 && bad) PEA_ATOM_ADD(Tb.hdr + 1, (u64)bad);
 }
 
@@ -373,11 +339,11 @@ __global__ __launch_bounds__(kClBlock) void k_disc_clusters(const DiscK K, const
 template <typename T, bool GRAD>
 __global__ __launch_bounds__(kBlock) void k_disc_pull(const size_t S, const unsigned chunks, const DiscK K, const T* __restrict__ e,
                                                       const int32_t* __restrict__ labels, const Tables Tb, const Ctx C) {
-  const unsigned chunk = blockIdx.x % chunks;
-  const size_t b = blockIdx.x / chunks;
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const size_t w0 = (size_t)chunk * kRun + (size_t)wave * kWaveRun;
-  if (w0 >= S) return;
+  const BlockAt at = block_at(chunks);
+  const size_t b = at.plane;
+  const int lane = threadIdx.x & 63;
+  size_t w0;
+  if (!wave_start(at.chunk, S, &w0)) return;
   WaveRun W;
   wave_labels(W, labels + b * S, w0, S, K.N, K.bg, lane);
   const T* __restrict__ eb = e + b * K.D * S;
@@ -418,7 +384,7 @@ __global__ __launch_bounds__(kBlock) void k_disc_pull(const size_t S, const unsi
   {  // var_b: per id the wave's sum of h^2, weighted, into the image's accumulator
     unsigned open = W.act, mm;
     int cur;
-    while (peel(W, open, cur, mm)) {
+    while (peel(W.lab, open, cur, mm)) {
       float hh = 0.f;
 #pragma unroll
       for (int i = 0; i < kQuad; ++i)
@@ -507,9 +473,9 @@ template <typename T>
 __global__ __launch_bounds__(kBlock) void k_disc_bwd(const size_t S, const unsigned chunks, const DiscK K, const T* __restrict__ e,
                                                      const int32_t* __restrict__ labels, const Ctx C, const float* __restrict__ dloss,
                                                      T* __restrict__ de) {
-  const unsigned chunk = blockIdx.x % chunks;
-  const size_t b = blockIdx.x / chunks;
-  const size_t i0 = (size_t)chunk * kBwdRun + (size_t)threadIdx.x * kQuad;
+  const BlockAt at = block_at(chunks);
+  const size_t b = at.plane;
+  const size_t i0 = quad_start(at.chunk);
   if (i0 >= S) return;
   const int nv = quad_nv(i0, S);
   const int32_t* __restrict__ lp = labels + b * S + i0;
@@ -560,26 +526,9 @@ __global__ __launch_bounds__(kBlock) void k_disc_bwd(const size_t S, const unsig
   }
 }
 
-// pea_disc_workspace_init: all zero but for the magic word
-__global__ __launch_bounds__(kBlock) void k_disc_init(u64* __restrict__ w, size_t words) {
-  for (size_t i = (size_t)blockIdx.x * kBlock + threadIdx.x; i < words; i += (size_t)gridDim.x * kBlock) w[i] = i == 0 ? (u64)kDiscMagic : 0ull;
-}
-
-inline void launch_init(void* ws, size_t bytes, hipStream_t s) {
-  const size_t words = bytes / 8;
-  const size_t g = (words + kBlock - 1) / kBlock;
-  hipLaunchKernelGGL(k_disc_init, dim3((unsigned)(g < 1024 ? g : 1024)), dim3(kBlock), 0, s, (u64*)ws, words);
-}
-
-// workgroups of a streaming launch, one per `run` pixels of an image; false: S or the grid exceeds 2^31 - 1
-inline bool stream_grid(const PeaDiscDesc* d, int run, unsigned* chunks, unsigned* groups) {
-  if (d->S > 0x7fffffffLL) return false;
-  const uint64_t c = ((uint64_t)d->S + run - 1) / run;
-  const uint64_t g = c * (uint64_t)d->B;
-  if (g > 0x7fffffffULL) return false;
-  *chunks = (unsigned)c;
-  *groups = (unsigned)g;
-  return true;
+// workgroups of a streaming launch over the images' pixels; false: S or the grid exceeds 2^31 - 1
+inline bool disc_grid(const PeaDiscDesc* d, unsigned* chunks, unsigned* groups) {
+  return d->S <= 0x7fffffffLL && stream_grid((uint64_t)d->S, (uint64_t)d->B, kQuadRun, chunks, groups);
 }
 
 inline DiscK disc_params(const PeaDiscDesc* d) {
@@ -612,11 +561,7 @@ extern "C" size_t pea_disc_workspace_bytes(const PeaDiscDesc* d) { return pea_di
 extern "C" size_t pea_disc_context_bytes(const PeaDiscDesc* d) { return pea_disc_validate(d) ? 0 : ctx_layout(d, nullptr, nullptr); }
 
 extern "C" int pea_disc_workspace_init(void* workspace, size_t bytes, void* stream) {
-  if (!workspace) return PEA_E_NULL;
-  if (misaligned(workspace, 8)) return PEA_E_ALIGN;
-  if (bytes < 8 * kHdrWords || bytes % 8) return PEA_E_WORKSPACE;
-  launch_init(workspace, bytes, (hipStream_t)stream);
-  return hip_rc();
+  return table_workspace_init<kDiscMagic>(workspace, bytes, stream);
 }
 
 extern "C" int pea_disc_loss_fwd(const PeaDiscDesc* d, const void* e, const int32_t* labels, float* loss, double* stats, void* ctx,
@@ -630,7 +575,7 @@ extern "C" int pea_disc_loss_fwd(const PeaDiscDesc* d, const void* e, const int3
   const size_t need = pea_disc_workspace_bytes(d);
   if (!workspace || workspace_bytes < need) return PEA_E_WORKSPACE;
   unsigned chunks, groups;
-  if (!stream_grid(d, kRun, &chunks, &groups)) return PEA_E_UNSUPPORTED;
+  if (!disc_grid(d, &chunks, &groups)) return PEA_E_UNSUPPORTED;
 
   hipStream_t s = (hipStream_t)stream;
   const DiscK K = disc_params(d);
@@ -652,11 +597,7 @@ extern "C" int pea_disc_loss_fwd(const PeaDiscDesc* d, const void* e, const int3
     hipLaunchKernelGGL(k_disc_finish, dim3(1), dim3(kClBlock), 0, s, K, Tb, C, loss, stats);
     return hip_rc();
   });
-  if (rc) {  // partials may be queued without what zeroes them: prepare the block again (the contract of pea_disc_workspace_init)
-    launch_init(workspace, need, s);
-    (void)hipGetLastError();
-  }
-  return rc;
+  return or_prepare_again(rc, [&] { launch_table_init<kDiscMagic>(workspace, need, s); });
 }
 
 extern "C" int pea_disc_loss_bwd(const PeaDiscDesc* d, const void* e, const int32_t* labels, const void* ctx, const float* dloss, void* de,
@@ -667,7 +608,7 @@ extern "C" int pea_disc_loss_bwd(const PeaDiscDesc* d, const void* e, const int3
   const size_t eb = dtype_bytes(d->dtype);
   if (misaligned(e, eb) || misaligned(de, eb) || misaligned(labels, 4) || misaligned(dloss, 4) || misaligned(ctx, 8)) return PEA_E_ALIGN;
   unsigned chunks, groups;
-  if (!stream_grid(d, kBwdRun, &chunks, &groups)) return PEA_E_UNSUPPORTED;
+  if (!disc_grid(d, &chunks, &groups)) return PEA_E_UNSUPPORTED;
   const DiscK K = disc_params(d);
   Ctx C;
   ctx_layout(d, const_cast<void*>(ctx), &C);

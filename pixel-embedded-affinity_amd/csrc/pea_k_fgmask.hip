@@ -2,7 +2,7 @@
 // cross-entropy of scripts_bbbc039v1/loss/loss.py:187-194 on the binary_seg logits as ONE streaming reduction launch and one small
 // finish, its gradient as ONE streaming launch, and the validation mask of scripts_bbbc039v1/main.py:406-410.
 //
-// The walk is that of pea_k_metrics.hip.  A workgroup of 256 lanes owns a RUN of kRun = 4096 consecutive pixels of one image; a lane
+// The walk is the lane run of pea_stream.h, as in pea_k_metrics.hip.  A workgroup of 256 lanes owns a RUN of kRun = 4096 consecutive pixels of one image; a lane
 // takes four steps of four x-adjacent pixels (pixel (step * 256 + lane) * 4 + e of the run), so a step of a wave is 1 KiB of each f32
 // logit plane and of i32 labels.  A lane's quad is one wide access (dwordx4 for f32 / i32, dwordx2 for 16-bit logits, one dword for u8
 // labels) where its address is aligned to four elements and the quad is whole, four scalar accesses otherwise; the two logit planes
@@ -20,7 +20,7 @@
 // profiles/fgmask_ab.json): forward 10 us, finish 4 us, backward 6 us in a kernel trace; nothing was tuned.
 #include "../../include/pea_fgmask.h"
 #include "pea_dispatch.h"
-#include "pea_quad.h"
+#include "pea_stream.h"
 
 #pragma clang fp contract(off)
 
@@ -28,13 +28,9 @@ using namespace pea;
 
 namespace {
 
-constexpr int kSteps = 4;                       // steps per lane
-constexpr int kRun = kBlock * kQuad * kSteps;   // pixels of one image per workgroup
 constexpr int kSums = 4;                        // S0, S1, n0, n1: indices of the one loss state
 static_assert(kSums <= PEA_MAX_K, "the four sums are indices of one state");
 static_assert(kSums * kLossSlots == 64, "the finish is one wave");
-static_assert(kRun < (1 << 24), "a workgroup's count is an exact f32 integer");
-constexpr int kMaskRun = kBlock * kQuad;        // output pixels per workgroup of the argmax
 constexpr unsigned kKnownFlags = PEA_FG_SKIP_EMPTY_CLASS;
 
 // a quad of labels (pea_quad.h has the logits' ld_quad / st_quad): y = [label > 0] (i32: one dwordx4, u8: one dword)
@@ -63,16 +59,16 @@ __device__ __forceinline__ float wrong_minus_right(float l0, float l1, bool y) {
 template <typename T, typename LT>
 __global__ __launch_bounds__(kBlock) void k_fg_fwd(const size_t S, const unsigned chunks, const T* __restrict__ logits,
                                                    const LT* __restrict__ labels, LossState* __restrict__ st) {
-  const unsigned chunk = blockIdx.x % chunks;
-  const size_t b = blockIdx.x / chunks;
+  const BlockAt at = block_at(chunks);
+  const size_t b = at.plane;
   const T* __restrict__ p0 = logits + b * 2 * S;
   const T* __restrict__ p1 = p0 + S;
   const LT* __restrict__ lp = labels + b * S;
 
   float s0 = 0.f, s1 = 0.f, c0 = 0.f, c1 = 0.f;
-  const size_t run0 = (size_t)chunk * kRun;
+  const size_t run0 = (size_t)at.chunk * kLaneRun;
 #pragma unroll 1
-  for (int j = 0; j < kSteps; ++j) {
+  for (int j = 0; j < kSteps; ++j) {  // (lane_run written out: see profiles/README.md, Stream refactor)
     const size_t i0 = run0 + ((size_t)j * kBlock + threadIdx.x) * kQuad;
     if (i0 >= S) break;
     const int nv = S - i0 >= (size_t)kQuad ? kQuad : (int)(S - i0);
@@ -130,8 +126,8 @@ template <typename T, typename LT>
 __global__ __launch_bounds__(kBlock) void k_fg_bwd(const size_t S, const unsigned chunks, const int skip_empty, const T* __restrict__ logits,
                                                    const LT* __restrict__ labels, const double* __restrict__ stats,
                                                    const float* __restrict__ dloss, T* __restrict__ dlogits) {
-  const unsigned chunk = blockIdx.x % chunks;
-  const size_t b = blockIdx.x / chunks;
+  const BlockAt at = block_at(chunks);
+  const size_t b = at.plane;
   const T* __restrict__ p0 = logits + b * 2 * S;
   const T* __restrict__ p1 = p0 + S;
   const LT* __restrict__ lp = labels + b * S;
@@ -146,9 +142,9 @@ __global__ __launch_bounds__(kBlock) void k_fg_bwd(const size_t S, const unsigne
   const float cn0 = all_nan ? __builtin_nanf("") : (float)(dl / (2.0 * n0));
   const float cn1 = all_nan ? __builtin_nanf("") : (float)(dl / (2.0 * n1));
 
-  const size_t run0 = (size_t)chunk * kRun;
+  const size_t run0 = (size_t)at.chunk * kLaneRun;
 #pragma unroll 1
-  for (int j = 0; j < kSteps; ++j) {
+  for (int j = 0; j < kSteps; ++j) {  // (lane_run written out, as in k_fg_fwd)
     const size_t i0 = run0 + ((size_t)j * kBlock + threadIdx.x) * kQuad;
     if (i0 >= S) break;
     const int nv = S - i0 >= (size_t)kQuad ? kQuad : (int)(S - i0);
@@ -181,26 +177,20 @@ struct CropParams {
 // a lane owns four consecutive elements of the (dense) output; the logits are gathered row by row behind the crop
 template <typename T>
 __global__ __launch_bounds__(kBlock) void k_fg_argmax(const CropParams P, const T* __restrict__ logits, uint8_t* __restrict__ out) {
-  const size_t i0 = ((size_t)blockIdx.x * kBlock + threadIdx.x) * kQuad;
+  const size_t i0 = quad_start(blockIdx.x);
   if (i0 >= P.n) return;
-  const int nv = P.n - i0 >= (size_t)kQuad ? kQuad : (int)(P.n - i0);
-  const size_t oplane = (size_t)P.OY * P.OX;
-  size_t b = i0 / oplane;
-  const size_t r = i0 - b * oplane;
-  unsigned y = (unsigned)(r / P.OX), x = (unsigned)(r - (size_t)y * P.OX);
+  const int nv = quad_nv(i0, P.n);
+  CropCursor at(i0, P.OY, P.OX);  // (image, y, x) of the output
   unsigned m[kQuad];
 #pragma unroll
   for (int e = 0; e < kQuad; ++e) {
     m[e] = 0;
     if (e < nv) {
-      const size_t o = b * 2 * P.S + (size_t)(y + (unsigned)P.oy) * P.X + (x + (unsigned)P.ox);
+      const size_t o = at.o * 2 * P.S + (size_t)(at.y + (unsigned)P.oy) * P.X + (at.x + (unsigned)P.ox);
       const float l0 = ld<T>(logits, o), l1 = ld<T>(logits, o + P.S);
       m[e] = l1 > l0 ? 1u : 0u;  // a tie or a NaN: 0
     }
-    if (++x == P.OX) {
-      x = 0;
-      if (++y == P.OY) { y = 0; ++b; }
-    }
+    at.step(P.OY, P.OX);
   }
   uint8_t* __restrict__ op = out + i0;
   if (nv == kQuad && ((uintptr_t)op & 3) == 0) {
@@ -212,15 +202,10 @@ __global__ __launch_bounds__(kBlock) void k_fg_argmax(const CropParams P, const 
   }
 }
 
-// workgroups of a loss launch (one per kRun pixels of an image); 0: more than 2^31 - 1
+// workgroups of a loss launch (one per lane run of an image); false: more than 2^31 - 1
 inline bool loss_grid(const PeaFgDesc* d, uint64_t* S, unsigned* chunks, unsigned* groups) {
   *S = (uint64_t)d->Y * (uint64_t)d->X;
-  const uint64_t c = *S / kRun + (*S % kRun ? 1 : 0);
-  const uint64_t g = mul_sat((uint64_t)d->B, c);
-  if (g > 0x7fffffffULL) return false;
-  *chunks = (unsigned)c;
-  *groups = (unsigned)g;
-  return true;
+  return stream_grid(*S, (uint64_t)d->B, kLaneRun, chunks, groups);
 }
 
 // f(Tag<T>{}, Tag<LT>{}): the logits' storage type and the labels' element type
@@ -274,11 +259,7 @@ extern "C" int pea_fgmask_loss_fwd(const PeaFgDesc* d, const void* logits, const
     hipLaunchKernelGGL(k_fg_finish, dim3(1), dim3(64), 0, s, st, loss, stats, (d->flags & PEA_FG_SKIP_EMPTY_CLASS) ? 1 : 0);
     rc = hip_rc();
   }
-  if (rc) {  // partials may be queued without a finish: prepare the state again (the contract of pea_workspace_init)
-    launch_loss_state_init(st, 1, s);
-    (void)hipGetLastError();
-  }
-  return rc;
+  return or_prepare_again(rc, [&] { launch_loss_state_init(st, 1, s); });
 }
 
 extern "C" int pea_fgmask_loss_bwd(const PeaFgDesc* d, const void* logits, const void* labels, const double* stats, const float* dloss,
@@ -316,12 +297,12 @@ extern "C" int pea_fgmask_argmax(const PeaFgDesc* d, const void* logits, uint8_t
   P.X = d->X; P.oy = d->origin[0]; P.ox = d->origin[1];
   P.OY = (unsigned)d->out_dims[0]; P.OX = (unsigned)d->out_dims[1];
   const uint64_t n = mul_sat(mul_sat((uint64_t)d->B, (uint64_t)P.OY), (uint64_t)P.OX);
-  const uint64_t groups = n / kMaskRun + (n % kMaskRun ? 1 : 0);
-  if (groups > 0x7fffffffULL) return PEA_E_UNSUPPORTED;
+  unsigned chunks, groups;  // one quad run per workgroup over all images' output
+  if (!stream_grid(n, 1, kQuadRun, &chunks, &groups)) return PEA_E_UNSUPPORTED;
   P.n = (size_t)n;
   with_storage(d->logits_dtype, [&](auto t) {
     using T = typename decltype(t)::type;
-    hipLaunchKernelGGL((k_fg_argmax<T>), dim3((unsigned)groups), dim3(kBlock), 0, (hipStream_t)stream, P, (const T*)logits, mask_out);
+    hipLaunchKernelGGL((k_fg_argmax<T>), dim3(groups), dim3(kBlock), 0, (hipStream_t)stream, P, (const T*)logits, mask_out);
   });
   return hip_rc();
 }

@@ -27,7 +27,7 @@
 // with STORE), two logf per element: bandwidth-bound.
 #include "../../include/pea_metrics.h"
 #include "pea_dispatch.h"
-#include "pea_quad.h"
+#include "pea_stream.h"
 
 #pragma clang fp contract(off)
 
@@ -35,11 +35,8 @@ using namespace pea;
 
 namespace {
 
-constexpr int kSteps = 4;                       // steps per lane
-constexpr int kRun = kBlock * kQuad * kSteps;   // elements of one plane per workgroup
 constexpr int kStates = 5;                      // mse, bce, tp, fp, fn
 static_assert(kStates == PEA_METRICS_COLS, "one state per column");
-static_assert(kRun < (1 << 24), "a workgroup's count is an exact f32 integer");
 constexpr unsigned kKnownFlags = PEA_MET_RELU | PEA_MET_DIVIDE | PEA_MET_STORE | PEA_MET_MASK_F32;
 
 struct MetParams {
@@ -58,9 +55,9 @@ __global__ __launch_bounds__(kBlock) void k_metrics(const MetParams P, float* __
                                                     const float* __restrict__ target, const MT* __restrict__ mask,
                                                     LossState* __restrict__ st) {
   // blockIdx -> (b, c, chunk): uniform over the workgroup
-  const unsigned chunk = blockIdx.x % P.chunks, bc = blockIdx.x / P.chunks;
-  const unsigned c = bc % (unsigned)P.CW;
-  const size_t b = bc / (unsigned)P.CW;
+  const BlockAt at = block_at(P.chunks);
+  const unsigned c = at.plane % (unsigned)P.CW;
+  const size_t b = at.plane / (unsigned)P.CW;
   const bool eval = !STORE || (int)c < P.C;  // channels c >= C of a STORE walk are finished and stored, not evaluated
   const size_t RS = (size_t)P.Z * P.Y * P.X, PS = (size_t)P.PZ * P.PY * P.PX;
   const size_t n = STORE ? PS : RS;  // elements of the walked plane
@@ -72,12 +69,7 @@ __global__ __launch_bounds__(kBlock) void k_metrics(const MetParams P, float* __
   const unsigned WY = STORE ? P.PY : P.Y, WX = STORE ? P.PX : P.X;
 
   float s_mse = 0.f, s_bce = 0.f, s_tp = 0.f, s_fp = 0.f, s_fn = 0.f;
-  const size_t run0 = (size_t)chunk * kRun;
-#pragma unroll 1
-  for (int j = 0; j < kSteps; ++j) {
-    const size_t i0 = run0 + ((size_t)j * kBlock + threadIdx.x) * kQuad;
-    if (i0 >= n) break;
-    const int nv = n - i0 >= (size_t)kQuad ? kQuad : (int)(n - i0);
+  lane_run(at.chunk, n, [&](size_t i0, int nv) {
     float x[kQuad], w[kQuad], t[kQuad], m[kQuad];
     bool in[kQuad];
 #pragma unroll
@@ -92,13 +84,11 @@ __global__ __launch_bounds__(kBlock) void k_metrics(const MetParams P, float* __
       if (mp) ld_quad(mp + i0, nv, m);
     }
     if (!P.dense && eval) {  // the other side of a cropped walk: the quad's first voxel in the walk's coordinates, then step by step
-      const size_t wplane = (size_t)WY * WX;
-      unsigned z = (unsigned)(i0 / wplane);
-      const size_t r = i0 - (size_t)z * wplane;
-      unsigned y = (unsigned)(r / WX), xx = (unsigned)(r - (size_t)y * WX);
+      CropCursor vox(i0, WY, WX);
 #pragma unroll
       for (int e = 0; e < kQuad; ++e) {
         if (e < nv) {
+          const unsigned z = (unsigned)vox.o, y = vox.y, xx = vox.x;
           if (STORE) {  // pred's voxel -> the region's, where it lies inside
             const unsigned rz = z - (unsigned)P.oz, ry = y - (unsigned)P.oy, rx = xx - (unsigned)P.ox;
             in[e] = rz < (unsigned)P.Z && ry < (unsigned)P.Y && rx < (unsigned)P.X;
@@ -113,10 +103,7 @@ __global__ __launch_bounds__(kBlock) void k_metrics(const MetParams P, float* __
             if (DIVIDE) w[e] = wmap[o];
           }
         }
-        if (++xx == WX) {
-          xx = 0;
-          if (++y == WY) { y = 0; ++z; }
-        }
+        vox.step(WY, WX);
       }
     }
 
@@ -143,7 +130,7 @@ __global__ __launch_bounds__(kBlock) void k_metrics(const MetParams P, float* __
       }
     }
     if (STORE) st_quad(pp + i0, nv, x);
-  }
+  });
   if (!eval) return;  // (uniform: the whole workgroup leaves before the barrier)
 
   float q[kStates] = {s_mse, s_bce, s_tp, s_fp, s_fn};
@@ -222,15 +209,12 @@ extern "C" int pea_affs_metrics(const PeaMetricsDesc* d, float* pred, const floa
   P.lo = d->clip_lo; P.hi = d->clip_hi;
   const uint64_t RS = mul_sat(mul_sat((uint64_t)P.Z, (uint64_t)P.Y), (uint64_t)P.X);
   const uint64_t PS = mul_sat(mul_sat((uint64_t)P.PZ, (uint64_t)P.PY), (uint64_t)P.PX);
-  const uint64_t walk = store ? PS : RS;
-  const uint64_t chunks = walk / kRun + (walk % kRun ? 1 : 0);
-  const uint64_t groups = mul_sat(mul_sat((uint64_t)d->B, (uint64_t)P.CW), chunks);
-  if (groups > 0x7fffffffULL) return PEA_E_UNSUPPORTED;
-  P.chunks = (unsigned)chunks;
+  unsigned groups;
+  if (!stream_grid(store ? PS : RS, mul_sat((uint64_t)d->B, (uint64_t)P.CW), kLaneRun, &P.chunks, &groups)) return PEA_E_UNSUPPORTED;
 
   hipStream_t s = (hipStream_t)stream;
   LossState* st = (LossState*)workspace;
-  const dim3 grid((unsigned)groups), blk(kBlock);
+  const dim3 grid(groups), blk(kBlock);
   with_bool(mf32, [&](auto mf) {
     using MT = std::conditional_t<decltype(mf)::value, float, uint8_t>;
     with_bool(divide, [&](auto dv) {
@@ -246,9 +230,5 @@ extern "C" int pea_affs_metrics(const PeaMetricsDesc* d, float* pred, const floa
     hipLaunchKernelGGL(k_metrics_finish, dim3(1), dim3(64 * kStates), 0, s, st, out, P.C, n);
     rc = hip_rc();
   }
-  if (rc) {  // partials may be queued without a finish: prepare the states again (the contract of pea_workspace_init)
-    launch_loss_state_init(st, kStates, s);
-    (void)hipGetLastError();
-  }
-  return rc;
+  return or_prepare_again(rc, [&] { launch_loss_state_init(st, kStates, s); });
 }

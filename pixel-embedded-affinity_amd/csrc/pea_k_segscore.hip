@@ -26,8 +26,7 @@
 // pair (counted in n_overflow) and the kernel ends.  Lookups in later launches are plain loads behind the kernel boundary.
 // Slot placement depends on arrival order; nothing that is summed in floating point runs over slots (header: Arithmetic).
 #include "../../include/pea_segscore.h"
-#include "pea_host.h"
-#include "pea_quad.h"
+#include "pea_stream.h"
 
 #pragma clang fp contract(off)
 
@@ -35,10 +34,8 @@ using namespace pea;
 
 namespace {
 
-constexpr int kWaveRun = 64 * kQuad;            // pixels of one image per wave: one quad per lane
-constexpr int kRun = kWaveRun * (kBlock / 64);  // .. per workgroup of the pass over pixels
 constexpr unsigned kSegMagic = 0x50454153u;     // "PEAS"
-constexpr int kHdrWords = 8;                    // u64 words: [0] magic
+constexpr int kHdrWords = kTableHdrWords;       // u64 words: [0] magic
 constexpr int kImgWords = 32;                   // per image, below
 constexpr int kPairWords = 2;                   // per pair slot: key + 1, n_ij
 constexpr int kMargWords = 4;                   // per row slot: id + 1, a_i, a'_i, best Dice bits; per column slot: id + 1, b_j, best Dice bits, -
@@ -120,26 +117,13 @@ __device__ __forceinline__ long long slot_find(const u64* __restrict__ tab, u64 
   return -1;
 }
 
-__device__ __forceinline__ u64 wsum(u64 v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-__device__ __forceinline__ u64 wmax(u64 v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const u64 w = __shfl_xor(v, o, 64);
-    v = w > v ? w : v;
-  }
-  return v;
-}
-// a lane's wave total into a per-image word (all 64 lanes call)
+// a lane's wave total / wave maximum into a per-image word (all 64 lanes call)
 __device__ __forceinline__ void wave_add(u64* p, u64 v, int lane) {
-  v = wsum(v);
+  v = wave_sum(v);
   if (lane == 0 && v) PEA_ATOM_ADD(p, v);
 }
-__device__ __forceinline__ void wave_max(u64* p, u64 v, int lane) {
-  v = wmax(v);
+__device__ __forceinline__ void wave_max_into(u64* p, u64 v, int lane) {
+  v = wave_max(v);
   if (lane == 0 && v) PEA_ATOM_MAX(p, v);
 }
 // v >= 0, finite, below 2^63 -> fixed point with 32 fractional bits, truncated: lo = the fraction's digits, hi = the whole part
@@ -167,32 +151,20 @@ __device__ __forceinline__ double fx_diff(const u64* p, const u64* q) {
 __device__ __forceinline__ long long label_min(u64 w) { return w ? (long long)0x80000000ll - (long long)w : 0; }
 __device__ __forceinline__ long long label_max(u64 w) { return w ? (long long)w - 1 : 0; }
 
-__device__ __forceinline__ int quad_nv(size_t i0, size_t S) { return i0 >= S ? 0 : (S - i0 >= (size_t)kQuad ? kQuad : (int)(S - i0)); }
-
-__device__ __forceinline__ void ld_labels(const int32_t* __restrict__ p, int nv, int (&l)[kQuad]) {
-  if (nv == kQuad && ((uintptr_t)p & 15) == 0) {
-    const iquad_t v = *(const iquad_t*)p;
-    l[0] = v.x; l[1] = v.y; l[2] = v.z; l[3] = v.w;
-  } else {
-#pragma unroll
-    for (int i = 0; i < kQuad; ++i) l[i] = i < nv ? p[i] : -1;
-  }
-}
-
 // ---- 1: the joint histogram -------------------------------------------------------------------------------------------------------------
 // pred / gt: image 0 of the launch; img / pairs: the words and the table of image 0 of the launch (pea_seg_table launches one image)
 __global__ __launch_bounds__(kBlock) void k_seg_pairs(const size_t S, const unsigned chunks, const u64 cap, const int32_t* __restrict__ pred,
                                                       const int32_t* __restrict__ gt, u64* __restrict__ img, u64* __restrict__ pairs) {
-  const unsigned chunk = blockIdx.x % chunks;
-  const size_t b = blockIdx.x / chunks;
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const size_t w0 = (size_t)chunk * kRun + (size_t)wave * kWaveRun;
-  if (w0 >= S) return;  // the whole wave; nothing below meets another wave
+  const BlockAt at = block_at(chunks);
+  const size_t b = at.plane;
+  const int lane = threadIdx.x & 63;
+  size_t w0;
+  if (!wave_start(at.chunk, S, &w0)) return;
   const size_t i0 = w0 + (size_t)lane * kQuad;
   const int nv = quad_nv(i0, S);
   int lp[kQuad], lg[kQuad];
-  ld_labels(pred + b * S + (nv ? i0 : 0), nv, lp);
-  ld_labels(gt + b * S + (nv ? i0 : 0), nv, lg);
+  ld_iquad(pred + b * S + (nv ? i0 : 0), nv, -1, lp);
+  ld_iquad(gt + b * S + (nv ? i0 : 0), nv, -1, lg);
   u64 key[kQuad];
   unsigned open = 0;
   u64 bad = 0;
@@ -218,20 +190,10 @@ __global__ __launch_bounds__(kBlock) void k_seg_pairs(const size_t S, const unsi
     mykey = 0;
   };
   int r = 0;
-  for (;;) {
-    const unsigned long long any = __ballot(open != 0);
-    if (!any) break;
-    u64 cand = 0;
-#pragma unroll
-    for (int i = kQuad - 1; i >= 0; --i)
-      if ((open >> i) & 1u) cand = key[i];
-    const u64 cur = __shfl(cand, __ffsll(any) - 1, 64);
-    unsigned mm = 0;
-#pragma unroll
-    for (int i = 0; i < kQuad; ++i)
-      if (((open >> i) & 1u) && key[i] == cur) mm |= 1u << i;
-    open &= ~mm;
-    const u64 cnt = wsum((u64)__popc(mm));
+  u64 cur;
+  unsigned mm;
+  while (peel(key, open, cur, mm)) {
+    const u64 cnt = wave_sum((u64)__popc(mm));
     if (lane == r) { mykey = cur; mycnt = cnt; }
     if (++r == 64) { flush(); r = 0; }
   }
@@ -285,10 +247,10 @@ __global__ __launch_bounds__(kBlock) void k_seg_marginals(const Tables T) {
   wave_add(w + I_NLN, lo, lane);
   wave_add(w + I_NLN + 1, hi, lane);
   wave_add(w + I_OVF, ovf, lane);
-  wave_max(w + I_MAXP, mxp, lane);
-  wave_max(w + I_MINP, mnp, lane);
-  wave_max(w + I_MAXG, mxg, lane);
-  wave_max(w + I_MING, mng, lane);
+  wave_max_into(w + I_MAXP, mxp, lane);
+  wave_max_into(w + I_MINP, mnp, lane);
+  wave_max_into(w + I_MAXG, mxg, lane);
+  wave_max_into(w + I_MING, mng, lane);
 }
 
 // ---- 3: the Dice of every pair, the sums over rows and columns ----------------------------------------------------------------------------
@@ -461,24 +423,10 @@ __global__ __launch_bounds__(64) void k_seg_table_finish(const u64* __restrict__
   img[I_BAD] = 0;
 }
 
-// pea_seg_workspace_init: all zero but for the magic word
-__global__ __launch_bounds__(kBlock) void k_seg_init(u64* __restrict__ w, size_t words) {
-  for (size_t i = (size_t)blockIdx.x * kBlock + threadIdx.x; i < words; i += (size_t)gridDim.x * kBlock) w[i] = i == 0 ? (u64)kSegMagic : 0ull;
-}
-
-inline void launch_init(void* ws, size_t bytes, hipStream_t s) {
-  const size_t words = bytes / 8;
-  const size_t g = (words + kBlock - 1) / kBlock;
-  hipLaunchKernelGGL(k_seg_init, dim3((unsigned)(g < 1024 ? g : 1024)), dim3(kBlock), 0, s, (u64*)ws, words);
-}
-
 // workgroups of the pass over `images` images' pixels and of a pass over their slots; false: a grid exceeds 2^31 - 1
 inline bool seg_grids(const PeaSegDesc* d, uint64_t images, unsigned* chunks, unsigned* pixel_groups, unsigned* slot_groups) {
-  const uint64_t c = ((uint64_t)d->S + kRun - 1) / kRun;
-  const uint64_t g = c * images, sg = images * ((uint64_t)d->capacity / kBlock + ((uint64_t)d->capacity % kBlock ? 1 : 0));
-  if (g > 0x7fffffffULL || sg > 0x7fffffffULL) return false;
-  *chunks = (unsigned)c;
-  *pixel_groups = (unsigned)g;
+  const uint64_t sg = images * ((uint64_t)d->capacity / kBlock + ((uint64_t)d->capacity % kBlock ? 1 : 0));
+  if (!stream_grid((uint64_t)d->S, images, kQuadRun, chunks, pixel_groups) || sg > 0x7fffffffULL) return false;
   *slot_groups = (unsigned)((images * (uint64_t)d->capacity + kBlock - 1) / kBlock);
   return true;
 }
@@ -497,11 +445,7 @@ extern "C" int pea_seg_validate(const PeaSegDesc* d) {
 extern "C" size_t pea_seg_workspace_bytes(const PeaSegDesc* d) { return pea_seg_validate(d) ? 0 : tables_layout(d, nullptr, nullptr); }
 
 extern "C" int pea_seg_workspace_init(void* workspace, size_t bytes, void* stream) {
-  if (!workspace) return PEA_E_NULL;
-  if (misaligned(workspace, 8)) return PEA_E_ALIGN;
-  if (bytes < 8 * kHdrWords || bytes % 8) return PEA_E_WORKSPACE;
-  launch_init(workspace, bytes, (hipStream_t)stream);
-  return hip_rc();
+  return table_workspace_init<kSegMagic>(workspace, bytes, stream);
 }
 
 extern "C" int pea_seg_scores(const PeaSegDesc* d, const int32_t* pred, const int32_t* gt, double* out, void* workspace, size_t workspace_bytes,
@@ -531,11 +475,7 @@ extern "C" int pea_seg_scores(const PeaSegDesc* d, const int32_t* pred, const in
     hipLaunchKernelGGL(k_seg_finish, dim3((unsigned)((d->B + 63) / 64)), dim3(64), 0, s, T, out);
     return hip_rc();
   }();
-  if (rc) {  // counts may be queued without what zeroes them: prepare the block again (the contract of pea_seg_workspace_init)
-    launch_init(workspace, need, s);
-    (void)hipGetLastError();
-  }
-  return rc;
+  return or_prepare_again(rc, [&] { launch_table_init<kSegMagic>(workspace, need, s); });
 }
 
 extern "C" int pea_seg_table(const PeaSegDesc* d, const int32_t* pred, const int32_t* gt, int32_t b, int32_t* pred_ids, int32_t* gt_ids,
@@ -565,9 +505,5 @@ extern "C" int pea_seg_table(const PeaSegDesc* d, const int32_t* pred, const int
     hipLaunchKernelGGL(k_seg_table_finish, dim3(1), dim3(64), 0, s, (const u64*)T.hdr, T.img, n_out);
     return hip_rc();
   }();
-  if (rc) {
-    launch_init(workspace, need, s);
-    (void)hipGetLastError();
-  }
-  return rc;
+  return or_prepare_again(rc, [&] { launch_table_init<kSegMagic>(workspace, need, s); });
 }

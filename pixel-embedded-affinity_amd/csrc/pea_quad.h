@@ -1,6 +1,7 @@
-// pea_quad.h -- a lane's QUAD of four consecutive elements, shared by the streaming kernels that walk a flat pixel range (pea_k_fgmask.hip,
-// pea_k_disc.hip, pea_k_metrics.hip): one wide access (dwordx4 for f32 / i32, dwordx2 for 16-bit storage) where the address is aligned to four elements
-// and the quad is whole, four scalar accesses otherwise.  Which of the two is taken changes no bit of any value.
+// pea_quad.h -- a lane's QUAD of four consecutive elements, shared by the streaming kernels that walk a flat pixel range (pea_k_metrics.hip,
+// pea_k_fgmask.hip, pea_k_disc.hip, pea_k_segscore.hip, through pea_stream.h): one wide access (dwordx4 for f32 / i32, dwordx2 for 16-bit
+// storage, one dword for u8) where the address is aligned to four elements and the quad is whole, four scalar accesses otherwise.  Which of
+// the two is taken changes no bit of any value.
 #pragma once
 #include "pea_common.h"
 
@@ -50,6 +51,16 @@ __device__ __forceinline__ void ld_quad(const uint8_t* __restrict__ p, int nv, f
     for (int e = 0; e < kQuad; ++e) o[e] = e < nv ? (float)p[e] : 0.f;
   }
 }
+// the same for int32 labels (one dwordx4); the caller names the value of the lanes past nv
+__device__ __forceinline__ void ld_iquad(const int32_t* __restrict__ p, int nv, int fill, int (&o)[kQuad]) {
+  if (nv == kQuad && ((uintptr_t)p & 15) == 0) {
+    const iquad_t v = *(const iquad_t*)p;
+    o[0] = v.x; o[1] = v.y; o[2] = v.z; o[3] = v.w;
+  } else {
+#pragma unroll
+    for (int e = 0; e < kQuad; ++e) o[e] = e < nv ? p[e] : fill;
+  }
+}
 template <typename T>
 __device__ __forceinline__ void st_quad(T* __restrict__ p, int nv, const float (&v)[kQuad]) {
   if (nv == kQuad && ((uintptr_t)p & (kQuad * sizeof(T) - 1)) == 0) {
@@ -67,30 +78,6 @@ __device__ __forceinline__ void st_quad(T* __restrict__ p, int nv, const float (
 #pragma unroll
     for (int e = 0; e < kQuad; ++e)
       if (e < nv) st(p, e, v[e]);
-  }
-}
-
-// The end of a streaming reduction of N sums per lane in a workgroup of kBlock lanes: a wave reduces each with __shfl_xor (a butterfly:
-// a fixed order), the four waves meet in LDS and lane 0 of the workgroup hands sum k, ((p0 + p1) + p2) + p3 of the waves' partials, to
-// f(k, v).  The whole workgroup calls it (a barrier).
-template <int N, typename F>
-__device__ __forceinline__ void block_sums(float (&q)[N], const F& f) {
-  static_assert(kBlock / 64 == 4, "the fixed order is written for four waves");
-  __shared__ float s_part[N][kBlock / 64];
-#pragma unroll
-  for (int k = 0; k < N; ++k) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) q[k] += __shfl_xor(q[k], o, 64);
-  }
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  if (lane == 0) {
-#pragma unroll
-    for (int k = 0; k < N; ++k) s_part[k][wave] = q[k];
-  }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-#pragma unroll
-    for (int k = 0; k < N; ++k) f(k, ((s_part[k][0] + s_part[k][1]) + s_part[k][2]) + s_part[k][3]);
   }
 }
 

@@ -12,26 +12,7 @@ import ctypes
 import torch
 
 from .. import _lib
-from ..affinity_op import _DTYPE_CODE, _RAW_STREAM, _labels_int32, _on_device, _ptr, _require_gpu, _stream
-
-_WS = {}
-_RETIRED = []
-
-
-def _workspace(dev, nb):
-    """the accumulator tables of pea_disc_loss_fwd for the CURRENT stream of `dev`: one block per stream, prepared once and replaced by
-    a larger one when a call needs more (every call leaves the block all zero but for its magic word, which is ready for ANY
-    descriptor that fits; calls on one stream cannot overlap)"""
-    idx = dev.index if dev.index is not None else torch.cuda.current_device()
-    raw = _RAW_STREAM(idx) if _RAW_STREAM is not None else torch.cuda.current_stream(dev).cuda_stream
-    w = _WS.get((idx, raw))
-    if w is None or w.numel() * 8 < nb:
-        if w is not None:
-            _RETIRED.append(w)  # a captured graph may still replay on the smaller block: it is kept, not freed
-        w = torch.empty(nb // 8, dtype=torch.float64, device=dev)
-        _lib.check(_lib.lib().pea_disc_workspace_init(ctypes.c_void_p(w.data_ptr()), nb, ctypes.c_void_p(raw)), "pea_disc_workspace_init")
-        _WS[(idx, raw)] = w
-    return w
+from ..affinity_op import _DTYPE_CODE, _labels_int32, _on_device, _ptr, _require_gpu, _stream, stream_workspace
 
 
 def _args(embedding, seg_gt, num_ids, gpu=True):
@@ -101,7 +82,8 @@ class DiscriminativeLoss(torch.autograd.Function):
             stats = torch.empty(_lib.DISC_STATS + 4 * d.B, dtype=torch.float64, device=dev)
             saved = torch.empty(int(L.pea_disc_context_bytes(ctypes.byref(d))) // 8, dtype=torch.float64, device=dev)
             nb = int(L.pea_disc_workspace_bytes(ctypes.byref(d)))
-            work = _workspace(dev, nb)
+            # (every call leaves the tables all zero but for the magic word: ready for ANY descriptor that fits)
+            work = stream_workspace("disc", dev, nb, L.pea_disc_workspace_init, "pea_disc_workspace_init")
             _lib.check(L.pea_disc_loss_fwd(ctypes.byref(d), _ptr(e.detach()), _ptr(lab), _ptr(loss), _ptr(stats), _ptr(saved), _ptr(work), nb,
                                            _stream()), "pea_disc_loss_fwd")
         ctx.desc = d

@@ -13,24 +13,7 @@ import ctypes
 import torch
 
 from .. import _lib
-from ..affinity_op import _DTYPE_CODE, _RAW_STREAM, _on_device, _ptr, _require_gpu, _stream
-
-_WS = {}
-
-
-def _workspace(dev):
-    """(tensor, bytes): the loss state of pea_fgmask_loss_fwd for the CURRENT stream of `dev`, initialised once (every call leaves
-    it ready for the next one, and calls on one stream cannot overlap)"""
-    L = _lib.lib()
-    idx = dev.index if dev.index is not None else torch.cuda.current_device()
-    raw = _RAW_STREAM(idx) if _RAW_STREAM is not None else torch.cuda.current_stream(dev).cuda_stream
-    nb = int(L.pea_fgmask_workspace_bytes())
-    w = _WS.get((idx, raw))
-    if w is None:
-        w = torch.empty(nb // 8, dtype=torch.float64, device=dev)
-        _lib.check(L.pea_workspace_init(ctypes.c_void_p(w.data_ptr()), nb, ctypes.c_void_p(raw)), "pea_workspace_init")
-        _WS[(idx, raw)] = w
-    return w, nb
+from ..affinity_op import _DTYPE_CODE, _on_device, _ptr, _require_gpu, _stream, stream_workspace
 
 
 def _logits_arg(logits, gpu=True):
@@ -99,7 +82,8 @@ class ForegroundMaskCE(torch.autograd.Function):
         with _on_device(dev):
             loss = torch.empty((), dtype=torch.float32, device=dev)
             stats = torch.empty(_lib.FG_STATS, dtype=torch.float64, device=dev)
-            work, nb = _workspace(dev)
+            nb = int(L.pea_fgmask_workspace_bytes())  # one loss state
+            work = stream_workspace("fgmask", dev, nb, L.pea_workspace_init, "pea_workspace_init")
             _lib.check(L.pea_fgmask_loss_fwd(ctypes.byref(d), _ptr(lg.detach()), _ptr(lab), _ptr(loss), _ptr(stats), _ptr(work), nb, _stream()),
                        "pea_fgmask_loss_fwd")
         ctx.desc = d

@@ -15,24 +15,7 @@ import numpy as np
 import torch
 
 from .. import _lib
-from ..affinity_op import _RAW_STREAM, _on_device, _ptr, _stream
-
-_WS = {}
-
-
-def _workspace(dev):
-    """(tensor, bytes): the five loss states of pea_affs_metrics for the CURRENT stream of `dev`, initialised once (every call
-    leaves them ready for the next one, and calls on one stream cannot overlap)"""
-    L = _lib.lib()
-    idx = dev.index if dev.index is not None else torch.cuda.current_device()
-    raw = _RAW_STREAM(idx) if _RAW_STREAM is not None else torch.cuda.current_stream(dev).cuda_stream
-    nb = int(L.pea_metrics_workspace_bytes())
-    w = _WS.get((idx, raw))
-    if w is None:
-        w = torch.empty(nb // 8, dtype=torch.float64, device=dev)
-        _lib.check(L.pea_workspace_init(ctypes.c_void_p(w.data_ptr()), nb, ctypes.c_void_p(raw)), "pea_workspace_init")
-        _WS[(idx, raw)] = w
-    return w, nb
+from ..affinity_op import _on_device, _ptr, _stream, stream_workspace
 
 
 class AffinityMetrics(object):
@@ -143,7 +126,8 @@ def affinity_metrics(pred, target, mask=None, *, relu=False, store=False, clip=(
     dev = pred.device
     with _on_device(dev):
         out = torch.empty((1 + C, _lib.METRICS_COLS), dtype=torch.float64, device=dev)
-        work, nb = _workspace(dev)
+        nb = int(L.pea_metrics_workspace_bytes())  # five loss states
+        work = stream_workspace("metrics", dev, nb, L.pea_workspace_init, "pea_workspace_init")
         _lib.check(L.pea_affs_metrics(ctypes.byref(d), _ptr(pred), _ptr(weight_map), _ptr(target), _ptr(mask), _ptr(out), _ptr(work), nb,
                                       _stream()), "pea_affs_metrics")
     if store:

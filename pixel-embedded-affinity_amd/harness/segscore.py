@@ -15,10 +15,8 @@ import numpy as np
 import torch
 
 from .. import _lib
-from ..affinity_op import _RAW_STREAM, _on_device, _ptr, _stream
+from ..affinity_op import _on_device, _ptr, _stream, stream_workspace
 
-_WS = {}
-_RETIRED = []
 CAPACITY_FLOOR, CAPACITY_CAP = 256, 32768  # of the default capacity (default_capacity)
 _NARROW = (torch.uint8, torch.int8, torch.int16, torch.uint16, torch.int32)
 _WIDE = (torch.int64, torch.uint64)
@@ -36,19 +34,9 @@ def default_capacity(S):
 
 
 def _workspace(dev, nb):
-    """the tables of pea_seg_scores for the CURRENT stream of `dev`: one block per stream, prepared once and replaced by a larger one
-    when a call needs more (every call leaves the block all zero but for its magic word, which is ready for ANY descriptor that fits;
-    calls on one stream cannot overlap)"""
-    idx = dev.index if dev.index is not None else torch.cuda.current_device()
-    raw = _RAW_STREAM(idx) if _RAW_STREAM is not None else torch.cuda.current_stream(dev).cuda_stream
-    w = _WS.get((idx, raw))
-    if w is None or w.numel() * 8 < nb:
-        if w is not None:
-            _RETIRED.append(w)  # a captured graph may still replay on the smaller block: it is kept, not freed
-        w = torch.empty(nb // 8, dtype=torch.float64, device=dev)
-        _lib.check(_lib.lib().pea_seg_workspace_init(ctypes.c_void_p(w.data_ptr()), nb, ctypes.c_void_p(raw)), "pea_seg_workspace_init")
-        _WS[(idx, raw)] = w
-    return w
+    """the tables of pea_seg_scores / pea_seg_table for the CURRENT stream of `dev` (every call leaves them all zero but for the magic
+    word: ready for ANY descriptor that fits)"""
+    return stream_workspace("seg", dev, nb, _lib.lib().pea_seg_workspace_init, "pea_seg_workspace_init")
 
 
 def labels_int32(x, name="labels", device=None):

@@ -19,7 +19,8 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import kernel_resources as kr  # noqa: E402
 
 FP = re.compile(r"^v_(pk_)?(fma|fmac|mul|sub|subrev|add|mad|mac|max|min|rcp|rsq|sqrt|log|exp|div_\w+|cvt|ldexp|frexp_\w+|dot\w*)_?\w*(f32|f16|f64|bf16)\w*")
-UNPACK = {"v_pk_fma_f32": ("v_fma_f32", 2), "v_pk_mul_f32": ("v_mul_f32", 2), "v_pk_add_f32": ("v_add_f32", 2)}
+UNPACK = {"v_pk_fma_f32": ("v_fma_f32", 2), "v_pk_mul_f32": ("v_mul_f32", 2), "v_pk_add_f32": ("v_add_f32", 2),
+          "v_cvt_pk_f16_f32": ("v_cvt_f16_f32", 2), "v_cvt_f16_f32_e32": ("v_cvt_f16_f32", 1), "v_cvt_f16_f32_sdwa": ("v_cvt_f16_f32", 1)}
 ALIAS = {"v_fmac_f32_e32": "v_fma_f32", "v_fmac_f32_e64": "v_fma_f32", "v_mul_f32_e32": "v_mul_f32", "v_mul_f32_e64": "v_mul_f32",
          "v_add_f32_e32": "v_add_f32", "v_add_f32_e64": "v_add_f32", "v_sub_f32_e32": "v_sub_f32", "v_sub_f32_e64": "v_sub_f32",
          "v_subrev_f32_e32": "v_sub_f32", "v_subrev_f32_e64": "v_sub_f32", "v_fmac_f32_dpp": "v_fma_f32"}
@@ -43,6 +44,12 @@ def mixes(so):
                 t = line.split()
                 if cur is not None and t and FP.match(t[0]):
                     name, n = UNPACK.get(t[0], (ALIAS.get(t[0], t[0]), 1))
+                    if t[0] == "v_pk_add_f32" and "neg_lo:[" in line:  # a negated source in both halves: a - b as a + (-b), or
+                        neg = re.search(r"neg_lo:\[([01,]+)\] neg_hi:\[\1\]", line)  # (-a) + (-0), the packed form of a sign flip
+                        if neg and neg.group(1) in ("0,1", "1,0"):
+                            name = "v_sub_f32"
+                        elif neg and neg.group(1) == "1,1" and t[3].rstrip(",") == "0":
+                            continue
                     cur[name] += n
     return out
 
