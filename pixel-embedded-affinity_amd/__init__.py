@@ -42,6 +42,9 @@ from .harness.segscore import SegmentationScores, segmentation_scores
 from .utils import evaluate, seg_scores
 from .utils.evaluate import AbsDiffFGLabels, BestDice, Dice, DiffFGLabels, FGBGDice, SymmetricBestDice
 from .utils.seg_scores import adapted_rand_error, variation_of_information
+from .harness.instscore import InstanceScores, instance_scores
+from .utils import metrics_bbbc
+from .utils.metrics_bbbc import agg_jc_index, get_fast_pq, pixel_f1, remap_label
 from .harness.handoff import AffsCollector
 from .harness.head_loss import HeadAffinityMSE, head_embedding_loss
 from .harness.train_step import CvpppTrainStep, convert_consistency_flip, label_pyramid, make_optimizer
@@ -81,3 +84,5 @@ SEGSCORE_EXPORTS = (
     "segmentation_scores", "SegmentationScores", "evaluate", "seg_scores", "DiffFGLabels", "BestDice", "FGBGDice", "Dice",
     "AbsDiffFGLabels", "SymmetricBestDice", "adapted_rand_error", "variation_of_information",
 )
+# likewise the instance scores of the BBBC039V1 validation loop (include/pea_instscore.h)
+INSTSCORE_EXPORTS = ("instance_scores", "InstanceScores", "metrics_bbbc", "agg_jc_index", "get_fast_pq", "pixel_f1", "remap_label")

@@ -24,6 +24,7 @@ HEADER_DISC = os.path.join(HERE, "..", "include", "pea_disc.h")
 HEADER_CROP = os.path.join(HERE, "..", "include", "pea_crop.h")
 HEADER_DIST = os.path.join(HERE, "..", "include", "pea_dist.h")
 HEADER_SEGSCORE = os.path.join(HERE, "..", "include", "pea_segscore.h")
+HEADER_INSTSCORE = os.path.join(HERE, "..", "include", "pea_instscore.h")
 
 PEA_ABI_VERSION = 2
 PEA_MAX_K = 32
@@ -52,6 +53,10 @@ SEG_MIN_CAPACITY, SEG_COLS = 64, 19  # include/pea_segscore.h PEA_SEG_MIN_CAPACI
 # the columns of pea_seg_scores' out [B][SEG_COLS] in order (include/pea_segscore.h PEA_SEG_<NAME>)
 SEG_COLUMNS = ("n_overflow", "n_bad", "best_dice", "best_dice_rev", "sbd", "diff_fg", "fgbg_dice", "voi_split", "voi_merge", "are",
                "are_precision", "are_recall", "sum_nij2", "sum_ai2", "sum_bj2", "n_prime", "n_pred_ids", "n_gt_ids", "n_pairs")
+INST_MIN_CAPACITY, INST_MAX_ID, INST_COLS = 64, 65535, 18  # include/pea_instscore.h PEA_INST_MIN_CAPACITY, PEA_INST_MAX_ID, PEA_INST_COLS
+# the columns of pea_inst_scores' out [B][INST_COLS] in order (include/pea_instscore.h PEA_INST_<NAME>)
+INST_COLUMNS = ("n_overflow", "n_bad", "aji", "aji_inter", "aji_union", "dq", "sq", "pq", "tp", "fp", "fn", "sum_iou", "pixel_f1", "pix_tp",
+                "pix_fp", "pix_fn", "n_pred_ids", "n_gt_ids")
 DISC_STATS = 5  # loss, var, dist, reg, n_bad; then var_b, dist_b, reg_b, C_b per image (include/pea_disc.h PEA_DISC_STATS)
 
 EXPORTS = ("pea_version", "pea_strerror", "pea_desc_validate", "pea_workspace_bytes", "pea_workspace_init", "pea_reload_env",
@@ -84,6 +89,8 @@ EXPORTS_CROP = ("pea_affs_crop_zero",)
 EXPORTS_DIST = ("pea_dist_validate", "pea_dist_affinity", "pea_dist_affinity_vjp")
 # the entry points of include/pea_segscore.h (the segmentation scores of the validation loops from one contingency table per image)
 EXPORTS_SEGSCORE = ("pea_seg_validate", "pea_seg_workspace_bytes", "pea_seg_workspace_init", "pea_seg_scores", "pea_seg_table")
+# the entry points of include/pea_instscore.h (the instance scores of the BBBC039V1 validation loop: AJI, PQ, pixel F1)
+EXPORTS_INSTSCORE = ("pea_inst_validate", "pea_inst_workspace_bytes", "pea_inst_workspace_init", "pea_inst_scores")
 
 
 class PeaLibraryError(RuntimeError):
@@ -153,6 +160,12 @@ class PeaSegDesc(ctypes.Structure):
     _fields_ = [("B", ctypes.c_int32), ("S", ctypes.c_int64), ("capacity", ctypes.c_int64), ("flags", ctypes.c_uint32)]
 
 
+class PeaInstDesc(ctypes.Structure):
+    """mirror of `struct PeaInstDesc` in include/pea_instscore.h"""
+    _fields_ = [("B", ctypes.c_int32), ("S", ctypes.c_int64), ("capacity", ctypes.c_int64), ("max_id", ctypes.c_int32),
+                ("match_iou", ctypes.c_double), ("flags", ctypes.c_uint32)]
+
+
 HIPCC_FLAGS = ["-O3", "--offload-arch=gfx950", "-std=c++17", "-fPIC"]
 OBJ_DIR = os.path.join(CSRC, "build")
 
@@ -178,7 +191,7 @@ def build(force=False, verbose=False, jobs=None):
 
 def _build_locked(force, verbose, jobs):
     srcs = sources()
-    hdrs = [HEADER, HEADER_INFER, HEADER_MULTI, HEADER_FLIP, HEADER_MULTI_LABELS, HEADER_HEAD16, HEADER_METRICS, HEADER_FGMASK, HEADER_DISC, HEADER_CROP, HEADER_DIST, HEADER_SEGSCORE] + [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".h")]
+    hdrs = [HEADER, HEADER_INFER, HEADER_MULTI, HEADER_FLIP, HEADER_MULTI_LABELS, HEADER_HEAD16, HEADER_METRICS, HEADER_FGMASK, HEADER_DISC, HEADER_CROP, HEADER_DIST, HEADER_SEGSCORE, HEADER_INSTSCORE] + [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".h")]
     newest_hdr = max(os.path.getmtime(h) for h in hdrs)
     if not force and os.path.exists(SO_PATH) and os.path.getmtime(SO_PATH) >= max([newest_hdr] + [os.path.getmtime(x) for x in srcs]):
         return SO_PATH
@@ -242,7 +255,7 @@ def lib():
         L = ctypes.CDLL(SO_PATH)
     except OSError as ex:
         raise PeaLibraryError("cannot load %s: %s" % (SO_PATH, ex))
-    for name in EXPORTS + EXPORTS_INFER + EXPORTS_MULTI + EXPORTS_FLIP + EXPORTS_MULTI_LABELS + EXPORTS_HEAD16 + EXPORTS_METRICS + EXPORTS_FGMASK + EXPORTS_DISC + EXPORTS_CROP + EXPORTS_DIST + EXPORTS_SEGSCORE:
+    for name in EXPORTS + EXPORTS_INFER + EXPORTS_MULTI + EXPORTS_FLIP + EXPORTS_MULTI_LABELS + EXPORTS_HEAD16 + EXPORTS_METRICS + EXPORTS_FGMASK + EXPORTS_DISC + EXPORTS_CROP + EXPORTS_DIST + EXPORTS_SEGSCORE + EXPORTS_INSTSCORE:
         if not hasattr(L, name):
             raise PeaLibraryError("%s does not export %s" % (SO_PATH, name))
     vp, dp = ctypes.c_void_p, ctypes.POINTER(PeaDesc)
@@ -387,6 +400,15 @@ def lib():
     L.pea_seg_scores.argtypes = [sg, vp, vp, vp, vp, ctypes.c_size_t, vp]
     L.pea_seg_table.restype = ctypes.c_int
     L.pea_seg_table.argtypes = [sg, vp, vp, ctypes.c_int32, vp, vp, vp, vp, ctypes.c_int64, vp, ctypes.c_size_t, vp]
+    it = ctypes.POINTER(PeaInstDesc)
+    L.pea_inst_validate.restype = ctypes.c_int
+    L.pea_inst_validate.argtypes = [it]
+    L.pea_inst_workspace_bytes.restype = ctypes.c_size_t
+    L.pea_inst_workspace_bytes.argtypes = [it]
+    L.pea_inst_workspace_init.restype = ctypes.c_int
+    L.pea_inst_workspace_init.argtypes = [vp, ctypes.c_size_t, vp]
+    L.pea_inst_scores.restype = ctypes.c_int
+    L.pea_inst_scores.argtypes = [it, vp, vp, vp, vp, vp, vp, ctypes.c_size_t, vp]
     if L.pea_version() != PEA_ABI_VERSION:
         raise PeaLibraryError("ABI mismatch: library %d, binding %d" % (L.pea_version(), PEA_ABI_VERSION))
     _lib = L
