@@ -45,6 +45,9 @@ from .utils.seg_scores import adapted_rand_error, variation_of_information
 from .harness.instscore import InstanceScores, instance_scores
 from .utils import metrics_bbbc
 from .utils.metrics_bbbc import agg_jc_index, get_fast_pq, pixel_f1, remap_label
+from .harness.cc import ConnectedComponents, connected_components, remove_small_components
+from .utils import postprocessing
+from .utils.postprocessing import remove_samll_object
 from .harness.handoff import AffsCollector
 from .harness.head_loss import HeadAffinityMSE, head_embedding_loss
 from .harness.train_step import CvpppTrainStep, convert_consistency_flip, label_pyramid, make_optimizer
@@ -86,3 +89,5 @@ SEGSCORE_EXPORTS = (
 )
 # likewise the instance scores of the BBBC039V1 validation loop (include/pea_instscore.h)
 INSTSCORE_EXPORTS = ("instance_scores", "InstanceScores", "metrics_bbbc", "agg_jc_index", "get_fast_pq", "pixel_f1", "remap_label")
+# likewise connected-component labelling (include/pea_cc.h) and the reference's remove_samll_object on it
+CC_EXPORTS = ("connected_components", "ConnectedComponents", "remove_small_components", "postprocessing", "remove_samll_object")

@@ -25,6 +25,7 @@ HEADER_CROP = os.path.join(HERE, "..", "include", "pea_crop.h")
 HEADER_DIST = os.path.join(HERE, "..", "include", "pea_dist.h")
 HEADER_SEGSCORE = os.path.join(HERE, "..", "include", "pea_segscore.h")
 HEADER_INSTSCORE = os.path.join(HERE, "..", "include", "pea_instscore.h")
+HEADER_CC = os.path.join(HERE, "..", "include", "pea_cc.h")
 
 PEA_ABI_VERSION = 2
 PEA_MAX_K = 32
@@ -57,6 +58,7 @@ INST_MIN_CAPACITY, INST_MAX_ID, INST_COLS = 64, 65535, 18  # include/pea_instsco
 # the columns of pea_inst_scores' out [B][INST_COLS] in order (include/pea_instscore.h PEA_INST_<NAME>)
 INST_COLUMNS = ("n_overflow", "n_bad", "aji", "aji_inter", "aji_union", "dq", "sq", "pq", "tp", "fp", "fn", "sum_iou", "pixel_f1", "pix_tp",
                 "pix_fp", "pix_fn", "n_pred_ids", "n_gt_ids")
+CC_IN_U8, CC_IN_I32 = 0, 1  # element type of the input of pea_cc_label (include/pea_cc.h PEA_CC_IN_*)
 DISC_STATS = 5  # loss, var, dist, reg, n_bad; then var_b, dist_b, reg_b, C_b per image (include/pea_disc.h PEA_DISC_STATS)
 
 EXPORTS = ("pea_version", "pea_strerror", "pea_desc_validate", "pea_workspace_bytes", "pea_workspace_init", "pea_reload_env",
@@ -91,6 +93,8 @@ EXPORTS_DIST = ("pea_dist_validate", "pea_dist_affinity", "pea_dist_affinity_vjp
 EXPORTS_SEGSCORE = ("pea_seg_validate", "pea_seg_workspace_bytes", "pea_seg_workspace_init", "pea_seg_scores", "pea_seg_table")
 # the entry points of include/pea_instscore.h (the instance scores of the BBBC039V1 validation loop: AJI, PQ, pixel F1)
 EXPORTS_INSTSCORE = ("pea_inst_validate", "pea_inst_workspace_bytes", "pea_inst_workspace_init", "pea_inst_scores")
+# the entry points of include/pea_cc.h (connected components: label, size filter, mask)
+EXPORTS_CC = ("pea_cc_validate", "pea_cc_workspace_bytes", "pea_cc_label")
 
 
 class PeaLibraryError(RuntimeError):
@@ -166,6 +170,12 @@ class PeaInstDesc(ctypes.Structure):
                 ("match_iou", ctypes.c_double), ("flags", ctypes.c_uint32)]
 
 
+class PeaCcDesc(ctypes.Structure):
+    """mirror of `struct PeaCcDesc` in include/pea_cc.h"""
+    _fields_ = [("ndim", ctypes.c_int32), ("B", ctypes.c_int32), ("dims", ctypes.c_int32 * 3), ("in_type", ctypes.c_int32),
+                ("connectivity", ctypes.c_int32), ("min_size", ctypes.c_int32), ("flags", ctypes.c_uint32)]
+
+
 HIPCC_FLAGS = ["-O3", "--offload-arch=gfx950", "-std=c++17", "-fPIC"]
 OBJ_DIR = os.path.join(CSRC, "build")
 
@@ -191,7 +201,7 @@ def build(force=False, verbose=False, jobs=None):
 
 def _build_locked(force, verbose, jobs):
     srcs = sources()
-    hdrs = [HEADER, HEADER_INFER, HEADER_MULTI, HEADER_FLIP, HEADER_MULTI_LABELS, HEADER_HEAD16, HEADER_METRICS, HEADER_FGMASK, HEADER_DISC, HEADER_CROP, HEADER_DIST, HEADER_SEGSCORE, HEADER_INSTSCORE] + [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".h")]
+    hdrs = [HEADER, HEADER_INFER, HEADER_MULTI, HEADER_FLIP, HEADER_MULTI_LABELS, HEADER_HEAD16, HEADER_METRICS, HEADER_FGMASK, HEADER_DISC, HEADER_CROP, HEADER_DIST, HEADER_SEGSCORE, HEADER_INSTSCORE, HEADER_CC] + [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".h")]
     newest_hdr = max(os.path.getmtime(h) for h in hdrs)
     if not force and os.path.exists(SO_PATH) and os.path.getmtime(SO_PATH) >= max([newest_hdr] + [os.path.getmtime(x) for x in srcs]):
         return SO_PATH
@@ -255,7 +265,7 @@ def lib():
         L = ctypes.CDLL(SO_PATH)
     except OSError as ex:
         raise PeaLibraryError("cannot load %s: %s" % (SO_PATH, ex))
-    for name in EXPORTS + EXPORTS_INFER + EXPORTS_MULTI + EXPORTS_FLIP + EXPORTS_MULTI_LABELS + EXPORTS_HEAD16 + EXPORTS_METRICS + EXPORTS_FGMASK + EXPORTS_DISC + EXPORTS_CROP + EXPORTS_DIST + EXPORTS_SEGSCORE + EXPORTS_INSTSCORE:
+    for name in EXPORTS + EXPORTS_INFER + EXPORTS_MULTI + EXPORTS_FLIP + EXPORTS_MULTI_LABELS + EXPORTS_HEAD16 + EXPORTS_METRICS + EXPORTS_FGMASK + EXPORTS_DISC + EXPORTS_CROP + EXPORTS_DIST + EXPORTS_SEGSCORE + EXPORTS_INSTSCORE + EXPORTS_CC:
         if not hasattr(L, name):
             raise PeaLibraryError("%s does not export %s" % (SO_PATH, name))
     vp, dp = ctypes.c_void_p, ctypes.POINTER(PeaDesc)
@@ -409,6 +419,13 @@ def lib():
     L.pea_inst_workspace_init.argtypes = [vp, ctypes.c_size_t, vp]
     L.pea_inst_scores.restype = ctypes.c_int
     L.pea_inst_scores.argtypes = [it, vp, vp, vp, vp, vp, vp, ctypes.c_size_t, vp]
+    cc = ctypes.POINTER(PeaCcDesc)
+    L.pea_cc_validate.restype = ctypes.c_int
+    L.pea_cc_validate.argtypes = [cc]
+    L.pea_cc_workspace_bytes.restype = ctypes.c_size_t
+    L.pea_cc_workspace_bytes.argtypes = [cc]
+    L.pea_cc_label.restype = ctypes.c_int
+    L.pea_cc_label.argtypes = [cc, vp, vp, vp, vp, vp, ctypes.c_size_t, vp]
     if L.pea_version() != PEA_ABI_VERSION:
         raise PeaLibraryError("ABI mismatch: library %d, binding %d" % (L.pea_version(), PEA_ABI_VERSION))
     _lib = L

@@ -14,6 +14,7 @@ import torch
 
 from .. import _lib
 from ..affinity_op import _DTYPE_CODE, _on_device, _ptr, _require_gpu, _stream, stream_workspace
+from .cc import remove_small_components
 
 
 def _logits_arg(logits, gpu=True):
@@ -116,10 +117,14 @@ def foreground_mask_loss(logits, labels, skip_empty=False):
     return ForegroundMaskCE.apply(logits, labels, bool(skip_empty))
 
 
-def foreground_mask(logits, crop=((0, 0), (0, 0))):
+def foreground_mask(logits, crop=((0, 0), (0, 0)), min_size=0):
     """uint8 [B, H', W'] = [l1 > l0] on logits[..., top:H - bottom, left:W - right], crop = ((top, bottom), (left, right)): the
     reference's argmax(softmax(pred_mask), dim=1) and its [92:-92, 4:-4] (scripts_bbbc039v1/main.py:406-410) in one launch, left on the
-    device.  A tie or a NaN gives 0."""
+    device.  A tie or a NaN gives 0.  min_size > 0: the mask then loses its connected components (8-neighbourhood) of fewer than
+    min_size pixels -- remove_samll_object of main.py:411, pea_cc_label with mask_out only (harness/cc.py); 0 adds no launch."""
+    ms = int(min_size)
+    if ms < 0:
+        raise ValueError("min_size must be >= 0, got %r" % (min_size,))
     lg = _logits_arg(logits).detach()
     (top, bottom), (left, right) = crop
     H, W = int(lg.shape[2]), int(lg.shape[3])
@@ -131,4 +136,6 @@ def foreground_mask(logits, crop=((0, 0), (0, 0))):
     with _on_device(lg.device):
         out = torch.empty((lg.shape[0], d.out_dims[0], d.out_dims[1]), dtype=torch.uint8, device=lg.device)
         _lib.check(_lib.lib().pea_fgmask_argmax(ctypes.byref(d), _ptr(lg), _ptr(out), _stream()), "pea_fgmask_argmax")
+    if ms > 0:
+        out = remove_small_components(out, ms)
     return out

@@ -114,3 +114,22 @@ def synth_inputs_3d(B, D, Z, Y, X, offsets, seed):
     t, _ = affinity_targets(lab, _offsets3(offsets), padding=False, both_foreground=True)
     w = class_balance_weights(t)
     return e, t, w
+
+
+def synth_nuclei(B, Y, X, n, radius, seed, specks=0):
+    """[B, Y, X] int32: about n discs of about `radius` pixels per image, later ones drawn over earlier ones, ids 1 .. in drawing order
+    (the nuclei images of the BBBC039V1 loop, roughly); specks: that many single pixels and 2 x 2 squares of id n + 1 strewn over each
+    image -- what remove_samll_object is there to take out of an argmax mask."""
+    out = np.zeros((B, Y, X), np.int32)
+    yy, xx = np.mgrid[0:Y, 0:X]
+    for b in range(B):
+        rng = np.random.default_rng(seed + b)
+        cy, cx, r = rng.integers(0, Y, n), rng.integers(0, X, n), rng.integers(max(1, radius - 3), radius + 4, n)
+        for k in range(n):
+            y0, y1, x0, x1 = max(0, cy[k] - r[k]), min(Y, cy[k] + r[k] + 1), max(0, cx[k] - r[k]), min(X, cx[k] + r[k] + 1)
+            disc = (yy[y0:y1, x0:x1] - cy[k]) ** 2 + (xx[y0:y1, x0:x1] - cx[k]) ** 2 <= r[k] ** 2
+            out[b, y0:y1, x0:x1][disc] = k + 1
+        for k in range(specks):
+            y, x, s = int(rng.integers(0, Y)), int(rng.integers(0, X)), 1 + k % 2
+            out[b, y:y + s, x:x + s] = n + 1
+    return out
