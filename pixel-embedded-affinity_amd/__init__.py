@@ -48,6 +48,9 @@ from .utils.metrics_bbbc import agg_jc_index, get_fast_pq, pixel_f1, remap_label
 from .harness.cc import ConnectedComponents, connected_components, remove_small_components
 from .utils import postprocessing
 from .utils.postprocessing import remove_samll_object
+from .harness.rag import RegionAdjacency, project_node_labels, region_adjacency
+from .utils import lmc
+from .utils.lmc import mc_baseline, multicut_multi, probs_to_costs, transform_probabilities_to_costs
 from .harness.handoff import AffsCollector
 from .harness.head_loss import HeadAffinityMSE, head_embedding_loss
 from .harness.train_step import CvpppTrainStep, convert_consistency_flip, label_pyramid, make_optimizer
@@ -91,3 +94,6 @@ SEGSCORE_EXPORTS = (
 INSTSCORE_EXPORTS = ("instance_scores", "InstanceScores", "metrics_bbbc", "agg_jc_index", "get_fast_pq", "pixel_f1", "remap_label")
 # likewise connected-component labelling (include/pea_cc.h) and the reference's remove_samll_object on it
 CC_EXPORTS = ("connected_components", "ConnectedComponents", "remove_small_components", "postprocessing", "remove_samll_object")
+# likewise the region adjacency graph (include/pea_rag.h) and the reference's utils/lmc.py on it
+RAG_EXPORTS = ("region_adjacency", "RegionAdjacency", "project_node_labels", "lmc", "mc_baseline", "multicut_multi", "probs_to_costs",
+               "transform_probabilities_to_costs")

@@ -26,6 +26,7 @@ HEADER_DIST = os.path.join(HERE, "..", "include", "pea_dist.h")
 HEADER_SEGSCORE = os.path.join(HERE, "..", "include", "pea_segscore.h")
 HEADER_INSTSCORE = os.path.join(HERE, "..", "include", "pea_instscore.h")
 HEADER_CC = os.path.join(HERE, "..", "include", "pea_cc.h")
+HEADER_RAG = os.path.join(HERE, "..", "include", "pea_rag.h")
 
 PEA_ABI_VERSION = 2
 PEA_MAX_K = 32
@@ -59,6 +60,10 @@ INST_MIN_CAPACITY, INST_MAX_ID, INST_COLS = 64, 65535, 18  # include/pea_instsco
 INST_COLUMNS = ("n_overflow", "n_bad", "aji", "aji_inter", "aji_union", "dq", "sq", "pq", "tp", "fp", "fn", "sum_iou", "pixel_f1", "pix_tp",
                 "pix_fp", "pix_fn", "n_pred_ids", "n_gt_ids")
 CC_IN_U8, CC_IN_I32 = 0, 1  # element type of the input of pea_cc_label (include/pea_cc.h PEA_CC_IN_*)
+RAG_ONE_MINUS, RAG_IGNORE_ZERO = 1, 2  # include/pea_rag.h PEA_RAG_ONE_MINUS, PEA_RAG_IGNORE_ZERO
+RAG_MAX_K, RAG_MIN_CAPACITY, RAG_STATS = 32, 64, 8  # include/pea_rag.h PEA_RAG_MAX_K, PEA_RAG_MIN_CAPACITY, PEA_RAG_STATS
+# the columns of pea_rag_build's stats [B][RAG_STATS] in order (include/pea_rag.h PEA_RAG_N_<NAME>)
+RAG_STAT_COLUMNS = ("edges", "edges_dropped", "pairs_dropped", "no_id", "not_touching", "skipped", "reserved0", "reserved1")
 DISC_STATS = 5  # loss, var, dist, reg, n_bad; then var_b, dist_b, reg_b, C_b per image (include/pea_disc.h PEA_DISC_STATS)
 
 EXPORTS = ("pea_version", "pea_strerror", "pea_desc_validate", "pea_workspace_bytes", "pea_workspace_init", "pea_reload_env",
@@ -95,6 +100,8 @@ EXPORTS_SEGSCORE = ("pea_seg_validate", "pea_seg_workspace_bytes", "pea_seg_work
 EXPORTS_INSTSCORE = ("pea_inst_validate", "pea_inst_workspace_bytes", "pea_inst_workspace_init", "pea_inst_scores")
 # the entry points of include/pea_cc.h (connected components: label, size filter, mask)
 EXPORTS_CC = ("pea_cc_validate", "pea_cc_workspace_bytes", "pea_cc_label")
+# the entry points of include/pea_rag.h (the region adjacency graph with affinity and boundary statistics; the projection)
+EXPORTS_RAG = ("pea_rag_validate", "pea_rag_workspace_bytes", "pea_rag_workspace_init", "pea_rag_build", "pea_rag_project")
 
 
 class PeaLibraryError(RuntimeError):
@@ -176,6 +183,19 @@ class PeaCcDesc(ctypes.Structure):
                 ("connectivity", ctypes.c_int32), ("min_size", ctypes.c_int32), ("flags", ctypes.c_uint32)]
 
 
+class PeaRagDesc(ctypes.Structure):
+    """mirror of `struct PeaRagDesc` in include/pea_rag.h"""
+    _fields_ = [("ndim", ctypes.c_int32), ("B", ctypes.c_int32), ("dims", ctypes.c_int32 * 3), ("K", ctypes.c_int32),
+                ("offsets", (ctypes.c_int32 * 3) * RAG_MAX_K), ("max_id", ctypes.c_int32), ("capacity", ctypes.c_int64),
+                ("max_edges", ctypes.c_int64), ("flags", ctypes.c_uint32)]
+
+
+class PeaRagBuffers(ctypes.Structure):
+    """mirror of `struct PeaRagBuffers` in include/pea_rag.h"""
+    _fields_ = [(n, ctypes.c_void_p) for n in ("fragments", "affs", "boundary", "uv", "size", "count", "mean", "bmean", "min", "max",
+                                               "node_size", "stats")]
+
+
 HIPCC_FLAGS = ["-O3", "--offload-arch=gfx950", "-std=c++17", "-fPIC"]
 OBJ_DIR = os.path.join(CSRC, "build")
 
@@ -201,7 +221,7 @@ def build(force=False, verbose=False, jobs=None):
 
 def _build_locked(force, verbose, jobs):
     srcs = sources()
-    hdrs = [HEADER, HEADER_INFER, HEADER_MULTI, HEADER_FLIP, HEADER_MULTI_LABELS, HEADER_HEAD16, HEADER_METRICS, HEADER_FGMASK, HEADER_DISC, HEADER_CROP, HEADER_DIST, HEADER_SEGSCORE, HEADER_INSTSCORE, HEADER_CC] + [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".h")]
+    hdrs = [HEADER, HEADER_INFER, HEADER_MULTI, HEADER_FLIP, HEADER_MULTI_LABELS, HEADER_HEAD16, HEADER_METRICS, HEADER_FGMASK, HEADER_DISC, HEADER_CROP, HEADER_DIST, HEADER_SEGSCORE, HEADER_INSTSCORE, HEADER_CC, HEADER_RAG] + [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".h")]
     newest_hdr = max(os.path.getmtime(h) for h in hdrs)
     if not force and os.path.exists(SO_PATH) and os.path.getmtime(SO_PATH) >= max([newest_hdr] + [os.path.getmtime(x) for x in srcs]):
         return SO_PATH
@@ -265,7 +285,7 @@ def lib():
         L = ctypes.CDLL(SO_PATH)
     except OSError as ex:
         raise PeaLibraryError("cannot load %s: %s" % (SO_PATH, ex))
-    for name in EXPORTS + EXPORTS_INFER + EXPORTS_MULTI + EXPORTS_FLIP + EXPORTS_MULTI_LABELS + EXPORTS_HEAD16 + EXPORTS_METRICS + EXPORTS_FGMASK + EXPORTS_DISC + EXPORTS_CROP + EXPORTS_DIST + EXPORTS_SEGSCORE + EXPORTS_INSTSCORE + EXPORTS_CC:
+    for name in EXPORTS + EXPORTS_INFER + EXPORTS_MULTI + EXPORTS_FLIP + EXPORTS_MULTI_LABELS + EXPORTS_HEAD16 + EXPORTS_METRICS + EXPORTS_FGMASK + EXPORTS_DISC + EXPORTS_CROP + EXPORTS_DIST + EXPORTS_SEGSCORE + EXPORTS_INSTSCORE + EXPORTS_CC + EXPORTS_RAG:
         if not hasattr(L, name):
             raise PeaLibraryError("%s does not export %s" % (SO_PATH, name))
     vp, dp = ctypes.c_void_p, ctypes.POINTER(PeaDesc)
@@ -426,6 +446,17 @@ def lib():
     L.pea_cc_workspace_bytes.argtypes = [cc]
     L.pea_cc_label.restype = ctypes.c_int
     L.pea_cc_label.argtypes = [cc, vp, vp, vp, vp, vp, ctypes.c_size_t, vp]
+    rg = ctypes.POINTER(PeaRagDesc)
+    L.pea_rag_validate.restype = ctypes.c_int
+    L.pea_rag_validate.argtypes = [rg]
+    L.pea_rag_workspace_bytes.restype = ctypes.c_size_t
+    L.pea_rag_workspace_bytes.argtypes = [rg]
+    L.pea_rag_workspace_init.restype = ctypes.c_int
+    L.pea_rag_workspace_init.argtypes = [vp, ctypes.c_size_t, vp]
+    L.pea_rag_build.restype = ctypes.c_int
+    L.pea_rag_build.argtypes = [rg, ctypes.POINTER(PeaRagBuffers), vp, ctypes.c_size_t, vp]
+    L.pea_rag_project.restype = ctypes.c_int
+    L.pea_rag_project.argtypes = [ctypes.c_int64, vp, vp, ctypes.c_int64, vp, vp, vp]
     if L.pea_version() != PEA_ABI_VERSION:
         raise PeaLibraryError("ABI mismatch: library %d, binding %d" % (L.pea_version(), PEA_ABI_VERSION))
     _lib = L

@@ -21,6 +21,7 @@
 //   pea_k_instscore.hip  the instance scores of the BBBC039V1 loop (include/pea_instscore.h) on the pair table of the segmentation
 //                      scores (pea_segtable.h: the pass over pixels and the slot helpers, shared by the two files)
 //   pea_k_cc.hip       connected components (include/pea_cc.h): tile pass in LDS, border merge, compress and count, scan, write
+//   pea_k_rag.hip      the region adjacency graph with affinity and boundary statistics (include/pea_rag.h) on the table of pea_segtable.h
 // Each kernel file exports a few plain functions (declared here) that pick the instantiation and launch it; a function returns
 // false when its family has no kernel for the descriptor and the caller tries the next one.  No device code crosses a file.
 // pea_dispatch.h holds what the launchers share to get from run-time facts (storage dtype, D, border, mask type, ..) to template
