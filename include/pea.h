@@ -359,6 +359,9 @@ int pea_fill_border_relu(float *affs, int B, int K, int Z, int Y, int X, int shi
  *          scripts_ac3ac4/data/data_affinity.py:53-102); neighbour outside: PEA_TGT_PADDING ? 1 : 0
  *   mask   [B,K,Z,Y,X] u8  = 1 iff p + o_i lies inside the image (nullable)
  *   weight [B,K,Z,Y,X] f32 = class balance per (b, channel) (nullable)
+ * An offset may reach past the image (|o_i| >= the dimension, which every other entry point refuses with PEA_E_DESC): every neighbour
+ * of that channel is then outside, as in gen_affs_ours, which shifts by the true offset -- target = padding, mask = 0, weight = 1.  The
+ * same holds for pea_label_weights and pea_targets_workspace_bytes; the rest of the descriptor is judged as pea_desc_validate judges it.
  * workspace: pea_targets_workspace_bytes(desc) bytes (integer counts; zeroed by the call). */
 #define PEA_TGT_PADDING 1u
 #define PEA_TGT_BOTH_FOREGROUND 2u

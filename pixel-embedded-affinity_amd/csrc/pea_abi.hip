@@ -51,6 +51,19 @@ int validate(const PeaDesc* d) {
   return PEA_OK;
 }
 
+// The label -> target calls (pea_gen_targets, pea_label_weights, pea_targets_workspace_bytes) read B, dims, K and the offsets only, and
+// for them an offset may reach past the image: gen_affs_ours shifts the label image by the true offset, every neighbour is then
+// outside (mask 0, target = padding) -- the coarsest deep-supervision scales are smaller than the stencil's reach.  Everything else is
+// judged as validate() judges it; the kernels get such an offset clamped to +-dim (gparams, pea_k_labels.hip).
+int validate_targets(const PeaDesc* d) {
+  if (!d) return PEA_E_NULL;
+  PeaDesc c = *d;
+  for (int i = 0; i < PEA_MAX_K; ++i)
+    for (int a = 0; a < 3; ++a)
+      if (c.dims[a] >= 1 && (c.offsets[i][a] <= -c.dims[a] || c.offsets[i][a] >= c.dims[a])) c.offsets[i][a] = 0;
+  return validate(&c);
+}
+
 KParams make_params(const PeaDesc* d) {
   KParams P;
   memset(&P, 0, sizeof(P));  // padding bytes too: KParams is the key of the plan memo (pea_host.h PlanCache)
@@ -341,13 +354,13 @@ int pea_affinity_bwd(const PeaDesc* desc, const void* e, const void* e_other, co
 }
 
 size_t pea_targets_workspace_bytes(const PeaDesc* desc) {
-  if (validate(desc)) return 0;
+  if (validate_targets(desc)) return 0;
   return label_counts_bytes(desc);
 }
 
 int pea_gen_targets(const PeaDesc* desc, const int32_t* labels, unsigned flags, float* target, uint8_t* mask, float* weight,
                     void* workspace, size_t workspace_bytes, void* stream) {
-  const int rc = validate(desc);
+  const int rc = validate_targets(desc);
   if (rc) return rc;
   if (!labels || !target) return PEA_E_NULL;
   if (misaligned(labels, 4) || misaligned(target, 4) || misaligned(weight, 4) || misaligned(workspace, 4)) return PEA_E_ALIGN;
@@ -359,7 +372,7 @@ int pea_gen_targets(const PeaDesc* desc, const int32_t* labels, unsigned flags, 
 
 int pea_label_weights(const PeaDesc* desc, const int32_t* labels, unsigned flags, float* wtab, void* workspace,
                       size_t workspace_bytes, void* stream) {
-  const int rc = validate(desc);
+  const int rc = validate_targets(desc);
   if (rc) return rc;
   if (!labels || !wtab) return PEA_E_NULL;
   if (misaligned(labels, 4) || misaligned(wtab, 4) || misaligned(workspace, 4)) return PEA_E_ALIGN;

@@ -203,7 +203,19 @@ __global__ __launch_bounds__(256) void k_scale_inplace(T* __restrict__ buf, size
     }
     if (i < n - 4 * n4) ((float*)buf)[4 * n4 + i] *= sc;
   } else {
-    for (size_t k = i * 4; k < min(n, i * 4 + 4); ++k) st(buf, k, ld(buf, k) * sc);
+    // The products exist as f32 before they are rounded to the storage type: folded into v_fma_mixlo_f16 (x * sc + 0) an f16 product of
+    // exactly zero loses its sign -- -1 * 0 came out as +0.  Four at a time where the lane has four (one 8-byte access each way).
+    const size_t k0 = i * 4;
+    if (k0 + 4 <= n) {
+      float v[4];
+#pragma unroll
+      for (int k = 0; k < 4; ++k) v[k] = ld(buf, k0 + k) * sc;
+      if constexpr (std::is_same<T, __half>::value) asm volatile("" : "+v"(v[0]), "+v"(v[1]), "+v"(v[2]), "+v"(v[3]));
+#pragma unroll
+      for (int k = 0; k < 4; ++k) st(buf, k0 + k, v[k]);
+    } else {
+      for (size_t k = k0; k < n; ++k) st_rounded(buf, k, ld(buf, k) * sc);
+    }
   }
 }
 
@@ -329,7 +341,7 @@ __global__ __launch_bounds__(256) void k_scale_multi(const ScaleMulti M, const f
     }
     for (size_t i = 4 * n4 + t; i < n; i += stride) st(buf, i, ld(buf, i) * sc);
   } else {
-    for (size_t i = t; i < n; i += stride) st(buf, i, ld(buf, i) * sc);
+    for (size_t i = t; i < n; i += stride) st_rounded(buf, i, ld(buf, i) * sc);  // (the sign of an f16 zero: see k_scale_inplace)
   }
 }
 
@@ -399,9 +411,10 @@ int pea_stitch_finalize(float* out_affs, const float* weight_map, int C, size_t 
   if (!out_affs || !weight_map) return PEA_E_NULL;
   if (C < 1) return PEA_E_DESC;
   if (misaligned(out_affs, 4) || misaligned(weight_map, 4)) return PEA_E_ALIGN;
+  if (voxels == 0) return PEA_OK;  // nothing to do: no launch and no question to the runtime (as pea_scale_inplace with n == 0)
   const size_t blocks = (voxels + 255) / 256;
   if (blocks > 0x7fffffffULL) return PEA_E_UNSUPPORTED;
-  if (voxels) hipLaunchKernelGGL(k_stitch_finalize, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, out_affs, weight_map, C, voxels);
+  hipLaunchKernelGGL(k_stitch_finalize, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, out_affs, weight_map, C, voxels);
   return hip_rc();
 }
 

@@ -58,8 +58,11 @@ GParams gparams(const PeaDesc* desc, unsigned flags) {
   G.B = desc->B; G.Z = desc->dims[0]; G.Y = desc->dims[1]; G.X = desc->dims[2]; G.K = desc->K;
   G.S = G.Z * G.Y * G.X;
   G.flags = flags;
+  // an offset that reaches past the image (|o| >= dim: every neighbour outside) goes to the kernels as +-dim -- the same answer, with
+  // coordinate + offset inside (-dim, 2 * dim)
+  const int dims[3] = {G.Z, G.Y, G.X};
   for (int i = 0; i < PEA_MAX_K; ++i)
-    for (int a = 0; a < 3; ++a) G.off[i][a] = i < desc->K ? desc->offsets[i][a] : 0;
+    for (int a = 0; a < 3; ++a) G.off[i][a] = i < desc->K ? std::min(std::max(desc->offsets[i][a], -dims[a]), dims[a]) : 0;
   return G;
 }
 

@@ -14,6 +14,24 @@ from .. import _lib
 from ..affinity_op import _labels_int32, AffinitySpec, make_desc
 
 
+def _targets_desc(spec, lab):
+    """the descriptor of pea_gen_targets for the int32 label image `lab`.  That call takes offsets that reach past the image (|o| >= dim:
+    every neighbour outside, as gen_affs_ours has it -- what embedding_loss_from_labels falls back to on the coarsest scales), which
+    pea_desc_validate, the rule of the embedding calls behind make_desc, refuses: such a table gets a descriptor of its own."""
+    dims = [1] * (4 - lab.dim()) + list(lab.shape[1:])
+    if all(abs(o[a]) < dims[a] for o in spec.offsets for a in range(3)):
+        # make_desc reads B / D / spatial dims off an embedding-shaped tensor: a meta tensor carries just the shape
+        return make_desc(spec, torch.empty((lab.shape[0], 1) + tuple(lab.shape[1:]), dtype=torch.float32, device="meta"))
+    d = _lib.PeaDesc()
+    d.abi, d.ndim, d.B, d.D, d.K = _lib.PEA_ABI_VERSION, spec.ndim, lab.shape[0], 1, spec.K
+    d.dims[:] = dims
+    d.border, d.norm, d.eps, d.dtype = spec.border, spec.norm, spec.eps, _lib.F32
+    for i, o in enumerate(spec.offsets):
+        d.offsets[i][:] = o
+        d.lam[i] = spec.lam[i]
+    return d
+
+
 def gen_targets(labels, offsets, padding=True, both_foreground=False, want_mask=True, want_weight=True):
     """labels: int tensor [B,H,W] or [B,Z,Y,X] on the GPU -> (target f32, mask u8 or None, weight f32 or None),
     each [B,K,...].  One call per scale of the deep-supervision pyramid."""
@@ -26,10 +44,8 @@ def gen_targets(labels, offsets, padding=True, both_foreground=False, want_mask=
     ndim = labels.dim() - 1
     lab = _labels_int32(labels)
     spec = AffinitySpec(ndim, offsets, None, _lib.BORDER_CROP_ZERO, _lib.NORM_FULL)
-    # make_desc reads B / D / spatial dims off an embedding-shaped tensor: a meta tensor carries just the shape
-    shape_probe = torch.empty((lab.shape[0], 1) + tuple(lab.shape[1:]), dtype=torch.float32, device="meta")
     with torch.cuda.device(lab.device):
-        d = make_desc(spec, shape_probe)
+        d = _targets_desc(spec, lab)
         kshape = (lab.shape[0], spec.K) + tuple(lab.shape[1:])
         target = torch.empty(kshape, dtype=torch.float32, device=lab.device)
         mask = torch.empty(kshape, dtype=torch.uint8, device=lab.device) if want_mask else None
