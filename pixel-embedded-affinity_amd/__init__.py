@@ -51,6 +51,8 @@ from .utils.postprocessing import remove_samll_object
 from .harness.rag import RegionAdjacency, project_node_labels, region_adjacency
 from .utils import lmc
 from .utils.lmc import mc_baseline, multicut_multi, probs_to_costs, transform_probabilities_to_costs
+from .harness.ws import (Watershed, WatershedSeeds, distance_transform_watershed, plateau_maxima, seeded_watershed, watershed_seeds)
+from .utils import fragment
 from .harness.handoff import AffsCollector
 from .harness.head_loss import HeadAffinityMSE, head_embedding_loss
 from .harness.train_step import CvpppTrainStep, convert_consistency_flip, label_pyramid, make_optimizer
@@ -97,3 +99,5 @@ CC_EXPORTS = ("connected_components", "ConnectedComponents", "remove_small_compo
 # likewise the region adjacency graph (include/pea_rag.h) and the reference's utils/lmc.py on it
 RAG_EXPORTS = ("region_adjacency", "RegionAdjacency", "project_node_labels", "lmc", "mc_baseline", "multicut_multi", "probs_to_costs",
                "transform_probabilities_to_costs")
+# likewise the watershed fragments (include/pea_ws.h) and the reference's scripts_ac3ac4/utils/fragment.py on them
+WS_EXPORTS = ("watershed_seeds", "WatershedSeeds", "seeded_watershed", "Watershed", "distance_transform_watershed", "plateau_maxima", "fragment")

@@ -27,6 +27,7 @@ HEADER_SEGSCORE = os.path.join(HERE, "..", "include", "pea_segscore.h")
 HEADER_INSTSCORE = os.path.join(HERE, "..", "include", "pea_instscore.h")
 HEADER_CC = os.path.join(HERE, "..", "include", "pea_cc.h")
 HEADER_RAG = os.path.join(HERE, "..", "include", "pea_rag.h")
+HEADER_WS = os.path.join(HERE, "..", "include", "pea_ws.h")
 
 PEA_ABI_VERSION = 2
 PEA_MAX_K = 32
@@ -64,6 +65,7 @@ RAG_ONE_MINUS, RAG_IGNORE_ZERO = 1, 2  # include/pea_rag.h PEA_RAG_ONE_MINUS, PE
 RAG_MAX_K, RAG_MIN_CAPACITY, RAG_STATS = 32, 64, 8  # include/pea_rag.h PEA_RAG_MAX_K, PEA_RAG_MIN_CAPACITY, PEA_RAG_STATS
 # the columns of pea_rag_build's stats [B][RAG_STATS] in order (include/pea_rag.h PEA_RAG_N_<NAME>)
 RAG_STAT_COLUMNS = ("edges", "edges_dropped", "pairs_dropped", "no_id", "not_touching", "skipped", "reserved0", "reserved1")
+WS_STACK_IDS, WS_FIELD, WS_MAX_RADIUS = 1, 2, 32  # include/pea_ws.h PEA_WS_STACK_IDS, PEA_WS_FIELD, PEA_WS_MAX_RADIUS
 DISC_STATS = 5  # loss, var, dist, reg, n_bad; then var_b, dist_b, reg_b, C_b per image (include/pea_disc.h PEA_DISC_STATS)
 
 EXPORTS = ("pea_version", "pea_strerror", "pea_desc_validate", "pea_workspace_bytes", "pea_workspace_init", "pea_reload_env",
@@ -102,6 +104,8 @@ EXPORTS_INSTSCORE = ("pea_inst_validate", "pea_inst_workspace_bytes", "pea_inst_
 EXPORTS_CC = ("pea_cc_validate", "pea_cc_workspace_bytes", "pea_cc_label")
 # the entry points of include/pea_rag.h (the region adjacency graph with affinity and boundary statistics; the projection)
 EXPORTS_RAG = ("pea_rag_validate", "pea_rag_workspace_bytes", "pea_rag_workspace_init", "pea_rag_build", "pea_rag_project")
+# the entry points of include/pea_ws.h (the watershed fragments: distance transform, seeds, flood)
+EXPORTS_WS = ("pea_ws_validate", "pea_ws_seeds_workspace_bytes", "pea_ws_flood_workspace_bytes", "pea_ws_seeds", "pea_ws_flood")
 
 
 class PeaLibraryError(RuntimeError):
@@ -196,6 +200,14 @@ class PeaRagBuffers(ctypes.Structure):
                                                "node_size", "stats")]
 
 
+class PeaWsDesc(ctypes.Structure):
+    """mirror of `struct PeaWsDesc` in include/pea_ws.h"""
+    _fields_ = [("N", ctypes.c_int32), ("Y", ctypes.c_int32), ("X", ctypes.c_int32), ("threshold", ctypes.c_float),
+                ("sigma_seeds", ctypes.c_float), ("sigma_weights", ctypes.c_float), ("alpha", ctypes.c_float),
+                ("maxima_connectivity", ctypes.c_int32), ("seed_connectivity", ctypes.c_int32), ("min_size", ctypes.c_int32),
+                ("flags", ctypes.c_uint32)]
+
+
 HIPCC_FLAGS = ["-O3", "--offload-arch=gfx950", "-std=c++17", "-fPIC"]
 OBJ_DIR = os.path.join(CSRC, "build")
 
@@ -221,7 +233,7 @@ def build(force=False, verbose=False, jobs=None):
 
 def _build_locked(force, verbose, jobs):
     srcs = sources()
-    hdrs = [HEADER, HEADER_INFER, HEADER_MULTI, HEADER_FLIP, HEADER_MULTI_LABELS, HEADER_HEAD16, HEADER_METRICS, HEADER_FGMASK, HEADER_DISC, HEADER_CROP, HEADER_DIST, HEADER_SEGSCORE, HEADER_INSTSCORE, HEADER_CC, HEADER_RAG] + [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".h")]
+    hdrs = [HEADER, HEADER_INFER, HEADER_MULTI, HEADER_FLIP, HEADER_MULTI_LABELS, HEADER_HEAD16, HEADER_METRICS, HEADER_FGMASK, HEADER_DISC, HEADER_CROP, HEADER_DIST, HEADER_SEGSCORE, HEADER_INSTSCORE, HEADER_CC, HEADER_RAG, HEADER_WS] + [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".h")]
     newest_hdr = max(os.path.getmtime(h) for h in hdrs)
     if not force and os.path.exists(SO_PATH) and os.path.getmtime(SO_PATH) >= max([newest_hdr] + [os.path.getmtime(x) for x in srcs]):
         return SO_PATH
@@ -285,7 +297,7 @@ def lib():
         L = ctypes.CDLL(SO_PATH)
     except OSError as ex:
         raise PeaLibraryError("cannot load %s: %s" % (SO_PATH, ex))
-    for name in EXPORTS + EXPORTS_INFER + EXPORTS_MULTI + EXPORTS_FLIP + EXPORTS_MULTI_LABELS + EXPORTS_HEAD16 + EXPORTS_METRICS + EXPORTS_FGMASK + EXPORTS_DISC + EXPORTS_CROP + EXPORTS_DIST + EXPORTS_SEGSCORE + EXPORTS_INSTSCORE + EXPORTS_CC + EXPORTS_RAG:
+    for name in EXPORTS + EXPORTS_INFER + EXPORTS_MULTI + EXPORTS_FLIP + EXPORTS_MULTI_LABELS + EXPORTS_HEAD16 + EXPORTS_METRICS + EXPORTS_FGMASK + EXPORTS_DISC + EXPORTS_CROP + EXPORTS_DIST + EXPORTS_SEGSCORE + EXPORTS_INSTSCORE + EXPORTS_CC + EXPORTS_RAG + EXPORTS_WS:
         if not hasattr(L, name):
             raise PeaLibraryError("%s does not export %s" % (SO_PATH, name))
     vp, dp = ctypes.c_void_p, ctypes.POINTER(PeaDesc)
@@ -457,6 +469,17 @@ def lib():
     L.pea_rag_build.argtypes = [rg, ctypes.POINTER(PeaRagBuffers), vp, ctypes.c_size_t, vp]
     L.pea_rag_project.restype = ctypes.c_int
     L.pea_rag_project.argtypes = [ctypes.c_int64, vp, vp, ctypes.c_int64, vp, vp, vp]
+    ws = ctypes.POINTER(PeaWsDesc)
+    L.pea_ws_validate.restype = ctypes.c_int
+    L.pea_ws_validate.argtypes = [ws]
+    L.pea_ws_seeds_workspace_bytes.restype = ctypes.c_size_t
+    L.pea_ws_seeds_workspace_bytes.argtypes = [ws]
+    L.pea_ws_flood_workspace_bytes.restype = ctypes.c_size_t
+    L.pea_ws_flood_workspace_bytes.argtypes = [ws]
+    L.pea_ws_seeds.restype = ctypes.c_int
+    L.pea_ws_seeds.argtypes = [ws, vp, vp, vp, vp, vp, vp, vp, ctypes.c_size_t, vp]
+    L.pea_ws_flood.restype = ctypes.c_int
+    L.pea_ws_flood.argtypes = [ws, vp, vp, vp, vp, vp, vp, ctypes.c_size_t, vp]
     if L.pea_version() != PEA_ABI_VERSION:
         raise PeaLibraryError("ABI mismatch: library %d, binding %d" % (L.pea_version(), PEA_ABI_VERSION))
     _lib = L

@@ -244,29 +244,7 @@ __global__ __launch_bounds__(kBlock) void k_cc_compress(const CcParams P, int* _
 }
 
 // ---- 4 - 6. the scan ----------------------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ int wave_scan_incl(int v, int lane) {
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const int t = __shfl_up(v, o, 64);
-    if (lane >= o) v += t;
-  }
-  return v;
-}
-// the exclusive prefix of v over the workgroup's lanes and the workgroup's total (the whole workgroup calls it: two barriers)
-__device__ __forceinline__ int block_scan_excl(int v, int* total) {
-  static_assert(kBlock / 64 == 4, "written for four waves");
-  __shared__ int s_wave[kBlock / 64];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int incl = wave_scan_incl(v, lane);
-  if (lane == 63) s_wave[wave] = incl;
-  __syncthreads();
-  int before = 0;
-#pragma unroll
-  for (int w = 0; w < kBlock / 64; ++w) before += w < wave ? s_wave[w] : 0;
-  *total = s_wave[0] + s_wave[1] + s_wave[2] + s_wave[3];
-  __syncthreads();
-  return before + incl - v;
-}
+// (wave_scan_incl and block_scan_excl: pea_stream.h, shared with pea_k_ws.hip)
 // the lane's quad: bit e of *root: pixel i0 + e is a root; bit e of *kept: a root of at least min_size pixels
 __device__ __forceinline__ void quad_roots(const CcParams& P, const int* __restrict__ par, const int* __restrict__ sz, size_t i0, int nv,
                                            unsigned* root, unsigned* kept) {

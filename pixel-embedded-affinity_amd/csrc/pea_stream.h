@@ -5,6 +5,7 @@
 //              + e of the run, so a step of a wave is 1 KiB of an f32 tensor (lane_run)
 //   quad run   a workgroup owns kQuadRun = 1024 elements, a lane ONE quad (quad_start); seen by waves, a WAVE owns kWaveRun = 256
 //              consecutive elements and keeps them in registers (wave_start: the same element-to-lane assignment)
+//   scans      wave_scan_incl, block_scan_excl: the prefix sums of pea_k_cc.hip and pea_k_ws.hip
 #pragma once
 #include "pea_host.h"
 #include "pea_quad.h"
@@ -88,6 +89,30 @@ __device__ __forceinline__ T wave_max(T v) {
   return v;
 }
 
+// ---- scans (pea_k_cc.hip, pea_k_ws.hip) -----------------------------------------------------------------------------------------------
+__device__ __forceinline__ int wave_scan_incl(int v, int lane) {
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1) {
+    const int t = __shfl_up(v, o, 64);
+    if (lane >= o) v += t;
+  }
+  return v;
+}
+// the exclusive prefix of v over the workgroup's lanes and the workgroup's total (the whole workgroup calls it: two barriers)
+__device__ __forceinline__ int block_scan_excl(int v, int* total) {
+  static_assert(kBlock / 64 == 4, "written for four waves");
+  __shared__ int s_wave[kBlock / 64];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int incl = wave_scan_incl(v, lane);
+  if (lane == 63) s_wave[wave] = incl;
+  __syncthreads();
+  int before = 0;
+#pragma unroll
+  for (int w = 0; w < kBlock / 64; ++w) before += w < wave ? s_wave[w] : 0;
+  *total = s_wave[0] + s_wave[1] + s_wave[2] + s_wave[3];
+  __syncthreads();
+  return before + incl - v;
+}
 // The end of a streaming reduction of N sums per lane: a wave reduces each with wave_sum, the four waves meet in LDS and lane 0 of the
 // workgroup hands sum k, ((p0 + p1) + p2) + p3 of the waves' partials, to f(k, v).  The whole workgroup calls it (a barrier).
 template <int N, typename F>

@@ -133,3 +133,43 @@ def synth_nuclei(B, Y, X, n, radius, seed, specks=0):
             y, x, s = int(rng.integers(0, Y)), int(rng.integers(0, X)), 1 + k % 2
             out[b, y:y + s, x:x + s] = n + 1
     return out
+
+
+def synth_membranes(N, Y, X, cells, seed, gap=2, gaps_per_plane=6, inside=0.05, noise=0.0):
+    """a synthetic boundary map [N, Y, X] float32: the walls of `cells` Voronoi cells per plane (1 on a pixel whose right or lower
+    neighbour belongs to another cell, `inside` elsewhere), `gaps_per_plane` stretches of `gap` wall pixels set back to `inside`, plus
+    `noise` * uniform[0, 1) -> (boundary, cells int32 [N, Y, X]).  The cells are found on a coarse grid of sites, so the cost does not
+    grow with cells * pixels."""
+    rng = np.random.default_rng(seed)
+    b = np.empty((N, Y, X), np.float32)
+    lab = np.empty((N, Y, X), np.int32)
+    gy = max(1, int(round(np.sqrt(cells * Y / float(X)))))
+    gx = max(1, int(round(cells / float(gy))))
+    yy, xx = np.mgrid[0:Y, 0:X]
+    cy, cx = np.minimum(yy * gy // Y, gy - 1), np.minimum(xx * gx // X, gx - 1)
+    for n in range(N):
+        # one jittered site per grid box: the nearest site of a pixel lies in its box or one of the 24 around it
+        sy = (np.arange(gy)[:, None] + rng.uniform(0.1, 0.9, (gy, gx))) * (Y / float(gy))
+        sx = (np.arange(gx)[None, :] + rng.uniform(0.1, 0.9, (gy, gx))) * (X / float(gx))
+        best = np.full((Y, X), np.inf)
+        c = np.zeros((Y, X), np.int32)
+        for dy in range(-2, 3):
+            for dx in range(-2, 3):
+                by, bx = np.clip(cy + dy, 0, gy - 1), np.clip(cx + dx, 0, gx - 1)
+                d = (yy - sy[by, bx]) ** 2 + (xx - sx[by, bx]) ** 2
+                closer = d < best
+                best = np.where(closer, d, best)
+                c = np.where(closer, by * gx + bx + 1, c).astype(np.int32)
+        wall = np.zeros((Y, X), bool)
+        wall[:, :-1] |= c[:, 1:] != c[:, :-1]
+        wall[:-1, :] |= c[1:, :] != c[:-1, :]
+        ys, xs = np.nonzero(wall[:, :max(1, X - gap)])
+        if len(ys):
+            for k in rng.choice(len(ys), size=min(gaps_per_plane, len(ys)), replace=False):
+                wall[ys[k], xs[k]:xs[k] + gap] = False
+        plane = np.where(wall, 1.0, inside)
+        if noise:
+            plane = plane + noise * rng.uniform(0.0, 1.0, (Y, X))
+        b[n] = plane
+        lab[n] = c
+    return b, lab
