@@ -92,8 +92,9 @@ typedef struct PeaDiscDesc {
  * D > PEA_DISC_MAX_D (checked last). */
 int pea_disc_validate(const PeaDiscDesc *d);
 
-/* Host-only: bytes of the transient accumulator tables (a multiple of 8; 0 for a descriptor that pea_disc_validate refuses): a
- * header, one accumulator per image and one row of 2 + 3 D words per (image, id). */
+/* Host-only: bytes of the transient accumulator tables (a multiple of 8): a header of 8 words, an accumulator of 4 words per image and
+ * one row of 2 + 3 D words per (image, id).  0 for a descriptor that does not validate; SIZE_MAX where the count does not fit (no
+ * descriptor that validates reaches it: B < 2^31, num_ids <= 4096, D <= 64). */
 size_t pea_disc_workspace_bytes(const PeaDiscDesc *d);
 
 /* Prepare `bytes` bytes at `workspace` (8-byte aligned, bytes >= 64 and a multiple of 8) once per allocation: all zero but for a
@@ -102,9 +103,10 @@ size_t pea_disc_workspace_bytes(const PeaDiscDesc *d);
  * of 8). */
 int pea_disc_workspace_init(void *workspace, size_t bytes, void *stream);
 
-/* Host-only: bytes of what the forward leaves for the backward (a multiple of 8; 0 for a refused descriptor): per image C_b, dist_b
- * and reg_b; per (image, id) n_c, the compacted id list, k_c and w_c; per (image, id, channel) mu_c and the finished G_c / n_c.  The
- * forward writes every byte of it.  It stays valid until the caller overwrites it. */
+/* Host-only: bytes of what the forward leaves for the backward (a multiple of 8): per image C_b, dist_b and reg_b; per (image, id)
+ * n_c, the compacted id list, k_c and w_c; per (image, id, channel) mu_c and the finished G_c / n_c; every array padded to 8 bytes.
+ * 0 for a descriptor that does not validate; SIZE_MAX where the count does not fit (as above: never reached).  The forward writes
+ * every byte of it.  It stays valid until the caller overwrites it. */
 size_t pea_disc_context_bytes(const PeaDiscDesc *d);
 
 /* e [B, D, S] of dtype; labels int32 [B, S]; loss f32 [1]; stats f64 [PEA_DISC_STATS + 4 B] = { loss, var, dist, reg, n_bad, then per

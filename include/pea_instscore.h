@@ -93,8 +93,10 @@ typedef struct PeaInstDesc {
  * 1; any flag bit; or PEA_E_UNSUPPORTED for match_iou < 0.5 (the Munkres branch) or S > 2^31 - 1 (checked last). */
 int pea_inst_validate(const PeaInstDesc *d);
 
-/* Host-only: bytes of the workspace (a multiple of 8; 0 for a descriptor that pea_inst_validate refuses).  Strictly increasing in
- * B, capacity and max_id; S plays no part. */
+/* Host-only: bytes of the workspace (a multiple of 8): a header of 8 words, 32 words per image, 6 words per (image, slot), 2 words per
+ * (image, present gt id) with room for min(max_id + 1, capacity) of them, and three int32 per (image, id), padded to 8 bytes together.
+ * Strictly increasing in B, capacity and max_id; S plays no part.  0 for a descriptor that does not validate; SIZE_MAX where the
+ * count does not fit. */
 size_t pea_inst_workspace_bytes(const PeaInstDesc *d);
 
 /* Prepare `bytes` bytes at `ws` (8-byte aligned, bytes >= 64 and a multiple of 8) once per allocation: all zero but for a magic word.

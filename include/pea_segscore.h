@@ -93,8 +93,9 @@ typedef struct PeaSegDesc {
  * PEA_SEG_MIN_CAPACITY, above 2^31 or no power of two; any flag bit; or PEA_E_UNSUPPORTED for S > 2^31 - 1 (checked last). */
 int pea_seg_validate(const PeaSegDesc *d);
 
-/* Host-only: bytes of the tables (a multiple of 8; 0 for a descriptor that pea_seg_validate refuses): a header, 32 words per image
- * and 10 words per (image, slot).  Strictly increasing in capacity and in B; S plays no part. */
+/* Host-only: bytes of the tables (a multiple of 8): a header of 8 words, 32 words per image and 10 words per (image, slot).  Strictly
+ * increasing in capacity and in B; S plays no part.  0 for a descriptor that does not validate; SIZE_MAX where the count does not
+ * fit. */
 size_t pea_seg_workspace_bytes(const PeaSegDesc *d);
 
 /* Prepare `bytes` bytes at `workspace` (8-byte aligned, bytes >= 64 and a multiple of 8) once per allocation: all zero but for a

@@ -245,6 +245,11 @@ def stream_workspace(family, dev, nb, init, name):
     return w
 
 
+def _no_init(_ptr_, _bytes, _stream_):
+    """the `init` of a stream_workspace that is scratch (pea_cc_label, pea_ws_seeds, pea_ws_flood): it needs no preparation"""
+    return 0
+
+
 def workspace(dev, desc, nstates=1):
     """(tensor, bytes): the loss-state block(s) of the training forward for the CURRENT stream of `dev` (include/pea.h,
     pea_workspace_bytes), ~16 KB per state: the stream_workspace of ("loss", nstates)."""

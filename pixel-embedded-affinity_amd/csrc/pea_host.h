@@ -33,13 +33,18 @@
 // pea_epilogue.h holds what every training forward ends with: the loss term of a pair (scalar and quad form), wave_sum63 and the
 // workgroup's tail into the loss state; pea_gather.h and the LDS-staged families include it.
 // pea_stream.h (on pea_quad.h: a lane's quad loads and stores) holds what the four streaming reductions are made of: the lane-run and
-// wave-run walks, the tail quad, wave_sum / wave_max / block_sums, the peel, the cropped cursor, the table workspace, stream_grid.
+// wave-run walks, the tail quad, wave_sum / wave_max / block_sums, the peel, the cropped cursor, the table workspace, stream_grid;
+// and what the label kernels share: the workgroup scan, the relaxed agent-scope accesses, f32_ord, the launch chain.
+// pea_carve.h (plain C++) holds mul_sat / add_sat / al8 and the Carver, over which every label family states its workspace once.
 #pragma once
 #include <stdint.h>
 #include <stdlib.h>
 #include <string.h>
 
+#include "pea_carve.h"
 #include "pea_loss.h"
+
+struct PeaCcDesc;  // include/pea_cc.h
 
 namespace pea {
 
@@ -74,11 +79,6 @@ void env_reload();          // pea_reload_env(): tests that change a switch call
 unsigned env_generation();  // = env().gen; a new one with every env_reload(): memoised plans that baked a switch in (PEA_ZBLK_*, ..) are dropped
 
 inline bool misaligned(const void* p, size_t a) { return ((uintptr_t)p & (a - 1)) != 0; }
-// a * b, UINT64_MAX where it does not fit
-inline uint64_t mul_sat(uint64_t a, uint64_t b) {
-  uint64_t r;
-  return __builtin_mul_overflow(a, b, &r) ? UINT64_MAX : r;
-}
 // bytes per element of the embedding's storage dtype (validate() admits PEA_F32, PEA_F16 and PEA_BF16 only)
 inline size_t dtype_bytes(int dtype) { return dtype == PEA_F32 ? 4 : 2; }
 // N_i of include/pea.h: what the loss of offset i is divided by (1 / N_i in the loss finish, 2 lambda_i / N_i in g)
@@ -227,6 +227,10 @@ size_t label_counts_bytes(const PeaDesc* d);
 int label_weights(const PeaDesc* d, const int32_t* labels, unsigned flags, float* wtab, void* ws, hipStream_t s);
 int gen_targets(const PeaDesc* d, const int32_t* labels, unsigned flags, float* target, uint8_t* mask, float* weight, void* ws,
                 size_t need, hipStream_t s);
+
+// connected components (pea_k_cc.hip): does pea_cc_label take the descriptor's extent (S < 2^31, the tile grid, the pixel grid)?  Asked
+// by pea_ws_seeds (pea_k_ws.hip), which calls pea_cc_label between its own launches and refuses before its first one
+bool cc_grids_fit(const PeaCcDesc* d);
 
 // caller epilogues, stitcher, rescale (pea_k_direct.hip); head and target generation (pea_k_head.hip): the ABI functions
 // themselves live in those files (they need no descriptor logic)

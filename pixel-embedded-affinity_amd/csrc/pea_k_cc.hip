@@ -22,11 +22,12 @@
 //   3 k_cc_compress  every pixel finds its root and writes it back; a wave peels its equal roots (pea_stream.h) and adds one count per
 //                    (wave, root) to size[root] -- a blob that fills a tile costs 16 atomics on its root, not 1024.
 //   4 k_cc_totals    per 1024 pixels of an image: how many roots, how many kept ones (parent[i] == i, size[i] >= min_size)
-//   5 k_cc_scan      one workgroup per image: exclusive prefix of the kept totals, in place; counts[b]
+//   5 k_cc_scan      one workgroup per image: exclusive prefix of the kept totals (block_scan_excl, pea_stream.h), in place; counts[b]
 //   6 k_cc_apply     size[root] = the root's new id = prefix of its block + its rank in the block + 1, 0 for a dropped one.  A root is its
 //                    component's first pixel, so the scan in flat order IS the raster-order numbering.
 //   7 k_cc_write     labels_out[p] = size[parent[p]], mask_out[p] = that != 0
 // Every value is an integer; roots are minima and sizes integer sums, so no result depends on the order in which workgroups arrive.
+// Host: cc_layout carves the three blocks (pea_carve.h), cc_grids decides what pea_cc_label takes (pea::cc_grids_fit for pea_k_ws.hip).
 #include "../../include/pea_cc.h"
 #include "pea_stream.h"
 
@@ -39,9 +40,6 @@ constexpr int kTilePix = kTile * kTile;
 constexpr int kTileSteps = kTilePix / kBlock;  // pixels per lane: local index step * 256 + lane, so a wave reads two rows of the tile
 constexpr int kNoLabel = 0x7fffffff;        // the LDS label of a background pixel
 static_assert(kTilePix == kBlock * kTileSteps && kBlock % kTile == 0, "a workgroup's step is whole rows of the tile");
-
-#define PEA_CC_LD(p) __hip_atomic_load((p), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)
-#define PEA_CC_ST(p, v) __hip_atomic_store((p), (v), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)
 
 struct CcParams {
   size_t S;            // Z * Y * X
@@ -139,7 +137,7 @@ __global__ __launch_bounds__(kBlock) void k_cc_tile(const CcParams P, const T* _
 // the root of x: a step goes to a strictly smaller index or the walk is over, so it ends whatever the words hold
 __device__ __forceinline__ int cc_find(int* par, int x) {
   for (;;) {
-    const int p = PEA_CC_LD(par + x);
+    const int p = PEA_LD_AGENT(par + x);
     if (p >= x || p < 0) return x;
     x = p;
   }
@@ -219,10 +217,10 @@ __global__ __launch_bounds__(kBlock) void k_cc_compress(const CcParams P, int* _
   for (int e = 0; e < kQuad; ++e) {
     key[e] = 0;
     if (e < nv) {
-      const int first = PEA_CC_LD(par + i0 + e);
+      const int first = PEA_LD_AGENT(par + i0 + e);
       if (first >= 0) {
         const int r = cc_find(par, first);
-        if (r != first) PEA_CC_ST(par + i0 + e, r);  // (whoever walks through this word meets the old ancestor or the root)
+        if (r != first) PEA_ST_AGENT(par + i0 + e, r);  // (whoever walks through this word meets the old ancestor or the root)
         key[e] = r + 1;
         open |= 1u << e;
       }
@@ -244,7 +242,6 @@ __global__ __launch_bounds__(kBlock) void k_cc_compress(const CcParams P, int* _
 }
 
 // ---- 4 - 6. the scan ----------------------------------------------------------------------------------------------------------------------
-// (wave_scan_incl and block_scan_excl: pea_stream.h, shared with pea_k_ws.hip)
 // the lane's quad: bit e of *root: pixel i0 + e is a root; bit e of *kept: a root of at least min_size pixels
 __device__ __forceinline__ void quad_roots(const CcParams& P, const int* __restrict__ par, const int* __restrict__ sz, size_t i0, int nv,
                                            unsigned* root, unsigned* kept) {
@@ -356,7 +353,38 @@ __global__ __launch_bounds__(kBlock) void k_cc_write(const CcParams P, const int
 inline uint64_t cc_pixels(const PeaCcDesc* d) { return mul_sat(mul_sat((uint64_t)d->dims[0], (uint64_t)d->dims[1]), (uint64_t)d->dims[2]); }
 inline uint64_t cc_chunks(uint64_t S) { return S / kQuadRun + (S % kQuadRun ? 1 : 0); }
 
+// parent and size, int32 [B, S] each, then the scan's totals, int32 [B, chunks, 2]: three blocks without padding
+struct CcWs { int *parent, *size, *tot; };
+inline size_t cc_layout(const PeaCcDesc* d, void* base, CcWs* w) {
+  const uint64_t S = cc_pixels(d), BS = mul_sat((uint64_t)d->B, S);
+  Carver c(base);
+  w->parent = c.take<int>(BS, 4);
+  w->size = c.take<int>(BS, 4);
+  w->tot = c.take<int>(mul_sat(mul_sat((uint64_t)d->B, cc_chunks(S)), 2), 4);
+  return c.bytes();
+}
+
+// S < 2^31, a grid of one workgroup per tile and one per kQuadRun pixels of an image: P's geometry and the two grids
+inline bool cc_grids(const PeaCcDesc* d, CcParams* P, unsigned* tiles, unsigned* groups) {
+  const uint64_t S = cc_pixels(d);
+  if (S >= (1ull << 31)) return false;
+  P->S = (size_t)S;
+  P->Z = d->dims[0]; P->Y = d->dims[1]; P->X = d->dims[2];
+  P->ty = (unsigned)((d->dims[1] + kTile - 1) / kTile);
+  P->tx = (unsigned)((d->dims[2] + kTile - 1) / kTile);
+  const uint64_t t = mul_sat(mul_sat((uint64_t)d->B, (uint64_t)d->dims[0]), (uint64_t)P->ty * P->tx);
+  if (t > 0x7fffffffULL || !stream_grid(S, (uint64_t)d->B, kQuadRun, &P->chunks, groups)) return false;
+  *tiles = (unsigned)t;
+  return true;
+}
+
 }  // namespace
+
+bool pea::cc_grids_fit(const PeaCcDesc* d) {
+  CcParams P;
+  unsigned tiles, groups;
+  return cc_grids(d, &P, &tiles, &groups);
+}
 
 extern "C" int pea_cc_validate(const PeaCcDesc* d) {
   if (!d) return PEA_E_NULL;
@@ -370,14 +398,9 @@ extern "C" int pea_cc_validate(const PeaCcDesc* d) {
   return PEA_OK;
 }
 
-// parent and size, int32 [B, S] each, then the scan's totals, int32 [B, chunks, 2]
 extern "C" size_t pea_cc_workspace_bytes(const PeaCcDesc* d) {
-  if (pea_cc_validate(d)) return 0;
-  const uint64_t S = cc_pixels(d);
-  if (S == UINT64_MAX) return SIZE_MAX;
-  const uint64_t per_image = mul_sat(8, S + cc_chunks(S));
-  const uint64_t all = mul_sat((uint64_t)d->B, per_image);
-  return all > (uint64_t)SIZE_MAX ? SIZE_MAX : (size_t)all;
+  CcWs w;
+  return pea_cc_validate(d) ? 0 : cc_layout(d, nullptr, &w);
 }
 
 extern "C" int pea_cc_label(const PeaCcDesc* d, const void* in, int32_t* labels_out, uint8_t* mask_out, int32_t* counts, void* workspace,
@@ -387,40 +410,24 @@ extern "C" int pea_cc_label(const PeaCcDesc* d, const void* in, int32_t* labels_
   if (!in || !counts || (!labels_out && !mask_out)) return PEA_E_NULL;
   if ((d->in_type == PEA_CC_IN_I32 && misaligned(in, 4)) || misaligned(labels_out, 4) || misaligned(counts, 4) || misaligned(workspace, 4))
     return PEA_E_ALIGN;
-  if (!workspace || workspace_bytes < pea_cc_workspace_bytes(d)) return PEA_E_WORKSPACE;
-  const uint64_t S = cc_pixels(d);
-  if (S >= (1ull << 31)) return PEA_E_UNSUPPORTED;
+  CcWs w;
+  if (!workspace || workspace_bytes < cc_layout(d, workspace, &w)) return PEA_E_WORKSPACE;
   CcParams P;
-  P.S = (size_t)S;
-  P.Z = d->dims[0]; P.Y = d->dims[1]; P.X = d->dims[2];
-  P.ty = (unsigned)((d->dims[1] + kTile - 1) / kTile);
-  P.tx = (unsigned)((d->dims[2] + kTile - 1) / kTile);
+  unsigned tiles, groups;
+  if (!cc_grids(d, &P, &tiles, &groups)) return PEA_E_UNSUPPORTED;
   P.conn = d->connectivity;
   P.min_size = d->min_size;
-  const uint64_t tiles = mul_sat(mul_sat((uint64_t)d->B, (uint64_t)d->dims[0]), (uint64_t)P.ty * P.tx);
-  unsigned groups;
-  if (tiles > 0x7fffffffULL || !stream_grid(S, (uint64_t)d->B, kQuadRun, &P.chunks, &groups)) return PEA_E_UNSUPPORTED;
 
-  hipStream_t s = (hipStream_t)stream;
-  int* parent = (int*)workspace;
-  int* size = parent + (size_t)d->B * P.S;
-  int* tot = size + (size_t)d->B * P.S;
-  const dim3 tg((unsigned)tiles), fg(groups), blk(kBlock);
-  int rc;
-  if (d->in_type == PEA_CC_IN_U8) hipLaunchKernelGGL(k_cc_tile<uint8_t>, tg, blk, 0, s, P, (const uint8_t*)in, parent, size);
-  else hipLaunchKernelGGL(k_cc_tile<int32_t>, tg, blk, 0, s, P, (const int32_t*)in, parent, size);
-  if ((rc = hip_rc())) return rc;
-  if (d->in_type == PEA_CC_IN_U8) hipLaunchKernelGGL(k_cc_merge<uint8_t>, tg, blk, 0, s, P, (const uint8_t*)in, parent);
-  else hipLaunchKernelGGL(k_cc_merge<int32_t>, tg, blk, 0, s, P, (const int32_t*)in, parent);
-  if ((rc = hip_rc())) return rc;
-  hipLaunchKernelGGL(k_cc_compress, fg, blk, 0, s, P, parent, size);
-  if ((rc = hip_rc())) return rc;
-  hipLaunchKernelGGL(k_cc_totals, fg, blk, 0, s, P, (const int*)parent, (const int*)size, tot);
-  if ((rc = hip_rc())) return rc;
-  hipLaunchKernelGGL(k_cc_scan, dim3((unsigned)d->B), blk, 0, s, P, tot, counts);
-  if ((rc = hip_rc())) return rc;
-  hipLaunchKernelGGL(k_cc_apply, fg, blk, 0, s, P, (const int*)parent, size, (const int*)tot);
-  if ((rc = hip_rc())) return rc;
-  hipLaunchKernelGGL(k_cc_write, fg, blk, 0, s, P, (const int*)parent, (const int*)size, labels_out, mask_out);
-  return hip_rc();
+  LaunchChain chain(stream);
+  const bool u8 = d->in_type == PEA_CC_IN_U8;
+  if (u8) chain(k_cc_tile<uint8_t>, tiles, kBlock, P, (const uint8_t*)in, w.parent, w.size);
+  else chain(k_cc_tile<int32_t>, tiles, kBlock, P, (const int32_t*)in, w.parent, w.size);
+  if (u8) chain(k_cc_merge<uint8_t>, tiles, kBlock, P, (const uint8_t*)in, w.parent);
+  else chain(k_cc_merge<int32_t>, tiles, kBlock, P, (const int32_t*)in, w.parent);
+  chain(k_cc_compress, groups, kBlock, P, w.parent, w.size);
+  chain(k_cc_totals, groups, kBlock, P, w.parent, w.size, w.tot);
+  chain(k_cc_scan, d->B, kBlock, P, w.tot, counts);
+  chain(k_cc_apply, groups, kBlock, P, w.parent, w.size, w.tot);
+  chain(k_cc_write, groups, kBlock, P, w.parent, w.size, labels_out, mask_out);
+  return chain.rc;
 }

@@ -73,30 +73,26 @@ struct DiscK {
 };
 
 inline size_t tables_layout(const PeaDiscDesc* d, void* base, Tables* t) {
-  const size_t R = kRowHead + 3 * (size_t)d->D;
-  if (t) {
-    t->hdr = (u64*)base;
-    t->img = t->hdr + kHdrWords;
-    t->rows = t->img + (size_t)kImgWords * d->B;
-    t->R = (int)R;
-  }
-  return 8 * (kHdrWords + (size_t)kImgWords * d->B + (size_t)d->B * d->num_ids * R);
+  const uint64_t B = (uint64_t)d->B, R = kRowHead + 3 * (uint64_t)d->D;
+  Carver c(base);
+  t->hdr = c.take<u64>(kHdrWords);
+  t->img = c.take<u64>(kImgWords * B);
+  t->rows = c.take<u64>(mul_sat(B * (uint64_t)d->num_ids, R));
+  t->R = (int)R;
+  return c.bytes();
 }
-inline size_t ctx_layout(const PeaDiscDesc* d, void* base, Ctx* c) {
-  const size_t B = d->B, BN = B * d->num_ids, BND = BN * d->D;
-  size_t o = 0;
-  char* p = (char*)base;
-  Ctx x;
-  x.img = (double*)(p + o); o += 16 * B;
-  x.cb = (int*)(p + o); o += al8(4 * B);
-  x.n = (int*)(p + o); o += al8(4 * BN);
-  x.ids = (int*)(p + o); o += al8(4 * BN);
-  x.kc = (float*)(p + o); o += al8(4 * BN);
-  x.w = (float*)(p + o); o += al8(4 * BN);
-  x.mu = (float*)(p + o); o += al8(4 * BND);
-  x.gn = (float*)(p + o); o += al8(4 * BND);
-  if (c) *c = x;
-  return o;
+inline size_t ctx_layout(const PeaDiscDesc* d, void* base, Ctx* x) {
+  const uint64_t B = (uint64_t)d->B, BN = B * (uint64_t)d->num_ids, BND = mul_sat(BN, (uint64_t)d->D);
+  Carver c(base);
+  x->img = c.take<double>(2 * B);
+  x->cb = c.take<int>(B);
+  x->n = c.take<int>(BN);
+  x->ids = c.take<int>(BN);
+  x->kc = c.take<float>(BN);
+  x->w = c.take<float>(BN);
+  x->mu = c.take<float>(BND);
+  x->gn = c.take<float>(BND);
+  return c.bytes();
 }
 
 // wave_sum(float) of pea_stream.h written out for k_disc_pull, which came out 0.8 % slower behind the template (profiles/README.md)
@@ -556,9 +552,15 @@ extern "C" int pea_disc_validate(const PeaDiscDesc* d) {
   return PEA_OK;
 }
 
-extern "C" size_t pea_disc_workspace_bytes(const PeaDiscDesc* d) { return pea_disc_validate(d) ? 0 : tables_layout(d, nullptr, nullptr); }
+extern "C" size_t pea_disc_workspace_bytes(const PeaDiscDesc* d) {
+  Tables t;
+  return pea_disc_validate(d) ? 0 : tables_layout(d, nullptr, &t);
+}
 
-extern "C" size_t pea_disc_context_bytes(const PeaDiscDesc* d) { return pea_disc_validate(d) ? 0 : ctx_layout(d, nullptr, nullptr); }
+extern "C" size_t pea_disc_context_bytes(const PeaDiscDesc* d) {
+  Ctx c;
+  return pea_disc_validate(d) ? 0 : ctx_layout(d, nullptr, &c);
+}
 
 extern "C" int pea_disc_workspace_init(void* workspace, size_t bytes, void* stream) {
   return table_workspace_init<kDiscMagic>(workspace, bytes, stream);
@@ -572,32 +574,25 @@ extern "C" int pea_disc_loss_fwd(const PeaDiscDesc* d, const void* e, const int3
   if (misaligned(e, dtype_bytes(d->dtype)) || misaligned(labels, 4) || misaligned(loss, 4) || misaligned(stats, 8) || misaligned(ctx, 8) ||
       misaligned(workspace, 8))
     return PEA_E_ALIGN;
-  const size_t need = pea_disc_workspace_bytes(d);
+  Tables Tb;
+  const size_t need = tables_layout(d, workspace, &Tb);
   if (!workspace || workspace_bytes < need) return PEA_E_WORKSPACE;
   unsigned chunks, groups;
   if (!disc_grid(d, &chunks, &groups)) return PEA_E_UNSUPPORTED;
 
-  hipStream_t s = (hipStream_t)stream;
   const DiscK K = disc_params(d);
-  Tables Tb;
   Ctx C;
-  tables_layout(d, workspace, &Tb);
   ctx_layout(d, ctx, &C);
-  const size_t S = (size_t)d->S;
-  int rc = with_storage(d->dtype, [&](auto t) {
+  LaunchChain chain(stream);
+  with_storage(d->dtype, [&](auto t) {
     using T = typename decltype(t)::type;
-    hipLaunchKernelGGL((k_disc_sums<T>), dim3(groups), dim3(kBlock), 0, s, S, chunks, K, (const T*)e, labels, Tb);
-    int r = hip_rc();
-    if (r) return r;
-    hipLaunchKernelGGL(k_disc_clusters, dim3((unsigned)d->B), dim3(kClBlock), 0, s, K, Tb, C);
-    if ((r = hip_rc())) return r;
-    if (K.grad) hipLaunchKernelGGL((k_disc_pull<T, true>), dim3(groups), dim3(kBlock), 0, s, S, chunks, K, (const T*)e, labels, Tb, C);
-    else hipLaunchKernelGGL((k_disc_pull<T, false>), dim3(groups), dim3(kBlock), 0, s, S, chunks, K, (const T*)e, labels, Tb, C);
-    if ((r = hip_rc())) return r;
-    hipLaunchKernelGGL(k_disc_finish, dim3(1), dim3(kClBlock), 0, s, K, Tb, C, loss, stats);
-    return hip_rc();
+    chain(k_disc_sums<T>, groups, kBlock, d->S, chunks, K, (const T*)e, labels, Tb);
+    chain(k_disc_clusters, d->B, kClBlock, K, Tb, C);
+    if (K.grad) chain(k_disc_pull<T, true>, groups, kBlock, d->S, chunks, K, (const T*)e, labels, Tb, C);
+    else chain(k_disc_pull<T, false>, groups, kBlock, d->S, chunks, K, (const T*)e, labels, Tb, C);
+    chain(k_disc_finish, 1, kClBlock, K, Tb, C, loss, stats);
   });
-  return or_prepare_again(rc, [&] { launch_table_init<kDiscMagic>(workspace, need, s); });
+  return or_prepare_again(chain.rc, [&] { launch_table_init<kDiscMagic>(workspace, need, chain.s); });
 }
 
 extern "C" int pea_disc_loss_bwd(const PeaDiscDesc* d, const void* e, const int32_t* labels, const void* ctx, const float* dloss, void* de,
@@ -612,10 +607,10 @@ extern "C" int pea_disc_loss_bwd(const PeaDiscDesc* d, const void* e, const int3
   const DiscK K = disc_params(d);
   Ctx C;
   ctx_layout(d, const_cast<void*>(ctx), &C);
+  LaunchChain chain(stream);
   with_storage(d->dtype, [&](auto t) {
     using T = typename decltype(t)::type;
-    hipLaunchKernelGGL((k_disc_bwd<T>), dim3(groups), dim3(kBlock), 0, (hipStream_t)stream, (size_t)d->S, chunks, K, (const T*)e, labels, C,
-                       dloss, (T*)de);
+    chain(k_disc_bwd<T>, groups, kBlock, d->S, chunks, K, (const T*)e, labels, C, dloss, (T*)de);
   });
-  return hip_rc();
+  return chain.rc;
 }

@@ -247,19 +247,15 @@ extern "C" int pea_fgmask_loss_fwd(const PeaFgDesc* d, const void* logits, const
   unsigned chunks, groups;
   if (!loss_grid(d, &S, &chunks, &groups)) return PEA_E_UNSUPPORTED;
 
-  hipStream_t s = (hipStream_t)stream;
+  LaunchChain chain(stream);
   LossState* st = (LossState*)workspace;
   with_fg_types(d, [&](auto t, auto lt) {
     using T = typename decltype(t)::type;
     using LT = typename decltype(lt)::type;
-    hipLaunchKernelGGL((k_fg_fwd<T, LT>), dim3(groups), dim3(kBlock), 0, s, (size_t)S, chunks, (const T*)logits, (const LT*)labels, st);
+    chain(k_fg_fwd<T, LT>, groups, kBlock, S, chunks, (const T*)logits, (const LT*)labels, st);
   });
-  int rc = hip_rc();
-  if (!rc) {
-    hipLaunchKernelGGL(k_fg_finish, dim3(1), dim3(64), 0, s, st, loss, stats, (d->flags & PEA_FG_SKIP_EMPTY_CLASS) ? 1 : 0);
-    rc = hip_rc();
-  }
-  return or_prepare_again(rc, [&] { launch_loss_state_init(st, 1, s); });
+  chain(k_fg_finish, 1, 64, st, loss, stats, (d->flags & PEA_FG_SKIP_EMPTY_CLASS) ? 1 : 0);
+  return or_prepare_again(chain.rc, [&] { launch_loss_state_init(st, 1, chain.s); });
 }
 
 extern "C" int pea_fgmask_loss_bwd(const PeaFgDesc* d, const void* logits, const void* labels, const double* stats, const float* dloss,
@@ -275,15 +271,14 @@ extern "C" int pea_fgmask_loss_bwd(const PeaFgDesc* d, const void* logits, const
   unsigned chunks, groups;
   if (!loss_grid(d, &S, &chunks, &groups)) return PEA_E_UNSUPPORTED;
 
-  hipStream_t s = (hipStream_t)stream;
+  LaunchChain chain(stream);
   const int skip = (d->flags & PEA_FG_SKIP_EMPTY_CLASS) ? 1 : 0;
   with_fg_types(d, [&](auto t, auto lt) {
     using T = typename decltype(t)::type;
     using LT = typename decltype(lt)::type;
-    hipLaunchKernelGGL((k_fg_bwd<T, LT>), dim3(groups), dim3(kBlock), 0, s, (size_t)S, chunks, skip, (const T*)logits, (const LT*)labels,
-                       stats, dloss, (T*)dlogits);
+    chain(k_fg_bwd<T, LT>, groups, kBlock, S, chunks, skip, (const T*)logits, (const LT*)labels, stats, dloss, (T*)dlogits);
   });
-  return hip_rc();
+  return chain.rc;
 }
 
 extern "C" int pea_fgmask_argmax(const PeaFgDesc* d, const void* logits, uint8_t* mask_out, void* stream) {
@@ -300,9 +295,10 @@ extern "C" int pea_fgmask_argmax(const PeaFgDesc* d, const void* logits, uint8_t
   unsigned chunks, groups;  // one quad run per workgroup over all images' output
   if (!stream_grid(n, 1, kQuadRun, &chunks, &groups)) return PEA_E_UNSUPPORTED;
   P.n = (size_t)n;
+  LaunchChain chain(stream);
   with_storage(d->logits_dtype, [&](auto t) {
     using T = typename decltype(t)::type;
-    hipLaunchKernelGGL((k_fg_argmax<T>), dim3(groups), dim3(kBlock), 0, (hipStream_t)stream, P, (const T*)logits, mask_out);
+    chain(k_fg_argmax<T>, groups, kBlock, P, (const T*)logits, mask_out);
   });
-  return hip_rc();
+  return chain.rc;
 }

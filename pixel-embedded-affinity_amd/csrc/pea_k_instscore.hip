@@ -7,7 +7,8 @@
 //   k_inst_marginals   over the pair slots: a_i and b_j into DENSE arrays [max_id + 1] (the ids are bounded: no hash lookup later), the
 //                      pixel counts, the number of entries of every gt row; the match tables are zeroed
 //   k_inst_scan        a workgroup per image: an exclusive scan of the row lengths (the table as a CSR by gt id) and of the present
-//                      flags (b_j > 0: the sorted list of present gt ids, one record (j, row start, row length, b_j) each); n_pred_ids
+//                      flags (b_j > 0: the sorted list of present gt ids, one record (j, row start, row length, b_j) each) as ONE u64
+//                      scan of the packed pair (block_scan_excl of pea_stream.h, eight ids a lane); n_pred_ids
 //   k_inst_pairs       over the pair slots: iou of every pair, the PQ pairs (tp, the fixed-point sum_iou, pq_match) and the scatter of
 //                      (pred id, n_ij, a_i, iou bits) into the rows; the order within a row is arrival order, nothing depends on it
 //   k_inst_walk        ONE WAVE per image: the greedy AJI matching, a dependent chain of one step per present gt id
@@ -60,21 +61,20 @@ struct Inst {
 };
 
 inline size_t inst_layout(const PeaInstDesc* d, void* base, Inst* t) {
-  const size_t B = (size_t)d->B, cap = (size_t)d->capacity, M = (size_t)d->max_id + 1;
-  const size_t R = M < cap ? M : cap;
-  const size_t words = kHdrWords + kImgWords * B + B * cap * (kPairWords + kEntWords) + B * R * kRecWords;
-  if (t) {
-    t->hdr = (u64*)base;
-    t->img = t->hdr + kHdrWords;
-    t->pairs = t->img + kImgWords * B;
-    t->ents = t->pairs + B * cap * kPairWords;
-    t->recs = t->ents + B * cap * kEntWords;
-    t->a = (u32*)(t->recs + B * R * kRecWords);
-    t->bc = t->a + B * M;
-    t->cur = t->bc + B * M;
-    t->cap = cap; t->R = R; t->M = (u32)M; t->B = d->B;
-  }
-  return 8 * words + al8(4 * 3 * B * M);
+  const uint64_t B = (uint64_t)d->B, cap = (uint64_t)d->capacity, M = (uint64_t)d->max_id + 1;
+  const uint64_t R = M < cap ? M : cap;
+  Carver c(base);
+  t->hdr = c.take<u64>(kHdrWords);
+  t->img = c.take<u64>(kImgWords * B);
+  t->pairs = c.take<u64>(mul_sat(B * cap, kPairWords));
+  t->ents = c.take<u64>(mul_sat(B * cap, kEntWords));
+  t->recs = c.take<u64>(B * R * kRecWords);
+  Carver tail(c.take<u32>(3 * B * M));
+  t->a = tail.take<u32>(B * M, 4);
+  t->bc = tail.take<u32>(B * M, 4);
+  t->cur = tail.take<u32>(B * M, 4);
+  t->cap = cap; t->R = R; t->M = (u32)M; t->B = d->B;
+  return c.bytes();
 }
 
 __device__ __forceinline__ bool prepared(const Inst& T) { return *(const unsigned*)T.hdr == kInstMagic; }
@@ -112,11 +112,9 @@ __global__ __launch_bounds__(kBlock) void k_inst_marginals(const Inst T, int32_t
 
 // ---- 3: the CSR by gt id and the list of present gt ids ------------------------------------------------------------------------------------
 __global__ __launch_bounds__(kBlock) void k_inst_scan(const Inst T) {
-  static_assert(kBlock / 64 == 4, "the prefix over the waves is written for four");
-  __shared__ u64 s_wave[kBlock / 64];
   if (!prepared(T)) return;
   const size_t b = blockIdx.x;
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int lane = threadIdx.x & 63;
   const u32* a = T.a + b * T.M;
   const u32* bc = T.bc + b * T.M;
   u32* cur = T.cur + b * T.M;
@@ -136,17 +134,9 @@ __global__ __launch_bounds__(kBlock) void k_inst_scan(const Inst T) {
       npred += (u64)(ok && a[j] != 0);
       mine += ((u64)len[e] << 32) | (u64)(bj[e] != 0);
     }
-    u64 incl = mine;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-      const u64 t = __shfl_up(incl, o, 64);
-      if (lane >= o) incl += t;
-    }
-    if (lane == 63) s_wave[wave] = incl;
-    __syncthreads();
-    u64 run = carry + incl - mine;
-    for (int w = 0; w < wave; ++w) run += s_wave[w];
-    carry += ((s_wave[0] + s_wave[1]) + s_wave[2]) + s_wave[3];
+    u64 total;
+    u64 run = carry + block_scan_excl(mine, &total);
+    carry += total;
 #pragma unroll
     for (int e = 0; e < kScanPer; ++e) {
       if (bj[e]) {
@@ -159,7 +149,6 @@ __global__ __launch_bounds__(kBlock) void k_inst_scan(const Inst T) {
       }
       run += ((u64)len[e] << 32) | (u64)(bj[e] != 0);
     }
-    __syncthreads();
   }
   u64* w = T.img + b * kImgWords;
   if (threadIdx.x == 0) w[I_NPRES] = carry & 0xffffffffull;
@@ -377,7 +366,10 @@ extern "C" int pea_inst_validate(const PeaInstDesc* d) {
   return PEA_OK;
 }
 
-extern "C" size_t pea_inst_workspace_bytes(const PeaInstDesc* d) { return pea_inst_validate(d) ? 0 : inst_layout(d, nullptr, nullptr); }
+extern "C" size_t pea_inst_workspace_bytes(const PeaInstDesc* d) {
+  Inst T;
+  return pea_inst_validate(d) ? 0 : inst_layout(d, nullptr, &T);
+}
 
 extern "C" int pea_inst_workspace_init(void* ws, size_t bytes, void* stream) { return table_workspace_init<kInstMagic>(ws, bytes, stream); }
 
@@ -388,28 +380,18 @@ extern "C" int pea_inst_scores(const PeaInstDesc* d, const int32_t* pred, const 
   if (!pred || !gt || !out) return PEA_E_NULL;
   if (misaligned(pred, 4) || misaligned(gt, 4) || misaligned(aji_match, 4) || misaligned(pq_match, 4) || misaligned(out, 8) || misaligned(ws, 8))
     return PEA_E_ALIGN;
-  const size_t need = pea_inst_workspace_bytes(d);
+  Inst T;
+  const size_t need = inst_layout(d, ws, &T);
   if (!ws || ws_bytes < need) return PEA_E_WORKSPACE;
   unsigned chunks, pgroups, sgroups;
   if (!pea::seg_grids((uint64_t)d->S, (uint64_t)d->capacity, (uint64_t)d->B, &chunks, &pgroups, &sgroups)) return PEA_E_UNSUPPORTED;
 
-  hipStream_t s = (hipStream_t)stream;
-  Inst T;
-  inst_layout(d, ws, &T);
-  int rc = [&]() {
-    hipLaunchKernelGGL(k_seg_pairs<true>, dim3(pgroups), dim3(kBlock), 0, s, (size_t)d->S, chunks, T.cap, pred, gt, T.img, T.pairs, (int)d->max_id);
-    int r = hip_rc();
-    if (r) return r;
-    hipLaunchKernelGGL(k_inst_marginals, dim3(sgroups), dim3(kBlock), 0, s, T, aji_match, pq_match);
-    if ((r = hip_rc())) return r;
-    hipLaunchKernelGGL(k_inst_scan, dim3((unsigned)d->B), dim3(kBlock), 0, s, T);
-    if ((r = hip_rc())) return r;
-    hipLaunchKernelGGL(k_inst_pairs, dim3(sgroups), dim3(kBlock), 0, s, T, d->match_iou, pq_match);
-    if ((r = hip_rc())) return r;
-    hipLaunchKernelGGL(k_inst_walk, dim3((unsigned)d->B), dim3(64), 0, s, T, aji_match);
-    if ((r = hip_rc())) return r;
-    hipLaunchKernelGGL(k_inst_finish, dim3(sgroups), dim3(kBlock), 0, s, T, out);
-    return hip_rc();
-  }();
-  return or_prepare_again(rc, [&] { launch_table_init<kInstMagic>(ws, need, s); });
+  LaunchChain chain(stream);
+  chain(k_seg_pairs<true>, pgroups, kBlock, d->S, chunks, T.cap, pred, gt, T.img, T.pairs, d->max_id);
+  chain(k_inst_marginals, sgroups, kBlock, T, aji_match, pq_match);
+  chain(k_inst_scan, d->B, kBlock, T);
+  chain(k_inst_pairs, sgroups, kBlock, T, d->match_iou, pq_match);
+  chain(k_inst_walk, d->B, 64, T, aji_match);
+  chain(k_inst_finish, sgroups, kBlock, T, out);
+  return or_prepare_again(chain.rc, [&] { launch_table_init<kInstMagic>(ws, need, chain.s); });
 }

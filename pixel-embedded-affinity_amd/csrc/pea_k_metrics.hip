@@ -212,23 +212,16 @@ extern "C" int pea_affs_metrics(const PeaMetricsDesc* d, float* pred, const floa
   unsigned groups;
   if (!stream_grid(store ? PS : RS, mul_sat((uint64_t)d->B, (uint64_t)P.CW), kLaneRun, &P.chunks, &groups)) return PEA_E_UNSUPPORTED;
 
-  hipStream_t s = (hipStream_t)stream;
+  LaunchChain chain(stream);
   LossState* st = (LossState*)workspace;
-  const dim3 grid(groups), blk(kBlock);
   with_bool(mf32, [&](auto mf) {
     using MT = std::conditional_t<decltype(mf)::value, float, uint8_t>;
     with_bool(divide, [&](auto dv) {
       with_bool(store, [&](auto sv) {
-        hipLaunchKernelGGL((k_metrics<MT, decltype(dv)::value, decltype(sv)::value>), grid, blk, 0, s, P, pred, weight_map, target,
-                           (const MT*)mask, st);
+        chain(k_metrics<MT, decltype(dv)::value, decltype(sv)::value>, groups, kBlock, P, pred, weight_map, target, (const MT*)mask, st);
       });
     });
   });
-  int rc = hip_rc();
-  if (!rc) {
-    const double n = (double)d->B * (double)RS;
-    hipLaunchKernelGGL(k_metrics_finish, dim3(1), dim3(64 * kStates), 0, s, st, out, P.C, n);
-    rc = hip_rc();
-  }
-  return or_prepare_again(rc, [&] { launch_loss_state_init(st, kStates, s); });
+  chain(k_metrics_finish, 1, 64 * kStates, st, out, P.C, (double)d->B * (double)RS);
+  return or_prepare_again(chain.rc, [&] { launch_loss_state_init(st, kStates, chain.s); });
 }

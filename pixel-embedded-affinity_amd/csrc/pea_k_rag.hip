@@ -13,7 +13,8 @@
 //                  and LOOKED UP (slot_find, behind the kernel boundary): a miss is a pair that does not touch.  min and max are
 //                  integer maxima of the order-preserving image of the f32 (min: of its complement), so a zero word is "none yet"
 //   k_rag_degree   over the slots: edges by u into a dense array; the number of edges
-//   k_rag_scan     a workgroup per image: the exclusive scan of the degrees, the row starts
+//   k_rag_scan     a workgroup per image: the exclusive scan of the degrees (eight ids a lane, block_scan_excl of pea_stream.h over the
+//                  lanes, a carry from step to step), the row starts
 //   k_rag_scatter  over the slots: (slot, v) of every edge into its row, in arrival order
 //   k_rag_rows     a LANE PER EDGE, so a row is served by as many lanes as it has entries (a hub of thousands of neighbours is spread
 //                  over its own waves, whose lanes read the same row-mate at the same time): the rank of v among the row-mates, the
@@ -59,27 +60,24 @@ struct Rag {
 
 struct RagOffs { int o[PEA_RAG_MAX_K][3]; };
 
+// u64 words (header, per image, slots), then the u32 arrays as ONE block padded to a word
 inline size_t rag_layout(const PeaRagDesc* d, void* base, Rag* t) {
   const uint64_t B = (uint64_t)d->B, cap = (uint64_t)d->capacity, M = (uint64_t)d->max_id + 1;
-  const uint64_t words = kHdrWords + kImgWords * B + mul_sat(mul_sat(B, cap), kSlotWords);
-  const uint64_t tail = mul_sat(4, mul_sat(B, 2 * cap + 3 * M));
-  const uint64_t bytes = mul_sat(8, words) + tail;
-  if (bytes < tail || bytes > (uint64_t)SIZE_MAX - 8 || mul_sat(8, words) == UINT64_MAX || tail == UINT64_MAX) return SIZE_MAX;
-  if (t) {
-    t->hdr = (u64*)base;
-    t->img = t->hdr + kHdrWords;
-    t->slots = t->img + kImgWords * B;
-    t->order = (u32*)(t->slots + B * cap * kSlotWords);
-    t->rowv = t->order + B * cap;
-    t->deg = t->rowv + B * cap;
-    t->start = t->deg + B * M;
-    t->cur = t->start + B * M;
-    t->cap = cap; t->max_edges = (u64)d->max_edges;
-    t->X = (u32)d->dims[2]; t->Y = (u32)d->dims[1]; t->Z = (u32)d->dims[0];
-    t->S = (size_t)d->dims[0] * d->dims[1] * d->dims[2];
-    t->M = (u32)M; t->B = d->B; t->K = d->K; t->flags = d->flags;
-  }
-  return al8((size_t)bytes);
+  Carver c(base);
+  t->hdr = c.take<u64>(kHdrWords);
+  t->img = c.take<u64>(kImgWords * B);
+  t->slots = c.take<u64>(mul_sat(mul_sat(B, cap), kSlotWords));
+  Carver tail(c.take<u32>(mul_sat(B, 2 * cap + 3 * M)));
+  t->order = tail.take<u32>(B * cap, 4);
+  t->rowv = tail.take<u32>(B * cap, 4);
+  t->deg = tail.take<u32>(B * M, 4);
+  t->start = tail.take<u32>(B * M, 4);
+  t->cur = tail.take<u32>(B * M, 4);
+  t->cap = cap; t->max_edges = (u64)d->max_edges;
+  t->X = (u32)d->dims[2]; t->Y = (u32)d->dims[1]; t->Z = (u32)d->dims[0];
+  t->S = (size_t)d->dims[0] * d->dims[1] * d->dims[2];
+  t->M = (u32)M; t->B = d->B; t->K = d->K; t->flags = d->flags;
+  return c.bytes();
 }
 
 __device__ __forceinline__ bool prepared(const Rag& T) { return *(const unsigned*)T.hdr == kRagMagic; }
@@ -104,12 +102,6 @@ __device__ __forceinline__ double fx_signed(u64 lo, u64 hi) {
   const long long whole = (long long)hi + (long long)(lo >> 32);
   return (double)whole + (double)(lo & 0xffffffffull) / kFx;
 }
-// the order-preserving unsigned image of an f32 and back
-__device__ __forceinline__ u32 f32_ord(float x) {
-  const u32 b = __builtin_bit_cast(u32, x);
-  return (b >> 31) ? ~b : (b | 0x80000000u);
-}
-__device__ __forceinline__ float ord_f32(u32 o) { return __builtin_bit_cast(float, (o >> 31) ? (o ^ 0x80000000u) : ~o); }
 
 // ---- 1: clear ---------------------------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(kBlock) void k_rag_clear(const Rag T, const PeaRagBuffers io, const size_t per) {
@@ -380,11 +372,8 @@ __global__ __launch_bounds__(kBlock) void k_rag_degree(const Rag T) {
 
 // ---- 5: the row starts ------------------------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(kBlock) void k_rag_scan(const Rag T) {
-  static_assert(kBlock / 64 == 4, "the prefix over the waves is written for four");
-  __shared__ u32 s_wave[kBlock / 64];
   if (!prepared(T)) return;
   const size_t b = blockIdx.x;
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const u32* deg = T.deg + b * T.M;
   u32* start = T.start + b * T.M;
   u32 carry = 0;
@@ -396,23 +385,14 @@ __global__ __launch_bounds__(kBlock) void k_rag_scan(const Rag T) {
       len[e] = j0 + e < T.M ? deg[j0 + e] : 0u;
       mine += len[e];
     }
-    u32 incl = mine;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-      const u32 t = __shfl_up(incl, o, 64);
-      if (lane >= o) incl += t;
-    }
-    if (lane == 63) s_wave[wave] = incl;
-    __syncthreads();
-    u32 run = carry + incl - mine;
-    for (int w = 0; w < wave; ++w) run += s_wave[w];
-    carry += ((s_wave[0] + s_wave[1]) + s_wave[2]) + s_wave[3];
+    u32 total;
+    u32 run = carry + block_scan_excl(mine, &total);
+    carry += total;
 #pragma unroll
     for (int e = 0; e < kScanPer; ++e) {
       if (j0 + e < T.M) start[j0 + e] = run;
       run += len[e];
     }
-    __syncthreads();
   }
 }
 
@@ -556,7 +536,10 @@ extern "C" int pea_rag_validate(const PeaRagDesc* d) {
   return PEA_OK;
 }
 
-extern "C" size_t pea_rag_workspace_bytes(const PeaRagDesc* d) { return pea_rag_validate(d) ? 0 : rag_layout(d, nullptr, nullptr); }
+extern "C" size_t pea_rag_workspace_bytes(const PeaRagDesc* d) {
+  Rag T;
+  return pea_rag_validate(d) ? 0 : rag_layout(d, nullptr, &T);
+}
 
 extern "C" int pea_rag_workspace_init(void* ws, size_t bytes, void* stream) { return table_workspace_init<kRagMagic>(ws, bytes, stream); }
 
@@ -568,10 +551,9 @@ extern "C" int pea_rag_build(const PeaRagDesc* d, const PeaRagBuffers* io, void*
       misaligned(io->max, 4) || misaligned(io->size, 8) || misaligned(io->count, 8) || misaligned(io->mean, 8) || misaligned(io->bmean, 8) ||
       misaligned(io->node_size, 8) || misaligned(io->stats, 8) || misaligned(ws, 8))
     return PEA_E_ALIGN;
-  const size_t need = pea_rag_workspace_bytes(d);
-  if (!ws || need == SIZE_MAX || ws_bytes < need) return PEA_E_WORKSPACE;
   Rag T;
-  rag_layout(d, ws, &T);
+  const size_t need = rag_layout(d, ws, &T);
+  if (!ws || need == SIZE_MAX || ws_bytes < need) return PEA_E_WORKSPACE;
   const bool sampled = io->affs && d->K > 0;
   unsigned chunks, pgroups, sgroups, kchunks, kgroups = 0, cgroups;
   if (!pea::seg_grids((uint64_t)T.S, (uint64_t)d->capacity, (uint64_t)d->B, &chunks, &pgroups, &sgroups)) return PEA_E_UNSUPPORTED;
@@ -584,33 +566,20 @@ extern "C" int pea_rag_build(const PeaRagDesc* d, const PeaRagBuffers* io, void*
   const uint64_t tg = mul_sat((uint64_t)d->B, tper) / kBlock + 1;
   if (mul_sat((uint64_t)d->B, tper) == UINT64_MAX || tg > 0x7fffffffULL) return PEA_E_UNSUPPORTED;
 
-  hipStream_t s = (hipStream_t)stream;
   RagOffs O;
   memcpy(O.o, d->offsets, sizeof(O.o));
   const PeaRagBuffers A = *io;
-  int rc = [&]() {
-    hipLaunchKernelGGL(k_rag_clear, dim3(cgroups), dim3(kBlock), 0, s, T, A, (size_t)per);
-    int r = hip_rc();
-    if (r) return r;
-    if (A.boundary) hipLaunchKernelGGL(k_rag_edges<true>, dim3(pgroups), dim3(kBlock), 0, s, T, chunks, A.fragments, A.boundary, (long long*)A.node_size);
-    else hipLaunchKernelGGL(k_rag_edges<false>, dim3(pgroups), dim3(kBlock), 0, s, T, chunks, A.fragments, A.boundary, (long long*)A.node_size);
-    if ((r = hip_rc())) return r;
-    if (sampled) {
-      hipLaunchKernelGGL(k_rag_samples, dim3(kgroups), dim3(kBlock), 0, s, T, O, kchunks, A.fragments, A.affs);
-      if ((r = hip_rc())) return r;
-    }
-    hipLaunchKernelGGL(k_rag_degree, dim3(sgroups), dim3(kBlock), 0, s, T);
-    if ((r = hip_rc())) return r;
-    hipLaunchKernelGGL(k_rag_scan, dim3((unsigned)d->B), dim3(kBlock), 0, s, T);
-    if ((r = hip_rc())) return r;
-    hipLaunchKernelGGL(k_rag_scatter, dim3(sgroups), dim3(kBlock), 0, s, T);
-    if ((r = hip_rc())) return r;
-    hipLaunchKernelGGL(k_rag_rows, dim3(sgroups), dim3(kBlock), 0, s, T, A);
-    if ((r = hip_rc())) return r;
-    hipLaunchKernelGGL(k_rag_stats, dim3((unsigned)tg), dim3(kBlock), 0, s, T, (long long*)A.stats, (size_t)tper);
-    return hip_rc();
-  }();
-  return or_prepare_again(rc, [&] { launch_table_init<kRagMagic>(ws, need, s); });
+  LaunchChain chain(stream);
+  chain(k_rag_clear, cgroups, kBlock, T, A, per);
+  if (A.boundary) chain(k_rag_edges<true>, pgroups, kBlock, T, chunks, A.fragments, A.boundary, (long long*)A.node_size);
+  else chain(k_rag_edges<false>, pgroups, kBlock, T, chunks, A.fragments, A.boundary, (long long*)A.node_size);
+  if (sampled) chain(k_rag_samples, kgroups, kBlock, T, O, kchunks, A.fragments, A.affs);
+  chain(k_rag_degree, sgroups, kBlock, T);
+  chain(k_rag_scan, d->B, kBlock, T);
+  chain(k_rag_scatter, sgroups, kBlock, T);
+  chain(k_rag_rows, sgroups, kBlock, T, A);
+  chain(k_rag_stats, (unsigned)tg, kBlock, T, (long long*)A.stats, tper);
+  return or_prepare_again(chain.rc, [&] { launch_table_init<kRagMagic>(ws, need, chain.s); });
 }
 
 extern "C" int pea_rag_project(int64_t n, const int32_t* fragments, const int32_t* node_labels, int64_t n_labels, int32_t* seg, int64_t* n_bad,
@@ -621,6 +590,7 @@ extern "C" int pea_rag_project(int64_t n, const int32_t* fragments, const int32_
   unsigned chunks, groups;
   if (!stream_grid((uint64_t)n, 1, kLaneRun, &chunks, &groups)) return PEA_E_UNSUPPORTED;
   const u32 nl = n_labels > 0x80000000LL ? 0x80000000u : (u32)n_labels;  // (an int32 id is below 2^31)
-  hipLaunchKernelGGL(k_rag_project, dim3(groups), dim3(kBlock), 0, (hipStream_t)stream, (size_t)n, fragments, node_labels, nl, seg, (u64*)n_bad);
-  return hip_rc();
+  LaunchChain chain(stream);
+  chain(k_rag_project, groups, kBlock, n, fragments, node_labels, nl, seg, (u64*)n_bad);
+  return chain.rc;
 }

@@ -48,17 +48,16 @@ struct Tables {
 };
 
 inline size_t tables_layout(const PeaSegDesc* d, void* base, Tables* t) {
-  const size_t B = (size_t)d->B, cap = (size_t)d->capacity;
-  if (t) {
-    t->hdr = (u64*)base;
-    t->img = t->hdr + kHdrWords;
-    t->pairs = t->img + kImgWords * B;
-    t->rows = t->pairs + B * cap * kPairWords;
-    t->cols = t->rows + B * cap * kMargWords;
-    t->cap = cap;
-    t->B = d->B;
-  }
-  return 8 * (kHdrWords + kImgWords * B + B * cap * (kPairWords + 2 * kMargWords));
+  const uint64_t B = (uint64_t)d->B, cap = (uint64_t)d->capacity;
+  Carver c(base);
+  t->hdr = c.take<u64>(kHdrWords);
+  t->img = c.take<u64>(kImgWords * B);
+  t->pairs = c.take<u64>(mul_sat(B * cap, kPairWords));
+  t->rows = c.take<u64>(mul_sat(B * cap, kMargWords));
+  t->cols = c.take<u64>(mul_sat(B * cap, kMargWords));
+  t->cap = cap;
+  t->B = d->B;
+  return c.bytes();
 }
 
 __device__ __forceinline__ double nlog2n(u64 n) { return n > 1 ? (double)n * log2((double)n) : 0.0; }
@@ -302,7 +301,10 @@ extern "C" int pea_seg_validate(const PeaSegDesc* d) {
   return PEA_OK;
 }
 
-extern "C" size_t pea_seg_workspace_bytes(const PeaSegDesc* d) { return pea_seg_validate(d) ? 0 : tables_layout(d, nullptr, nullptr); }
+extern "C" size_t pea_seg_workspace_bytes(const PeaSegDesc* d) {
+  Tables T;
+  return pea_seg_validate(d) ? 0 : tables_layout(d, nullptr, &T);
+}
 
 extern "C" int pea_seg_workspace_init(void* workspace, size_t bytes, void* stream) {
   return table_workspace_init<kSegMagic>(workspace, bytes, stream);
@@ -314,28 +316,19 @@ extern "C" int pea_seg_scores(const PeaSegDesc* d, const int32_t* pred, const in
   if (vrc) return vrc;
   if (!pred || !gt || !out) return PEA_E_NULL;
   if (misaligned(pred, 4) || misaligned(gt, 4) || misaligned(out, 8) || misaligned(workspace, 8)) return PEA_E_ALIGN;
-  const size_t need = pea_seg_workspace_bytes(d);
+  Tables T;
+  const size_t need = tables_layout(d, workspace, &T);
   if (!workspace || workspace_bytes < need) return PEA_E_WORKSPACE;
   unsigned chunks, pgroups, sgroups;
   if (!seg_grids(d, (uint64_t)d->B, &chunks, &pgroups, &sgroups)) return PEA_E_UNSUPPORTED;
 
-  hipStream_t s = (hipStream_t)stream;
-  Tables T;
-  tables_layout(d, workspace, &T);
-  int rc = [&]() {
-    hipLaunchKernelGGL(k_seg_pairs<false>, dim3(pgroups), dim3(kBlock), 0, s, (size_t)d->S, chunks, T.cap, pred, gt, T.img, T.pairs, 0);
-    int r = hip_rc();
-    if (r) return r;
-    hipLaunchKernelGGL(k_seg_marginals, dim3(sgroups), dim3(kBlock), 0, s, T);
-    if ((r = hip_rc())) return r;
-    hipLaunchKernelGGL(k_seg_dice, dim3(sgroups), dim3(kBlock), 0, s, T);
-    if ((r = hip_rc())) return r;
-    hipLaunchKernelGGL(k_seg_best, dim3(sgroups), dim3(kBlock), 0, s, T);
-    if ((r = hip_rc())) return r;
-    hipLaunchKernelGGL(k_seg_finish, dim3((unsigned)((d->B + 63) / 64)), dim3(64), 0, s, T, out);
-    return hip_rc();
-  }();
-  return or_prepare_again(rc, [&] { launch_table_init<kSegMagic>(workspace, need, s); });
+  LaunchChain chain(stream);
+  chain(k_seg_pairs<false>, pgroups, kBlock, d->S, chunks, T.cap, pred, gt, T.img, T.pairs, 0);
+  chain(k_seg_marginals, sgroups, kBlock, T);
+  chain(k_seg_dice, sgroups, kBlock, T);
+  chain(k_seg_best, sgroups, kBlock, T);
+  chain(k_seg_finish, (unsigned)((d->B + 63) / 64), 64, T, out);
+  return or_prepare_again(chain.rc, [&] { launch_table_init<kSegMagic>(workspace, need, chain.s); });
 }
 
 extern "C" int pea_seg_table(const PeaSegDesc* d, const int32_t* pred, const int32_t* gt, int32_t b, int32_t* pred_ids, int32_t* gt_ids,
@@ -347,23 +340,16 @@ extern "C" int pea_seg_table(const PeaSegDesc* d, const int32_t* pred, const int
   if (misaligned(pred, 4) || misaligned(gt, 4) || misaligned(pred_ids, 4) || misaligned(gt_ids, 4) || misaligned(counts, 8) ||
       misaligned(n_out, 8) || misaligned(workspace, 8))
     return PEA_E_ALIGN;
-  const size_t need = pea_seg_workspace_bytes(d);
+  Tables T;
+  const size_t need = tables_layout(d, workspace, &T);
   if (!workspace || workspace_bytes < need) return PEA_E_WORKSPACE;
   unsigned chunks, pgroups, sgroups;
   if (!seg_grids(d, 1, &chunks, &pgroups, &sgroups)) return PEA_E_UNSUPPORTED;
 
-  hipStream_t s = (hipStream_t)stream;
-  Tables T;
-  tables_layout(d, workspace, &T);
   const size_t off = (size_t)b * (size_t)d->S;
-  int rc = [&]() {
-    hipLaunchKernelGGL(k_seg_pairs<false>, dim3(pgroups), dim3(kBlock), 0, s, (size_t)d->S, chunks, T.cap, pred + off, gt + off, T.img, T.pairs, 0);
-    int r = hip_rc();
-    if (r) return r;
-    hipLaunchKernelGGL(k_seg_compact, dim3(sgroups), dim3(kBlock), 0, s, T.cap, T.img, T.pairs, pred_ids, gt_ids, counts, (u64)max_triples);
-    if ((r = hip_rc())) return r;
-    hipLaunchKernelGGL(k_seg_table_finish, dim3(1), dim3(64), 0, s, (const u64*)T.hdr, T.img, n_out);
-    return hip_rc();
-  }();
-  return or_prepare_again(rc, [&] { launch_table_init<kSegMagic>(workspace, need, s); });
+  LaunchChain chain(stream);
+  chain(k_seg_pairs<false>, pgroups, kBlock, d->S, chunks, T.cap, pred + off, gt + off, T.img, T.pairs, 0);
+  chain(k_seg_compact, sgroups, kBlock, T.cap, T.img, T.pairs, pred_ids, gt_ids, counts, max_triples);
+  chain(k_seg_table_finish, 1, 64, T.hdr, T.img, n_out);
+  return or_prepare_again(chain.rc, [&] { launch_table_init<kSegMagic>(workspace, need, chain.s); });
 }

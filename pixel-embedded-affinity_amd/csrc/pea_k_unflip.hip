@@ -112,11 +112,6 @@ __global__ __launch_bounds__(kBlock) void k_unflip(const T* __restrict__ src, T*
   }
 }
 
-inline uint64_t add_sat(uint64_t a, uint64_t b) {
-  uint64_t r;
-  return __builtin_add_overflow(a, b, &r) ? UINT64_MAX : r;
-}
-
 }  // namespace
 
 extern "C" int pea_consistency_unflip(int B, int C, int Z, int Y, int X, int dtype, const void* src, void* dst, const void* rules,

@@ -23,7 +23,8 @@
 //               of the last compress, and only parents of roots are written;  k_ws_compress  every pixel follows par[] from its old
 //               root by path halving (a chain can be as long as a plane) and writes root[p]; the slots are cleared
 //   k_ws_tally .. k_ws_write   sizes per seed id, the size filter (then a second flood), the rank of the kept ids, the offsets of the
-//               planes, the labels
+//               planes, the labels (k_ws_rank and k_ws_offsets on block_scan_excl of pea_stream.h)
+// Host: seeds_layout and flood_layout carve the two workspaces (pea_carve.h); pea_cc_label's grid acceptance is pea::cc_grids_fit.
 #include "../../include/pea_ws.h"
 #include "../../include/pea_cc.h"
 #include "pea_stream.h"
@@ -44,9 +45,6 @@ constexpr int kMaxRounds = 32;       // ceil(log2(S)) + 1 <= 31 for S < 2^30
 enum { W_FOUND = 40, W_KEPT, W_ZEROS, W_OFFSET, W_NKEPT };
 constexpr int kGaussTileX = 64, kGaussTileY = 32;
 
-#define PEA_WS_LD(p) __hip_atomic_load((p), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)
-#define PEA_WS_ST(p, v) __hip_atomic_store((p), (v), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)
-
 struct WsParams {
   int N, Y, X;
   int S;            // Y * X
@@ -64,11 +62,6 @@ __device__ __forceinline__ bool pixel_at(const WsParams& P, int* n, int* p) {
   *n = (int)(blockIdx.x / P.chunks);
   *p = (int)((blockIdx.x % P.chunks) * kBlock + threadIdx.x);
   return *p < P.S;
-}
-// the order-preserving unsigned image of an f32 (that of pea_k_rag.hip)
-__device__ __forceinline__ unsigned f32_ord(float x) {
-  const unsigned b = __builtin_bit_cast(unsigned, x);
-  return (b >> 31) ? ~b : (b | 0x80000000u);
 }
 
 // ---- the distance transform ---------------------------------------------------------------------------------------------------------
@@ -351,11 +344,11 @@ __global__ __launch_bounds__(kBlock) void k_ws_compress(const WsParams P, const 
   // ancestor of its node, whoever writes it, so a walk only ever moves up a forest and ends at the root.
   int x = F.root[base + p];
   for (;;) {
-    const int px = PEA_WS_LD(par + x);
+    const int px = PEA_LD_AGENT(par + x);
     if (px == x) break;
-    const int gp = PEA_WS_LD(par + px);
+    const int gp = PEA_LD_AGENT(par + px);
     if (gp == px) { x = px; break; }
-    PEA_WS_ST(par + x, gp);
+    PEA_ST_AGENT(par + x, gp);
     x = gp;
   }
   F.root[base + p] = x;
@@ -457,8 +450,6 @@ __global__ __launch_bounds__(kBlock) void k_ws_stats(int N, const Flood F, int32
 }
 
 // ---- host -------------------------------------------------------------------------------------------------------------------------------------
-inline uint64_t al8u(uint64_t x) { return x > UINT64_MAX - 7 ? UINT64_MAX : (x + 7) & ~7ull; }
-inline uint64_t add_sat(uint64_t a, uint64_t b) { return a > UINT64_MAX - b ? UINT64_MAX : a + b; }
 inline uint64_t ws_pixels(const PeaWsDesc* d) { return mul_sat((uint64_t)d->Y, (uint64_t)d->X); }
 // (int)(3 sigma + 0.5), decided in floating point first: a radius past the served one comes back as PEA_WS_MAX_RADIUS + 1, so no sigma
 // however large (validate admits any finite one) reaches a conversion that does not fit an int
@@ -474,36 +465,42 @@ inline void cc_desc(const PeaWsDesc* d, int in_type, int conn, PeaCcDesc* c) {
   c->in_type = in_type; c->connectivity = conn; c->min_size = 0; c->flags = 0;
 }
 
-// the blocks of the seeds' workspace in order, each a multiple of 8 bytes
-struct SeedsWs { uint64_t a, b, c, d, e, f, flag, mask, small, cc, total; };
-inline SeedsWs seeds_ws(const PeaWsDesc* d) {
-  SeedsWs w;
-  const uint64_t per = mul_sat((uint64_t)d->N, ws_pixels(d));
-  const uint64_t img = al8u(mul_sat(4, per));
+// the blocks of the seeds' workspace in order, each a multiple of 8 bytes: six images of 4 bytes a pixel (g then the keys; dt2; dt; the
+// Gaussian's row pass; the height map before smoothing then the plateau ids; dts), a flag per plateau id, the mask, per plane the
+// extrema of dt2 and the counts of pea_cc_label, the workspace of pea_cc_label
+struct SeedsWs {
+  int *a, *dt2;
+  float *dtf, *tmp, *pre, *dts;
+  int* flag;
+  uint8_t* mask;
+  int *ext, *ccc;
+  char* cc;
+  size_t cc_bytes;
+};
+inline size_t seeds_layout(const PeaWsDesc* d, void* base, SeedsWs* w) {
+  const uint64_t N = (uint64_t)d->N, per = mul_sat(N, ws_pixels(d));
   PeaCcDesc c;
   cc_desc(d, PEA_CC_IN_I32, 1, &c);
-  const size_t ccb = pea_cc_workspace_bytes(&c);  // (the same for either element type and connectivity)
-  w.a = 0; w.b = img; w.c = mul_sat(2, img); w.d = mul_sat(3, img); w.e = mul_sat(4, img); w.f = mul_sat(5, img);
-  w.flag = mul_sat(6, img);
-  w.mask = add_sat(w.flag, al8u(mul_sat(4, mul_sat((uint64_t)d->N, add_sat(ws_pixels(d), 1)))));
-  w.small = add_sat(w.mask, al8u(per));
-  w.cc = add_sat(w.small, al8u(mul_sat(16, (uint64_t)d->N)));  // per plane: the extrema of dt2, the counts of pea_cc_label
-  w.total = ccb == SIZE_MAX ? UINT64_MAX : add_sat(w.cc, (uint64_t)ccb);
-  if (img == UINT64_MAX || w.flag == UINT64_MAX) w.total = UINT64_MAX;
-  return w;
+  w->cc_bytes = pea_cc_workspace_bytes(&c);  // (the same for either element type and connectivity)
+  Carver k(base);
+  w->a = k.take<int>(per); w->dt2 = k.take<int>(per);
+  w->dtf = k.take<float>(per); w->tmp = k.take<float>(per); w->pre = k.take<float>(per); w->dts = k.take<float>(per);
+  w->flag = k.take<int>(mul_sat(N, add_sat(ws_pixels(d), 1)));
+  w->mask = k.take<uint8_t>(per);
+  w->ext = k.take<int>(2 * N); w->ccc = k.take<int>(2 * N);
+  w->cc = k.take<char>(w->cc_bytes, 1);
+  return k.bytes();
 }
 
-struct FloodWs { uint64_t root, par, seed, slot, cnt, pl, total; };
-inline FloodWs flood_ws(const PeaWsDesc* d) {
-  FloodWs w;
-  const uint64_t per = mul_sat((uint64_t)d->N, ws_pixels(d));
-  const uint64_t img = al8u(mul_sat(4, per));
-  w.root = 0; w.par = img; w.seed = mul_sat(2, img); w.slot = mul_sat(3, img);
-  w.cnt = add_sat(w.slot, mul_sat(8, per));
-  w.pl = add_sat(w.cnt, al8u(mul_sat(4, mul_sat((uint64_t)d->N, add_sat(ws_pixels(d), 1)))));
-  w.total = add_sat(w.pl, mul_sat(4 * kPlaneWords, (uint64_t)d->N));
-  if (img == UINT64_MAX || w.slot == UINT64_MAX) w.total = UINT64_MAX;
-  return w;
+// the flood's blocks: root, par and seed (4 bytes a pixel each), the slots (8), a counter per seed id, 64 words per plane
+inline size_t flood_layout(const PeaWsDesc* d, void* base, Flood* F) {
+  const uint64_t N = (uint64_t)d->N, per = mul_sat(N, ws_pixels(d));
+  Carver k(base);
+  F->root = k.take<int>(per); F->par = k.take<int>(per); F->seed = k.take<int>(per);
+  F->slot = k.take<u64t>(per);
+  F->cnt = k.take<int>(mul_sat(N, add_sat(ws_pixels(d), 1)));
+  F->pl = k.take<int>(kPlaneWords * N);
+  return k.bytes();
 }
 
 // S < 2^30 and a grid of one workgroup per 256 pixels of a plane
@@ -532,15 +529,12 @@ inline GaussW gauss_weights(float sigma) {
 }
 
 // out = G(sigma) * in through tmp (in != out, in != tmp; tmp != out)
-inline int launch_gauss(const WsParams& P, float sigma, const float* in, float* tmp, float* out, hipStream_t s) {
+inline void launch_gauss(LaunchChain& chain, const WsParams& P, float sigma, const float* in, float* tmp, float* out) {
   const GaussW G = gauss_weights(sigma);
   const unsigned cx = (unsigned)((P.X + kBlock - 1) / kBlock);
   const unsigned ty = (unsigned)((P.Y + kGaussTileY - 1) / kGaussTileY), tx = (unsigned)((P.X + kGaussTileX - 1) / kGaussTileX);
-  hipLaunchKernelGGL(k_ws_gauss_x, dim3((unsigned)((uint64_t)P.N * P.Y * cx)), dim3(kBlock), 0, s, P, G, cx, in, tmp);
-  int rc;
-  if ((rc = hip_rc())) return rc;
-  hipLaunchKernelGGL(k_ws_gauss_y, dim3((unsigned)((uint64_t)P.N * ty * tx)), dim3(kBlock), 0, s, P, G, ty, tx, (const float*)tmp, out);
-  return hip_rc();
+  chain(k_ws_gauss_x, (unsigned)((uint64_t)P.N * P.Y * cx), kBlock, P, G, cx, in, tmp);
+  chain(k_ws_gauss_y, (unsigned)((uint64_t)P.N * ty * tx), kBlock, P, G, ty, tx, tmp, out);
 }
 // is a Gaussian of this sigma served on the planes, and do its grids fit?
 inline bool gauss_ok(const PeaWsDesc* d, float sigma) {
@@ -566,19 +560,14 @@ extern "C" int pea_ws_validate(const PeaWsDesc* d) {
   return PEA_OK;
 }
 
-// six images of 4 bytes a pixel (g then the keys; dt2; dt; the Gaussian's row pass; the height map before smoothing then the plateau
-// ids; dts), a flag per plateau id, the mask, four words per plane, the workspace of pea_cc_label
 extern "C" size_t pea_ws_seeds_workspace_bytes(const PeaWsDesc* d) {
-  if (pea_ws_validate(d)) return 0;
-  const uint64_t t = seeds_ws(d).total;
-  return t > (uint64_t)SIZE_MAX ? SIZE_MAX : (size_t)t;
+  SeedsWs w;
+  return pea_ws_validate(d) ? 0 : seeds_layout(d, nullptr, &w);
 }
 
-// root, par and seed (4 bytes a pixel each), the slots (8), a counter per seed id, 64 words per plane
 extern "C" size_t pea_ws_flood_workspace_bytes(const PeaWsDesc* d) {
-  if (pea_ws_validate(d)) return 0;
-  const uint64_t t = flood_ws(d).total;
-  return t > (uint64_t)SIZE_MAX ? SIZE_MAX : (size_t)t;
+  Flood F;
+  return pea_ws_validate(d) ? 0 : flood_layout(d, nullptr, &F);
 }
 
 extern "C" int pea_ws_seeds(const PeaWsDesc* d, const float* boundary, int32_t* dt2, float* dts, float* hmap, int32_t* seeds, int32_t* counts,
@@ -590,7 +579,8 @@ extern "C" int pea_ws_seeds(const PeaWsDesc* d, const float* boundary, int32_t* 
   if (misaligned(boundary, 4) || misaligned(dt2, 4) || misaligned(dts, 4) || misaligned(hmap, 4) || misaligned(seeds, 4) ||
       misaligned(counts, 4) || misaligned(workspace, 8))
     return PEA_E_ALIGN;
-  if (!workspace || workspace_bytes < pea_ws_seeds_workspace_bytes(d)) return PEA_E_WORKSPACE;
+  SeedsWs W;
+  if (!workspace || workspace_bytes < seeds_layout(d, workspace, &W)) return PEA_E_WORKSPACE;
   WsParams P;
   unsigned groups;
   if (!ws_grid(d, &P, &groups)) return PEA_E_UNSUPPORTED;
@@ -598,60 +588,36 @@ extern "C" int pea_ws_seeds(const PeaWsDesc* d, const float* boundary, int32_t* 
   if (big >= (1ull << 31)) return PEA_E_UNSUPPORTED;
   P.big = (int)big;
   if (!gauss_ok(d, d->sigma_seeds) || (hmap && !gauss_ok(d, d->sigma_weights))) return PEA_E_UNSUPPORTED;
-  const uint64_t tiles = mul_sat((uint64_t)d->N, (((uint64_t)d->Y + 31) / 32) * (((uint64_t)d->X + 31) / 32));  // of pea_cc_label
-  const uint64_t rows = ((uint64_t)d->N * d->Y + kBlock / 64 - 1) / (kBlock / 64);
-  if (tiles > 0x7fffffffULL || rows > 0x7fffffffULL) return PEA_E_UNSUPPORTED;
-
-  hipStream_t s = (hipStream_t)stream;
-  const SeedsWs W = seeds_ws(d);
-  char* base = (char*)workspace;
-  int* A = (int*)(base + W.a);
-  int* dt2p = dt2 ? dt2 : (int*)(base + W.b);
-  float* dtf = (float*)(base + W.c);
-  float* tmp = (float*)(base + W.d);
-  float* pre = (float*)(base + W.e);
-  float* dtsp = dts ? dts : (float*)(base + W.f);
-  int* flag = (int*)(base + W.flag);
-  uint8_t* mask = (uint8_t*)(base + W.mask);
-  int* ext = (int*)(base + W.small);
-  int* ccc = ext + (size_t)d->N * 2;
-  void* ccw = base + W.cc;
-  const size_t ccb = (size_t)(W.total - W.cc);
-  const dim3 pg(groups), blk(kBlock);
-  int rc;
-  if (field) {
-    if (d->sigma_seeds == 0.0f) {
-      hipLaunchKernelGGL(k_ws_copy, pg, blk, 0, s, P, boundary, dtsp);
-      if ((rc = hip_rc())) return rc;
-    } else if ((rc = launch_gauss(P, d->sigma_seeds, boundary, tmp, dtsp, s))) return rc;
-  } else {
-    hipLaunchKernelGGL(k_ws_rowdist, dim3((unsigned)rows), blk, 0, s, P, boundary, A, ext);
-    if ((rc = hip_rc())) return rc;
-    hipLaunchKernelGGL(k_ws_coldist, pg, blk, 0, s, P, (const int*)A, dt2p, ext);
-    if ((rc = hip_rc())) return rc;
-    const bool smooth_s = d->sigma_seeds != 0.0f, smooth_w = d->sigma_weights != 0.0f;
-    hipLaunchKernelGGL(k_ws_pre, pg, blk, 0, s, P, boundary, (const int*)dt2p, (const int*)ext, smooth_s ? dtf : dtsp,
-                       hmap ? (smooth_w ? pre : hmap) : (float*)nullptr);
-    if ((rc = hip_rc())) return rc;
-    if (smooth_s && (rc = launch_gauss(P, d->sigma_seeds, dtf, tmp, dtsp, s))) return rc;
-    if (hmap && smooth_w && (rc = launch_gauss(P, d->sigma_weights, pre, tmp, hmap, s))) return rc;
-  }
-  // plateaus of dts, the maxima among them, the components of their mask
-  int* plab = (int*)pre;
-  hipLaunchKernelGGL(k_ws_key, pg, blk, 0, s, P, (const float*)dtsp, A, flag);
-  if ((rc = hip_rc())) return rc;
   PeaCcDesc c;
   cc_desc(d, PEA_CC_IN_I32, d->maxima_connectivity, &c);
-  if ((rc = pea_cc_label(&c, A, plab, nullptr, ccc, ccw, ccb, stream))) return rc;
+  const uint64_t rows = ((uint64_t)d->N * d->Y + kBlock / 64 - 1) / (kBlock / 64);
+  if (!cc_grids_fit(&c) || rows > 0x7fffffffULL) return PEA_E_UNSUPPORTED;  // (every refusal comes before the first launch)
+
+  LaunchChain chain(stream);
+  int* dt2p = dt2 ? dt2 : W.dt2;
+  float* dtsp = dts ? dts : W.dts;
+  if (field) {
+    if (d->sigma_seeds == 0.0f) chain(k_ws_copy, groups, kBlock, P, boundary, dtsp);
+    else launch_gauss(chain, P, d->sigma_seeds, boundary, W.tmp, dtsp);
+  } else {
+    chain(k_ws_rowdist, (unsigned)rows, kBlock, P, boundary, W.a, W.ext);
+    chain(k_ws_coldist, groups, kBlock, P, W.a, dt2p, W.ext);
+    const bool smooth_s = d->sigma_seeds != 0.0f, smooth_w = d->sigma_weights != 0.0f;
+    chain(k_ws_pre, groups, kBlock, P, boundary, dt2p, W.ext, smooth_s ? W.dtf : dtsp, hmap ? (smooth_w ? W.pre : hmap) : nullptr);
+    if (smooth_s) launch_gauss(chain, P, d->sigma_seeds, W.dtf, W.tmp, dtsp);
+    if (hmap && smooth_w) launch_gauss(chain, P, d->sigma_weights, W.pre, W.tmp, hmap);
+  }
+  // plateaus of dts, the maxima among them, the components of their mask
+  int* plab = (int*)W.pre;
+  chain(k_ws_key, groups, kBlock, P, dtsp, W.a, W.flag);
+  if (!chain.rc) chain.rc = pea_cc_label(&c, W.a, plab, nullptr, W.ccc, W.cc, W.cc_bytes, stream);
   P.conn = d->maxima_connectivity;
-  hipLaunchKernelGGL(k_ws_disq, pg, blk, 0, s, P, (const int*)A, (const int*)plab, flag);
-  if ((rc = hip_rc())) return rc;
-  hipLaunchKernelGGL(k_ws_mask, pg, blk, 0, s, P, (const int*)plab, (const int*)flag, mask);
-  if ((rc = hip_rc())) return rc;
+  chain(k_ws_disq, groups, kBlock, P, W.a, plab, W.flag);
+  chain(k_ws_mask, groups, kBlock, P, plab, W.flag, W.mask);
   cc_desc(d, PEA_CC_IN_U8, d->seed_connectivity, &c);
-  if ((rc = pea_cc_label(&c, mask, seeds, nullptr, ccc, ccw, ccb, stream))) return rc;
-  hipLaunchKernelGGL(k_ws_seed_counts, dim3((unsigned)((d->N + kBlock - 1) / kBlock)), blk, 0, s, d->N, (const int*)ccc, counts);
-  return hip_rc();
+  if (!chain.rc) chain.rc = pea_cc_label(&c, W.mask, seeds, nullptr, W.ccc, W.cc, W.cc_bytes, stream);
+  chain(k_ws_seed_counts, (unsigned)((d->N + kBlock - 1) / kBlock), kBlock, d->N, W.ccc, counts);
+  return chain.rc;
 }
 
 extern "C" int pea_ws_flood(const PeaWsDesc* d, const float* hmap, const int32_t* seeds, int32_t* labels, int32_t* counts, int32_t* stats,
@@ -662,52 +628,35 @@ extern "C" int pea_ws_flood(const PeaWsDesc* d, const float* hmap, const int32_t
   if (misaligned(hmap, 4) || misaligned(seeds, 4) || misaligned(labels, 4) || misaligned(counts, 4) || misaligned(stats, 4) ||
       misaligned(workspace, 8))
     return PEA_E_ALIGN;
-  if (!workspace || workspace_bytes < pea_ws_flood_workspace_bytes(d)) return PEA_E_WORKSPACE;
+  Flood F;
+  if (!workspace || workspace_bytes < flood_layout(d, workspace, &F)) return PEA_E_WORKSPACE;
   WsParams P;
   unsigned groups;
   if (!ws_grid(d, &P, &groups)) return PEA_E_UNSUPPORTED;
   // stacked ids are int32 sums of the kept counts, which a seed on every pixel makes N * Y * X
   if ((d->flags & PEA_WS_STACK_IDS) && mul_sat((uint64_t)d->N, (uint64_t)P.S) >= (1ull << 31)) return PEA_E_UNSUPPORTED;
 
-  hipStream_t s = (hipStream_t)stream;
-  const FloodWs W = flood_ws(d);
-  char* base = (char*)workspace;
-  Flood F;
-  F.root = (int*)(base + W.root); F.par = (int*)(base + W.par); F.seed = (int*)(base + W.seed);
-  F.slot = (u64t*)(base + W.slot); F.cnt = (int*)(base + W.cnt); F.pl = (int*)(base + W.pl);
   int rounds = 1;  // ceil(log2(S)) + 1
   while ((1ll << (rounds - 1)) < (long long)P.S) ++rounds;
-  const dim3 pg(groups), blk(kBlock), ng((unsigned)((d->N + kBlock - 1) / kBlock));
-  int rc;
-  const auto flood = [&](int first) -> int {
-    hipLaunchKernelGGL(k_ws_finit, pg, blk, 0, s, P, F, seeds, first);
-    if ((rc = hip_rc())) return rc;
-    for (int k = 0; k < rounds; ++k) {
-      hipLaunchKernelGGL(k_ws_pick, pg, blk, 0, s, P, F, hmap, k);
-      if ((rc = hip_rc())) return rc;
-      hipLaunchKernelGGL(k_ws_hook, pg, blk, 0, s, P, F, k);
-      if ((rc = hip_rc())) return rc;
-      hipLaunchKernelGGL(k_ws_compress, pg, blk, 0, s, P, F, k);
-      if ((rc = hip_rc())) return rc;
+  LaunchChain chain(stream);
+  const auto flood = [&](int first) {
+    chain(k_ws_finit, groups, kBlock, P, F, seeds, first);
+    for (int k = 0; k < rounds && !chain.rc; ++k) {
+      chain(k_ws_pick, groups, kBlock, P, F, hmap, k);
+      chain(k_ws_hook, groups, kBlock, P, F, k);
+      chain(k_ws_compress, groups, kBlock, P, F, k);
     }
-    return 0;
   };
-  if ((rc = flood(1))) return rc;
-  hipLaunchKernelGGL(k_ws_tally, pg, blk, 0, s, P, F);
-  if ((rc = hip_rc())) return rc;
-  hipLaunchKernelGGL(k_ws_found, pg, blk, 0, s, P, F);
-  if ((rc = hip_rc())) return rc;
+  flood(1);
+  chain(k_ws_tally, groups, kBlock, P, F);
+  chain(k_ws_found, groups, kBlock, P, F);
   if (d->min_size > 1) {
-    hipLaunchKernelGGL(k_ws_filter, pg, blk, 0, s, P, F);
-    if ((rc = hip_rc())) return rc;
-    if ((rc = flood(0))) return rc;
+    chain(k_ws_filter, groups, kBlock, P, F);
+    flood(0);
   }
-  hipLaunchKernelGGL(k_ws_rank, dim3((unsigned)d->N), blk, 0, s, P, F, counts);
-  if ((rc = hip_rc())) return rc;
-  hipLaunchKernelGGL(k_ws_offsets, dim3(1), blk, 0, s, P, F);
-  if ((rc = hip_rc())) return rc;
-  hipLaunchKernelGGL(k_ws_write, pg, blk, 0, s, P, F, labels);
-  if ((rc = hip_rc())) return rc;
-  hipLaunchKernelGGL(k_ws_stats, ng, blk, 0, s, d->N, F, stats);
-  return hip_rc();
+  chain(k_ws_rank, d->N, kBlock, P, F, counts);
+  chain(k_ws_offsets, 1, kBlock, P, F);
+  chain(k_ws_write, groups, kBlock, P, F, labels);
+  chain(k_ws_stats, (unsigned)((d->N + kBlock - 1) / kBlock), kBlock, d->N, F, stats);
+  return chain.rc;
 }

@@ -31,9 +31,6 @@ constexpr u64 kMaxCapacity = 1ull << 31;
 constexpr double kFx = 4294967296.0;            // 2^32: the fixed-point sums carry 32 fractional bits
 enum { I_BAD = 0, I_OVF = 1 };                  // labels that are no ids; pixels of pairs that found no slot
 
-#define PEA_LD_AGENT(p) __hip_atomic_load((p), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)
-#define PEA_ATOM_MAX(p, v) (void)__hip_atomic_fetch_max((p), (v), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)
-
 __device__ __forceinline__ u64 mix64(u64 x) {
   x ^= x >> 33; x *= 0xff51afd7ed558ccdull;
   x ^= x >> 33; x *= 0xc4ceb9fe1a85ec53ull;

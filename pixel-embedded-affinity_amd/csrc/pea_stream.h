@@ -5,7 +5,11 @@
 //              + e of the run, so a step of a wave is 1 KiB of an f32 tensor (lane_run)
 //   quad run   a workgroup owns kQuadRun = 1024 elements, a lane ONE quad (quad_start); seen by waves, a WAVE owns kWaveRun = 256
 //              consecutive elements and keeps them in registers (wave_start: the same element-to-lane assignment)
-//   scans      wave_scan_incl, block_scan_excl: the prefix sums of pea_k_cc.hip and pea_k_ws.hip
+// and what the label kernels (pea_k_cc.hip, pea_k_ws.hip, pea_k_rag.hip, pea_k_instscore.hip, pea_k_segscore.hip) share beyond the walks:
+//   scans      wave_scan_incl, block_scan_excl over int, u32 or u64: the workgroup's exclusive prefix
+//   atomics    PEA_LD_AGENT / PEA_ST_AGENT / PEA_ATOM_MAX (relaxed, agent scope; PEA_ATOM_ADD: pea_loss.h), f32_ord / ord_f32
+//   host       the table workspace, stream_grid, or_prepare_again, and LaunchChain: a launch entry as a straight list of launches
+//              (the layout of a workspace: pea_carve.h through pea_host.h)
 #pragma once
 #include "pea_host.h"
 #include "pea_quad.h"
@@ -89,24 +93,39 @@ __device__ __forceinline__ T wave_max(T v) {
   return v;
 }
 
-// ---- scans (pea_k_cc.hip, pea_k_ws.hip) -----------------------------------------------------------------------------------------------
-__device__ __forceinline__ int wave_scan_incl(int v, int lane) {
+// ---- relaxed agent-scope accesses of words that other workgroups write meanwhile (PEA_ATOM_ADD: pea_loss.h) ----------------------------
+#define PEA_LD_AGENT(p) __hip_atomic_load((p), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)
+#define PEA_ST_AGENT(p, v) __hip_atomic_store((p), (v), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)
+#define PEA_ATOM_MAX(p, v) (void)__hip_atomic_fetch_max((p), (v), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)
+
+// the order-preserving unsigned image of an f32 and back
+__device__ __forceinline__ unsigned f32_ord(float x) {
+  const unsigned b = __builtin_bit_cast(unsigned, x);
+  return (b >> 31) ? ~b : (b | 0x80000000u);
+}
+__device__ __forceinline__ float ord_f32(unsigned o) { return __builtin_bit_cast(float, (o >> 31) ? (o ^ 0x80000000u) : ~o); }
+
+// ---- scans: T is int, u32 or u64 ----------------------------------------------------------------------------------------------------------
+template <typename T>
+__device__ __forceinline__ T wave_scan_incl(T v, int lane) {
 #pragma unroll
   for (int o = 1; o < 64; o <<= 1) {
-    const int t = __shfl_up(v, o, 64);
+    const T t = __shfl_up(v, o, 64);
     if (lane >= o) v += t;
   }
   return v;
 }
-// the exclusive prefix of v over the workgroup's lanes and the workgroup's total (the whole workgroup calls it: two barriers)
-__device__ __forceinline__ int block_scan_excl(int v, int* total) {
+// the exclusive prefix of v over the workgroup's lanes and the workgroup's total (the whole workgroup calls it: two barriers; four
+// words of LDS per element type)
+template <typename T>
+__device__ __forceinline__ T block_scan_excl(T v, T* total) {
   static_assert(kBlock / 64 == 4, "written for four waves");
-  __shared__ int s_wave[kBlock / 64];
+  __shared__ T s_wave[kBlock / 64];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int incl = wave_scan_incl(v, lane);
+  const T incl = wave_scan_incl(v, lane);
   if (lane == 63) s_wave[wave] = incl;
   __syncthreads();
-  int before = 0;
+  T before = 0;
 #pragma unroll
   for (int w = 0; w < kBlock / 64; ++w) before += w < wave ? s_wave[w] : 0;
   *total = s_wave[0] + s_wave[1] + s_wave[2] + s_wave[3];
@@ -156,7 +175,6 @@ __device__ __forceinline__ bool peel(const K (&key)[kQuad], unsigned& open, K& c
 
 // ---- the table workspace: u64 words, all zero but for the magic word in front -----------------------------------------------------------------
 constexpr int kTableHdrWords = 8;  // [0] magic; the rest of the header is the family's
-inline size_t al8(size_t x) { return (x + 7) & ~(size_t)7; }
 
 template <unsigned MAGIC>
 __global__ __launch_bounds__(kBlock) void k_table_init(u64* __restrict__ w, size_t words) {
@@ -188,6 +206,19 @@ inline bool stream_grid(uint64_t n, uint64_t planes, int run, unsigned* chunks, 
   *chunks = (unsigned)c; *groups = (unsigned)g;
   return true;
 }
+// A launch entry's list of launches: chain(kernel, grid, block, args..) launches on the stream unless an earlier launch failed; rc is
+// the first failure (hip_rc) or PEA_OK.  The arguments convert to the kernel's parameter types as in a plain call.
+struct LaunchChain {
+  hipStream_t s;
+  int rc = PEA_OK;
+  explicit LaunchChain(void* stream) : s((hipStream_t)stream) {}
+  template <typename... P, typename... A>
+  void operator()(void (*kernel)(P...), dim3 grid, dim3 block, const A&... args) {
+    if (rc) return;
+    hipLaunchKernelGGL(kernel, grid, block, 0, s, static_cast<P>(args)...);
+    rc = hip_rc();
+  }
+};
 // the end of a launch sequence on a prepared block: where a launch failed, partials may be queued without what zeroes them, so the
 // block is prepared again (the contract of its init entry) and the error of that launch, if any, is swallowed.  -> rc
 template <typename F>

@@ -15,15 +15,10 @@ import ctypes
 import torch
 
 from .. import _lib
-from ..affinity_op import _on_device, _ptr, _require_gpu, _stream, stream_workspace
+from ..affinity_op import _no_init, _on_device, _ptr, _require_gpu, _stream, stream_workspace
 
 _IN_CODE = {torch.bool: _lib.CC_IN_U8, torch.uint8: _lib.CC_IN_U8, torch.int32: _lib.CC_IN_I32}
 _INT32_MAX = 2 ** 31 - 1
-
-
-def _no_init(_ptr_, _bytes, _stream_):
-    """the workspace of pea_cc_label is scratch: it needs no preparation"""
-    return 0
 
 
 class ConnectedComponents(object):

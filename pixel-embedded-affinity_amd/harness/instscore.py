@@ -16,7 +16,7 @@ import torch
 
 from .. import _lib
 from ..affinity_op import _on_device, _ptr, _stream, stream_workspace
-from .segscore import _args, default_capacity
+from .segscore import _ScoreTable, _args, default_capacity
 
 _HOST_ID_FLOOR = 1  # max_id of an image without any id
 
@@ -76,7 +76,7 @@ def _launch(P, G, capacity, max_id, match_iou):
     return out, match
 
 
-class InstanceScores(object):
+class InstanceScores(_ScoreTable):
     """The device table [B, 18] (float64; columns _lib.INST_COLUMNS) of one instance_scores call and its two match tables.  Nothing is
     copied to the host until a value is asked for.  The properties give a Python number for a single image and a list over the batch
     otherwise: .aji / .dq / .sq / .pq / .pixel_f1 / .tp / .fp / .fn / .n_bad / .n_overflow; .table is the device tensor,
@@ -85,30 +85,16 @@ class InstanceScores(object):
     If the first read finds n_overflow != 0 (the table was too small for the image's pairs), the call is repeated ONCE with four times
     the capacity; if that overflows too, RuntimeError."""
 
+    COLUMNS = _lib.INST_COLUMNS
+
     def __init__(self, table, match, pred, gt, capacity, max_id, match_iou):
         self.table, self.match, self.capacity, self.max_id, self.match_iou = table, match, int(capacity), int(max_id), float(match_iou)
         self._pred, self._gt = pred, gt
         self._host = None
         self._host_match = None
 
-    def _rows(self):
-        if self._host is None:
-            host = self.table.detach().cpu().numpy()
-            if (host[:, 0] != 0).any():
-                first = self.capacity
-                self.table, self.match = _launch(self._pred, self._gt, 4 * first, self.max_id, self.match_iou)
-                self.capacity = 4 * first
-                host = self.table.detach().cpu().numpy()
-                if (host[:, 0] != 0).any():
-                    raise RuntimeError("the pair table overflowed at capacity %d and at %d (n_overflow %s): pass a larger capacity"
-                                       % (first, self.capacity, host[:, 0].tolist()))
-            self._host = host
-        return self._host
-
-    def _col(self, name, conv=float):
-        c = self._rows()[:, _lib.INST_COLUMNS.index(name)]
-        vals = [conv(v) if np.isfinite(v) else float(v) for v in c]
-        return vals[0] if len(vals) == 1 else vals
+    def _relaunch(self, capacity):
+        self.table, self.match = _launch(self._pred, self._gt, capacity, self.max_id, self.match_iou)
 
     aji = property(lambda self: self._col("aji"))
     dq = property(lambda self: self._col("dq"))

@@ -16,7 +16,7 @@ import torch
 
 from .. import _lib
 from ..affinity_op import _on_device, _ptr, _stream, stream_workspace
-from .segscore import CAPACITY_FLOOR, labels_int32
+from .segscore import default_capacity as _default_capacity, labels_int32
 
 CAPACITY_CAP = 1 << 22  # of the default capacity: edges grow with the voxels, so the ceiling is higher than the score tables'
 
@@ -25,9 +25,7 @@ def default_capacity(S):
     """slots per image when the caller names none: the rule of harness/segscore.py -- the power of two at or above S / 32, at least
     256 -- with a ceiling of 2^22 (64 bytes and two words per slot and image).  The default max_edges is half of it.  A table that
     turns out too small is retried once at four times the size when the results are read (RegionAdjacency)."""
-    want = max(1, (int(S) + 31) // 32)
-    cap = 1 << (want - 1).bit_length()
-    return min(CAPACITY_CAP, max(CAPACITY_FLOOR, cap))
+    return _default_capacity(S, CAPACITY_CAP)
 
 
 def _workspace(dev, nb):

@@ -23,14 +23,14 @@ _WIDE = (torch.int64, torch.uint64)
 _NP_OK = (np.uint8, np.int8, np.int16, np.uint16, np.int32, np.int64, np.uint64)
 
 
-def default_capacity(S):
+def default_capacity(S, ceiling=CAPACITY_CAP):
     """slots per image when the caller names none: the power of two at or above S / 32, at least 256 and at most 32768 (one slot
     per 32 pixels covers the drivers' images many times over: a 544 x 544 CVPPP image has some 100 pairs and gets 16384 slots, a
     1024 x 1024 image with several thousand ids gets 32768; 80 bytes per slot and image).  A table that turns out too small is
     retried once at four times the size when the scores are read (SegmentationScores)."""
     want = max(1, (int(S) + 31) // 32)
     cap = 1 << (want - 1).bit_length()
-    return min(CAPACITY_CAP, max(CAPACITY_FLOOR, cap))
+    return min(ceiling, max(CAPACITY_FLOOR, cap))
 
 
 def _workspace(dev, nb):
@@ -118,27 +118,21 @@ def _launch(P, G, capacity):
     return out, d
 
 
-class SegmentationScores(object):
-    """The device table [B, 19] (float64; columns _lib.SEG_COLUMNS) of one segmentation_scores call.  Nothing is copied to the host
-    until a value is asked for.  The properties give a Python number for a single image and a list over the batch otherwise:
-    .sbd / .best_dice / .best_dice_rev / .diff_fg / .abs_diff_fg / .fgbg_dice / .voi_split / .voi_merge / .voi (their sum) / .are /
-    .are_precision / .are_recall / .n_overflow / .n_bad; .table is the device tensor, .contingency(b) the (pred id, gt id, count)
-    triples of image b.
+class _ScoreTable(object):
+    """A device score table [B, columns] whose column 0 is n_overflow, read lazily: the first read copies it to the host and, where a
+    pair table overflowed, repeats the launch ONCE at four times the capacity.  A subclass names its COLUMNS and its _relaunch."""
+    COLUMNS = ()
 
-    If the first read finds n_overflow != 0 (the table was too small for the image's pairs), the call is repeated ONCE with four times
-    the capacity; if that overflows too, RuntimeError."""
-
-    def __init__(self, table, pred, gt, capacity):
-        self.table, self.capacity = table, int(capacity)
-        self._pred, self._gt = pred, gt
-        self._host = None
+    def _relaunch(self, capacity):
+        """launch again with `capacity`; sets self.table (and what else the launch returns)"""
+        raise NotImplementedError
 
     def _rows(self):
         if self._host is None:
             host = self.table.detach().cpu().numpy()
             if (host[:, 0] != 0).any():
                 first = self.capacity
-                self.table, _ = _launch(self._pred, self._gt, 4 * first)
+                self._relaunch(4 * first)
                 self.capacity = 4 * first
                 host = self.table.detach().cpu().numpy()
                 if (host[:, 0] != 0).any():
@@ -148,9 +142,30 @@ class SegmentationScores(object):
         return self._host
 
     def _col(self, name, conv=float):
-        c = self._rows()[:, _lib.SEG_COLUMNS.index(name)]
+        c = self._rows()[:, self.COLUMNS.index(name)]
         vals = [conv(v) if np.isfinite(v) else float(v) for v in c]
         return vals[0] if len(vals) == 1 else vals
+
+
+class SegmentationScores(_ScoreTable):
+    """The device table [B, 19] (float64; columns _lib.SEG_COLUMNS) of one segmentation_scores call.  Nothing is copied to the host
+    until a value is asked for.  The properties give a Python number for a single image and a list over the batch otherwise:
+    .sbd / .best_dice / .best_dice_rev / .diff_fg / .abs_diff_fg / .fgbg_dice / .voi_split / .voi_merge / .voi (their sum) / .are /
+    .are_precision / .are_recall / .n_overflow / .n_bad; .table is the device tensor, .contingency(b) the (pred id, gt id, count)
+    triples of image b.
+
+    If the first read finds n_overflow != 0 (the table was too small for the image's pairs), the call is repeated ONCE with four times
+    the capacity; if that overflows too, RuntimeError."""
+
+    COLUMNS = _lib.SEG_COLUMNS
+
+    def __init__(self, table, pred, gt, capacity):
+        self.table, self.capacity = table, int(capacity)
+        self._pred, self._gt = pred, gt
+        self._host = None
+
+    def _relaunch(self, capacity):
+        self.table, _ = _launch(self._pred, self._gt, capacity)
 
     sbd = property(lambda self: self._col("sbd"))
     best_dice = property(lambda self: self._col("best_dice"))

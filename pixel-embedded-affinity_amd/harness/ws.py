@@ -17,14 +17,9 @@ import numpy as np
 import torch
 
 from .. import _lib
-from ..affinity_op import _on_device, _ptr, _require_gpu, _stream, stream_workspace
+from ..affinity_op import _no_init, _on_device, _ptr, _require_gpu, _stream, stream_workspace
 
 _INT32_MAX = 2 ** 31 - 1
-
-
-def _no_init(_ptr_, _bytes, _stream_):
-    """the workspaces of pea_ws_seeds and pea_ws_flood are scratch: they need no preparation"""
-    return 0
 
 
 class WatershedSeeds(object):

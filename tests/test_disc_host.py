@@ -130,6 +130,24 @@ def test_sizes_are_monotone_multiples_of_eight(pkg, lib):
     assert lib.pea_disc_workspace_bytes(None) == 0 and lib.pea_disc_context_bytes(None) == 0
 
 
+def test_exact_sizes(pkg, lib):
+    ws = lambda **kw: lib.pea_disc_workspace_bytes(ctypes.byref(desc(pkg, **kw)))
+    cx = lambda **kw: lib.pea_disc_context_bytes(ctypes.byref(desc(pkg, **kw)))
+    al8 = lambda x: (x + 7) // 8 * 8
+    # odd B, B * num_ids and B * num_ids * D among them: every int32 / f32 array of the context is padded to 8 bytes on its own
+    cases = ((1, 1, 1), (1, 3, 5), (3, 1, 1), (3, 5, 7), (2, 64, 16), (5, 4095, 63), (33, 4096, 64), (7, 77, 1))
+    for B, N, D in cases:
+        # the tables: a header of 8 words, 4 words per image, a row of 2 + 3 D words per (image, id)
+        assert ws(B=B, num_ids=N, D=D) == 8 * (8 + 4 * B + B * N * (2 + 3 * D)), (B, N, D)
+        # the context: dist_b and reg_b (f64) per image, C_b; n_c, the id list, k_c and w_c per (image, id); mu_c and G_c / n_c per channel
+        assert cx(B=B, num_ids=N, D=D) == 16 * B + al8(4 * B) + 4 * al8(4 * B * N) + 2 * al8(4 * B * N * D), (B, N, D)
+    # The largest descriptor that pea_disc_validate admits is B = 2^31 - 1, num_ids = 4096, D = 64: 8 * B * num_ids * 194 < 2^54 and
+    # 8 * B * num_ids * D = 2^52 bytes, so neither count can exceed 2^64 and neither query ever answers SIZE_MAX: the exact values
+    B, N, D = 2 ** 31 - 1, 4096, 64
+    assert ws(B=B, num_ids=N, D=D) == 8 * (8 + 4 * B + B * N * (2 + 3 * D)) < 2 ** 64 - 1
+    assert cx(B=B, num_ids=N, D=D) == 16 * B + al8(4 * B) + 4 * al8(4 * B * N) + 2 * al8(4 * B * N * D) < 2 ** 64 - 1
+
+
 def test_workspace_init_refusals(pkg, lib):
     f = lambda p, n: lib.pea_disc_workspace_init(vp(p), n, None)
     assert f(0, 4096) == E_NULL and f(WORK + 4, 4096) == E_ALIGN and f(WORK + 1, 4096) == E_ALIGN

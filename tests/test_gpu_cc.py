@@ -295,6 +295,15 @@ def test_graphed_step_replays_the_eager_result(pkg, dev):
 
 
 # ---- 7. the shape of the driver -----------------------------------------------------------------------------------------------------------------------
+def test_more_chunk_totals_than_a_step_of_the_scan(pkg, dev):
+    """k_cc_scan takes 256 chunk totals a step with a carry: 513 x 512 pixels are 257 chunks of 1024, an isolated pixel every third row
+    and column is a component of its own, and min_size 0 keeps them all, so every id past the first step rests on the carry"""
+    m = np.zeros((1, 513, 512), np.uint8)
+    m[:, ::3, ::3] = 1
+    labels, counts, _ = check("513 x 512 dots", pkg, dev, m, 2, 0)
+    assert counts.tolist() == [[171 * 171, 171 * 171]] and int(labels[0, 510, 510]) == 171 * 171
+
+
 def test_one_bbbc_image(pkg, dev):
     """1 x 520 x 696 with about 150 synthetic nuclei and 200 specks, once: connectivity 2, min_size 25 (remove_samll_object's call)"""
     import __graft_entry__ as ge

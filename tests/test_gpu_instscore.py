@@ -198,6 +198,23 @@ def test_ids_at_the_ceiling_and_at_the_floor(pkg, dev):
     assert bool(torch.isnan(out[0, COL["aji"]])) and bool(torch.isnan(out[0, COL["pq"]])) and float(out[0, COL["sq"]]) == 0
 
 
+@pytest.mark.parametrize("max_id", (2047, 2048, 2049))
+def test_ids_around_a_lane_and_a_step_of_the_scan(pkg, dev, max_id):
+    """k_inst_scan gives a lane 8 ids and takes 2048 ids a step, with a carry from step to step.  Image 0: gt ids 63, 64, 65, 2047, 2048
+    and 2049, each over two predictions; an id above max_id is a bad label (n_bad, NaN scores).  Image 1: the ids up to 2047 alone, so
+    that it is scored at every max_id"""
+    ids = (63, 64, 65, 2047, 2048, 2049)
+    gt = np.zeros((2, 16, 16), np.int32)
+    pred = np.zeros((2, 16, 16), np.int32)
+    for k, j in enumerate(ids):
+        gt[0, 2 * k + 1:2 * k + 3, 2:14] = j
+        pred[0, 2 * k + 1:2 * k + 3, 1:9], pred[0, 2 * k + 1:2 * k + 3, 9:15] = ids[5 - k], 7 + k
+    gt[1], pred[1] = np.where(gt[0] > 2047, 0, gt[0]), np.where(pred[0] > 2047, 3, pred[0])
+    ref = inst_reference(pred.reshape(2, -1), gt.reshape(2, -1), max_id)[0]
+    assert (ref[0, COL["n_bad"]] == 0) == (max_id == 2049) and ref[1, COL["n_bad"]] == 0 and ref[1, COL["n_gt_ids"]] == 4
+    check("max_id %d" % max_id, pkg, dev, pred.reshape(2, -1), gt.reshape(2, -1), 256, max_id)
+
+
 # ---- 3. bad labels and a full table ------------------------------------------------------------------------------------------------------------
 def test_bad_labels_stay_in_their_image(pkg, dev):
     pred, gt = base()

@@ -185,6 +185,21 @@ def test_hub_single_id_and_singletons(pkg, dev):
     compare("singletons", raw(pkg, dev, own, a[:, :, :, :24, :31].repeat(2, 0), offs, None, max_id=24 * 31 - 1, capacity=4096, max_edges=1500), refs)
 
 
+def test_ids_on_both_sides_of_a_step_of_the_row_start_scan(pkg, dev):
+    """k_rag_scan takes 2048 ids a step and carries the row starts from one step to the next: ids 0 .. 2303 with edges on both sides of
+    the step, then an image whose only ids lie around it"""
+    own = np.arange(48 * 48, dtype=np.int32).reshape(1, 1, 48, 48)
+    a = np.random.default_rng(48).random((1, 2, 1, 48, 48), dtype=np.float32)
+    offs = [[0, -1, 0], [0, 0, -1]]
+    refs = rag_reference_batch(own, a, offs, a[:, 0], max_id=2303)
+    assert refs[0]["stats"][0] == 2 * 47 * 48 and (refs[0]["uv"][:, 0] < 2048).any() and (refs[0]["uv"][:, 0] >= 2048).any()
+    compare("48 x 48 singletons", raw(pkg, dev, own, a, offs, a[:, 0], max_id=2303, capacity=8192, max_edges=4600), refs)
+    few = np.array([[2047, 2048, 2049, 2049], [2049, 2047, 2048, 2048]], np.int32).reshape(1, 1, 2, 4)
+    refs = rag_reference_batch(few, a[:, :, :, :2, :4], offs, None, max_id=2049)
+    assert refs[0]["uv"].tolist() == [[2047, 2048], [2047, 2049], [2048, 2049]]
+    compare("2047 2048 2049", raw(pkg, dev, few, a[:, :, :, :2, :4], offs, None, max_id=2049, capacity=64, max_edges=8), refs)
+
+
 # ---- 5. a table and an edge list too small on purpose: the call returns and says so ---------------------------------------------------------------
 def test_small_capacity_and_small_max_edges(pkg, dev):
     _, a, b = volume("3d")

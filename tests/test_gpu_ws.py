@@ -399,6 +399,18 @@ def test_skewed_pointers_give_the_same_bits(pkg, dev):
         assert all(torch.equal(got[k], aligned[k]) for k in aligned), skew
 
 
+def test_stacked_ids_over_more_planes_than_a_step_of_the_offsets(pkg, dev):
+    """k_ws_offsets takes 256 planes a step with a carry: 257 planes of 2 x 2 with one seed each, so the last plane's offset is 256"""
+    N = 257
+    h = torch.zeros((N, 2, 2), dtype=torch.float32, device=dev)
+    s = torch.zeros((N, 2, 2), dtype=torch.int32, device=dev)
+    s[:, 1, 0] = 3  # (any id in 1 .. Y * X is a seed id)
+    w = pkg.seeded_watershed(h, s, stack_ids=True)
+    want = torch.arange(1, N + 1, dtype=torch.int32, device=dev)[:, None, None].expand(N, 2, 2)
+    assert torch.equal(w.labels, want) and w.counts.tolist() == [[1, 1]] * N and int(w.stats[:, 1].sum()) == 0
+    assert torch.equal(pkg.seeded_watershed(h, s).labels, torch.ones_like(s))  # not stacked: every plane starts at 1
+
+
 # ---- 3. the Python layer, end to end -------------------------------------------------------------------------------------------------------------
 @functools.lru_cache(maxsize=None)
 def membranes():

@@ -169,6 +169,21 @@ def test_workspace_bytes_increase_strictly(pkg, lib):
     assert lib.pea_inst_workspace_bytes(None) == 0
 
 
+def test_workspace_bytes(pkg, lib):
+    ws = lambda **kw: lib.pea_inst_workspace_bytes(ctypes.byref(desc(pkg, **kw)))
+    al8 = lambda x: (x + 7) // 8 * 8
+    # a header of 8 words, 32 words per image, 6 words per (image, slot) (a pair and a row entry), 2 words per (image, present gt id) with
+    # room for min(max_id + 1, capacity) of them, and three int32 per (image, id) that are padded to 8 bytes TOGETHER.  max_id + 1 below,
+    # at and above the capacity; odd B * (max_id + 1) among them
+    cases = ((1, 64, 1), (1, 64, 2), (3, 64, 62), (3, 64, 63), (3, 64, 64), (5, 64, 200), (2, 256, 200), (7, 256, 255), (7, 256, 256),
+             (1, 1024, 65534), (33, 1 << 14, 65535), (3, 1 << 21, 4))
+    for B, cap, max_id in cases:
+        M = max_id + 1
+        assert ws(B=B, capacity=cap, max_id=max_id) == 8 * (8 + 32 * B + 6 * B * cap + 2 * B * min(M, cap)) + al8(12 * B * M), (B, cap, max_id)
+    # 48 * (2^31 - 1) * 2^31 bytes are more than 2^64: the count does not fit
+    assert ws(B=2 ** 31 - 1, capacity=2 ** 31) == 2 ** 64 - 1 and ws(B=2 ** 31 - 1, capacity=2 ** 31, max_id=65535) == 2 ** 64 - 1
+
+
 def test_workspace_init_refusals(pkg, lib):
     f = lambda p, n: lib.pea_inst_workspace_init(vp(p), n, None)
     assert f(0, 4096) == E_NULL and f(WORK + 4, 4096) == E_ALIGN and f(WORK + 1, 4096) == E_ALIGN

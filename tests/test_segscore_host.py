@@ -187,6 +187,16 @@ def test_workspace_bytes_are_monotone_in_capacity(pkg, lib):
     assert lib.pea_seg_workspace_bytes(None) == 0
 
 
+def test_workspace_bytes(pkg, lib):
+    ws = lambda **kw: lib.pea_seg_workspace_bytes(ctypes.byref(desc(pkg, **kw)))
+    # a header of 8 words, 32 words per image, 10 words per (image, slot): the pair table (2) and the row and column tables (4 each)
+    for B, cap in ((1, 64), (3, 64), (2, 256), (7, 1024), (33, 1 << 14), (1, 1 << 31), (2 ** 31 - 1, 64), (5, 1 << 21)):
+        assert ws(B=B, capacity=cap) == 8 * (8 + 32 * B + 10 * B * cap), (B, cap)
+    # 80 * (2^31 - 1) * 2^31 bytes are more than 2^64: the count does not fit
+    assert ws(B=2 ** 31 - 1, capacity=2 ** 31) == 2 ** 64 - 1
+    assert ws(B=2 ** 29, capacity=2 ** 31) == 2 ** 64 - 1 and ws(B=2 ** 26, capacity=2 ** 31) == 8 * (8 + 2 ** 31 + 10 * 2 ** 57)
+
+
 def test_workspace_init_refusals(pkg, lib):
     f = lambda p, n: lib.pea_seg_workspace_init(vp(p), n, None)
     assert f(0, 4096) == E_NULL and f(WORK + 4, 4096) == E_ALIGN and f(WORK + 1, 4096) == E_ALIGN
