@@ -43,9 +43,10 @@ def gpu_inputs(dev, B, D, dims, K, seed, f16=False, mask=True):
     return e, t, w, m
 
 
-def run(pkg, spec, e, t, w, m, dloss=1.0):
+def run(pkg, spec, e, t, w, m, dloss=1.0, eo=None):
+    """eo: the detached second operand of the cross loss (the EMA embedding), None for the self loss"""
     et = e.detach().clone().requires_grad_(True)
-    loss, affs, parts = pkg.affinity_op.FusedAffinityMSE.apply(et, None, t, w, m, spec)
+    loss, affs, parts = pkg.affinity_op.FusedAffinityMSE.apply(et, eo, t, w, m, spec)
     (loss * dloss).backward()
     return loss.detach(), affs, parts, et.grad
 
@@ -63,8 +64,9 @@ def full_norms(pkg, spec, B, dims):
     return out
 
 
-def window_vs_oracle(pkg, orc, spec, B, dims, e, t, w, m, affs, grad, b, lo, size, dloss, grad_tol=GRAD_RTOL):
-    """oracle on the window [lo, lo + size) of image b; compare the interior (margin = the stencil's reach per axis)"""
+def window_vs_oracle(pkg, orc, spec, B, dims, e, t, w, m, affs, grad, b, lo, size, dloss, grad_tol=GRAD_RTOL, eo=None):
+    """oracle on the window [lo, lo + size) of image b; compare the interior (margin = the stencil's reach per axis).
+    eo: the detached second operand of a cross loss"""
     sl = tuple(slice(lo[a], lo[a] + size[a]) for a in range(3))
     def cut(x):
         if x is None:
@@ -72,13 +74,13 @@ def window_vs_oracle(pkg, orc, spec, B, dims, e, t, w, m, affs, grad, b, lo, siz
         v = x[b][(slice(None),) + sl]
         return np.ascontiguousarray(v.cpu().numpy() if v.dtype == torch.uint8 else v.float().cpu().numpy())[None]
 
-    ew, tw, ww, mw = cut(e), cut(t), cut(w), cut(m)
+    ew, tw, ww, mw, ow = cut(e), cut(t), cut(w), cut(m), cut(eo)
     S_win = float(np.prod(size))
     lam = [spec.lam[i] * S_win / n for i, n in enumerate(full_norms(pkg, spec, B, dims))]
     offs = [list(o) for o in spec.offsets]
     d = orc.make_desc(1, ew.shape[1], list(size), offs, lam, spec.border, orc.NORM_FULL, ndim=3)
-    o_affs, _ = orc.c_fwd(d, ew, None, tw, ww, mw)
-    o_grad, _ = orc.c_bwd(d, ew, None, tw, ww, mw, dloss=dloss)
+    o_affs, _ = orc.c_fwd(d, ew, ow, tw, ww, mw)
+    o_grad, _ = orc.c_bwd(d, ew, ow, tw, ww, mw, dloss=dloss)
     reach = [max(abs(o[a]) for o in offs) for a in range(3)]
     inner = tuple(slice(reach[a], size[a] - reach[a]) if size[a] > 2 * reach[a] else slice(0, size[a]) for a in range(3))
     # an axis the window covers completely (e.g. all of z) needs no margin: the window's border there IS the volume's border

@@ -264,3 +264,28 @@ def test_grid_limits_are_refused_before_any_device_call(pkg, lib):
         d = desc(pkg, B=B, dims=(Z, 1, 1), offsets=[(0, 0, 0)])
         assert wts(lib, d) == E_UNSUPPORTED
         assert wts(lib, d, ws=0) == E_WORKSPACE and wts(lib, d, flags=16) == E_DESC and wts(lib, d, labels=0) == E_NULL
+
+
+def test_pixel_count_edge_of_the_descriptor(pkg, lib):
+    """The label kernels index a plane with 32-bit integers (csrc/pea_targets.h: the pixel of a lane, the neighbour's flat index, the
+    weight kernel's p = block * 256 + lane), which is safe only while S + 255 fits an int32: the descriptor check in front of them
+    (csrc/pea_abi.hip validate: S <= 2^31 - 1 - 256) must sit exactly there.  S = 2^31 - 257 is the largest image served -- with a NULL
+    label pointer the call gets as far as PEA_E_NULL, and the workspace query answers --; S = 2^31 - 256 .. 2^31 - 1 are refused with
+    PEA_E_UNSUPPORTED whatever the pointers, and the query answers 0.  Nothing is launched."""
+    top = 2 ** 31 - 257
+    for S in (top - 1, top):
+        for dims in ((1, 1, S), (1, S, 1)):
+            d = desc(pkg, B=1, dims=dims, offsets=[(0, 0, 0)])
+            wgs = ((dims[2] + 63) // 64) * ((dims[1] + 31) // 32)
+            assert lib.pea_targets_workspace_bytes(ctypes.byref(d)) == 4 * wgs
+            assert gen(lib, d, labels=0) == E_NULL and wts(lib, d, labels=0) == E_NULL
+    d = desc(pkg, B=1, dims=(2, (top - 1) // 2, 1), offsets=[(0, 0, 0)])  # the same count as a volume
+    assert gen(lib, d, labels=0) == E_NULL
+    for S in (top + 1, top + 2, 2 ** 31 - 2, 2 ** 31 - 1):
+        for dims in ((1, 1, S), (1, S, 1)):
+            d = desc(pkg, B=1, dims=dims, offsets=[(0, 0, 0)])
+            assert lib.pea_targets_workspace_bytes(ctypes.byref(d)) == 0
+            assert gen(lib, d) == E_UNSUPPORTED and gen(lib, d, labels=0) == E_UNSUPPORTED
+            assert wts(lib, d) == E_UNSUPPORTED and wts(lib, d, labels=0) == E_UNSUPPORTED
+    d = desc(pkg, B=1, dims=(2, 2 ** 30 - 128, 1), offsets=[(0, 0, 0)])  # 2^31 - 256 voxels in two planes
+    assert gen(lib, d, labels=0) == E_UNSUPPORTED and lib.pea_targets_workspace_bytes(ctypes.byref(d)) == 0
