@@ -53,6 +53,8 @@ from .utils import lmc
 from .utils.lmc import mc_baseline, multicut_multi, probs_to_costs, transform_probabilities_to_costs
 from .harness.ws import (Watershed, WatershedSeeds, distance_transform_watershed, plateau_maxima, seeded_watershed, watershed_seeds)
 from .utils import fragment
+from .harness.mws import MutexWatershed, mutex_watershed
+from .utils.seg_mutex import mutex_watershed as elf_mutex_watershed, seg_mutex
 from .harness.handoff import AffsCollector
 from .harness.head_loss import HeadAffinityMSE, head_embedding_loss
 from .harness.train_step import CvpppTrainStep, convert_consistency_flip, label_pyramid, make_optimizer
@@ -101,3 +103,6 @@ RAG_EXPORTS = ("region_adjacency", "RegionAdjacency", "project_node_labels", "lm
                "transform_probabilities_to_costs")
 # likewise the watershed fragments (include/pea_ws.h) and the reference's scripts_ac3ac4/utils/fragment.py on them
 WS_EXPORTS = ("watershed_seeds", "WatershedSeeds", "seeded_watershed", "Watershed", "distance_transform_watershed", "plateau_maxima", "fragment")
+# likewise the mutex watershed (include/pea_mws.h) and the reference's utils/seg_mutex.py on it; elf's own mutex_watershed(1 - affs, ..)
+# is elf_mutex_watershed here and mutex_watershed in utils/seg_mutex.py, the module that the reference's call sites import from
+MWS_EXPORTS = ("mutex_watershed", "MutexWatershed", "seg_mutex", "elf_mutex_watershed")

@@ -28,6 +28,7 @@ HEADER_INSTSCORE = os.path.join(HERE, "..", "include", "pea_instscore.h")
 HEADER_CC = os.path.join(HERE, "..", "include", "pea_cc.h")
 HEADER_RAG = os.path.join(HERE, "..", "include", "pea_rag.h")
 HEADER_WS = os.path.join(HERE, "..", "include", "pea_ws.h")
+HEADER_MWS = os.path.join(HERE, "..", "include", "pea_mws.h")
 
 PEA_ABI_VERSION = 2
 PEA_MAX_K = 32
@@ -66,6 +67,10 @@ RAG_MAX_K, RAG_MIN_CAPACITY, RAG_STATS = 32, 64, 8  # include/pea_rag.h PEA_RAG_
 # the columns of pea_rag_build's stats [B][RAG_STATS] in order (include/pea_rag.h PEA_RAG_N_<NAME>)
 RAG_STAT_COLUMNS = ("edges", "edges_dropped", "pairs_dropped", "no_id", "not_touching", "skipped", "reserved0", "reserved1")
 WS_STACK_IDS, WS_FIELD, WS_MAX_RADIUS = 1, 2, 32  # include/pea_ws.h PEA_WS_STACK_IDS, PEA_WS_FIELD, PEA_WS_MAX_RADIUS
+MWS_MAX_K, MWS_MAX_ROUNDS, MWS_RESUME, MWS_STATS = 32, 65536, 1, 8  # include/pea_mws.h PEA_MWS_MAX_K, PEA_MWS_MAX_ROUNDS, PEA_MWS_RESUME, PEA_MWS_STATS
+MWS_INPUTS = {"affs": 0, "elf": 1, "weights": 2}  # include/pea_mws.h PEA_MWS_IN_AFFS, PEA_MWS_IN_ELF, PEA_MWS_IN_WEIGHTS
+# the columns of pea_mws_segment's stats [B][MWS_STATS] in order (include/pea_mws.h PEA_MWS_<NAME>)
+MWS_STAT_COLUMNS = ("rounds", "undecided", "merges", "exclusions", "missing_stride", "missing_mask", "missing_nan", "missing_outside")
 DISC_STATS = 5  # loss, var, dist, reg, n_bad; then var_b, dist_b, reg_b, C_b per image (include/pea_disc.h PEA_DISC_STATS)
 
 EXPORTS = ("pea_version", "pea_strerror", "pea_desc_validate", "pea_workspace_bytes", "pea_workspace_init", "pea_reload_env",
@@ -106,6 +111,8 @@ EXPORTS_CC = ("pea_cc_validate", "pea_cc_workspace_bytes", "pea_cc_label")
 EXPORTS_RAG = ("pea_rag_validate", "pea_rag_workspace_bytes", "pea_rag_workspace_init", "pea_rag_build", "pea_rag_project")
 # the entry points of include/pea_ws.h (the watershed fragments: distance transform, seeds, flood)
 EXPORTS_WS = ("pea_ws_validate", "pea_ws_seeds_workspace_bytes", "pea_ws_flood_workspace_bytes", "pea_ws_seeds", "pea_ws_flood")
+# the entry points of include/pea_mws.h (the mutex watershed)
+EXPORTS_MWS = ("pea_mws_validate", "pea_mws_workspace_bytes", "pea_mws_segment")
 
 
 class PeaLibraryError(RuntimeError):
@@ -208,6 +215,13 @@ class PeaWsDesc(ctypes.Structure):
                 ("flags", ctypes.c_uint32)]
 
 
+class PeaMwsDesc(ctypes.Structure):
+    """mirror of `struct PeaMwsDesc` in include/pea_mws.h"""
+    _fields_ = [("B", ctypes.c_int32), ("Z", ctypes.c_int32), ("Y", ctypes.c_int32), ("X", ctypes.c_int32), ("K", ctypes.c_int32),
+                ("n_attractive", ctypes.c_int32), ("offsets", (ctypes.c_int32 * 3) * MWS_MAX_K), ("strides", ctypes.c_int32 * 3),
+                ("input", ctypes.c_int32), ("rounds", ctypes.c_int32), ("flags", ctypes.c_uint32)]
+
+
 HIPCC_FLAGS = ["-O3", "--offload-arch=gfx950", "-std=c++17", "-fPIC"]
 OBJ_DIR = os.path.join(CSRC, "build")
 
@@ -233,7 +247,7 @@ def build(force=False, verbose=False, jobs=None):
 
 def _build_locked(force, verbose, jobs):
     srcs = sources()
-    hdrs = [HEADER, HEADER_INFER, HEADER_MULTI, HEADER_FLIP, HEADER_MULTI_LABELS, HEADER_HEAD16, HEADER_METRICS, HEADER_FGMASK, HEADER_DISC, HEADER_CROP, HEADER_DIST, HEADER_SEGSCORE, HEADER_INSTSCORE, HEADER_CC, HEADER_RAG, HEADER_WS] + [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".h")]
+    hdrs = [HEADER, HEADER_INFER, HEADER_MULTI, HEADER_FLIP, HEADER_MULTI_LABELS, HEADER_HEAD16, HEADER_METRICS, HEADER_FGMASK, HEADER_DISC, HEADER_CROP, HEADER_DIST, HEADER_SEGSCORE, HEADER_INSTSCORE, HEADER_CC, HEADER_RAG, HEADER_WS, HEADER_MWS] + [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".h")]
     newest_hdr = max(os.path.getmtime(h) for h in hdrs)
     if not force and os.path.exists(SO_PATH) and os.path.getmtime(SO_PATH) >= max([newest_hdr] + [os.path.getmtime(x) for x in srcs]):
         return SO_PATH
@@ -297,7 +311,7 @@ def lib():
         L = ctypes.CDLL(SO_PATH)
     except OSError as ex:
         raise PeaLibraryError("cannot load %s: %s" % (SO_PATH, ex))
-    for name in EXPORTS + EXPORTS_INFER + EXPORTS_MULTI + EXPORTS_FLIP + EXPORTS_MULTI_LABELS + EXPORTS_HEAD16 + EXPORTS_METRICS + EXPORTS_FGMASK + EXPORTS_DISC + EXPORTS_CROP + EXPORTS_DIST + EXPORTS_SEGSCORE + EXPORTS_INSTSCORE + EXPORTS_CC + EXPORTS_RAG + EXPORTS_WS:
+    for name in EXPORTS + EXPORTS_INFER + EXPORTS_MULTI + EXPORTS_FLIP + EXPORTS_MULTI_LABELS + EXPORTS_HEAD16 + EXPORTS_METRICS + EXPORTS_FGMASK + EXPORTS_DISC + EXPORTS_CROP + EXPORTS_DIST + EXPORTS_SEGSCORE + EXPORTS_INSTSCORE + EXPORTS_CC + EXPORTS_RAG + EXPORTS_WS + EXPORTS_MWS:
         if not hasattr(L, name):
             raise PeaLibraryError("%s does not export %s" % (SO_PATH, name))
     vp, dp = ctypes.c_void_p, ctypes.POINTER(PeaDesc)
@@ -480,6 +494,13 @@ def lib():
     L.pea_ws_seeds.argtypes = [ws, vp, vp, vp, vp, vp, vp, vp, ctypes.c_size_t, vp]
     L.pea_ws_flood.restype = ctypes.c_int
     L.pea_ws_flood.argtypes = [ws, vp, vp, vp, vp, vp, vp, ctypes.c_size_t, vp]
+    mw = ctypes.POINTER(PeaMwsDesc)
+    L.pea_mws_validate.restype = ctypes.c_int
+    L.pea_mws_validate.argtypes = [mw]
+    L.pea_mws_workspace_bytes.restype = ctypes.c_size_t
+    L.pea_mws_workspace_bytes.argtypes = [mw]
+    L.pea_mws_segment.restype = ctypes.c_int
+    L.pea_mws_segment.argtypes = [mw, vp, vp, vp, vp, vp, vp, ctypes.c_size_t, vp]
     if L.pea_version() != PEA_ABI_VERSION:
         raise PeaLibraryError("ABI mismatch: library %d, binding %d" % (L.pea_version(), PEA_ABI_VERSION))
     _lib = L

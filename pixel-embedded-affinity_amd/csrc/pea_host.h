@@ -24,6 +24,8 @@
 //   pea_k_rag.hip      the region adjacency graph with affinity and boundary statistics (include/pea_rag.h) on the table of pea_segtable.h
 //   pea_k_ws.hip       the watershed fragments (include/pea_ws.h): distance transform, Gaussians, plateau maxima (through pea_cc_label's
 //                      entry point), the Boruvka flood with its size filter and numbering
+//   pea_k_mws.hip      the mutex watershed (include/pea_mws.h): a state byte per edge, rounds of best / decide / hook / compress / rebuild of
+//                      the exclusion table, the raster-order numbering
 // Each kernel file exports a few plain functions (declared here) that pick the instantiation and launch it; a function returns
 // false when its family has no kernel for the descriptor and the caller tries the next one.  No device code crosses a file.
 // pea_dispatch.h holds what the launchers share to get from run-time facts (storage dtype, D, border, mask type, ..) to template

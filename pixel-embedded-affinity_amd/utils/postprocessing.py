@@ -7,7 +7,8 @@ there.
 
 merge_small_object and merge_func of the same file are NOT here and stay on the host: each merge rewrites the image that the next one
 reads, in id order (a small segment takes the id that is most frequent in a window around its centroid, and the segments after it see
-the result), so they are a sequential host algorithm by construction.  So are seg_mutex and relabel of the validation loop.
+the result), so they are a sequential host algorithm by construction.  So is relabel of the validation loop.  seg_mutex is not: it runs
+on the device (utils/seg_mutex.py, include/pea_mws.h).
 """
 import numpy as np
 import torch
