@@ -532,13 +532,16 @@ extern "C" int pea_mws_segment(const PeaMwsDesc* d, const float* x, const uint8_
   memset(P.off, 0, sizeof(P.off));
   memset(P.delta, 0, sizeof(P.delta));
   for (int k = 0; k < d->K; ++k) {
-    // an offset that leaves the image on its own makes a channel without edges; its delta is never added (clamped so the product fits)
+    // an offset that leaves the image on its own makes a channel without edges; its delta is never added (clamped so the product fits).
+    // A step is copied clamped to [-extent, extent] of its axis: one at or past the extent is outside for every pixel either way, and
+    // coordinate + step then fits an int in k_mws_init_edges whatever the caller wrote (2^31 - 1, -2^31).
     long long delta = 0;
     bool far = false;
     for (int a = 0; a < 3; ++a) {
-      P.off[k][a] = d->offsets[k][a];
       const int ext = a == 0 ? d->Z : (a == 1 ? d->Y : d->X);
-      if (d->offsets[k][a] >= ext || d->offsets[k][a] <= -ext) far = true;
+      const int step = d->offsets[k][a];
+      P.off[k][a] = step > ext ? ext : (step < -ext ? -ext : step);
+      if (step >= ext || step <= -ext) far = true;
     }
     if (!far) delta = ((long long)d->offsets[k][0] * d->Y + d->offsets[k][1]) * d->X + d->offsets[k][2];
     P.delta[k] = (int)delta;

@@ -4,6 +4,8 @@ test_gpu_mws.py, no test of its own):
   sequential(g)    (a) the definition: the edges by descending key through a union-find, a set of excluded roots per root
   naive(g)         (b) the same order, but "exclusive?" is answered by scanning every earlier repulsive edge that became an exclusion
   rounds(g)        (c) the round rule of the header as a simulation: prune, best, decide, hook, compress, carry, rebuild
+  rounds_trace(g)  (c) again, returning what the header fixes after every round: the partition, the rounds used and the counts of
+                   undecided, merged and active edges -- the integers of the stats columns of a call whose rounds ran out
 
 A graph g comes from edges(x, offsets, n_attractive, strides, mask, input) of ONE image x [K, Z, Y, X].  Every function returns the flat
 label image in the numbering of the header: clusters 1 .. n in raster order of their first pixel, invalid pixels 0.
@@ -97,8 +99,9 @@ def _find(par, a):
     return a
 
 
-def sequential(g, limit=None):
-    """(a).  limit: stop after that many edges of the order (a prefix of the procedure)"""
+def sequential(g, limit=None, with_exclusions=False):
+    """(a).  limit: stop after that many edges of the order (a prefix of the procedure).  with_exclusions: -> (labels, the number of
+    distinct unordered pairs of exclusive roots as the procedure stands at its end: half the sum of the set sizes)"""
     par = list(range(g.S))
     excl = {}
     n = len(g.p) if limit is None else limit
@@ -128,7 +131,11 @@ def sequential(g, limit=None):
                 excl[c].add(b)
                 eb.add(c)
             del excl[a]
-    return raster(np.array([_find(par, i) for i in range(g.S)]), g.valid)
+    labels = raster(np.array([_find(par, i) for i in range(g.S)]), g.valid)
+    if not with_exclusions:
+        return labels
+    assert all(par[r] == r and r not in e and all(r in excl[c] for c in e) for r, e in excl.items()), "the sets are not symmetric on roots"
+    return labels, sum(len(e) for e in excl.values()) // 2
 
 
 def naive(g):
@@ -152,7 +159,25 @@ def naive(g):
 
 
 def rounds(g, max_rounds=None, prune_table=True):
-    """(c) -> (labels, rounds in which an edge was decided, edges left undecided)"""
+    """(c) -> (labels, rounds in which an edge was decided, edges left undecided: those that survived the last prune and were not
+    decided since)"""
+    return _simulate(g, max_rounds, prune_table, None, False, None)[0]
+
+
+def rounds_trace(g, max_rounds=None, history=None, states=False, hooks=None):
+    """(c) -> (labels, used, undecided_slots, merged, active) as the state stands after the last round run, the round's rebuild of the
+    table and the death of duplicate exclusions included.  used: the rounds in which an edge was decided.  undecided_slots: the edges
+    whose state is still "undecided", those that the next round's prune would kill among them (what the kernels count; not the third
+    value of rounds()).  merged, active: the edges decided as merges, the active exclusions.  A round whose prune leaves nothing ends
+    the procedure and is no round of `used`: with max_rounds = n <= the rounds needed the state is the one after n rounds, without the
+    prune of round n + 1; with more, or None, the one after the last prune (undecided_slots == 0).
+    history: a list that receives the same tuple after every round of `used`.  states: the state bytes (0 undecided, 1 dead, 2 merged,
+    3 active exclusion, in the order of g's edges) are appended to every tuple.  hooks: a list that receives, per round, (the parent of
+    every root as the round hooked them, before any compression; the pointer doublings that changed a pointer)."""
+    return _simulate(g, max_rounds, True, history, states, hooks)[1]
+
+
+def _simulate(g, max_rounds, prune_table, history, states, hooks):
     S = g.S
     n = len(g.p)
     state = np.zeros(n, np.uint8)  # 0 undecided, 1 dead, 2 merged, 3 active exclusion
@@ -161,6 +186,11 @@ def rounds(g, max_rounds=None, prune_table=True):
     table = np.zeros(0, np.int64)
     used = 0
     und = n
+
+    def snapshot():
+        out = (raster(root, g.valid), used, int((state == 0).sum()), int((state == 2).sum()), int((state == 3).sum()))
+        return out + (state.copy(),) if states else out
+
     while max_rounds is None or used < max_rounds:
         # prune, on the state as the round finds it
         u = np.nonzero(state == 0)[0]
@@ -199,11 +229,15 @@ def rounds(g, max_rounds=None, prune_table=True):
         hascon[rb[act]] = True
         used += 1
         und -= int((pa | pb | act).sum())
+        hooked, doublings = par, 0
         while True:  # compress by pointer jumping
             nxt = par[par]
             if np.array_equal(nxt, par):
                 break
             par = nxt
+            doublings += 1
+        if hooks is not None:
+            hooks.append((hooked, doublings))
         moved = np.nonzero(hascon & (par != np.arange(S)))[0]
         hascon[par[moved]] = True
         root = par[root]
@@ -215,23 +249,30 @@ def rounds(g, max_rounds=None, prune_table=True):
         dup = np.ones(len(a), bool)
         dup[firsts] = False
         state[a[dup]] = 1
-    return raster(root, g.valid), used, und
+        if history is not None:
+            history.append(snapshot())
+    return (raster(root, g.valid), used, und), snapshot()
 
 
-def segment(x, offsets, n_attractive, strides=None, mask=None, input=IN_AFFS):
+def segment(x, offsets, n_attractive, strides=None, mask=None, input=IN_AFFS, with_rounds=False):
     """a batch x [B, K, Z, Y, X] (mask [B, Z, Y, X] or None) through (a) -> labels int32 [B, Z, Y, X], counts [B], missing int [B, 4] in
-    the order of the header's stats columns: stride, mask, nan, outside"""
+    the order of the header's stats columns: stride, mask, nan, outside.  with_rounds: two more, per image -- the exclusive pairs at
+    the end of (a), and the rounds that (c) used, whose partition is held to (a)'s on the way"""
     x = np.asarray(x, np.float32)
     labels = np.zeros((x.shape[0],) + x.shape[2:], np.int32)
     counts = np.zeros(x.shape[0], np.int32)
     missing = np.zeros((x.shape[0], 4), np.int64)
+    exclusions, used = np.zeros(x.shape[0], np.int64), np.zeros(x.shape[0], np.int64)
     for b in range(x.shape[0]):
         g = edges(x[b], offsets, n_attractive, strides, None if mask is None else mask[b], input)
-        lab = sequential(g)
+        lab, exclusions[b] = sequential(g, with_exclusions=True)
         labels[b] = lab.reshape(x.shape[2:])
         counts[b] = lab.max() if lab.size else 0
         missing[b] = [g.missing[k] for k in ("stride", "mask", "nan", "outside")]
-    return labels, counts, missing
+        if with_rounds:
+            sim, used[b], left, merged, active = rounds_trace(g)
+            assert np.array_equal(sim, lab) and left == 0 and active == exclusions[b] and merged == int(g.valid.sum()) - counts[b]
+    return (labels, counts, missing, exclusions, used) if with_rounds else (labels, counts, missing)
 
 
 def is_refinement(fine, coarse):

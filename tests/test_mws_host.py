@@ -14,6 +14,7 @@ import numpy as np
 import pytest
 import torch
 
+import mws_cases as C
 import mws_reference as R
 from conftest import ROOT
 
@@ -57,6 +58,21 @@ def test_three_restatements_agree(case):
     few, used_few, left_few = R.rounds(g, max_rounds=2)
     assert R.is_refinement(few, a) and (left_few > 0 or np.array_equal(few, a))
     assert R.is_refinement(R.sequential(g, limit=len(g.p) // 3), a)
+    # the trace is the same simulation; its counts at the end are those of the sequential form: the active exclusions are the distinct
+    # exclusive pairs, every merge took one cluster away
+    a2, pairs = R.sequential(g, with_exclusions=True)
+    t, t_used, slots, merged, active = R.rounds_trace(g)
+    assert np.array_equal(a2, a) and np.array_equal(t, c) and t_used == used and slots == 0
+    assert active == pairs and merged == int(g.valid.sum()) - int(a.max())
+    before = len(g.p)
+    for n in (1, 2, 5):
+        part, n_used, slots, merged, active = R.rounds_trace(g, n)
+        short, short_used, short_left = R.rounds(g, max_rounds=n)
+        assert np.array_equal(part, short) and n_used == short_used == min(n, used)
+        assert (short_left > 0 and slots > 0) if n < used else (n == used or short_left == slots == 0)
+        assert R.is_refinement(part, a) and slots <= before and slots + merged + active <= len(g.p)
+        assert merged == int(g.valid.sum()) - int(part.max()) and (n < used or np.array_equal(part, a))
+        before = slots
 
 
 def test_the_table_prune_is_part_of_the_rule():
@@ -66,6 +82,140 @@ def test_the_table_prune_is_part_of_the_rule():
     a, with_prune, _ = R.rounds(g)
     b, without, _ = R.rounds(g, prune_table=False)
     assert np.array_equal(a, b) and np.array_equal(a, R.sequential(g)) and without > with_prune
+
+
+# ---- the named graphs of test_gpu_mws_rounds.py: what each name promises, held on the reference alone --------------------------------------
+def traced(case, b=0):
+    """-> (graph, sequential labels, exclusive pairs, the trace's final tuple with the states, history, hooks)"""
+    g = C.graph(case, b)
+    lab, pairs = R.sequential(g, with_exclusions=True)
+    hist, hooks = [], []
+    end = R.rounds_trace(g, history=hist, states=True, hooks=hooks)
+    assert np.array_equal(end[0], lab) and end[2] == 0 and end[4] == pairs and end[3] == int(g.valid.sum()) - int(lab.max())
+    assert len(hist) == len(hooks) == end[1] and all(h[1] == i + 1 for i, h in enumerate(hist))
+    return g, lab, pairs, end, hist, hooks
+
+
+def one_chain(hooked):
+    """the hooks of a round are ONE chain through every node: one root (so one tree), which is the smaller end of the last, mutual
+    edge, and no node with more than two neighbours -- a path, with the root next to its far end"""
+    nodes = np.arange(len(hooked))
+    children = np.bincount(hooked[hooked != nodes], minlength=len(hooked))
+    degree = children + (hooked != nodes)
+    return int((hooked == nodes).sum()) == 1 and int(degree.max()) == 2 and int((degree == 1).sum()) == 2
+
+
+def test_named_rising_line_and_snake_hook_one_chain_in_one_round():
+    for name, edges_, S in (("rising line", 4099, 4100), ("snake", 4354, 65 * 67)):
+        g, lab, pairs, end, hist, hooks = traced(C.NAMED[name]())
+        assert len(g.p) == edges_ == S - 1 and g.att.all() and g.S == S
+        assert end[1] == 1 and hist[0][3] == edges_ and hist[0][2] == 0, name  # one round decides every edge
+        assert int(lab.max()) == 1 and pairs == 0
+        hooked, doublings = hooks[0]
+        assert one_chain(hooked) and doublings == 13, (name, doublings)  # 2^12 < 4098 and 4353 <= 2^13
+    g = C.graph(C.NAMED["snake"]())
+    assert g.missing == dict(stride=0, mask=0, nan=64 * 67 - 64, outside=65 + 67)
+    # the hooks of the snake run both ways along x and cross rows: ends one row apart, and x steps of both signs
+    hooked = traced(C.NAMED["snake"]())[5][0][0]
+    step = hooked - np.arange(g.S)
+    assert (step == 1).any() and (step == -1).any() and (np.abs(step) == 67).any()
+    assert C.NAMED["rising line"]()[0][0, 0, 0, 0, 4099] == 4099 and len(np.unique(g.w)) == len(g.w)
+
+
+def test_named_falling_lines_decide_one_edge_a_round():
+    g, lab, pairs, end, hist, hooks = traced(C.NAMED["falling line"]())
+    assert end[1] == 299 and int(lab.max()) == 2 and pairs == 1
+    # the first round makes the 150 repulsive edges exclusions; every later one decides exactly one edge, a merge
+    assert hist[0][3:5] == (0, 150) and all(hist[i][3] == i for i in range(1, 299))
+    assert [h[2] for h in hist] == sorted((h[2] for h in hist), reverse=True) and hist[-1][2] == 0
+    for n in (1, 2, 3, 50, 150, 298):  # the snapshot rounds of the GPU test: all different, none final
+        assert not np.array_equal(hist[n - 1][0], lab) and hist[n - 1][2] > 0
+    g, lab, pairs, end, hist, hooks = traced(C.NAMED["falling line, reach 2"]())
+    assert end[1] == 151 and int(lab.max()) == 150 and pairs == 149 and (np.bincount(lab)[1:] == 2).all()
+
+
+def test_named_three_tempos_end_at_different_rounds():
+    case = C.NAMED["three tempos"]()
+    used = [traced(case, b)[3][1] for b in range(3)]
+    assert used[0] == 1 and used[1] == 299 and 1 < used[2] < 32 and C.reference("three tempos")[4].tolist() == used
+    assert np.isnan(case[0][0, 1]).all() and not np.isnan(case[0][1:]).any()
+    assert np.array_equal(case[0][1], C.NAMED["falling line"]()[0][0])
+
+
+def test_named_fullest_table_loads_the_table():
+    case = C.NAMED["table at its fullest"]()
+    g, lab, pairs, end, hist, hooks = traced(case)
+    lattice = 16 * 21
+    cap = 64
+    while cap < 2 * 6 * lattice:
+        cap *= 2
+    assert cap == C.FULLEST_CAPACITY == 4096 and 2 * 6 * lattice == 4032
+    top = max(h[4] for h in hist)
+    print("active exclusions at most", top, "of", cap, "at the end", pairs)
+    assert top >= 0.35 * cap and pairs >= 1200
+    assert float(case[0][0, 2:].min()) >= 2 and float(case[0][0, :2].max()) < 1
+
+
+def test_named_twins_name_one_pair_more_than_once():
+    for kind in ("quantised", "noise"):
+        case = C.NAMED["twins " + kind]()
+        g, lab, pairs, end, hist, hooks = traced(case)
+        S, state = g.S, end[5]
+        zero = g.eid // S == 6
+        assert int(zero.sum()) == S and np.array_equal(g.p[zero], g.q[zero])  # every slot of the zero offset is inside and exists
+        assert (state[zero] == 1).all()
+        rep = ~g.att & ~zero
+        pair = np.minimum(g.p, g.q)[rep] * S + np.maximum(g.p, g.q)[rep]
+        names, inv, count = np.unique(pair, return_inverse=True, return_counts=True)
+        assert set(count.tolist()) == {3} and len(names) == 10 * 21  # (-3, 0) twice and (3, 0) name every pair of pixels 3 rows apart
+        active = np.bincount(inv, weights=state[rep] == 3, minlength=len(names))
+        assert active.max() == 1 and int(active.sum()) >= 1  # of the edges that name one pair at most one stays active, and some do
+        if kind == "quantised":  # the twins tie, the lower edge id goes first: channel 3 wins over channels 4 and 5
+            assert (np.asarray(case[0]) * 4 == np.round(np.asarray(case[0]) * 4)).all()
+            assert len(np.unique(g.w)) <= 8
+
+
+def test_named_positive_steps_and_its_order_preserving_map():
+    case = C.NAMED["positive steps 3D"]()
+    g, lab, pairs, end, hist, hooks = traced(case)
+    assert all(min(o) >= 0 for o in case[1][:3]) and all(max(o) > 0 for o in case[1]) and g.missing["stride"] > 0 and g.missing["mask"] > 0
+    assert int(lab.max()) > 2 and pairs > 0
+    mapped = C.graph(C.positive_steps(2, 1))
+    assert np.array_equal(mapped.w, np.float32(2) * g.w + np.float32(1)) and np.array_equal(mapped.w.astype(np.float64), 2 * g.w.astype(np.float64) + 1)
+    assert np.array_equal(mapped.eid, g.eid)  # the sorted order of the keys is the same edge for edge
+    # one channel and its negation: complete, both are the rows; after one round they are two different partitions
+    up, down = C.graph(C.one_channel(1)), C.graph(C.one_channel(-1))
+    assert np.array_equal(np.sort(up.eid), np.sort(down.eid)) and np.array_equal(up.eid, down.eid[::-1])
+    assert np.array_equal(R.sequential(up), R.sequential(down)) and int(R.sequential(up).max()) == 37
+    assert not np.array_equal(R.rounds_trace(up, 1)[0], R.rounds_trace(down, 1)[0])
+
+
+def test_named_k32_far_channels_hold_no_edge():
+    x, offsets, nA, strides, mask, input = C.NAMED["K32 far"]()
+    S = 9 * 11
+    far = [k for k, (dy, dx) in enumerate(offsets) if abs(dy) >= 9 or abs(dx) >= 11]
+    # (OFF2's own (-9, 0) reaches the 9 rows as well: it is there twice)
+    assert len(offsets) == 32 and len(C.FAR) == 10 and sorted(offsets[k] for k in far) == sorted(C.FAR + [[-9, 0]]) and min(far) >= nA
+    for k in far:  # alone, attracting or repelling, whatever x holds: outside, and under nothing else
+        assert np.isnan(x[0, k]).any() and not np.isnan(x[0, k]).all()
+        for att in (0, 1):
+            one = R.edges(x[0, k:k + 1], C.off3([offsets[k]]), att, C.st3(strides), None, input)
+            assert one.missing == dict(stride=0, mask=0, nan=0, outside=S) and len(one.p) == 0, offsets[k]
+    g = C.graph(C.NAMED["K32 far"]())
+    assert not np.isin(g.eid // S, far).any()
+    for k in (offsets.index([-8, -10]), offsets.index([8, 10])):  # one slot inside
+        one = R.edges(np.zeros((1, 1, 9, 11), np.float32), C.off3([offsets[k]]), 1, [1, 1, 1], None, input)
+        assert len(one.p) == 1 and one.missing["outside"] == S - 1
+    traced(C.NAMED["K32 far"]())
+
+
+def test_named_large_cases_cross_their_thresholds():
+    g, lab, pairs, end, hist, hooks = traced(C.NAMED["more than 65536 pixels"]())
+    assert g.S == 260 * 261 > 65536 and -(-g.S // 256) == 266
+    firsts = np.unique(lab, return_index=True)[1]
+    assert int(lab.max()) > 100 and (firsts < 65536).sum() > 1 and (firsts >= 65536).sum() > 1
+    ref = C.reference("more than 256 images")
+    assert len(ref[1]) == 257 and len(np.unique(ref[1])) >= 3 and len(np.unique(ref[4])) >= 2
 
 
 def test_missing_edges_are_counted_once_by_their_first_cause():
