@@ -55,6 +55,8 @@ from .harness.ws import (Watershed, WatershedSeeds, distance_transform_watershed
 from .utils import fragment
 from .harness.mws import MutexWatershed, mutex_watershed
 from .utils.seg_mutex import mutex_watershed as elf_mutex_watershed, seg_mutex
+from .harness.agglo import Agglomeration, agglomerate, agglomerate_graph
+from .utils.seg_waterz import seg_waterz
 from .harness.handoff import AffsCollector
 from .harness.head_loss import HeadAffinityMSE, head_embedding_loss
 from .harness.train_step import CvpppTrainStep, convert_consistency_flip, label_pyramid, make_optimizer
@@ -106,3 +108,6 @@ WS_EXPORTS = ("watershed_seeds", "WatershedSeeds", "seeded_watershed", "Watershe
 # likewise the mutex watershed (include/pea_mws.h) and the reference's utils/seg_mutex.py on it; elf's own mutex_watershed(1 - affs, ..)
 # is elf_mutex_watershed here and mutex_watershed in utils/seg_mutex.py, the module that the reference's call sites import from
 MWS_EXPORTS = ("mutex_watershed", "MutexWatershed", "seg_mutex", "elf_mutex_watershed")
+# likewise the hierarchical agglomeration of the fragment graph (include/pea_agglo.h) and the reference's seg_waterz on it; the module
+# pea.utils.seg_waterz also carries relabel and waterz's own agglomerate(affs, thresholds, ..)
+AGGLO_EXPORTS = ("agglomerate_graph", "agglomerate", "Agglomeration", "seg_waterz")

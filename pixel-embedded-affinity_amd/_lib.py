@@ -29,6 +29,7 @@ HEADER_CC = os.path.join(HERE, "..", "include", "pea_cc.h")
 HEADER_RAG = os.path.join(HERE, "..", "include", "pea_rag.h")
 HEADER_WS = os.path.join(HERE, "..", "include", "pea_ws.h")
 HEADER_MWS = os.path.join(HERE, "..", "include", "pea_mws.h")
+HEADER_AGGLO = os.path.join(HERE, "..", "include", "pea_agglo.h")
 
 PEA_ABI_VERSION = 2
 PEA_MAX_K = 32
@@ -71,6 +72,11 @@ MWS_MAX_K, MWS_MAX_ROUNDS, MWS_RESUME, MWS_STATS = 32, 65536, 1, 8  # include/pe
 MWS_INPUTS = {"affs": 0, "elf": 1, "weights": 2}  # include/pea_mws.h PEA_MWS_IN_AFFS, PEA_MWS_IN_ELF, PEA_MWS_IN_WEIGHTS
 # the columns of pea_mws_segment's stats [B][MWS_STATS] in order (include/pea_mws.h PEA_MWS_<NAME>)
 MWS_STAT_COLUMNS = ("rounds", "undecided", "merges", "exclusions", "missing_stride", "missing_mask", "missing_nan", "missing_outside")
+AGGLO_RESUME, AGGLO_IGNORE_ZERO = 1, 2  # include/pea_agglo.h PEA_AGGLO_RESUME, PEA_AGGLO_IGNORE_ZERO
+AGGLO_LINKAGES = {"mean": 0, "min": 1, "max": 2}  # include/pea_agglo.h PEA_AGGLO_MEAN, PEA_AGGLO_MIN, PEA_AGGLO_MAX
+AGGLO_MAX_ROUNDS, AGGLO_MAX_EDGES, AGGLO_STATS = 65536, 1 << 30, 8  # include/pea_agglo.h PEA_AGGLO_MAX_ROUNDS, PEA_AGGLO_MAX_EDGES, PEA_AGGLO_STATS
+# the columns of pea_agglo_merge's stats [B][AGGLO_STATS] in order (include/pea_agglo.h PEA_AGGLO_<NAME>)
+AGGLO_STAT_COLUMNS = ("rounds", "live", "mergeable", "merges", "clusters", "no_edge", "bad_value", "reserved")
 DISC_STATS = 5  # loss, var, dist, reg, n_bad; then var_b, dist_b, reg_b, C_b per image (include/pea_disc.h PEA_DISC_STATS)
 
 EXPORTS = ("pea_version", "pea_strerror", "pea_desc_validate", "pea_workspace_bytes", "pea_workspace_init", "pea_reload_env",
@@ -113,6 +119,8 @@ EXPORTS_RAG = ("pea_rag_validate", "pea_rag_workspace_bytes", "pea_rag_workspace
 EXPORTS_WS = ("pea_ws_validate", "pea_ws_seeds_workspace_bytes", "pea_ws_flood_workspace_bytes", "pea_ws_seeds", "pea_ws_flood")
 # the entry points of include/pea_mws.h (the mutex watershed)
 EXPORTS_MWS = ("pea_mws_validate", "pea_mws_workspace_bytes", "pea_mws_segment")
+# the entry points of include/pea_agglo.h (the hierarchical agglomeration of the fragment graph: waterz's merge loop)
+EXPORTS_AGGLO = ("pea_agglo_validate", "pea_agglo_workspace_bytes", "pea_agglo_merge")
 
 
 class PeaLibraryError(RuntimeError):
@@ -222,6 +230,17 @@ class PeaMwsDesc(ctypes.Structure):
                 ("input", ctypes.c_int32), ("rounds", ctypes.c_int32), ("flags", ctypes.c_uint32)]
 
 
+class PeaAggloDesc(ctypes.Structure):
+    """mirror of `struct PeaAggloDesc` in include/pea_agglo.h"""
+    _fields_ = [("B", ctypes.c_int32), ("max_id", ctypes.c_int32), ("max_edges", ctypes.c_int64), ("n_edges_stride", ctypes.c_int64),
+                ("linkage", ctypes.c_int32), ("rounds", ctypes.c_int32), ("threshold", ctypes.c_float), ("flags", ctypes.c_uint32)]
+
+
+class PeaAggloBuffers(ctypes.Structure):
+    """mirror of `struct PeaAggloBuffers` in include/pea_agglo.h"""
+    _fields_ = [(n, ctypes.c_void_p) for n in ("uv", "n_edges", "value", "weight", "node_size", "root", "labels", "counts", "stats")]
+
+
 HIPCC_FLAGS = ["-O3", "--offload-arch=gfx950", "-std=c++17", "-fPIC"]
 OBJ_DIR = os.path.join(CSRC, "build")
 
@@ -247,7 +266,7 @@ def build(force=False, verbose=False, jobs=None):
 
 def _build_locked(force, verbose, jobs):
     srcs = sources()
-    hdrs = [HEADER, HEADER_INFER, HEADER_MULTI, HEADER_FLIP, HEADER_MULTI_LABELS, HEADER_HEAD16, HEADER_METRICS, HEADER_FGMASK, HEADER_DISC, HEADER_CROP, HEADER_DIST, HEADER_SEGSCORE, HEADER_INSTSCORE, HEADER_CC, HEADER_RAG, HEADER_WS, HEADER_MWS] + [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".h")]
+    hdrs = [HEADER, HEADER_INFER, HEADER_MULTI, HEADER_FLIP, HEADER_MULTI_LABELS, HEADER_HEAD16, HEADER_METRICS, HEADER_FGMASK, HEADER_DISC, HEADER_CROP, HEADER_DIST, HEADER_SEGSCORE, HEADER_INSTSCORE, HEADER_CC, HEADER_RAG, HEADER_WS, HEADER_MWS, HEADER_AGGLO] + [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".h")]
     newest_hdr = max(os.path.getmtime(h) for h in hdrs)
     if not force and os.path.exists(SO_PATH) and os.path.getmtime(SO_PATH) >= max([newest_hdr] + [os.path.getmtime(x) for x in srcs]):
         return SO_PATH
@@ -311,7 +330,7 @@ def lib():
         L = ctypes.CDLL(SO_PATH)
     except OSError as ex:
         raise PeaLibraryError("cannot load %s: %s" % (SO_PATH, ex))
-    for name in EXPORTS + EXPORTS_INFER + EXPORTS_MULTI + EXPORTS_FLIP + EXPORTS_MULTI_LABELS + EXPORTS_HEAD16 + EXPORTS_METRICS + EXPORTS_FGMASK + EXPORTS_DISC + EXPORTS_CROP + EXPORTS_DIST + EXPORTS_SEGSCORE + EXPORTS_INSTSCORE + EXPORTS_CC + EXPORTS_RAG + EXPORTS_WS + EXPORTS_MWS:
+    for name in EXPORTS + EXPORTS_INFER + EXPORTS_MULTI + EXPORTS_FLIP + EXPORTS_MULTI_LABELS + EXPORTS_HEAD16 + EXPORTS_METRICS + EXPORTS_FGMASK + EXPORTS_DISC + EXPORTS_CROP + EXPORTS_DIST + EXPORTS_SEGSCORE + EXPORTS_INSTSCORE + EXPORTS_CC + EXPORTS_RAG + EXPORTS_WS + EXPORTS_MWS + EXPORTS_AGGLO:
         if not hasattr(L, name):
             raise PeaLibraryError("%s does not export %s" % (SO_PATH, name))
     vp, dp = ctypes.c_void_p, ctypes.POINTER(PeaDesc)
@@ -501,6 +520,13 @@ def lib():
     L.pea_mws_workspace_bytes.argtypes = [mw]
     L.pea_mws_segment.restype = ctypes.c_int
     L.pea_mws_segment.argtypes = [mw, vp, vp, vp, vp, vp, vp, ctypes.c_size_t, vp]
+    ag = ctypes.POINTER(PeaAggloDesc)
+    L.pea_agglo_validate.restype = ctypes.c_int
+    L.pea_agglo_validate.argtypes = [ag]
+    L.pea_agglo_workspace_bytes.restype = ctypes.c_size_t
+    L.pea_agglo_workspace_bytes.argtypes = [ag]
+    L.pea_agglo_merge.restype = ctypes.c_int
+    L.pea_agglo_merge.argtypes = [ag, ctypes.POINTER(PeaAggloBuffers), vp, ctypes.c_size_t, vp]
     if L.pea_version() != PEA_ABI_VERSION:
         raise PeaLibraryError("ABI mismatch: library %d, binding %d" % (L.pea_version(), PEA_ABI_VERSION))
     _lib = L

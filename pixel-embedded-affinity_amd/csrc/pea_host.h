@@ -26,6 +26,8 @@
 //                      entry point), the Boruvka flood with its size filter and numbering
 //   pea_k_mws.hip      the mutex watershed (include/pea_mws.h): a state byte per edge, rounds of best / decide / hook / compress / rebuild of
 //                      the exclusion table, the raster-order numbering
+//   pea_k_agglo.hip    the agglomeration of the fragment graph (include/pea_agglo.h): two tables of the live edges keyed by the root pair,
+//                      rounds of best / merge / compress / re-key / flip, the numbering in ascending root id
 // Each kernel file exports a few plain functions (declared here) that pick the instantiation and launch it; a function returns
 // false when its family has no kernel for the descriptor and the caller tries the next one.  No device code crosses a file.
 // pea_dispatch.h holds what the launchers share to get from run-time facts (storage dtype, D, border, mask type, ..) to template
