@@ -57,6 +57,9 @@ from .harness.mws import MutexWatershed, mutex_watershed
 from .utils.seg_mutex import mutex_watershed as elf_mutex_watershed, seg_mutex
 from .harness.agglo import Agglomeration, agglomerate, agglomerate_graph
 from .utils.seg_waterz import seg_waterz
+from .harness.merge import BBBC_MERGE_PASSES, CVPPP_MERGE_PASSES, MergedSegments, merge_small_objects
+from .utils import merge_objects
+from .utils.merge_objects import merge_func, merge_func_bbbc, merge_small_object
 from .harness.handoff import AffsCollector
 from .harness.head_loss import HeadAffinityMSE, head_embedding_loss
 from .harness.train_step import CvpppTrainStep, convert_consistency_flip, label_pyramid, make_optimizer
@@ -111,3 +114,7 @@ MWS_EXPORTS = ("mutex_watershed", "MutexWatershed", "seg_mutex", "elf_mutex_wate
 # likewise the hierarchical agglomeration of the fragment graph (include/pea_agglo.h) and the reference's seg_waterz on it; the module
 # pea.utils.seg_waterz also carries relabel and waterz's own agglomerate(affs, thresholds, ..)
 AGGLO_EXPORTS = ("agglomerate_graph", "agglomerate", "Agglomeration", "seg_waterz")
+# likewise the small-segment merges and the renumbering (include/pea_merge.h) and the reference's merge_func on them; the module
+# pea.utils.merge_objects also carries relabel (utils/postprocessing.py stays without them: tests/test_cc_host.py)
+MERGE_EXPORTS = ("merge_small_objects", "MergedSegments", "CVPPP_MERGE_PASSES", "BBBC_MERGE_PASSES", "merge_objects", "merge_small_object",
+                 "merge_func", "merge_func_bbbc")

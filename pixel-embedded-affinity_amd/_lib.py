@@ -30,6 +30,7 @@ HEADER_RAG = os.path.join(HERE, "..", "include", "pea_rag.h")
 HEADER_WS = os.path.join(HERE, "..", "include", "pea_ws.h")
 HEADER_MWS = os.path.join(HERE, "..", "include", "pea_mws.h")
 HEADER_AGGLO = os.path.join(HERE, "..", "include", "pea_agglo.h")
+HEADER_MERGE = os.path.join(HERE, "..", "include", "pea_merge.h")
 
 PEA_ABI_VERSION = 2
 PEA_MAX_K = 32
@@ -77,6 +78,9 @@ AGGLO_LINKAGES = {"mean": 0, "min": 1, "max": 2}  # include/pea_agglo.h PEA_AGGL
 AGGLO_MAX_ROUNDS, AGGLO_MAX_EDGES, AGGLO_STATS = 65536, 1 << 30, 8  # include/pea_agglo.h PEA_AGGLO_MAX_ROUNDS, PEA_AGGLO_MAX_EDGES, PEA_AGGLO_STATS
 # the columns of pea_agglo_merge's stats [B][AGGLO_STATS] in order (include/pea_agglo.h PEA_AGGLO_<NAME>)
 AGGLO_STAT_COLUMNS = ("rounds", "live", "mergeable", "merges", "clusters", "no_edge", "bad_value", "reserved")
+MERGE_RELABEL, MERGE_MAX_PASSES, MERGE_MAX_WINDOW, MERGE_STATS = 1, 8, 45, 8  # include/pea_merge.h PEA_MERGE_RELABEL, PEA_MERGE_MAX_PASSES, PEA_MERGE_MAX_WINDOW, PEA_MERGE_STATS
+# the columns of pea_merge_small's stats [B][MERGE_STATS] in order (include/pea_merge.h PEA_MERGE_<NAME>)
+MERGE_STAT_COLUMNS = ("candidates", "merges", "negative", "few", "out_of_range", "chain", "reserved", "reserved")
 DISC_STATS = 5  # loss, var, dist, reg, n_bad; then var_b, dist_b, reg_b, C_b per image (include/pea_disc.h PEA_DISC_STATS)
 
 EXPORTS = ("pea_version", "pea_strerror", "pea_desc_validate", "pea_workspace_bytes", "pea_workspace_init", "pea_reload_env",
@@ -121,6 +125,8 @@ EXPORTS_WS = ("pea_ws_validate", "pea_ws_seeds_workspace_bytes", "pea_ws_flood_w
 EXPORTS_MWS = ("pea_mws_validate", "pea_mws_workspace_bytes", "pea_mws_segment")
 # the entry points of include/pea_agglo.h (the hierarchical agglomeration of the fragment graph: waterz's merge loop)
 EXPORTS_AGGLO = ("pea_agglo_validate", "pea_agglo_workspace_bytes", "pea_agglo_merge")
+# the entry points of include/pea_merge.h (the small-segment merges and the renumbering: merge_func, relabel)
+EXPORTS_MERGE = ("pea_merge_validate", "pea_merge_workspace_bytes", "pea_merge_small")
 
 
 class PeaLibraryError(RuntimeError):
@@ -236,6 +242,12 @@ class PeaAggloDesc(ctypes.Structure):
                 ("linkage", ctypes.c_int32), ("rounds", ctypes.c_int32), ("threshold", ctypes.c_float), ("flags", ctypes.c_uint32)]
 
 
+class PeaMergeDesc(ctypes.Structure):
+    """mirror of `struct PeaMergeDesc` in include/pea_merge.h"""
+    _fields_ = [("B", ctypes.c_int32), ("Y", ctypes.c_int32), ("X", ctypes.c_int32), ("max_id", ctypes.c_int32), ("n_passes", ctypes.c_int32),
+                ("threshold", ctypes.c_int32 * MERGE_MAX_PASSES), ("window", ctypes.c_int32 * MERGE_MAX_PASSES), ("flags", ctypes.c_uint32)]
+
+
 class PeaAggloBuffers(ctypes.Structure):
     """mirror of `struct PeaAggloBuffers` in include/pea_agglo.h"""
     _fields_ = [(n, ctypes.c_void_p) for n in ("uv", "n_edges", "value", "weight", "node_size", "root", "labels", "counts", "stats")]
@@ -266,7 +278,7 @@ def build(force=False, verbose=False, jobs=None):
 
 def _build_locked(force, verbose, jobs):
     srcs = sources()
-    hdrs = [HEADER, HEADER_INFER, HEADER_MULTI, HEADER_FLIP, HEADER_MULTI_LABELS, HEADER_HEAD16, HEADER_METRICS, HEADER_FGMASK, HEADER_DISC, HEADER_CROP, HEADER_DIST, HEADER_SEGSCORE, HEADER_INSTSCORE, HEADER_CC, HEADER_RAG, HEADER_WS, HEADER_MWS, HEADER_AGGLO] + [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".h")]
+    hdrs = [HEADER, HEADER_INFER, HEADER_MULTI, HEADER_FLIP, HEADER_MULTI_LABELS, HEADER_HEAD16, HEADER_METRICS, HEADER_FGMASK, HEADER_DISC, HEADER_CROP, HEADER_DIST, HEADER_SEGSCORE, HEADER_INSTSCORE, HEADER_CC, HEADER_RAG, HEADER_WS, HEADER_MWS, HEADER_AGGLO, HEADER_MERGE] + [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".h")]
     newest_hdr = max(os.path.getmtime(h) for h in hdrs)
     if not force and os.path.exists(SO_PATH) and os.path.getmtime(SO_PATH) >= max([newest_hdr] + [os.path.getmtime(x) for x in srcs]):
         return SO_PATH
@@ -330,7 +342,7 @@ def lib():
         L = ctypes.CDLL(SO_PATH)
     except OSError as ex:
         raise PeaLibraryError("cannot load %s: %s" % (SO_PATH, ex))
-    for name in EXPORTS + EXPORTS_INFER + EXPORTS_MULTI + EXPORTS_FLIP + EXPORTS_MULTI_LABELS + EXPORTS_HEAD16 + EXPORTS_METRICS + EXPORTS_FGMASK + EXPORTS_DISC + EXPORTS_CROP + EXPORTS_DIST + EXPORTS_SEGSCORE + EXPORTS_INSTSCORE + EXPORTS_CC + EXPORTS_RAG + EXPORTS_WS + EXPORTS_MWS + EXPORTS_AGGLO:
+    for name in EXPORTS + EXPORTS_INFER + EXPORTS_MULTI + EXPORTS_FLIP + EXPORTS_MULTI_LABELS + EXPORTS_HEAD16 + EXPORTS_METRICS + EXPORTS_FGMASK + EXPORTS_DISC + EXPORTS_CROP + EXPORTS_DIST + EXPORTS_SEGSCORE + EXPORTS_INSTSCORE + EXPORTS_CC + EXPORTS_RAG + EXPORTS_WS + EXPORTS_MWS + EXPORTS_AGGLO + EXPORTS_MERGE:
         if not hasattr(L, name):
             raise PeaLibraryError("%s does not export %s" % (SO_PATH, name))
     vp, dp = ctypes.c_void_p, ctypes.POINTER(PeaDesc)
@@ -527,6 +539,13 @@ def lib():
     L.pea_agglo_workspace_bytes.argtypes = [ag]
     L.pea_agglo_merge.restype = ctypes.c_int
     L.pea_agglo_merge.argtypes = [ag, ctypes.POINTER(PeaAggloBuffers), vp, ctypes.c_size_t, vp]
+    mg = ctypes.POINTER(PeaMergeDesc)
+    L.pea_merge_validate.restype = ctypes.c_int
+    L.pea_merge_validate.argtypes = [mg]
+    L.pea_merge_workspace_bytes.restype = ctypes.c_size_t
+    L.pea_merge_workspace_bytes.argtypes = [mg]
+    L.pea_merge_small.restype = ctypes.c_int
+    L.pea_merge_small.argtypes = [mg, vp, vp, vp, vp, vp, ctypes.c_size_t, vp]
     if L.pea_version() != PEA_ABI_VERSION:
         raise PeaLibraryError("ABI mismatch: library %d, binding %d" % (L.pea_version(), PEA_ABI_VERSION))
     _lib = L

@@ -28,6 +28,9 @@
 //                      the exclusion table, the raster-order numbering
 //   pea_k_agglo.hip    the agglomeration of the fragment graph (include/pea_agglo.h): two tables of the live edges keyed by the root pair,
 //                      rounds of best / merge / compress / re-key / flip, the numbering in ascending root id
+//   pea_k_merge.hip    the small-segment merges and the renumbering (include/pea_merge.h): per-id moments by a peeled streaming pass, one
+//                      workgroup per image walking the small ids in order through an alias table and an LDS id table per crop, the
+//                      numbering in ascending id, the projection
 // Each kernel file exports a few plain functions (declared here) that pick the instantiation and launch it; a function returns
 // false when its family has no kernel for the descriptor and the caller tries the next one.  No device code crosses a file.
 // pea_dispatch.h holds what the launchers share to get from run-time facts (storage dtype, D, border, mask type, ..) to template

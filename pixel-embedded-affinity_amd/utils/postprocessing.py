@@ -5,10 +5,11 @@ full connectivity --, remove_small_objects(min_size) -- components of FEWER than
 one pea_cc_label call with mask_out only (harness/cc.py, include/pea_cc.h): the mask that pea.foreground_mask left on the device stays
 there.
 
-merge_small_object and merge_func of the same file are NOT here and stay on the host: each merge rewrites the image that the next one
-reads, in id order (a small segment takes the id that is most frequent in a window around its centroid, and the segments after it see
-the result), so they are a sequential host algorithm by construction.  So is relabel of the validation loop.  seg_mutex is not: it runs
-on the device (utils/seg_mutex.py, include/pea_mws.h).
+merge_small_object and merge_func of the same file are NOT in this module; they live in utils/merge_objects.py, with relabel of the
+validation loop.  Each merge rewrites the image that the next one reads, in id order (a small segment takes the id that is most
+frequent in a window around its centroid, and the segments after it see the result), so the merges are sequential by definition; they
+run on the device all the same, one workgroup per image walking the small ids in order through an alias table (include/pea_merge.h).
+seg_mutex runs on the device as well (utils/seg_mutex.py, include/pea_mws.h).
 """
 import numpy as np
 import torch
